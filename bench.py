@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mcells*iter/s of the Jacobi sweep at 4096^2 on MI355X.
 
-  python bench.py [--gpus N --steps K --warmup W]      (N > 1: starts its own N ranks as child processes)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   (N > 1: starts its own N ranks as child processes)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = `--sweeps-per-step` weighted-Jacobi sweeps plus one Deff evaluation
@@ -9,6 +9,13 @@ A step = `--sweeps-per-step` weighted-Jacobi sweeps plus one Deff evaluation
 already resident in HBM.  With N > 1 every rank solves its own image (image
 index = rank): the path shards as whole images, there is no data-path
 collective, scaling is weak.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times K steps, writes the last step's outputs if
+--dump-outputs is given, and prints the line (headline figure and the roofline of
+the timed launches).  Everything below that takes work of its own -- the
+explicit-kernel, omega = 1 and contracted-arithmetic rows, the 1024^2 / 2048^2
+single images, config #2 to tolerance, the residual, the live rocprofv3 child
+runs and the CPU baseline with its parity check -- runs only with --full.
 
 roofline (always a fraction of a real roof, <= 1 by construction):
   * the default kernel (temporally blocked, matrix-free) never moves the explicit operator's 64 B per
@@ -43,6 +50,22 @@ OWN_BYTES_PER_CELL_LAUNCH = 18.0  # matrix-free kernels: x 8 + code 2 read, xNew
 # -> 1024 SIMDs x 16 x 2.4 GHz = 39.3 T instructions-lanes/s; an FMA counts 2 flops (78.6 TFLOP/s vector peak)
 FP64_INSTR_PEAK_T = 39.3216
 FP64_INSTR_PER_CELL = {False: 11, True: 7}   # tb_cell(): default arithmetic / contracted (kernels_tb.hpp)
+DUMP_MAX_VALUES = 1 << 20        # --dump-outputs: an array larger than this is written as a fixed sample of this many values
+DUMP_SEED = 12345
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float64.  An array of more than DUMP_MAX_VALUES values (the
+    4096^2 field) is written as the values at DUMP_MAX_VALUES positions drawn once from a generator seeded with DUMP_SEED, in
+    increasing order: the same positions in every run of the same shape, at most 8 MB per array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_VALUES:
+            pick = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_VALUES, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def child_env():
@@ -200,7 +223,8 @@ def cpu_baseline(n, seconds_target=12.0, fixed_sweeps=None, with_reference_kerne
 
 def bench_slab_one_gpu(args, pkg, torch, local_rank):
     """--mode slab --slabs N on ONE GPU: the same image as N row slabs driven by one process (peer copies between the
-    slabs' buffers), with the exchange overlapped with the interior of the pass and without, next to the unsplit context.
+    slabs' buffers), with the exchange overlapped with the interior of the pass (and, with --full, without, next to the
+    unsplit context).
     The slabs share the GPU, so this measures what the slab machinery and the exposed part of the exchange COST per pass,
     not a speed-up."""
     n, S, N = args.size, args.sweeps_per_step, args.slabs
@@ -216,32 +240,38 @@ def bench_slab_one_gpu(args, pkg, torch, local_rank):
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / args.steps
 
-    with pkg.Solver(n, n, device=local_rank) as s:
-        s.synth_image(12345, 0)
-        s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
-        s.init_linear(0.0, 1.0)
-        out["one_context"] = run(s)
-        launches, T = s.last_launches()
-    for tag, ov in (("slabs_overlap", 2), ("slabs_serial", 0)):
+    # the headline: the slabs with the exchange overlapped; the unsplit context and the serial exchange only with --full
+    for tag, ov in (("slabs_overlap", 2),) + ((("slabs_serial", 0),) if args.full else ()):
         with pkg.SlabGroup(n, n, [local_rank] * N) as g:
             g.set_tuning("slab_overlap", ov)
             g.synth_image(12345, 0)
             g.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
             g.init_linear(0.0, 1.0)
             out[tag] = run(g)
-    passes = S // T + S % T
+            if tag == "slabs_overlap" and args.dump_outputs:
+                dump_outputs(args.dump_outputs, field=g.get_field())
     cells = float(n) * n
-    print(json.dumps({
+    line = {
         "metric": f"Mcells*iter/s (Jacobi sweep) at {n}^2, {N} row slabs on one GPU", "value": cells * S / out["slabs_overlap"] / 1e6,
         "unit": "Mcells*iter/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": out["slabs_overlap"] * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "f64", "data": "synthetic",
         "config": {"workload": f"ONE {n}x{n} synthetic two-phase image as {N} row slabs on one GPU (one process, peer copies), "
-                               f"8-row halos, one exchange per pass of {T} sweeps; step = {S} sweeps", "sweeps_per_step": S},
-        "per_pass_us": {k: v / passes * 1e6 for k, v in out.items()},
-        "exchange_exposed_us_per_pass": {"overlapped": (out["slabs_overlap"] - out["one_context"]) / passes * 1e6,
-                                         "serial": (out["slabs_serial"] - out["one_context"]) / passes * 1e6},
-        "Mcells_iter_per_s": {k: cells * S / v / 1e6 for k, v in out.items()}}), flush=True)
+                               f"8-row halos, one exchange per temporally blocked pass; step = {S} sweeps", "sweeps_per_step": S}}
+    if args.full:
+        with pkg.Solver(n, n, device=local_rank) as s:
+            s.synth_image(12345, 0)
+            s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+            s.init_linear(0.0, 1.0)
+            out["one_context"] = run(s)
+            launches, T = s.last_launches()
+        passes = S // T + S % T
+        line["config"]["workload"] = line["config"]["workload"].replace("temporally blocked pass", f"pass of {T} sweeps")
+        line["per_pass_us"] = {k: v / passes * 1e6 for k, v in out.items()}
+        line["exchange_exposed_us_per_pass"] = {"overlapped": (out["slabs_overlap"] - out["one_context"]) / passes * 1e6,
+                                                "serial": (out["slabs_serial"] - out["one_context"]) / passes * 1e6}
+        line["Mcells_iter_per_s"] = {k: cells * S / v / 1e6 for k, v in out.items()}
+    print(json.dumps(line), flush=True)
 
 
 def bench_slab(args, pkg, torch, dist, world, rank, local_rank, barrier, use_dist, gather_elapsed):
@@ -277,6 +307,10 @@ def bench_slab(args, pkg, torch, dist, world, rank, local_rank, barrier, use_dis
         every = gather_elapsed(elapsed)
         per_rank_ms = [t / args.steps * 1e3 for t in every]
         elapsed = max(every)
+    if args.dump_outputs:
+        field = s.get_field()                       # this rank's own rows of the image after the last step
+        if rank == 0:
+            dump_outputs(args.dump_outputs, field=field)
     if rank == 0:
         cells = float(n) * n
         print(json.dumps({
@@ -339,7 +373,7 @@ def launch_dry(world, rank, local_rank):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--sweeps-per-step", type=int, default=1200)   # multiple of every T
@@ -373,8 +407,16 @@ def main():
                          "value says nothing about scaling")
     ap.add_argument("--launch-dry", action="store_true", help="start the ranks, join a gloo group, report rank/world and "
                                                               "exit: the launcher's test (no GPU needed)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement and check (explicit / omega-1 / "
+                                                        "contracted rows, small images, tolerance solve, residual, rocprofv3 "
+                                                        "children, CPU baseline and parity); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; the field as a "
+                         "fixed seeded sample when it has more than 2^20 values)")
     args = ap.parse_args()
-    if args.primary_only:
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.primary_only or not args.full:
         args.no_cpu_baseline = args.no_small_image = args.no_live_traffic = args.no_live_stats = args.no_iters_to_tol = True
         args.explicit_sweeps = 0
 
@@ -430,7 +472,7 @@ def main():
 
     # N > 1: the scaling line needs the timed steps only; the secondary legs (explicit kernel, omega = 1, contracted arithmetic,
     # small images, residual, CPU baseline) are rank 0's business at N = 1 and would only keep the other ranks waiting
-    lean = args.primary_only or world > 1
+    lean = args.primary_only or not args.full or world > 1
     if world > 1:
         args.explicit_sweeps = 0
         args.no_small_image = args.no_iters_to_tol = args.no_cpu_baseline = True
@@ -445,9 +487,12 @@ def main():
     s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
     s.init_linear(0.0, 1.0)
 
+    last = {}                                   # what the last step returned to its caller (--dump-outputs)
+
     def step():
         ms = s.sweeps(S, args.omega)
-        deff, _, _ = s.flux()
+        deff, MFL, MFR = s.flux()
+        last.update(deff=deff, MFL=MFL, MFR=MFR)
         return ms, (deff if args.batch == 1 else float(deff[0]))
 
     for _ in range(args.warmup):
@@ -468,6 +513,9 @@ def main():
         every = gather_elapsed(elapsed)
         per_rank_ms = [t / args.steps * 1e3 for t in every]
         elapsed = max(every)
+    if args.dump_outputs and rank == 0:
+        # before any secondary leg sweeps the field further: Deff and wall fluxes of the last step, the field it left
+        dump_outputs(args.dump_outputs, deff=last["deff"], mfl=last["MFL"], mfr=last["MFR"], field=s.get_field())
 
     launches, sweeps_per_launch = s.last_launches()     # of the last step
     kernel_used = s.kernel_in_use()

@@ -120,3 +120,40 @@ def test_one_rank_under_the_drivers_launcher_with_rccl(mode):
     out = _json_line(r.stdout)
     assert out["n_gpus"] == 1 and out["steps"] == 2 and len(out["per_rank_ms_per_step"]) == 1
     assert abs(out["value"] - 1024.0 * 1024.0 * 64 / (out["ms_per_step"] * 1e-3) / 1e6) <= 1e-6 * out["value"]
+
+
+def test_dump_outputs_writes_a_fixed_float64_sample(tmp_path):
+    """--dump-outputs: float64 .npy files; an array larger than DUMP_MAX_VALUES is written as the same seeded sample in every
+    run (so two builds can be compared output for output), small arrays whole."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big = np.random.default_rng(1).random((2048, 2048))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), field=big, deff=0.25, mfl=np.arange(2048.0))
+    a, b = np.load(tmp_path / "a" / "field.npy"), np.load(tmp_path / "b" / "field.npy")
+    assert a.dtype == np.float64 and a.shape == (bench.DUMP_MAX_VALUES,) and np.array_equal(a, b)
+    assert np.isin(a, big).all() and len(np.unique(a)) == a.size          # values of the field, each position once
+    assert np.load(tmp_path / "a" / "deff.npy") == 0.25 and np.array_equal(np.load(tmp_path / "a" / "mfl.npy"), np.arange(2048.0))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_last_steps_results(tmp_path, oracle):
+    """bench.py --dump-outputs on a 1024^2 image (small enough to be written whole): the field, Deff and wall fluxes after
+    (warmup + steps) x sweeps-per-step sweeps are the oracle's, bit for bit; a plain run's line carries no --full rows."""
+    import numpy as np
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--size", "1024", "--steps", "2", "--warmup", "1",
+                        "--sweeps-per-step", "64", "--dump-outputs", str(tmp_path)], env=_env(), capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = _json_line(r.stdout)
+    assert out["steps"] == 2 and "cpu_baseline" not in out and "single_image_2048" not in out
+    n = 1024
+    D = oracle.fill_D_2phase(oracle.synth_mask(n, n, 12345, 0), 1.0, 1e-3)
+    A, b = oracle.discretize(D, 0.0, 1.0)
+    x = oracle.sweeps(A, b, oracle.linear_guess(n, n, 0.0, 1.0), 3 * 64)
+    deff, MFL, MFR = oracle.flux_deff(x, D, 0.0, 1.0)
+    assert np.array_equal(np.load(tmp_path / "field.npy"), x)
+    assert np.load(tmp_path / "deff.npy") == deff
+    assert np.array_equal(np.load(tmp_path / "mfl.npy"), MFL) and np.array_equal(np.load(tmp_path / "mfr.npy"), MFR)

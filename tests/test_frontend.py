@@ -46,12 +46,10 @@ def test_jpeg_decoder_byte_equal_to_stb_image(built, img00000, stb_recorded):
 
 
 def test_jpeg_decoder_on_second_reference_image(built, stb_recorded):
-    """00042.jpg (1002x2007, the image the shipped input.txt names; 771 KB, not committed): the decode must
-    hash to the SHA-256 of the reference's stb_image decode (stb_decode_recorded.json) -- on this image
-    libjpeg would flip 364 pixels across the 150 threshold.  Only runs where the reference is mounted."""
-    path = "/root/reference/Deff2DGPU/00042.jpg"
-    if not os.path.exists(path):
-        pytest.skip("reference not mounted")
+    """00042.jpg (1002x2007, the image the shipped input.txt names; the reference's file, committed under tests/golden/):
+    the decode must hash to the SHA-256 of the reference's stb_image decode (stb_decode_recorded.json) -- on this image
+    libjpeg would flip 364 pixels across the 150 threshold."""
+    path = os.path.join(GOLDEN, "00042.jpg")
     import hashlib
     import effectivediffusivityfvm_amd as pkg
     from PIL import Image

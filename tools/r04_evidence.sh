@@ -7,7 +7,7 @@ out=$root/gpurun_out/r04_evidence
 mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
-python3 "$root/bench.py" > "$out/bench_default.log" 2> "$out/bench_default.err" || { echo "bench failed"; tail -5 "$out/bench_default.err"; exit 1; }
+python3 "$root/bench.py" --full > "$out/bench_default.log" 2> "$out/bench_default.err" || { echo "bench failed"; tail -5 "$out/bench_default.err"; exit 1; }
 cp "$root/gpurun_out/bench_live_kernel_stats.csv" "$out/tb_kernel_stats.csv" 2>/dev/null
 cp "$root/gpurun_out/bench_live_explicit_kernel_stats.csv" "$out/explicit_kernel_stats.csv" 2>/dev/null
 for n in 4096 16384; do
