@@ -21,7 +21,7 @@ SYMBOLS = [
     "deff_create", "deff_create_batch", "deff_batch_size", "deff_recommended_batch", "deff_destroy", "deff_mesh", "deff_set_kernel", "deff_get_kernel",
     "deff_set_tuning", "deff_get_plan", "deff_set_image", "deff_synth_image", "deff_get_image",
     "deff_load_jpeg_gray", "deff_free", "deff_assemble_2phase", "deff_assemble_3phase", "deff_flood_fill", "deff_assemble_from_D", "deff_set_system", "deff_get_system",
-    "deff_init_linear", "deff_set_field", "deff_get_field", "deff_solve", "deff_solve_batch", "deff_sweeps",
+    "deff_init_linear", "deff_set_field", "deff_get_field", "deff_solve", "deff_solve_batch", "deff_solve_cg", "deff_sweeps",
     "deff_slab_group_create", "deff_slab_group_destroy", "deff_slab_group_layout", "deff_slab_group_set_tuning", "deff_slab_group_get_plan",
     "deff_slab_group_set_image", "deff_slab_group_synth_image", "deff_slab_group_assemble_2phase",
     "deff_slab_group_init_linear", "deff_slab_group_set_field", "deff_slab_group_get_field",
@@ -42,6 +42,11 @@ class DeffError(RuntimeError):
 class Result(C.Structure):
     _fields_ = [("iters", C.c_int64), ("checks", C.c_int64), ("deff_raw", C.c_double),
                 ("conv", C.c_double), ("loop_ms", C.c_double)]
+
+
+class CGResultC(C.Structure):
+    _fields_ = [("iters", C.c_int64), ("rel_residual", C.c_double), ("deff_raw", C.c_double),
+                ("loop_ms", C.c_double), ("converged", C.c_int)]
 
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int64, C.c_double, C.c_double, C.c_void_p)
@@ -104,6 +109,7 @@ def load():
                              C.c_void_p, C.c_void_p]
     L.deff_solve_batch.argtypes = [ctx, C.c_double, C.c_double, C.c_int64, C.c_int64, C.POINTER(Result),
                                    C.c_void_p, C.c_void_p]
+    L.deff_solve_cg.argtypes = [ctx, C.c_double, C.c_int64, C.c_int64, C.POINTER(CGResultC), C.c_void_p, C.c_void_p]
     L.deff_sweeps.argtypes = [ctx, C.c_int64, C.c_double, C.POINTER(C.c_float)]
     L.deff_flux.argtypes = [ctx, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
     L.deff_residual.argtypes = [ctx, C.POINTER(C.c_double), C.POINTER(C.c_float)]

@@ -131,6 +131,10 @@ try {
     if (c->res_flags) (void)hipFree(c->res_flags);
     if (c->res_abort) (void)hipFree(c->res_abort);
     if (c->res_backup) (void)hipFree(c->res_backup);
+    void *cg_bufs[] = {c->cg_r, c->cg_p[0], c->cg_p[1], c->cg_tab, c->cg_part, c->cg_scal, c->cg_flags};
+    for (void *p : cg_bufs) if (p) (void)hipFree(p);
+    if (c->cg_ev0) (void)hipEventDestroy(c->cg_ev0);
+    if (c->cg_ev1) (void)hipEventDestroy(c->cg_ev1);
     if (c->q_host) (void)hipHostFree(c->q_host);
     if (c->chain_counted) resident_chain_ctx_destroyed(c->device);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

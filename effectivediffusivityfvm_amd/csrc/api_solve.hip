@@ -468,6 +468,14 @@ static int try_dict(deff_ctx *c)
     return DEFF_OK;
 }
 
+// The dictionary of an explicit system for a solver that runs on the matrix-free form only (deff_solve_cg): harvested under
+// plan_sweeps' conditions, whatever kernel the sweeps are set to.
+int ensure_dictionary(deff_ctx *c)
+{
+    if (!c->have_matfree && c->have_explicit && !c->dict_tried && c->dict_enabled && !c->wrap_links) TRY(try_dict(c));
+    return DEFF_OK;
+}
+
 // Runs k_links_symmetric on the current (dictionary, codes) unless that was done since they last changed; the answer is
 // c->links_sym (1 yes, 2 no).  Needs c->res_abort (its flag word) and synchronises the stream.
 static int check_links_symmetric(deff_ctx *c)

@@ -3,6 +3,7 @@
 //   api_core.hip   library, context lifecycle, image, assembly (native / from D / imported), field
 //   api_solve.hip  row dictionary, launch plans, sweeps, wall fluxes, the solve loops (one image,
 //                  batch, streaming batch)
+//   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg)
 //   api_slab.hip   one image over several GPUs: row slabs (peer copies in one process, RCCL or a
 //                  caller-supplied transport with one process per GPU)
 // The library is built with -fvisibility=hidden; only the C ABI of include/deff_amd.h is exported.
@@ -206,6 +207,16 @@ struct deff_ctx {
     int tb_dealt_LY = 0, tb_dealt_nmax = 0;      // ... and what deff_get_plan reports of it (an inner strip's middle rank; most chunks per rank)
     int plan_ranked = 0;
     int64_t last_launches = 0;                   // sweep-kernel launches of the last deff_sweeps()/deff_solve()
+
+    // conjugate gradients (api_cg.hip): work vectors, CG table, per-image scalars and the loop's own event pair, allocated
+    // by the first deff_solve_cg
+    double *cg_r = nullptr, *cg_p[2] = {nullptr, nullptr};
+    double *cg_tab = nullptr;                    // device table [CG_PLANES][LUT_PLANE_STRIDE] (kernels_cg.hpp)
+    double *cg_part = nullptr;                   // partial sums, 3 per work item
+    size_t cg_part_cap = 0;
+    void *cg_scal = nullptr;                     // CgScal per image
+    unsigned *cg_flags = nullptr;                // [0] admissibility, [1] images restarted by a true-residual round
+    hipEvent_t cg_ev0 = nullptr, cg_ev1 = nullptr;
 };
 
 static inline int use_device(const deff_ctx *c)
@@ -336,7 +347,8 @@ int plan_sweeps(deff_ctx *c, double omega, SweepPlan *pl);
 void enqueue_sweep(deff_ctx *c, const SweepPlan &pl);
 int enqueue_tb_pass(deff_ctx *c, const SweepPlan &pl);
 int launch_tb_pass(deff_ctx *c, const SweepPlan &pl);    // the same launch without flipping x[cur]
-int dealt_watch(deff_ctx *c);                            // after a synchronisation: is the dispatch order the dealt tiles assume?
+int dealt_watch(deff_ctx *c);
+int ensure_dictionary(deff_ctx *c);                      // harvest the row dictionary of an explicit system, if allowed                            // after a synchronisation: is the dispatch order the dealt tiles assume?
 int enqueue_sweeps(deff_ctx *c, const SweepPlan &pl, int64_t n);   // stops at the first launch that fails
 // did a resident launch give up waiting?  (synchronises if one is pending; on an abort the interval is redone with one
 // launch per pass and the context stays in that mode)

@@ -10,6 +10,12 @@
 //
 //   deff2d [input.txt] [--device N | --devices 0,1,..] [--json results.json] [--field-bin prefix] [--batch-size B]
 //          [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K]
+//          [--solver jacobi|cg] [--cg-rtol R]
+// --solver cg: every solve of a one-GPU image runs preconditioned conjugate gradients to ||b - A x|| <= R ||b||
+// (deff_solve_cg, R = --cg-rtol, default 1e-10) instead of the reference's Jacobi loop; the 3-phase continuation
+// stages keep their structure.  The CSV columns stay: iterations = CG iterations, converge = the final relative
+// residual.  Row slabs (--devices with RunBatch 0) refuse it; batch mode then solves one image at a time per worker
+// instead of in stacked slots.
 // --arith contracted: products fused into adds the way a compiler contracts the reference's expressions
 // (kernels_sweep.hpp); default is the reference's written operation order.
 //
@@ -112,6 +118,8 @@ static int g_contracted = 0;       // --arith contracted: deff_set_tuning(ctx, "
 static int64_t g_precond_maxiter = 1000000;
 // threads that prepare images ahead of each worker's solver (2-phase batch mode), see Prefetcher
 static int g_prefetch_threads = 2;
+static bool g_solver_cg = false;   // --solver cg
+static double g_cg_rtol = 1e-10;   // --cg-rtol
 
 struct Session {                   // one solver context, re-created only when the mesh / batch size changes
     deff_ctx *ctx = nullptr;
@@ -134,6 +142,21 @@ static void progress(int64_t iter, double deff, double change, void *user)
     std::printf("Iteration = %d, Deff = %1.3e, Deff Change = %1.3e\n", (int)iter, deff / *(double *)user, change);   // cuh:1270
 }
 
+// --solver cg: deff_solve_cg in place of the Jacobi loop, reported in a deff_result (iters = CG iterations, conv = the final
+// relative residual ||b - A x|| / ||b||)
+static int solve_cg(deff_ctx *ctx, int64_t max_iter, deff_result *r)
+{
+    deff_cg_result c;
+    const int rc = deff_solve_cg(ctx, g_cg_rtol, max_iter, 64, &c, nullptr, nullptr);
+    if (rc != DEFF_OK) return rc;
+    r->iters = c.iters;
+    r->checks = 0;
+    r->deff_raw = c.deff_raw;
+    r->conv = c.rel_residual;
+    r->loop_ms = c.loop_ms;
+    return DEFF_OK;
+}
+
 // Where a 2-phase image is solved: one context on one GPU, or -- a single image with --devices
 // a,b,... -- row slabs over several GPUs (deff_slab_group_*, one exchange of 8 halo rows per
 // temporally blocked pass; results identical to the one-GPU run).
@@ -149,6 +172,7 @@ struct OneGpu {
     bool assemble(const Options &o, double DCF) { CK(deff_assemble_2phase(S.ctx, o.DCsolid, DCF, o.CLeft, o.CRight)); return true; }
     bool solve(const Options &o, double *scale, deff_result *r)
     {
+        if (g_solver_cg) { CK(solve_cg(S.ctx, o.MAX_ITER, r)); return true; }
         if (o.verbose == 1 && !o.BatchFlag) deff_set_progress(S.ctx, progress, scale);
         const int rc = deff_solve(S.ctx, 2.0 / 3.0, o.ConvergeCriteria, o.MAX_ITER, 10000, r, nullptr, nullptr);
         deff_set_progress(S.ctx, nullptr, nullptr);
@@ -164,6 +188,7 @@ struct OneGpu {
     }
     bool solve_with(const Options &o, double tol, int64_t max_iter, bool show, double *scale, deff_result *r)
     {
+        if (g_solver_cg) { CK(solve_cg(S.ctx, max_iter, r)); return true; }
         if (show && o.verbose == 1 && !o.BatchFlag) deff_set_progress(S.ctx, progress, scale);
         const int rc = deff_solve(S.ctx, 2.0 / 3.0, tol, max_iter, 10000, r, nullptr, nullptr);
         deff_set_progress(S.ctx, nullptr, nullptr);
@@ -677,8 +702,16 @@ int main(int argc, char **argv)
             g_precond_maxiter = (int64_t)std::strtod(argv[++a], nullptr);
             if (g_precond_maxiter < 1) { std::fprintf(stderr, "deff2d: --precond-maxiter must be >= 1\n"); return 2; }
         }
+        else if (s == "--solver" && a + 1 < argc) {
+            const std::string v = argv[++a];
+            if (v != "jacobi" && v != "cg") { std::fprintf(stderr, "deff2d: --solver jacobi|cg\n"); return 2; }
+            g_solver_cg = v == "cg";
+        } else if (s == "--cg-rtol" && a + 1 < argc) {
+            g_cg_rtol = std::strtod(argv[++a], nullptr);
+            if (!(g_cg_rtol >= 0.0) || !std::isfinite(g_cg_rtol)) { std::fprintf(stderr, "deff2d: --cg-rtol R (R >= 0)\n"); return 2; }
+        }
         else if (s == "-h" || s == "--help") {
-            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K]\n");
+            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R]\n");
             return 0;
         } else if (!s.empty() && s[0] != '-') input = s;
         else { std::fprintf(stderr, "deff2d: unknown argument %s\n", s.c_str()); return 2; }
@@ -688,6 +721,14 @@ int main(int argc, char **argv)
     if (!deff::read_input_file(input.c_str(), &o, &err)) { std::fprintf(stderr, "deff2d: %s\n", err.c_str()); return 1; }
     if (o.verbose == 1) deff::print_options(o);
 
+    if (g_solver_cg && !o.BatchFlag && devices.size() >= 2) {
+        std::fprintf(stderr, "deff2d: --solver cg runs on one GPU: row slabs (--devices with RunBatch 0) need an all-reduce per "
+                             "CG iteration and are not offered\n");
+        return 2;
+    }
+    if (g_solver_cg && o.BatchFlag && batch_size > 1)
+        std::fprintf(stderr, "deff2d: note: --solver cg solves one image at a time per worker (the stacked / streaming slots "
+                             "run the Jacobi loop only); --batch-size is ignored\n");
     const int count = o.BatchFlag ? o.NumImg : 1;
     std::vector<Row> rows((size_t)count);
     const bool want_field = o.printCmap == 1 || !field_prefix.empty();
@@ -839,8 +880,8 @@ int main(int argc, char **argv)
             if (want_field) emit_field(k, field.data(), nx, ny);
         }
     };
-    const bool streaming = o.BatchFlag && o.nPhase == 2;
-    const bool grouped3 = o.BatchFlag && o.nPhase == 3;
+    const bool streaming = o.BatchFlag && o.nPhase == 2 && !g_solver_cg;   // slots of the Jacobi loop (cg: one image at a time)
+    const bool grouped3 = o.BatchFlag && o.nPhase == 3 && !g_solver_cg;
     auto run = [&](int dev) { if (streaming) stream_worker(dev); else if (grouped3) worker3(dev); else worker(dev); };
     if (devices.size() <= 1 || count <= 1) {
         run(devices.empty() ? device : devices[0]);

@@ -30,6 +30,7 @@
 #include <stdint.h>
 #include "fvm_row.hpp"
 #include "kernels_sweep.hpp"
+#include "wave_reduce.hpp"
 
 namespace deff {
 
@@ -41,42 +42,6 @@ template <bool V> struct ResTag { static constexpr bool value = V; };
 struct ResTable {
     double g[3][8];                              // g[k][q]: q < 3 face to a cell of class q; 3: wall dy/(dx/2)*D[k]; 4..7 unused
 };
-
-template <int CTRL, int ROW_MASK, int BANK_MASK>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, BANK_MASK, true);     // lanes without a source read 0
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, BANK_MASK, true);
-    return __hiloint2double(hi, lo);
-}
-// lane i <- lane i - 1 (wave_shr:1) / lane i + 1 (wave_shl:1); the lane without a source (0 / 63) keeps `edge`
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64_keep(double v, double edge)
-{
-    int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(v), CTRL, 0xf, 0xf, false);
-    int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u32_keep(unsigned v, unsigned edge)
-{
-    return (unsigned)__builtin_amdgcn_update_dpp((int)edge, (int)v, CTRL, 0xf, 0xf, false);
-}
-
-// Sum of the 64 lanes' values; valid in lane 63.  Fixed order: within a row of 16 lanes prefix sums by row_shr 1, 2, 3, then
-// 4 and 8; rows 1 and 3 add lane 15 of the row below (row_bcast:15), rows 2 and 3 add lane 31 (row_bcast:31).
-__device__ __forceinline__ double wave_sum_to_lane63(double v)
-{
-    double t = v + dpp_f64<0x111, 0xf, 0xf>(v);                  // row_shr:1
-    t = t + dpp_f64<0x112, 0xf, 0xf>(v);                         // row_shr:2
-    t = t + dpp_f64<0x113, 0xf, 0xf>(v);                         // row_shr:3   -> t[i] = v[i-3..i]
-    t = t + dpp_f64<0x114, 0xf, 0xe>(t);                         // row_shr:4, banks 1-3
-    t = t + dpp_f64<0x118, 0xf, 0xc>(t);                         // row_shr:8, banks 2-3 -> lane 15 of a row = the row's sum
-    t = t + dpp_f64<0x142, 0xa, 0xf>(t);                         // row_bcast:15 into rows 1 and 3
-    t = t + dpp_f64<0x143, 0xc, 0xf>(t);                         // row_bcast:31 into rows 2 and 3
-    return t;
-}
 
 // pixel -> class CODE = 8 x class index (0 fluid, 1 solid, 2 gas; 24 = "wall"): the byte offset of the class in a row of the
 // table, and << 3 the byte offset of its own row.  PHASES = 2: cuh:1988-2000 (< 150 fluid); 3: cuh:1518-1529.

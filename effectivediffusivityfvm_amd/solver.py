@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import KERNEL_NAMES, DeffError, Result, check
+from ._capi import KERNEL_NAMES, CGResultC, DeffError, Result, check
 
 OMEGA_REFERENCE = 2.0 / 3.0     # updateX_SOR, Deff2D.cuh:72
 
@@ -20,6 +20,15 @@ class SolveResult:
     def __repr__(self):
         return (f"SolveResult(iters={self.iters}, checks={self.checks}, deff_raw={self.deff_raw!r}, "
                 f"conv={self.conv!r}, loop_ms={self.loop_ms:.3f})")
+
+
+class CGResult:
+    """deff_solve_cg of one image: CG iterations, ||b - A x|| / ||b|| recomputed from the returned field, its Deff (not / Df)."""
+    __slots__ = ("iters", "rel_residual", "deff_raw", "converged", "loop_ms", "MFL", "MFR")
+
+    def __repr__(self):
+        return (f"CGResult(iters={self.iters}, rel_residual={self.rel_residual!r}, deff_raw={self.deff_raw!r}, "
+                f"converged={self.converged}, loop_ms={self.loop_ms:.3f})")
 
 
 def recommended_batch(nx, ny, images, device=0):
@@ -170,6 +179,25 @@ class Solver:
             out = SolveResult()
             out.iters, out.checks = res[k].iters, res[k].checks
             out.deff_raw, out.conv, out.loop_ms = res[k].deff_raw, res[k].conv, res[k].loop_ms
+            out.MFL = MFL[k * self.ny:(k + 1) * self.ny]
+            out.MFR = MFR[k * self.ny:(k + 1) * self.ny]
+            outs.append(out)
+        return outs[0] if self.nimg == 1 else outs
+
+    def solve_cg(self, rtol=1e-10, max_iter=1_000_000, check_every=64, fluxes=True):
+        """Jacobi-preconditioned conjugate gradients from the current field to ||b - A x|| <= rtol ||b|| (deff_solve_cg):
+        not the reference's algorithm, the same fixed point.  One image: a CGResult; a stack: a list, one per image."""
+        res = (CGResultC * self.nimg)()
+        MFL = np.zeros(self.rows)
+        MFR = np.zeros(self.rows)
+        check(self._L.deff_solve_cg(self._ctx, float(rtol), int(max_iter), int(check_every), res,
+                                    MFL.ctypes.data_as(C.c_void_p) if fluxes else None,
+                                    MFR.ctypes.data_as(C.c_void_p) if fluxes else None))
+        outs = []
+        for k in range(self.nimg):
+            out = CGResult()
+            out.iters, out.rel_residual, out.deff_raw = res[k].iters, res[k].rel_residual, res[k].deff_raw
+            out.converged, out.loop_ms = bool(res[k].converged), res[k].loop_ms
             out.MFL = MFL[k * self.ny:(k + 1) * self.ny]
             out.MFR = MFR[k * self.ny:(k + 1) * self.ny]
             outs.append(out)

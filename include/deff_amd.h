@@ -152,6 +152,27 @@ int deff_solve(deff_ctx *ctx, double omega, double tol, int64_t max_iter, int64_
  * end, its field is frozen) while the others continue; MFL/MFR hold nimg*ny values */
 int deff_solve_batch(deff_ctx *ctx, double omega, double tol, int64_t max_iter, int64_t check_every,
                      deff_result *out, double *MFL, double *MFR);
+/* Preconditioned conjugate gradients to a residual tolerance (opt-in; NOT the reference's algorithm -- the reference
+ * has only the weighted Jacobi loop above).  Jacobi-preconditioned CG in FP64 on the matrix-free form converges to the
+ * same discrete fixed point (the same A, b and wall-flux Deff) in far fewer iterations.  The current field is the
+ * initial guess (deff_init_linear / deff_set_field); the solution is written into it, so deff_get_field, deff_flux,
+ * deff_residual and deff_device_field see it afterwards.  Plain and stack contexts (out[nimg], MFL/MFR nimg*ny values,
+ * may be NULL).  An image stops when ||r||_2 <= rtol * ||b||_2 (on the device, whatever check_every: the host looks at
+ * the images' flags every check_every iterations only; the results do not depend on it); the residual is then
+ * recomputed from x and the iteration restarted if it misses rtol.  Decoupled rows (four zero links and b = 0: cells
+ * outside the mesh, ImpSolid / FloodFill rows, a phase with D = 0) get x = 0 -- where the Jacobi loop of a 2-phase
+ * system with Ds = 0 gives NaN, CG gives a finite field.  DEFF_EINVAL: row-slab contexts, systems without a row
+ * dictionary or explicit-only ones (a wall link into the neighbouring row), and systems that are not symmetric (a link
+ * between two active cells that differs from its partner, an active row with A0 <= 0); nothing is changed then. */
+typedef struct deff_cg_result {
+    int64_t iters;         /* CG iterations of this image */
+    double  rel_residual;  /* ||b - A x||_2 / ||b||_2 of the returned field, recomputed from x */
+    double  deff_raw;      /* Deff of the returned field (cuh:1252-1263 expressions), not / Df */
+    double  loop_ms;       /* hipEvent time of the CG loop (shared by the images of a stack) */
+    int     converged;     /* rel_residual <= rtol */
+} deff_cg_result;
+int deff_solve_cg(deff_ctx *ctx, double rtol, int64_t max_iter, int64_t check_every,
+                  deff_cg_result *out /* [nimg] */, double *MFL, double *MFR);
 /* streaming batch (dataset generation): the nimg slots of a batch context are kept full -- when a
  * slot's image stops (its own rule), its result is reported and the slot is refilled with the next
  * image, which enters one sweep before a check of the running ones so that every image keeps the
