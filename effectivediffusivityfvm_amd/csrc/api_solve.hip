@@ -7,101 +7,162 @@
 #include "kernels_tb.hpp"
 #include "kernels_wgtile.hpp"
 #include <array>
+#include <map>
 #include <mutex>
 
 // ----------------------------------------------------------- sweeps -------
 
-// Workgroups of the temporally blocked kernel that are resident at once on this device.
-template <int T, bool F, bool G>
-static int tb_occ(int *per_cu)
+// ---- the kernels of a temporally blocked pass, each instantiation listed once ------------------------------------------
+// The planner takes its candidates from these tables and sizes a grid with the occupancy of the kernel it would launch; a plan
+// names its table entry and the launchers take the kernel from there.  So a shape the planner can pick always has a kernel.
+
+// make(f) for a compile-time flag f = false, true; make(f, g) for the four pairs, at index 2 f + g.  The flags come as TbTag
+// (kernels_tb.hpp): decltype(f)::value.
+template <class Make> static constexpr auto by_flag(Make make) { return std::array{make(TbTag<false>{}), make(TbTag<true>{})}; }
+template <class Make> static constexpr auto by_flags(Make make)
 {
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_sweep_matfree_tb<T, F, G>, 256, 0));
+    return std::array{make(TbTag<false>{}, TbTag<false>{}), make(TbTag<false>{}, TbTag<true>{}), make(TbTag<true>{}, TbTag<false>{}),
+                      make(TbTag<true>{}, TbTag<true>{})};
+}
+template <class E, size_t... N> static constexpr auto cat(const std::array<E, N> &...parts)
+{
+    std::array<E, (N + ...)> all{};
+    size_t k = 0;
+    auto put = [&](const auto &part) { for (const E &e : part) all[k++] = e; };
+    (put(parts), ...);
+    return all;
+}
+
+// Streaming form (kernels_tb.hpp), [tb_index(T)][2 fma + guard].  Only 2 cells per lane are instantiated: 4 per lane (twice the
+// work per wave, 244 VGPRs, 2 waves per SIMD) measured 20 % slower at 4096^2 -- the kernel needs the wave-level parallelism more
+// than it needs the smaller strip overlap.
+template <int... T> static constexpr auto streaming_passes()
+{
+    return std::array{by_flags([](auto f, auto g) { return k_sweep_matfree_tb<T, decltype(f)::value, decltype(g)::value>; })...};
+}
+static constexpr auto STREAMING = streaming_passes<1, 2, 4, 6, 8>();
+static int tb_index(int T) { return T == 1 ? 0 : T == 2 ? 1 : T == 4 ? 2 : T == 6 ? 3 : 4; }
+
+// Workgroup tiles (kernels_wgtile.hpp).  Every resident kernel takes the argument list launch_resident passes.
+using ResidentKernel = decltype(&k_sweep_wgsym<8, 4, false>);
+using PassKernel = decltype(&k_sweep_wgtile<8, 4, false, false>);
+struct TileKernel {
+    int NW = 0, T = 0;                // waves per tile, sweeps per pass
+    int rows[4] = {0, 0, 0, 0};       // rows of a wave by its age (wave >> 2: a SIMD serves its waves oldest first); NW / 4 ages
+    int R = 0;                        // deff_get_plan("tb_R"): the oldest wave's rows, a tall tile's rows / 16
+    bool fma = false, guard = false;
+    bool sym = false;                 // for link-symmetric systems only (the 7-lookup short-cut)
+    ResidentKernel kernel = nullptr;  // resident passes
+    PassKernel pass = nullptr;        // one launch per pass: 8-wave tiles only
+    constexpr int threads() const { return NW * 64; }
+    constexpr int tile_rows() const { return 4 * (rows[0] + rows[1] + rows[2] + rows[3]); }
+    constexpr bool aged() const { return rows[0] != rows[NW / 4 - 1]; }
+};
+
+// 8 waves x R rows, matrix rows in registers (2 waves per SIMD): resident (k_sweep_wgres) or one launch per pass
+// (k_sweep_wgtile).  R = 8 needs 256 VGPRs + 148 B of scratch per lane and ran 40 % SLOWER than R = 6: the spills sit in the
+// sweep loop.
+template <int T, int... R> static constexpr auto tiles8()
+{
+    return cat(by_flags([](auto f, auto g) {
+        constexpr bool F = decltype(f)::value, G = decltype(g)::value;
+        return TileKernel{WGT_WAVES, T, {R, R, 0, 0}, R, F, G, false, k_sweep_wgres<T, R, F, G>, k_sweep_wgtile<T, R, F, G>};
+    })...);
+}
+
+// Tall tiles: 16 waves, the rows of ages 0..3 summing to 4R, matrix rows looked up in every sweep (4 waves per SIMD).  Rows dealt
+// by age run k_sweep_wgage, equal rows k_sweep_wgres<.., TALL>.  Unguarded with and without the link-symmetric short-cut; the
+// guarded kernel branches on every link anyway and exists with equal rows only.
+template <int A, int B, int C, int D, bool F, bool G, bool SYM> static constexpr ResidentKernel tall_instance()
+{
+    if constexpr (A == D) return k_sweep_wgres<8, A, F, G, true, SYM>;
+    else return k_sweep_wgage<8, A, B, C, D, F, G, SYM>;
+}
+template <int R, int A = R, int B = R, int C = R, int D = R> static constexpr auto tall()
+{
+    static_assert(A + B + C + D == 4 * R, "rows dealt by age keep the tile of 16 R rows");
+    const auto unguarded = by_flags([](auto f, auto s) {
+        constexpr bool F = decltype(f)::value, S = decltype(s)::value;
+        return TileKernel{WGL_WAVES, 8, {A, B, C, D}, R, F, false, S, tall_instance<A, B, C, D, F, false, S>()};
+    });
+    if constexpr (A != D) return unguarded;
+    else return cat(unguarded, by_flag([](auto f) {
+        constexpr bool F = decltype(f)::value;
+        return TileKernel{WGL_WAVES, 8, {R, R, R, R}, R, F, true, false, tall_instance<R, R, R, R, F, true, false>()};
+    }));
+}
+
+// Link-symmetric 12-wave tiles, the rows of ages 0..2 (3 waves per SIMD): k_sweep_wgsym for equal rows, k_sweep_wgsage.
+template <int T, int A, int B, int C, bool F> static constexpr ResidentKernel sym_instance()
+{
+    if constexpr (A == C) return k_sweep_wgsym<T, A, F>;
+    else return k_sweep_wgsage<T, A, B, C, F>;
+}
+template <int T, int A, int B, int C> static constexpr auto sym()
+{
+    return by_flag([](auto f) {
+        constexpr bool F = decltype(f)::value;
+        return TileKernel{WGS_WAVES, T, {A, B, C, 0}, A, F, false, true, sym_instance<T, A, B, C, F>()};
+    });
+}
+
+// Within a form and T the planners take the first entry that fits, so each list runs from the fewest rows up.
+static constexpr auto TILES = cat(
+    tiles8<4, 4, 6, 7>(), tiles8<8, 4, 6, 7>(),
+    // (tall R = 16 -- 256-row tiles, images up to ~2600^2 -- spills inside the sweep loop: 9.9 us per sweep, slower than streaming)
+    tall<4>(), tall<5>(), tall<6>(), tall<7>(), tall<8>(), tall<9>(), tall<10>(), tall<11>(), tall<12>(), tall<13>(), tall<14>(),
+    // Rows by age for the tall tiles of R rows per wave: the 4R rows of a SIMD's four waves, oldest first.  Measured, not derived
+    // (profiles/r04_tall_rows_by_age_kbench.log: four candidate sets per R, one process, against equal rows): what wins gives the
+    // youngest wave about half its share and keeps the three older ones level; bodies of 9 and more rows spill, which is why R = 7
+    // stops at 8 rows, R = 9 deals one row only, and R = 13 found no set that beats equal rows -- four equal bodies in this kernel
+    // run 3-4 % behind the one-body kernel, which is what every set has to earn first (14 x 4 has nothing to deal).  Unguarded
+    // systems, link-symmetric (7 lookups per row) or not (10: the 3-phase assembly with impermeable solid), both arithmetics.
+    tall<5, 6, 6, 5, 3>(), tall<6, 8, 8, 5, 3>(), tall<7, 8, 8, 8, 4>(), tall<8, 9, 9, 9, 5>(), tall<9, 10, 9, 9, 8>(),
+    tall<10, 12, 12, 10, 6>(), tall<11, 13, 13, 11, 7>(), tall<12, 13, 13, 13, 9>(),
+    // 12-wave tiles.  For T = 8 also the shapes that give the younger waves a row less (k_sweep_wgsage): 5 / 5 / 4 is a 56-row tile
+    // that sweeps ~9 % faster than 5 / 5 / 5 and owns 40 rows instead of 44 -- one 1024^2 image: 234 tiles instead of 216, 853 ->
+    // 901 G; 4 / 4 / 3 and 5 / 4 / 4 likewise (704^2 ... 992^2: +6 ... 11 %, profiles/r04_sym_shapes_kbench.log).  The tests
+    // address T = 8's list by its 1-based position (tuning "tb_sym_shape").
+    // (R = 6 -- 72-row tiles, images up to ~1230^2 -- needs 168 VGPRs + ~100 B of scratch, which lands in the halo exchange: 1152^2
+    // 652 G against 704 G on tall tiles: not instantiated; R = 3 -- 36-row tiles -- is no faster than 8 waves x 4 rows, see
+    // plan_blocked_pass)
+    sym<8, 4, 4, 3>(), sym<8, 4, 4, 4>(), sym<8, 5, 4, 4>(), sym<8, 5, 5, 4>(), sym<8, 5, 5, 5>(),
+    sym<6, 4, 4, 4>(), sym<6, 5, 5, 5>(), sym<4, 4, 4, 4>(), sym<4, 5, 5, 5>());
+
+template <class Pred> static const TileKernel *find_tile(Pred pred)
+{
+    for (const TileKernel &t : TILES)
+        if (pred(t)) return &t;
+    return nullptr;
+}
+
+static int cu_count(const deff_ctx *c, int *cus)
+{
+    HIP_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, c->device));
     return DEFF_OK;
 }
 
-// Only 2 cells per lane are instantiated: 4 per lane (twice the work per wave, 244 VGPRs,
-// 2 waves per SIMD) measured 20 % slower at 4096^2 -- the kernel needs the wave-level
-// parallelism more than it needs the smaller strip overlap.
-#define TB_DISPATCH_FG(TC_, F_, G_, CALL)                                                   \
-    switch (((F_) ? 2 : 0) + ((G_) ? 1 : 0)) {                                              \
-    case 1: { CALL(TC_, false, true); } break;  case 2: { CALL(TC_, true, false); } break; \
-    case 3: { CALL(TC_, true, true); } break;   default: { CALL(TC_, false, false); } break; \
+// Workgroups of `kernel` (blocks of `threads`) resident at once on this device: asked for every candidate by every plan, so
+// remembered per (device, kernel).
+template <class Kernel> static int resident_blocks(const deff_ctx *c, Kernel kernel, int threads, int *resident)
+{
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, int> cache;
+    const std::pair<int, const void *> key(c->device, reinterpret_cast<const void *>(kernel));
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        const auto it = cache.find(key);
+        if (it != cache.end()) { *resident = it->second; return DEFF_OK; }
     }
-#define TB_DISPATCH(T_, F_, G_, CALL)                                                       \
-    do {                                                                                    \
-        switch (T_) {                                                                       \
-        case 1: TB_DISPATCH_FG(1, F_, G_, CALL); break;                                     \
-        case 2: TB_DISPATCH_FG(2, F_, G_, CALL); break;                                     \
-        case 4: TB_DISPATCH_FG(4, F_, G_, CALL); break;                                     \
-        case 6: TB_DISPATCH_FG(6, F_, G_, CALL); break;                                     \
-        default: TB_DISPATCH_FG(8, F_, G_, CALL); break;                                    \
-        }                                                                                   \
-    } while (0)
-
-static int tb_resident_blocks(const deff_ctx *c, int T, bool fma, bool guard, int *resident)
-{
     int per_cu = 0, cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-#define OCC_CALL(T_, C_, G_) TRY((tb_occ<T_, C_, G_>(&per_cu)))
-    TB_DISPATCH(T, fma, guard, OCC_CALL);
-#undef OCC_CALL
-    if (per_cu < 1) per_cu = 1;
+    TRY(cu_count(c, &cus));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0));
     *resident = per_cu * cus;
+    std::lock_guard<std::mutex> lock(mu);
+    cache[key] = *resident;
     return DEFF_OK;
 }
 
-// ---- workgroup-tile form (kernels_wgtile.hpp): instantiated for T in {4, 8} x R in {4, 6, 7} rows per wave
-// (R = 8 needs 256 VGPRs + 148 B of scratch per lane and ran 40 % SLOWER than R = 6: the spills sit in the sweep loop)
-#define WGT_DISPATCH_FG(T_, R_, F_, G_, CALL)                                                   \
-    switch (((F_) ? 2 : 0) + ((G_) ? 1 : 0)) {                                                 \
-    case 1: { CALL(T_, R_, false, true); } break;  case 2: { CALL(T_, R_, true, false); } break; \
-    case 3: { CALL(T_, R_, true, true); } break;   default: { CALL(T_, R_, false, false); } break; \
-    }
-#define WGT_DISPATCH_R(T_, R_, F_, G_, CALL)                                                    \
-    if ((R_) == 4) { WGT_DISPATCH_FG(T_, 4, F_, G_, CALL) }                                     \
-    else if ((R_) == 6) { WGT_DISPATCH_FG(T_, 6, F_, G_, CALL) }                                \
-    else { WGT_DISPATCH_FG(T_, 7, F_, G_, CALL) }
-#define WGT_DISPATCH(T_, R_, F_, G_, CALL)                                                      \
-    do {                                                                                       \
-        if ((T_) == 4) { WGT_DISPATCH_R(4, R_, F_, G_, CALL) } else { WGT_DISPATCH_R(8, R_, F_, G_, CALL) } \
-    } while (0)
-
-template <int T, int R, bool F, bool G>
-static int wgt_occ(int *per_cu)
-{
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_sweep_wgtile<T, R, F, G>, WGT_WAVES * 64, 0));
-    return DEFF_OK;
-}
-
-static int wgt_resident_blocks(const deff_ctx *c, int T, int R, bool fma, bool guard, int *resident)
-{
-    int per_cu = 0, cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-#define OCC_CALL(T_, R_, C_, G_) TRY((wgt_occ<T_, R_, C_, G_>(&per_cu)))
-    WGT_DISPATCH(T, R, fma, guard, OCC_CALL);
-#undef OCC_CALL
-    if (per_cu < 1) per_cu = 1;
-    *resident = per_cu * cus;
-    return DEFF_OK;
-}
-
-// tall resident tiles (kernels_wgtile.hpp: 16 waves, matrix rows looked up in every sweep): T = 8, R in WGL_ROWS
-#define WGL_DISPATCH(R_, F_, G_, CALL)                                                          \
-    do {                                                                                       \
-        if ((R_) == 4) { WGT_DISPATCH_FG(8, 4, F_, G_, CALL) }                                  \
-        else if ((R_) == 5) { WGT_DISPATCH_FG(8, 5, F_, G_, CALL) }                             \
-        else if ((R_) == 6) { WGT_DISPATCH_FG(8, 6, F_, G_, CALL) }                             \
-        else if ((R_) == 7) { WGT_DISPATCH_FG(8, 7, F_, G_, CALL) }                             \
-        else if ((R_) == 8) { WGT_DISPATCH_FG(8, 8, F_, G_, CALL) }                             \
-        else if ((R_) == 9) { WGT_DISPATCH_FG(8, 9, F_, G_, CALL) }                             \
-        else if ((R_) == 10) { WGT_DISPATCH_FG(8, 10, F_, G_, CALL) }                           \
-        else if ((R_) == 11) { WGT_DISPATCH_FG(8, 11, F_, G_, CALL) }                           \
-        else if ((R_) == 12) { WGT_DISPATCH_FG(8, 12, F_, G_, CALL) }                           \
-        else if ((R_) == 13) { WGT_DISPATCH_FG(8, 13, F_, G_, CALL) }                           \
-        else { WGT_DISPATCH_FG(8, 14, F_, G_, CALL) }                                           \
-    } while (0)
-// (R = 16 -- 256-row tiles, images up to ~2600^2 -- spills inside the sweep loop: 9.9 us per sweep, slower than streaming)
-static const int WGL_ROWS[] = {4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14};
 // Row tiles a tall-tile image of own_h rows needs at R rows per wave.  A tall tile carries no halo rows beyond a wall of
 // the mesh (its rows start at the image's first row, kernels_wgtile.hpp), so ONE tile holds 16R rows, two tiles 16R - T
 // each, three or more 16R - 2T (the inner ones).  A 128^2 image of a stack is one tile of 16 x 8 rows: nothing recomputed,
@@ -113,102 +174,6 @@ static int wgl_row_tiles(int own_h, int R, int T)
     if (own_h <= 2 * (rows - T)) return 2;
     const int lymax = rows - 2 * T;
     return (own_h + lymax - 1) / lymax;
-}
-static bool wgl_has_R(int R) { for (int r : WGL_ROWS) if (r == R) return true; return false; }
-
-template <int T, int R, bool F, bool G>
-static int wgl_occ(int *per_cu)
-{
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_sweep_wgres<T, R, F, G, true>, WGL_WAVES * 64, 0));
-    return DEFF_OK;
-}
-
-static int wgl_resident_blocks(const deff_ctx *c, int R, bool fma, bool guard, int *resident)
-{
-    // asked for every candidate R by every plan: remembered per (device, R, arithmetic, guard)
-    static std::mutex mu;
-    static int cache[64][16][4];
-    const int d = c->device, key = (fma ? 2 : 0) + (guard ? 1 : 0);
-    if (d >= 0 && d < 64 && R >= 0 && R < 16) {
-        std::lock_guard<std::mutex> lock(mu);
-        if (cache[d][R][key] > 0) { *resident = cache[d][R][key]; return DEFF_OK; }
-    }
-    int per_cu = 0, cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-#define OCC_CALL(T_, R_, C_, G_) TRY((wgl_occ<T_, R_, C_, G_>(&per_cu)))
-    WGL_DISPATCH(R, fma, guard, OCC_CALL);
-#undef OCC_CALL
-    *resident = per_cu * cus;
-    if (d >= 0 && d < 64 && R >= 0 && R < 16 && *resident > 0) {
-        std::lock_guard<std::mutex> lock(mu);
-        cache[d][R][key] = *resident;
-    }
-    return DEFF_OK;
-}
-
-// link-symmetric 12-wave tiles (kernels_wgtile.hpp, k_sweep_wgsym): T = 8, 6 or 4, R in WGS_ROWS
-#define WGS_DISPATCH_T(T_, R_, F_, CALL)                                                        \
-    do {                                                                                       \
-        if ((R_) == 4) { if (F_) { CALL(T_, 4, true); } else { CALL(T_, 4, false); } }          \
-        else { if (F_) { CALL(T_, 5, true); } else { CALL(T_, 5, false); } }                    \
-    } while (0)
-#define WGS_DISPATCH(T_, R_, F_, CALL)                                                          \
-    do {                                                                                       \
-        if ((T_) == 6) WGS_DISPATCH_T(6, R_, F_, CALL);                                        \
-        else if ((T_) == 4) WGS_DISPATCH_T(4, R_, F_, CALL);                                   \
-        else WGS_DISPATCH_T(8, R_, F_, CALL);                                                  \
-    } while (0)
-// (R = 6 -- 72-row tiles, images up to ~1230^2 -- needs 168 VGPRs + ~100 B of scratch, which lands in the halo exchange: 1152^2
-// 652 G against 704 G on tall tiles: not instantiated;
-// R = 3 -- 36-row tiles -- is no faster than 8 waves x 4 rows, see plan_blocked_pass)
-static const int WGS_ROWS[] = {4, 5};
-static bool wgs_has_R(int R) { for (int r : WGS_ROWS) if (r == R) return true; return false; }
-
-template <int T, int R, bool F>
-static int wgs_occ(int *per_cu)
-{
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_sweep_wgsym<T, R, F>, WGS_WAVES * 64, 0));
-    return DEFF_OK;
-}
-
-static int wgs_resident_blocks(const deff_ctx *c, int T, int R, bool fma, int *resident)
-{
-    static std::mutex mu;
-    static int cache[64][8][2][3];
-    const int d = c->device, t6 = T == 6 ? 1 : T == 4 ? 2 : 0;
-    if (d >= 0 && d < 64 && R >= 0 && R < 8) {
-        std::lock_guard<std::mutex> lock(mu);
-        if (cache[d][R][fma][t6] > 0) { *resident = cache[d][R][fma][t6]; return DEFF_OK; }
-    }
-    int per_cu = 0, cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-#define OCC_CALL(T_, R_, C_) TRY((wgs_occ<T_, R_, C_>(&per_cu)))
-    WGS_DISPATCH(T, R, fma, OCC_CALL);
-#undef OCC_CALL
-    *resident = per_cu * cus;
-    if (d >= 0 && d < 64 && R >= 0 && R < 8 && *resident > 0) {
-        std::lock_guard<std::mutex> lock(mu);
-        cache[d][R][fma][t6] = *resident;
-    }
-    return DEFF_OK;
-}
-
-template <int T, int R, bool F, bool G>
-static int wgr_occ(int *per_cu)
-{
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_sweep_wgres<T, R, F, G>, WGT_WAVES * 64, 0));
-    return DEFF_OK;
-}
-
-static int wgr_resident_blocks(const deff_ctx *c, int T, int R, bool fma, bool guard, int *resident)
-{
-    int per_cu = 0, cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-#define OCC_CALL(T_, R_, C_, G_) TRY((wgr_occ<T_, R_, C_, G_>(&per_cu)))
-    WGT_DISPATCH(T, R, fma, guard, OCC_CALL);
-#undef OCC_CALL
-    *resident = per_cu * cus;
-    return DEFF_OK;
 }
 
 // Resident launches of this process, chained per device: a resident kernel must have all its workgroups on the chip to
@@ -256,9 +221,8 @@ static hipError_t resident_chain_end(const deff_ctx *c)
     return hipEventRecord(g_res_ev[d], c->stream);
 }
 
-template <class Kernel>
-static hipError_t launch_resident(deff_ctx *c, const SweepPlan &pl, Kernel kernel, int threads, double *xa, double *xb, int npass,
-                                  unsigned base)
+// One resident launch of the plan's tile kernel (all of them take this argument list)
+static hipError_t launch_resident(deff_ctx *c, const SweepPlan &pl, double *xa, double *xb, int npass, unsigned base)
 {
     unsigned long long *stamps = c->tb_stamps;
     unsigned xbytes = (unsigned)(c->n * sizeof(double));
@@ -275,45 +239,12 @@ static hipError_t launch_resident(deff_ctx *c, const SweepPlan &pl, Kernel kerne
     std::lock_guard<std::mutex> lock(g_res_mu);
     hipError_t e = resident_chain_begin(c);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(pl.tblocks), dim3(threads), 0, c->stream, lut, code, xa,
+    hipLaunchKernelGGL(pl.tile->kernel, dim3(pl.tblocks), dim3(pl.tile->threads()), 0, c->stream, lut, code, xa,
                        xb, nx, ny, img_stride, dom_lo, own_lo, own_h, cpi, ly, mask, ntx, gy, xmajor, allb, nrows, shift,
                        omw, npass, flags, base, abort_flag, xbytes, stall_tile, stamps);
     e = hipPeekAtLastError();
     if (e != hipSuccess) return e;
     return resident_chain_end(c);
-}
-
-template <int T, int R, bool F, bool G, bool TALL = false, bool SYM = false>
-static hipError_t launch_wgres(deff_ctx *c, const SweepPlan &pl, double *xa, double *xb, int npass, unsigned base)
-{
-    return launch_resident(c, pl, k_sweep_wgres<T, R, F, G, TALL, SYM>, (TALL ? WGL_WAVES : WGT_WAVES) * 64, xa, xb, npass, base);
-}
-
-template <int RA, int RB, int RC, int RD, bool F, bool G, bool SYM>
-static hipError_t launch_wgage(deff_ctx *c, const SweepPlan &pl, double *xa, double *xb, int npass, unsigned base)
-{
-    return launch_resident(c, pl, k_sweep_wgage<8, RA, RB, RC, RD, F, G, SYM>, WGL_WAVES * 64, xa, xb, npass, base);
-}
-
-// Rows by age for the tall tiles of R rows per wave (k_sweep_wgage): the 4R rows of a SIMD's four waves, oldest first.  Measured,
-// not derived (profiles/r04_tall_rows_by_age_kbench.log: four candidate sets per R, one process, against equal rows): what wins
-// gives the youngest wave about half its share and keeps the three older ones level; bodies of 9 and more rows spill, which is why
-// R = 7 stops at 8 rows, R = 9 deals one row only, and R = 13 found no set that beats equal rows -- four equal bodies in this kernel
-// run 3-4 % behind the one-body kernel, which is what every set has to earn first (14 x 4 has nothing to deal).  Unguarded systems,
-// link-symmetric (7 lookups per row) or not (10: the 3-phase assembly with impermeable solid), both arithmetics.
-#define WGAGE_SETS(X) X(5, 6, 6, 5, 3) X(6, 8, 8, 5, 3) X(7, 8, 8, 8, 4) X(8, 9, 9, 9, 5) X(9, 10, 9, 9, 8) X(10, 12, 12, 10, 6) X(11, 13, 13, 11, 7) X(12, 13, 13, 13, 9)
-static bool wgage_has(int R)
-{
-#define X(R_, A_, B_, C_, D_) if (R == R_) return true;
-    WGAGE_SETS(X)
-#undef X
-    return false;
-}
-
-template <int T, int R, bool F>
-static hipError_t launch_wgsym(deff_ctx *c, const SweepPlan &pl, double *xa, double *xb, int npass, unsigned base)
-{
-    return launch_resident(c, pl, k_sweep_wgsym<T, R, F>, WGS_WAVES * 64, xa, xb, npass, base);
 }
 
 // Did a resident launch give up?  Reads the flag (one 4-byte copy + a stream synchronisation) only when such a launch was
@@ -542,7 +473,28 @@ static bool resident_allowed(const deff_ctx *c, const SweepPlan *pl)
     return c->tb_resident && !c->slab && pl->band_h <= 0 && !pl->T_override && c->n * sizeof(double) < ((size_t)1 << 31);
 }
 
-// Tall resident tiles (16 waves x R rows, kernels_wgtile.hpp): the smallest R in WGL_ROWS whose tiles all fit the chip -- or
+// The kernel of a tall tile of R rows per wave: rows dealt by age where TILES has a set for R and the system is unguarded
+// (tuning "tb_tall_deal"), the 7-lookup short-cut when `sym` (the system is verified link-symmetric) and unguarded.
+static const TileKernel *tall_tile(const deff_ctx *c, int R, bool fma, bool sym)
+{
+    const bool guard = c->lut_guard;
+    const TileKernel *t = nullptr;
+    if (c->tb_tall_deal && !guard)
+        t = find_tile([&](const TileKernel &e) { return e.NW == WGL_WAVES && e.R == R && e.fma == fma && e.sym == sym && e.aged(); });
+    if (!t)
+        t = find_tile([&](const TileKernel &e) {
+            return e.NW == WGL_WAVES && e.R == R && e.fma == fma && e.guard == guard && e.sym == (sym && !guard) && !e.aged();
+        });
+    return t;
+}
+
+static int set_tall_tile(const deff_ctx *c, SweepPlan *pl, int R, bool sym)
+{
+    pl->tile = tall_tile(c, R, pl->fma, sym);
+    return pl->tile ? DEFF_OK : fail(DEFF_ESTATE, "internal: no tall-tile kernel of %d rows per wave", R);
+}
+
+// Tall resident tiles (16 waves x R rows, kernels_wgtile.hpp): the smallest R of TILES whose tiles all fit the chip -- or
 // whose tiles are whole images, which wait for nobody and may queue for the CUs in any number --, or 0.  T = 8 only; not when
 // the caller shapes the 8-wave tiles (tb_R, tb_LY) or insists on them (tb_NW = 8).
 static int choose_tall_R(const deff_ctx *c, const SweepPlan *pl, int T, int own_h, int *tall_R)
@@ -550,14 +502,19 @@ static int choose_tall_R(const deff_ctx *c, const SweepPlan *pl, int T, int own_
     *tall_R = 0;
     if (T != 8 || !resident_allowed(c, pl) || c->tb_NW == WGT_WAVES || c->tb_NW == WGS_WAVES) return DEFF_OK;
     if (c->tb_NW != WGL_WAVES && (c->tb_R != 0 || c->tb_LY != 0)) return DEFF_OK;
-    for (int R : WGL_ROWS) {
-        if (c->tb_NW == WGL_WAVES && wgl_has_R(c->tb_R) && R != c->tb_R) continue;
-        const int row_tiles = wgl_row_tiles(own_h, R, T);
+    const bool caller_R = c->tb_NW == WGL_WAVES && tall_tile(c, c->tb_R, pl->fma, false);
+    for (const TileKernel &t : TILES) {
+        if (t.NW != WGL_WAVES || t.aged() || t.sym || t.fma != pl->fma || t.guard != c->lut_guard) continue;   // each R once
+        if (caller_R && t.R != c->tb_R) continue;
+        const int row_tiles = wgl_row_tiles(own_h, t.R, T);
         const long tiles = (long)pl->ntx * row_tiles * c->nimg;
+        // the occupancy of the kernel plan_tall launches (whether the system is link-symmetric is only known there: the
+        // short-cut kernels have the same, tests/test_kernel_resources.py)
+        const TileKernel *k = tall_tile(c, t.R, pl->fma, false);
         int res = 0;
-        TRY(wgl_resident_blocks(c, R, pl->fma, c->lut_guard, &res));
+        TRY(resident_blocks(c, k->kernel, k->threads(), &res));
         const bool whole_images = pl->ntx == 1 && row_tiles == 1;
-        if (((tiles + 7) / 8) * 8 <= res || whole_images) { *tall_R = R; break; }
+        if (((tiles + 7) / 8) * 8 <= res || whole_images) { *tall_R = t.R; break; }
     }
     return DEFF_OK;
 }
@@ -566,33 +523,40 @@ static int choose_tall_R(const deff_ctx *c, const SweepPlan *pl, int T, int own_
 static int plan_tiles8(deff_ctx *c, SweepPlan *pl, int T, int own_h)
 {
     pl->impl = 2;
-    pl->NW = WGT_WAVES;
-    pl->guard = c->lut_guard;
+    auto tile8 = [&](const TileKernel &t) { return t.NW == WGT_WAVES && t.T == T && t.fma == pl->fma && t.guard == c->lut_guard; };
     int resident = c->tb_wg;
-    if (c->tb_R == 4 || c->tb_R == 6 || c->tb_R == 7) {
-        pl->R = c->tb_R;
-    } else {
+    const TileKernel *tile = find_tile([&](const TileKernel &t) { return tile8(t) && t.R == c->tb_R; });
+    if (!tile) {
         // rows per wave: the fewest (shortest sweeps) whose tiles are all resident at once; if none is, 6
         // (7 needs 256 VGPRs and a few spilled registers: fine for one round, slower over several)
-        pl->R = 6;
-        for (int R : {4, 6, 7}) {
-            const int lymax = wgt_rows_owned(T, R);
+        tile = find_tile([&](const TileKernel &t) { return tile8(t) && t.R == 6; });
+        for (const TileKernel &t : TILES) {
+            if (!tile8(t)) continue;
+            const int lymax = wgt_rows_owned(T, t.R);
             if (lymax < 1) continue;
             int res = resident;
-            if (!res) TRY(wgt_resident_blocks(c, T, R, pl->fma, c->lut_guard, &res));
+            if (!res) {
+                TRY(resident_blocks(c, t.pass, t.threads(), &res));
+                if (res < 1) TRY(cu_count(c, &res));               // at least one workgroup per CU
+            }
             const long tiles = (long)pl->ntx * ((own_h + lymax - 1) / lymax) * c->nimg;
-            if (tiles <= res) { pl->R = R; break; }
+            if (tiles <= res) { tile = &t; break; }
         }
     }
+    if (!tile) return fail(DEFF_ESTATE, "internal: no 8-wave tile kernel for T = %d", T);
+    pl->tile = tile;
     // rows a tile owns: at most 8R - 2T; spread the image's rows evenly over its row tiles
-    const int lymax = wgt_rows_owned(T, pl->R);
+    const int lymax = wgt_rows_owned(T, tile->R);
     int cpi = (own_h + lymax - 1) / lymax;
     if (c->tb_LY > 0 && c->tb_LY < lymax) cpi = (own_h + c->tb_LY - 1) / c->tb_LY;
     pl->LY = (own_h + cpi - 1) / cpi;
     pl->tcpi = (own_h + pl->LY - 1) / pl->LY;
     pl->tgy = pl->tcpi * c->nimg;
     const long tiles = (long)pl->ntx * pl->tgy;
-    if (!resident) TRY(wgt_resident_blocks(c, T, pl->R, pl->fma, c->lut_guard, &resident));
+    if (!resident) {
+        TRY(resident_blocks(c, tile->pass, tile->threads(), &resident));
+        if (resident < 1) TRY(cu_count(c, &resident));
+    }
     pl->tgx = (int)tiles;
     pl->tblocks = (int)(((tiles + 7) / 8) * 8);
     if (pl->tblocks > resident) pl->tblocks = resident >= 8 ? resident / 8 * 8 : 8;
@@ -601,7 +565,7 @@ static int plan_tiles8(deff_ctx *c, SweepPlan *pl, int T, int own_h)
     pl->resident = false;
     if (resident_allowed(c, pl) && (pl->LY >= T || pl->tcpi == 1)) {
         int res = 0;
-        TRY(wgr_resident_blocks(c, T, pl->R, pl->fma, c->lut_guard, &res));
+        TRY(resident_blocks(c, tile->kernel, tile->threads(), &res));
         if ((long)((tiles + 7) / 8) * 8 <= res) {
             pl->resident = true;
             pl->tblocks = (int)(((tiles + 7) / 8) * 8);
@@ -615,9 +579,6 @@ static int plan_tiles8(deff_ctx *c, SweepPlan *pl, int T, int own_h)
 static int plan_tall(deff_ctx *c, SweepPlan *pl, int T, int own_h, int R)
 {
     pl->impl = 2;
-    pl->NW = WGL_WAVES;
-    pl->R = R;
-    pl->guard = c->lut_guard;
     const int cpi = wgl_row_tiles(own_h, R, T);
     pl->LY = (own_h + cpi - 1) / cpi;
     pl->tcpi = (own_h + pl->LY - 1) / pl->LY;
@@ -628,68 +589,52 @@ static int plan_tall(deff_ctx *c, SweepPlan *pl, int T, int own_h, int R)
     pl->resident = true;
     TRY(ensure_resident_buffers(c, tiles));
     if (c->tb_sym != 2) TRY(check_links_symmetric(c));            // once per (codes, dictionary): one pass over the codes
-    pl->sym = c->tb_sym != 2 && c->links_sym == 1;
-    pl->aged = c->tb_tall_deal && wgage_has(R) && !pl->guard;     // rows dealt by age: k_sweep_wgage (unguarded systems, symmetric or not)
-    return DEFF_OK;
+    return set_tall_tile(c, pl, R, c->tb_sym != 2 && c->links_sym == 1);
 }
 
 // Link-symmetric 12-wave tiles (k_sweep_wgsym): matrix rows in registers at 3 waves per SIMD.  A tile of 12 x R rows has the
 // shape of an 8-wave tile of 1.5 R rows and sweeps it faster (three waves of a SIMD issue FP64 every ~5 clocks, two every ~6),
-// so wherever the system is verified link-symmetric and unguarded this form replaces the 8-wave tiles: the fewest rows per
-// wave whose tiles all fit the chip.  *R = 0: not applicable (not symmetric, guarded, too many tiles, caller insists on
-// another form).  T = 8, resident launches only.
-// Shapes of a 12-wave tile: the rows of the waves of age 0 / 1 / 2 (wave >> 2: a SIMD serves its three waves oldest first, and
-// a tile's waves meet at a barrier in every sweep -- see k_sweep_wgage).  Equal rows (k_sweep_wgsym<T, R>) for every T; for T = 8
-// also the shapes that give the younger waves a row less (k_sweep_wgsage): 5 / 5 / 4 is a 56-row tile that sweeps ~9 % faster
-// than 5 / 5 / 5 and owns 40 rows instead of 44 -- one 1024^2 image: 234 tiles instead of 216, 853 -> 901 G; 4 / 4 / 3 and 5 / 4 / 4
-// likewise (704^2 ... 992^2: +6 ... 11 %, profiles/r04_sym_shapes_kbench.log).  The planner takes the
-// first shape of this list (fewest rows first) whose tiles all fit the chip.  Encoded for the callers as R | a << 8 | b << 16 |
-// c << 24 (R = the most rows a wave holds; a = 0: equal rows).
-struct SymShape { int a, b, c; bool aged; };
-static const SymShape SYM_SHAPES_T8[] = {{4, 4, 3, true}, {4, 4, 4, false}, {5, 4, 4, true}, {5, 5, 4, true}, {5, 5, 5, false}};
-static const SymShape SYM_SHAPES[] = {{4, 4, 4, false}, {5, 5, 5, false}};
-static int sym_shape_rows(int enc) { return (enc >> 8) ? 4 * (((enc >> 8) & 0xFF) + ((enc >> 16) & 0xFF) + ((enc >> 24) & 0xFF)) : WGS_WAVES * (enc & 0xFF); }
-
-static int choose_sym_R(deff_ctx *c, const SweepPlan *pl, int T, int own_h, int *sym_R)
+// so wherever the system is verified link-symmetric and unguarded this form replaces the 8-wave tiles: the first shape of TILES
+// for this T (fewest rows first) whose tiles all fit the chip.  *sym = null: not applicable (not symmetric, guarded, too many
+// tiles, caller insists on another form).  T = 8, resident launches only.
+// The shapes with a row less for the younger waves (k_sweep_wgsage: a SIMD serves its three waves oldest first, and a tile's
+// waves meet at a barrier in every sweep -- see k_sweep_wgage) are candidates for T = 8 unless tb_sym_age = 0.
+static int choose_sym_tile(deff_ctx *c, const SweepPlan *pl, int T, int own_h, const TileKernel **sym)
 {
-    *sym_R = 0;
+    *sym = nullptr;
     if ((T != 8 && T != 6 && T != 4) || !resident_allowed(c, pl) || c->lut_guard || c->tb_sym == 2) return DEFF_OK;
     if (c->tb_NW != 0 && c->tb_NW != WGS_WAVES) return DEFF_OK;
     if (T != 8 && c->tb_T && c->tb_NW != WGS_WAVES) return DEFF_OK;  // a caller's T = 4 / 6 means these tiles only together with tb_NW = 12
     if (c->tb_NW != WGS_WAVES && (c->tb_R != 0 || c->tb_LY != 0)) return DEFF_OK;
-    int found = 0;
     const bool t8 = T == 8 && c->tb_sym_age;
-    const SymShape *shapes = t8 ? SYM_SHAPES_T8 : SYM_SHAPES;
-    const int nshapes = t8 ? (int)(sizeof SYM_SHAPES_T8 / sizeof SYM_SHAPES_T8[0]) : (int)(sizeof SYM_SHAPES / sizeof SYM_SHAPES[0]);
-    for (int k = 0; k < nshapes; ++k) {
-        const SymShape &sh = shapes[k];
-        const int R = sh.a;
-        if (c->tb_NW == WGS_WAVES && wgs_has_R(c->tb_R) && (R != c->tb_R || sh.aged)) continue;   // a caller's R: equal rows of that many
-        if (t8 && c->tb_sym_shape && k + 1 != c->tb_sym_shape) continue;                          // tests: this shape of SYM_SHAPES_T8 or none
-        const int enc = sh.aged ? (R | sh.a << 8 | sh.b << 16 | sh.c << 24) : R;
-        const int lymax = sym_shape_rows(enc) - 2 * T;
+    const bool caller_R = c->tb_NW == WGS_WAVES && find_tile([&](const TileKernel &t) { return t.NW == WGS_WAVES && t.R == c->tb_R && !t.aged(); });
+    const TileKernel *found = nullptr;
+    int k = 0;
+    for (const TileKernel &t : TILES) {
+        if (t.NW != WGS_WAVES || t.T != T || t.fma != pl->fma || (t.aged() && !t8)) continue;
+        ++k;
+        if (caller_R && (t.R != c->tb_R || t.aged())) continue;          // a caller's R: equal rows of that many
+        if (t8 && c->tb_sym_shape && k != c->tb_sym_shape) continue;     // tests: this shape of T = 8's list or none
+        const int lymax = t.tile_rows() - 2 * T;
         const int cpi = (own_h + lymax - 1) / lymax;
         const int LY = (own_h + cpi - 1) / cpi;
         if (LY < T && cpi > 1) continue;                            // a tile's halo must end inside its immediate neighbours
         const long tiles = (long)pl->ntx * cpi * c->nimg;
         int res = 0;
-        TRY(wgs_resident_blocks(c, T, R, pl->fma, &res));
-        if (((tiles + 7) / 8) * 8 <= res) { found = enc; break; }
+        TRY(resident_blocks(c, t.kernel, t.threads(), &res));
+        if (((tiles + 7) / 8) * 8 <= res) { found = &t; break; }
     }
     if (!found) return DEFF_OK;
     TRY(check_links_symmetric(c));                                  // once per (codes, dictionary): one pass over the codes
-    if (c->links_sym == 1) *sym_R = found;
+    if (c->links_sym == 1) *sym = found;
     return DEFF_OK;
 }
 
-static int plan_sym(deff_ctx *c, SweepPlan *pl, int T, int own_h, int enc)
+static int plan_sym(deff_ctx *c, SweepPlan *pl, int T, int own_h, const TileKernel *tile)
 {
     pl->impl = 2;
-    pl->NW = WGS_WAVES;
-    pl->R = enc & 0xFF;
-    pl->rows3 = enc >> 8;
-    pl->guard = false;
-    const int lymax = sym_shape_rows(enc) - 2 * T;
+    pl->tile = tile;
+    const int lymax = tile->tile_rows() - 2 * T;
     const int cpi = (own_h + lymax - 1) / lymax;
     pl->LY = (own_h + cpi - 1) / cpi;
     pl->tcpi = (own_h + pl->LY - 1) / pl->LY;
@@ -698,7 +643,6 @@ static int plan_sym(deff_ctx *c, SweepPlan *pl, int T, int own_h, int enc)
     pl->tgx = (int)tiles;
     pl->tblocks = (int)(((tiles + 7) / 8) * 8);
     pl->resident = true;
-    pl->sym = true;
     TRY(ensure_resident_buffers(c, tiles));
     return DEFF_OK;
 }
@@ -877,7 +821,8 @@ static int plan_streaming(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int own
     pl->guard = c->lut_guard;                          // the reference's non-zero link test matters only when a phase cannot diffuse
     int resident = c->tb_wg;
     if (!resident) {
-        TRY(tb_resident_blocks(c, T, pl->fma, c->lut_guard, &resident));
+        TRY(resident_blocks(c, STREAMING[tb_index(T)][2 * pl->fma + pl->guard], 256, &resident));
+        if (resident < 1) TRY(cu_count(c, &resident));                // at least one workgroup per CU
     }
     pl->dealt = nullptr;
     // (T = 8 only: the ranks' speeds were measured there; with them T = 6 gains 3 % at 4096^2 and loses 4 % at 8192^2)
@@ -920,11 +865,11 @@ static void record_plan(deff_ctx *c, const SweepPlan *pl)
     if (pl->band_h > 0 || (pl->impl != 2 && pl->T_override)) return;
     c->plan_T = pl->T; c->plan_LY = pl->LY; c->plan_ntx = pl->ntx; c->plan_cpi = pl->tcpi;
     c->plan_blocks = pl->tblocks; c->plan_impl = pl->impl;
-    c->plan_R = pl->impl == 2 ? pl->R : 0;
-    c->plan_NW = pl->impl == 2 ? pl->NW : 0;
+    c->plan_R = pl->impl == 2 ? pl->tile->R : 0;
+    c->plan_NW = pl->impl == 2 ? pl->tile->NW : 0;
     c->plan_resident = pl->impl == 2 && pl->resident ? 1 : 0;
     c->plan_ranked = pl->impl == 1 && pl->dealt ? 1 : 0;
-    c->plan_aged = pl->impl == 2 && ((pl->NW == WGL_WAVES && pl->aged) || (pl->NW == WGS_WAVES && pl->rows3)) ? 1 : 0;
+    c->plan_aged = pl->impl == 2 && pl->tile->aged() ? 1 : 0;
 }
 
 // The form of a blocked pass, in this order ("What the planner picks"): 8-wave tiles when they are all
@@ -942,7 +887,8 @@ static int plan_blocked_pass(deff_ctx *c, SweepPlan *pl)
     pl->own_lo = own_lo;
     pl->own_h = own_h;
     plan_strips(c, T, pl);
-    int tall_R = 0, sym_R = 0;
+    int tall_R = 0;
+    const TileKernel *sym = nullptr;
     TRY(choose_tall_R(c, pl, T, own_h, &tall_R));
     int want_impl = c->tb_impl ? c->tb_impl : default_tb_impl(c);
     // a context just above the 4 Mi cells where the streaming form takes over still runs faster on tall tiles when they fit
@@ -953,12 +899,12 @@ static int plan_blocked_pass(deff_ctx *c, SweepPlan *pl)
         const bool sym_only = c->tb_NW == WGS_WAVES && (T == 6 || T == 4) && c->tb_T;   // the caller asked for 12-wave tiles at this T
         // images that are ONE tall tile each (a stack of 128^2 images) recompute nothing and wait for nobody: nothing beats that
         const bool tall_whole = tall_R && pl->ntx == 1 && wgl_row_tiles(own_h, tall_R, T) == 1;
-        if (!tall_whole) TRY(choose_sym_R(c, pl, T, own_h, &sym_R));
+        if (!tall_whole) TRY(choose_sym_tile(c, pl, T, own_h, &sym));
         bool planned = false;
         if (tall_whole && c->tb_NW != WGT_WAVES) {
             TRY(plan_tall(c, pl, T, own_h, tall_R));
             planned = true;
-        } else if (sym_R) {
+        } else if (sym) {
             // Both coefficient-resident forms may fit the chip: a sweep costs a SIMD its share of the tile's rows times the
             // clocks a row takes at that occupancy -- measured (tools/wgr_stamps.py) ~160 at two waves per SIMD, ~142 at
             // three.  512^2 / 640^2 stay on 8 waves x 4 rows (303-476 G against 310-481 G on 12 x 3, which is therefore
@@ -967,9 +913,9 @@ static int plan_blocked_pass(deff_ctx *c, SweepPlan *pl)
             if (c->tb_NW != WGS_WAVES) {
                 SweepPlan alt = *pl;
                 TRY(plan_tiles8(c, &alt, T, own_h));
-                if (alt.resident && 2 * alt.R * 160 <= 3 * (sym_R & 0xFF) * 142) { *pl = alt; take_sym = false; }
+                if (alt.resident && 2 * alt.tile->R * 160 <= 3 * sym->R * 142) { *pl = alt; take_sym = false; }
             }
-            if (take_sym) TRY(plan_sym(c, pl, T, own_h, sym_R));
+            if (take_sym) TRY(plan_sym(c, pl, T, own_h, sym));
             planned = true;
         }
         if (!planned && sym_only) return fail(DEFF_EINVAL, "tb_T = %d on 12-wave tiles: the tiles are not co-resident or the system is not link-symmetric", T);
@@ -988,9 +934,9 @@ static int plan_blocked_pass(deff_ctx *c, SweepPlan *pl)
                     SweepPlan alt = *pl;
                     alt.T = Ts;
                     plan_strips(c, Ts, &alt);
-                    int rs = 0;
-                    TRY(choose_sym_R(c, &alt, Ts, own_h, &rs));
-                    if (Ts == 4 && rs && (rs & 0xFF) < 5 && tall_R && tall_R <= 4) rs = 0;      // (4 x 4 rows per sweep: no better than tall R = 4)
+                    const TileKernel *rs = nullptr;
+                    TRY(choose_sym_tile(c, &alt, Ts, own_h, &rs));
+                    if (Ts == 4 && rs && rs->R < 5 && tall_R && tall_R <= 4) rs = nullptr;      // (4 x 4 rows per sweep: no better than tall R = 4)
                     if (rs) { TRY(plan_sym(c, &alt, Ts, own_h, rs)); *pl = alt; shorter = true; break; }
                 }
             }
@@ -1038,6 +984,20 @@ int plan_sweeps(deff_ctx *c, double omega, SweepPlan *pl)
     return DEFF_OK;
 }
 
+// Single sweeps (kernels_sweep.hpp), [2 nt + fma] and, by rows per tile 1, 2, 4, 8, [rows_index(rows)][...]
+static constexpr auto SCALAR_SWEEPS = by_flags([](auto nt, auto f) { return k_sweep_scalar<decltype(nt)::value, decltype(f)::value>; });
+template <int... R> static constexpr auto explicit_sweeps()
+{
+    return std::array{by_flags([](auto nt, auto f) { return k_sweep_explicit<R, decltype(nt)::value, decltype(f)::value>; })...};
+}
+template <int... R> static constexpr auto matfree_sweeps()
+{
+    return std::array{by_flag([](auto f) { return k_sweep_matfree<2, R, decltype(f)::value>; })...};
+}
+static constexpr auto EXPLICIT_SWEEPS = explicit_sweeps<1, 2, 4, 8>();
+static constexpr auto MATFREE_SWEEPS = matfree_sweeps<1, 2, 4, 8>();
+static int rows_index(int rows) { return rows == 1 ? 0 : rows == 2 ? 1 : rows == 4 ? 2 : 3; }
+
 // Enqueue one sweep x[cur] -> x[cur^1] and flip (the reference copies instead, cuh:1281).
 void enqueue_sweep(deff_ctx *c, const SweepPlan &pl)
 {
@@ -1046,52 +1006,20 @@ void enqueue_sweep(deff_ctx *c, const SweepPlan &pl)
     const CoefConst cf{c->c0, c->aW, c->aE, c->aS, c->aN, c->b};
     const int flip = c->serpentine ? c->cur : 0;
     const uint8_t *mask = c->masked ? c->active : nullptr;
+    const int nt = c->nt_explicit ? 2 : 0;
     switch (pl.kernel) {
-    case DEFF_KERNEL_SCALAR: {
-#define LAUNCH_SCALAR(NT_, F_)                                                                              \
-    hipLaunchKernelGGL((k_sweep_scalar<NT_, F_>), dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0,       \
-                       c->stream, cf, xin, xout, c->nx, c->n, c->n_img, mask, pl.omw)
-        if (c->nt_explicit) { if (pl.fma) LAUNCH_SCALAR(true, true); else LAUNCH_SCALAR(true, false); }
-        else { if (pl.fma) LAUNCH_SCALAR(false, true); else LAUNCH_SCALAR(false, false); }
-#undef LAUNCH_SCALAR
+    case DEFF_KERNEL_SCALAR:
+        hipLaunchKernelGGL(SCALAR_SWEEPS[nt + pl.fma], dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, cf, xin, xout,
+                           c->nx, c->n, c->n_img, mask, pl.omw);
         break;
-    }
-    case DEFF_KERNEL_EXPLICIT: {
-#define LAUNCH_EXPLICIT_(R_, NT_, F_)                                                                        \
-    hipLaunchKernelGGL((k_sweep_explicit<R_, NT_, F_>), dim3(pl.blocks), dim3(256), 0, c->stream, cf, xin,   \
-                       xout, c->nx, c->ny, c->rows, pl.cpi, mask, pl.gx, pl.gy, flip, pl.omw)
-#define LAUNCH_EXPLICIT(R_)                                                                                  \
-    do {                                                                                                    \
-        if (c->nt_explicit) { if (pl.fma) LAUNCH_EXPLICIT_(R_, true, true); else LAUNCH_EXPLICIT_(R_, true, false); } \
-        else { if (pl.fma) LAUNCH_EXPLICIT_(R_, false, true); else LAUNCH_EXPLICIT_(R_, false, false); }   \
-    } while (0)
-        switch (pl.rows) {
-        case 1: LAUNCH_EXPLICIT(1); break;
-        case 2: LAUNCH_EXPLICIT(2); break;
-        case 4: LAUNCH_EXPLICIT(4); break;
-        default: LAUNCH_EXPLICIT(8); break;
-        }
-#undef LAUNCH_EXPLICIT
-#undef LAUNCH_EXPLICIT_
+    case DEFF_KERNEL_EXPLICIT:
+        hipLaunchKernelGGL(EXPLICIT_SWEEPS[rows_index(pl.rows)][nt + pl.fma], dim3(pl.blocks), dim3(256), 0, c->stream, cf, xin, xout,
+                           c->nx, c->ny, c->rows, pl.cpi, mask, pl.gx, pl.gy, flip, pl.omw);
         break;
-    }
-    default: {
-#define LAUNCH_MATFREE_(V_, R_, F_)                                                                          \
-    hipLaunchKernelGGL((k_sweep_matfree<V_, R_, F_>), dim3(pl.blocks), dim3(256), 0, c->stream, c->lut,      \
-                       c->code, xin, xout, c->nx, c->ny, c->rows, pl.cpi, mask, pl.gx, pl.gy, flip,          \
-                       c->lut_nrows, pl.omw)
-#define LAUNCH_MATFREE(V_, R_)                                                                               \
-    do { if (pl.fma) LAUNCH_MATFREE_(V_, R_, true); else LAUNCH_MATFREE_(V_, R_, false); } while (0)
-        switch (pl.rows) {
-        case 1: LAUNCH_MATFREE(2, 1); break;
-        case 2: LAUNCH_MATFREE(2, 2); break;
-        case 4: LAUNCH_MATFREE(2, 4); break;
-        default: LAUNCH_MATFREE(2, 8); break;
-        }
-#undef LAUNCH_MATFREE
-#undef LAUNCH_MATFREE_
+    default:
+        hipLaunchKernelGGL(MATFREE_SWEEPS[rows_index(pl.rows)][pl.fma], dim3(pl.blocks), dim3(256), 0, c->stream, c->lut, c->code, xin,
+                           xout, c->nx, c->ny, c->rows, pl.cpi, mask, pl.gx, pl.gy, flip, c->lut_nrows, pl.omw);
         break;
-    }
     }
     c->cur ^= 1;
 }
@@ -1127,27 +1055,19 @@ int launch_tb_pass(deff_ctx *c, const SweepPlan &pl)
     double *xout = c->x[c->cur ^ 1];
     const int flip = c->serpentine ? c->cur : 0;
     const uint8_t *mask = c->masked ? c->active : nullptr;
-    if (pl.impl == 2 && pl.NW != WGT_WAVES)
-        return fail(DEFF_ESTATE, "tiles of %d waves only exist as resident launches (plan again with tb_launch = 1)", pl.NW);
+    const int allb = (c->lut_allb || c->nx != c->nxt) ? 1 : 0;       // padded: the wall column may not be in the last strip
     if (pl.impl == 2) {
-#define LAUNCH_WGT(T_, R_, C_, G_)                                                                             \
-    hipLaunchKernelGGL((k_sweep_wgtile<T_, R_, C_, G_>), dim3(pl.tblocks), dim3(WGT_WAVES * 64), 0, c->stream, c->lut, \
-                       c->code, xin, xout, c->nx, c->mesh_ny, c->ny, c->dom_lo, pl.own_lo, pl.own_h, pl.tcpi, pl.LY, \
-                       mask, pl.ntx, pl.tgy, c->tb_xmajor, (c->lut_allb || c->nx != c->nxt) ? 1 : 0,         \
-                       c->lut_nrows, pl.shift, pl.omw, c->tb_stamps)
-        WGT_DISPATCH(pl.T, pl.R, pl.fma, pl.guard, LAUNCH_WGT);
-#undef LAUNCH_WGT
+        if (!pl.tile->pass)
+            return fail(DEFF_ESTATE, "tiles of %d waves only exist as resident launches (plan again with tb_launch = 1)", pl.tile->NW);
+        hipLaunchKernelGGL(pl.tile->pass, dim3(pl.tblocks), dim3(pl.tile->threads()), 0, c->stream, c->lut, c->code, xin, xout, c->nx,
+                           c->mesh_ny, c->ny, c->dom_lo, pl.own_lo, pl.own_h, pl.tcpi, pl.LY, mask, pl.ntx, pl.tgy, c->tb_xmajor, allb,
+                           c->lut_nrows, pl.shift, pl.omw, c->tb_stamps);
         HIP_TRY(hipPeekAtLastError());
         return DEFF_OK;
     }
-#define LAUNCH_TB(T_, C_, G_)                                                                                  \
-    hipLaunchKernelGGL((k_sweep_matfree_tb<T_, C_, G_>), dim3(pl.tblocks), dim3(256), 0, c->stream, c->lut,    \
-                       c->code, xin, xout, c->nx, c->mesh_ny, c->ny, c->dom_lo, pl.own_lo, pl.own_h, pl.tcpi, \
-                       mask, pl.LY, pl.ntx, pl.tgx, pl.tgy, flip, c->tb_xmajor,                              \
-                       (c->lut_allb || c->nx != c->nxt) ? 1 : 0, /* padded: the wall column may not be in the last strip */ \
-                       c->lut_nrows, pl.shift, pl.omw, c->tb_stamps, pl.dealt)
-    TB_DISPATCH(pl.T, pl.fma, pl.guard, LAUNCH_TB);
-#undef LAUNCH_TB
+    hipLaunchKernelGGL(STREAMING[tb_index(pl.T)][2 * pl.fma + pl.guard], dim3(pl.tblocks), dim3(256), 0, c->stream, c->lut, c->code,
+                       xin, xout, c->nx, c->mesh_ny, c->ny, c->dom_lo, pl.own_lo, pl.own_h, pl.tcpi, mask, pl.LY, pl.ntx, pl.tgx, pl.tgy,
+                       flip, c->tb_xmajor, allb, c->lut_nrows, pl.shift, pl.omw, c->tb_stamps, pl.dealt);
     HIP_TRY(hipPeekAtLastError());
     if (pl.dealt) c->tb_dealt_waves += (int64_t)pl.tblocks * 4;
     return DEFF_OK;
@@ -1178,47 +1098,7 @@ static int launch_resident_passes(deff_ctx *c, const SweepPlan &pl, int64_t *n)
             HIP_TRY(hipMemsetAsync(c->res_flags, 0, sizeof(unsigned) * c->res_flags_n * WGR_FLAG_STRIDE, c->stream));
             c->res_epoch = 0;
         }
-        hipError_t e = hipSuccess;
-        if (pl.NW == WGS_WAVES && pl.rows3) {
-            e = hipErrorInvalidConfiguration;                       // (stays if SYM_SHAPES_T8 names a shape without a kernel)
-#define SAGE(A_, B_, C_)                                                                                                    \
-            if (pl.T == 8 && pl.rows3 == (A_ | B_ << 8 | C_ << 16)) {                                                        \
-                if (pl.fma) e = launch_resident(c, pl, k_sweep_wgsage<8, A_, B_, C_, true>, WGS_WAVES * 64, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch);  \
-                else e = launch_resident(c, pl, k_sweep_wgsage<8, A_, B_, C_, false>, WGS_WAVES * 64, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch);        \
-            }
-            SAGE(4, 4, 3) SAGE(5, 4, 4) SAGE(5, 5, 4)
-#undef SAGE
-        } else if (pl.NW == WGS_WAVES) {
-#define LAUNCH_WGS(T_, R_, C_) e = launch_wgsym<T_, R_, C_>(c, pl, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch)
-            WGS_DISPATCH(pl.T, pl.R, pl.fma, LAUNCH_WGS);
-#undef LAUNCH_WGS
-        } else if (pl.NW == WGL_WAVES && pl.aged) {
-            e = hipErrorInvalidConfiguration;                       // (stays if the table has no set for pl.R: plan_tall asked wgage_has)
-#define X(R_, A_, B_, C_, D_)                                                                                               \
-            if (pl.R == R_) {                                                                                                \
-                if (pl.sym) {                                                                                                \
-                    if (pl.fma) e = launch_wgage<A_, B_, C_, D_, true, false, true>(c, pl, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch);  \
-                    else e = launch_wgage<A_, B_, C_, D_, false, false, true>(c, pl, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch);        \
-                } else {                                                                                                     \
-                    if (pl.fma) e = launch_wgage<A_, B_, C_, D_, true, false, false>(c, pl, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch); \
-                    else e = launch_wgage<A_, B_, C_, D_, false, false, false>(c, pl, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch);       \
-                }                                                                                                            \
-            }
-            WGAGE_SETS(X)
-#undef X
-        } else if (pl.NW == WGL_WAVES) {
-            // (the symmetric short-cut exists in the unguarded kernels only: the guarded one branches on every link anyway)
-#define LAUNCH_WGL(T_, R_, C_, G_) e = launch_wgres<T_, R_, C_, G_, true, false>(c, pl, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch)
-#define LAUNCH_WGLS(T_, R_, C_, G_) e = launch_wgres<T_, R_, C_, false, true, true>(c, pl, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch)
-            if (pl.sym && !pl.guard) { WGL_DISPATCH(pl.R, pl.fma, false, LAUNCH_WGLS); }
-            else { WGL_DISPATCH(pl.R, pl.fma, pl.guard, LAUNCH_WGL); }
-#undef LAUNCH_WGL
-#undef LAUNCH_WGLS
-        } else {
-#define LAUNCH_WGR(T_, R_, C_, G_) e = launch_wgres<T_, R_, C_, G_>(c, pl, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch)
-            WGT_DISPATCH(pl.T, pl.R, pl.fma, pl.guard, LAUNCH_WGR);
-#undef LAUNCH_WGR
-        }
+        const hipError_t e = launch_resident(c, pl, c->x[c->cur], c->x[c->cur ^ 1], chunk, c->res_epoch);
         if (e != hipSuccess) return fail(DEFF_EHIP, "resident launch failed: %s", hipGetErrorString(e));
         c->res_epoch += (unsigned)chunk;
         c->res_pending = true;
@@ -1242,9 +1122,9 @@ int enqueue_sweeps(deff_ctx *c, const SweepPlan &pl, int64_t n)
         return enqueue_sweeps(c, again, n);
     }
     // (while resident launches are in flight unchecked, whatever follows them is part of what a fallback must redo)
-    if (pl.kernel == DEFF_KERNEL_MATFREE_TB && pl.impl == 2 && pl.resident && n >= (pl.NW != WGT_WAVES ? 1 : 2) * pl.T)
+    if (pl.kernel == DEFF_KERNEL_MATFREE_TB && pl.impl == 2 && pl.resident && n >= (pl.tile->pass ? 2 : 1) * pl.T)
         TRY(launch_resident_passes(c, pl, &n));
-    if (pl.kernel == DEFF_KERNEL_MATFREE_TB && !(pl.impl == 2 && pl.NW != WGT_WAVES)) {
+    if (pl.kernel == DEFF_KERNEL_MATFREE_TB && !(pl.impl == 2 && !pl.tile->pass)) {
         while (n >= pl.T) { TRY(enqueue_tb_pass(c, pl)); n -= pl.T; ++c->last_launches; if (c->res_pending) c->res_redo += pl.T; }
     }
     for (; n > 0; --n) { enqueue_sweep(c, pl); ++c->last_launches; if (c->res_pending) ++c->res_redo; }
@@ -1602,10 +1482,10 @@ try {
         }
         TRY(refill());                                 // newcomers start with the sweep that precedes the next check
         // new images, new codes: the symmetric short-cut of the tall tiles is re-verified, not carried over
-        if (pl.impl == 2 && pl.NW == WGL_WAVES && c->tb_sym != 2 && c->links_sym == 0) {
+        if (pl.impl == 2 && pl.tile->NW == WGL_WAVES && c->tb_sym != 2 && c->links_sym == 0) {
             TRY(check_links_symmetric(c));
-            pl.sym = c->links_sym == 1;
-        } else if (pl.impl == 2 && pl.NW == WGS_WAVES && c->links_sym == 0) {
+            TRY(set_tall_tile(c, &pl, pl.tile->R, c->links_sym == 1));
+        } else if (pl.impl == 2 && pl.tile->NW == WGS_WAVES && c->links_sym == 0) {
             TRY(check_links_symmetric(c));
             if (c->links_sym != 1) { pl = SweepPlan(); TRY(plan_sweeps(c, omega, &pl)); }   // (never for the native assembly)
         }

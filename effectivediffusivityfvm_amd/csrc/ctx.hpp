@@ -189,10 +189,10 @@ struct deff_ctx {
     // Streaming kernel, chunk heights by service order (deal_ranked_tiles, api_solve.hip): 0 = equal chunks, 1 = dealt tiles.
     // tb_rank_w: the relative speed (per mille) of a SIMD's oldest / second / youngest wave, tb_rank_wall: what a row of a wall strip
     // costs, per mille of an inner strip's (its waves look up b as well)
-    int tb_tall_deal = 1;                        // tall tiles: rows dealt by the waves' age where a kernel for it exists (api_solve.hip, WGAGE_SETS)
+    int tb_tall_deal = 1;                        // tall tiles: rows dealt by the waves' age where a kernel for it exists (api_solve.hip, TILES)
     int plan_aged = 0;
-    int tb_sym_age = 1;                          // 12-wave tiles: the shapes with a row less for the youngest waves (api_solve.hip, SYM_SHAPES_T8)
-    int tb_sym_shape = 0;                        // tests: 1-based index into SYM_SHAPES_T8 (0: the planner's choice)
+    int tb_sym_age = 1;                          // 12-wave tiles: the shapes with a row less for the youngest waves (api_solve.hip, TILES)
+    int tb_sym_shape = 0;                        // tests: 1-based index into the 12-wave shapes of T = 8 in TILES (0: the planner's choice)
     int tb_ranked = 1;
     int tb_rank_w[3] = {460, 325, 215};
     int tb_rank_wall = 1100;
@@ -309,6 +309,7 @@ static inline int api_exception() noexcept
 
 // ------------------------------------------------- shared internals -------
 
+struct TileKernel;
 struct SweepPlan {
     int kernel = 0;
     double omw = 0;
@@ -318,14 +319,12 @@ struct SweepPlan {
     int T = 0, LY = 0, tcpi = 0, ntx = 0, tgx = 0, tgy = 0, tblocks = 0;
     int shift = 0;                                        // column shift of the strips (0: no halo outside the walls)
     int T_override = 0;                                   // slab mode plans a T = 1 pass for remainders
-    bool guard = false;
+    bool guard = false;                                   // streaming kernel: the reference's non-zero link test
     double omega = 0;                                     // as given to plan_sweeps (omw = 1 - omega)
-    int impl = 1, R = 0, NW = 8;                          // 1 = streaming kernel, 2 = workgroup tiles of NW waves x R rows
+    int impl = 1;                                         // 1 = streaming kernel, 2 = workgroup tiles
+    const TileKernel *tile = nullptr;                     // impl 2: the tile's kernels, waves and rows (api_solve.hip, TILES)
     const int4 *dealt = nullptr;                          // streaming kernel: dealt tiles (chunk heights by service order), or none
     bool resident = false;                                // impl 2 only: all passes of a batch in one launch (k_sweep_wgres)
-    bool sym = false;                                     // tall tiles: the system is link-symmetric (7 lookups per row)
-    bool aged = false;                                    // tall tiles: rows dealt by the waves' age (k_sweep_wgage)
-    int rows3 = 0;                                        // 12-wave tiles: rows by age, a | b << 8 | c << 16 (0: R each)
     // rows the plan updates: band_h > 0 restricts it to the band [band_lo, band_lo + band_h) of the context's owned rows
     // (input); own_lo / own_h are what the planner resolved (output, passed to the kernels)
     int band_lo = 0, band_h = 0, own_lo = 0, own_h = 0;

@@ -140,6 +140,26 @@ def test_aged_tall_kernels_fit_four_waves_per_simd(usage):
     assert seen == {(6, 6, 5, 3), (8, 8, 5, 3), (8, 8, 8, 4), (9, 9, 9, 5), (10, 9, 9, 8), (12, 12, 10, 6), (13, 13, 11, 7), (13, 13, 13, 9)}
 
 
+def test_tall_tile_variants_share_occupancy_and_lds(usage):
+    """The planner sizes a tall tile with the occupancy of the kernel it would launch before it knows whether the system is
+    link-symmetric (plan_tall checks that later, on the stream): the SYM and non-SYM variants of a tall tile, rows dealt by age or
+    equal, must have the same waves per SIMD and LDS, or tiles could be taken for co-resident that are not."""
+    tiles = {}
+    for name, u in usage.items():
+        m = re.match(r"_ZN4deff13k_sweep_wgresILi8ELi(\d+)ELb([01])ELb0ELb1ELb[01]EEE", name)
+        if m:
+            key = (int(m.group(1)), m.group(2))                       # (R, FMA)
+        else:
+            m = re.match(r"_ZN4deff13k_sweep_wgageILi8ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELb0ELb[01]EEE", name)
+            if not m:
+                continue
+            key = (sum(int(v) for v in m.groups()[:4]) // 4, m.group(5))
+        tiles.setdefault(key, {})[name] = (u["Occupancy"], u["LDS"])
+    assert len(tiles) == 2 * 11
+    for key, variants in tiles.items():
+        assert len(variants) in (2, 4) and len(set(variants.values())) == 1, (key, variants)
+
+
 def test_symmetric_tile_kernel_fits_three_waves_per_simd(usage):
     """k_sweep_wgsym<8, R, FMA>: 12 waves per workgroup = 3 per SIMD = 168 VGPRs, symmetric matrix rows in registers (14 VGPRs
     per tile row); R = 4, 5 without any scratch (R = 6 would spill inside the sweep loop and is not instantiated);

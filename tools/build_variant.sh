@@ -10,10 +10,11 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 src=$root/effectivediffusivityfvm_amd/csrc
 out=$root/tools/ab
 mkdir -p "$out/obj_$name"
-make -s -C "$src" build/api_core.o build/api_slab.o build/api_residual.o
+make -s -C "$src" build/api_core.o build/api_slab.o build/api_residual.o build/api_cg.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fvisibility=hidden \
     -Wno-unused-function -Rpass-analysis=kernel-resource-usage "$@" -c -o "$out/obj_$name/api_solve.o" "$src/api_solve.hip" 2> "$out/$name.usage.txt"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o "$out/$name.so" "$out/obj_$name/api_solve.o" "$src/build/api_core.o" "$src/build/api_slab.o" "$src/build/api_residual.o" -L/opt/rocm/lib -lrccl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o "$out/$name.so" "$out/obj_$name/api_solve.o" "$src/build/api_core.o" "$src/build/api_slab.o" "$src/build/api_residual.o" \
+    "$src/build/api_cg.o" -L/opt/rocm/lib -lrccl
 rm -rf "$out/obj_$name"
 python3 - "$out/$name.usage.txt" <<'PY'
 import re, sys
