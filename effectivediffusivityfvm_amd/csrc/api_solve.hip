@@ -1187,17 +1187,9 @@ int flux_rows(deff_ctx *c, bool need_rows)
 // mf_host, or from the device's sums when flux_rows() produced them.
 static double deff_of_image(const deff_ctx *c, int k)
 {
-    double Q1 = 0, Q2 = 0;
-    if (c->q_valid) {
-        Q1 = c->q_host[2 * k];
-        Q2 = c->q_host[2 * k + 1];
-    } else {
-        const double *L = c->mf_host + (size_t)k * c->ny, *R = c->mf_host + c->rows + (size_t)k * c->ny;
-        for (int j = 0; j < c->ny; ++j) {
-            Q1 += L[j];
-            Q2 += R[j];
-        }
-    }
+    if (!c->q_valid)
+        return deff_of_fluxes(c->mf_host + (size_t)k * c->ny, c->mf_host + c->rows + (size_t)k * c->ny, c->ny, c->CL, c->CR);
+    const double Q1 = c->q_host[2 * k], Q2 = c->q_host[2 * k + 1];
     const double qAvg = (Q1 + Q2) / (2.0 * c->ny);
     return qAvg / ((c->CR - c->CL));
 }
@@ -1225,7 +1217,7 @@ DEFF_API_CATCH
 // JacobiGPU's loop, cuh:1232-1290, with the sweeps between two checks enqueued without host
 // round trips.  `iter` counts completed sweeps; the sweep with 0-based index k is followed by a
 // check iff k % check_every == 0 (cuh:1243).  All images of a batch start together, so their
-// checks coincide; each image carries its own deffOld / change and drops out (is frozen in the
+// checks coincide; each image carries its own JacobiCheck and drops out (is frozen in the
 // buffer it is in) as soon as ITS stopping rule fires -- exactly what a one-image-at-a-time run
 // of the reference's loop would do.
 extern "C" int deff_solve_batch(deff_ctx *c, double omega, double tol, int64_t max_iter, int64_t check_every,
@@ -1241,39 +1233,33 @@ try {
     reset_batch_state(c);                                            // every image iterates again
 
     const int B = c->nimg;
-    std::vector<double> deffNew(B, 1.0), deffOld(B, 5.0), change(B, 100.0), conv(B, 0.0);   // cuh:1171-1173
-    std::vector<int64_t> iters(B, 0), checks(B, 0);
-    int n_active = (max_iter > 0 && tol < 100.0) ? B : 0;           // cuh:1232 with change = 100
+    std::vector<JacobiCheck> chk(B);
+    std::vector<int64_t> iters(B, 0);
+    int n_active = (max_iter > 0 && JacobiCheck().more(tol)) ? B : 0;   // cuh:1232 before the first check
     if (n_active == 0) c->active_h.assign(B, 0);
     int64_t iter = 0;
     c->last_launches = 0;
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     while (iter < max_iter && n_active > 0) {                        // cuh:1232
-        const int64_t next_check = ((iter + check_every - 1) / check_every) * check_every;
-        const bool do_check = next_check < max_iter;
-        const int64_t batch = do_check ? next_check - iter + 1 : max_iter - iter;
-        TRY(enqueue_sweeps(c, pl, batch));
-        iter += batch;
+        const CheckStep st = check_step(iter, max_iter, check_every);
+        TRY(enqueue_sweeps(c, pl, st.sweeps));
+        iter += st.sweeps;
         for (int k = 0; k < B; ++k)
             if (c->active_h[k]) { iters[k] = iter; c->buf_of[k] = (uint8_t)c->cur; }
-        if (do_check) {
+        if (st.check) {
             TRY(flux_rows(c, MFL || MFR));
             bool froze = false;
             for (int k = 0; k < B; ++k) {
                 if (!c->active_h[k]) continue;
-                deffNew[k] = deff_of_image(c, k);
-                change[k] = (deffOld[k] - deffNew[k]) / (deffOld[k]);           // cuh:1265
-                deffOld[k] = deffNew[k];
-                conv[k] = change[k];                                             // cuh:1275
-                ++checks[k];
-                if (B == 1 && c->progress) c->progress(next_check, deffNew[k], change[k], c->progress_user);
-                if (!(tol < fabs(change[k]))) { c->active_h[k] = 0; --n_active; froze = true; }
+                chk[k].update(deff_of_image(c, k));
+                if (B == 1 && c->progress) c->progress(st.next_check, chk[k].deffNew, chk[k].change, c->progress_user);
+                if (!chk[k].more(tol)) { c->active_h[k] = 0; --n_active; froze = true; }
             }
             if (B == 1) copy_fluxes(c, MFL, MFR);
             else {
                 // keep, per image, the fluxes of ITS last check
                 for (int k = 0; k < B; ++k)
-                    if (checks[k] && iters[k] == iter) {
+                    if (chk[k].checks && iters[k] == iter) {
                         if (MFL) memcpy(MFL + (size_t)k * c->ny, c->mf_host + (size_t)k * c->ny, sizeof(double) * c->ny);
                         if (MFR) memcpy(MFR + (size_t)k * c->ny, c->mf_host + c->rows + (size_t)k * c->ny,
                                         sizeof(double) * c->ny);
@@ -1292,13 +1278,7 @@ try {
     HIP_TRY(hipEventSynchronize(c->ev1));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    for (int k = 0; k < B; ++k) {
-        out[k].iters = iters[k];
-        out[k].checks = checks[k];
-        out[k].deff_raw = deffNew[k];                                // cuh:1309: value at the last check
-        out[k].conv = conv[k];
-        out[k].loop_ms = ms;                                         // the batch shares one loop
-    }
+    for (int k = 0; k < B; ++k) out[k] = chk[k].result(iters[k], ms);     // the batch shares one loop (loop_ms)
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -1382,7 +1362,7 @@ try {
     HIP_TRY(hipMemsetAsync(c->x[1], 0, sizeof(double) * c->n, c->stream));
     reset_batch_state(c);
 
-    struct Slot { bool live = false; int64_t id = -1, iters = 0, checks = 0; double deffNew = 1, deffOld = 5, change = 100, conv = 0; };
+    struct Slot { bool live = false; int64_t id = -1, iters = 0; JacobiCheck chk; };
     std::vector<Slot> S(B);
     std::vector<uint8_t> pixbuf((size_t)W * H);
     bool more = true;
@@ -1403,8 +1383,7 @@ try {
         return DEFF_OK;
     };
     auto retire = [&](int k, float ms) {
-        deff_result r;
-        r.iters = S[k].iters; r.checks = S[k].checks; r.deff_raw = S[k].deffNew; r.conv = S[k].conv; r.loop_ms = ms;
+        const deff_result r = S[k].chk.result(S[k].iters, ms);
         c->active_h[k] = 0;
         --n_active;
         done(user, S[k].id, k, &r);                    // the slot's field is still readable (deff_get_slot_field)
@@ -1426,7 +1405,7 @@ try {
     TRY(plan_sweeps(c, omega, &pl));
     c->last_launches = 0;
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    if (!(max_iter > 0 && tol < 100.0)) {               // cuh:1232 with change = 100: no sweep at all
+    if (!(max_iter > 0 && JacobiCheck().more(tol))) {  // cuh:1232 before the first check: no sweep at all
         for (;;) {
             for (int k = 0; k < B; ++k) if (S[k].live) retire(k, 0.f);
             if (!more) break;
@@ -1446,13 +1425,8 @@ try {
         HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
         for (int k = 0; k < B; ++k) {
             if (!S[k].live) continue;
-            Slot &s = S[k];
-            s.deffNew = deff_of_image(c, k);
-            s.change = (s.deffOld - s.deffNew) / (s.deffOld);                     // cuh:1265
-            s.deffOld = s.deffNew;
-            s.conv = s.change;
-            ++s.checks;
-            if (!(tol < fabs(s.change)) || s.iters >= max_iter) retire(k, ms);
+            S[k].chk.update(deff_of_image(c, k));
+            if (!S[k].chk.more(tol) || S[k].iters >= max_iter) retire(k, ms);
         }
         if (n_active == 0 && !more) break;
         // up to the next check: C - 1 sweeps, split where images run into max_iter (they all carry

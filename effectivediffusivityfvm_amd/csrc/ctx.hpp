@@ -1,11 +1,13 @@
 // ctx.hpp -- what the translation units of libdeff_amd.so share: the solver context, the error
-// helpers and the internal entry points that cross files.
+// helpers, the internal entry points that cross files and the reference's stopping rule
+// (JacobiCheck, check_step, deff_of_fluxes), which every Jacobi solve loop uses.
 //   api_core.hip   library, context lifecycle, image, assembly (native / from D / imported), field
 //   api_solve.hip  row dictionary, launch plans, sweeps, wall fluxes, the solve loops (one image,
 //                  batch, streaming batch)
 //   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg)
-//   api_slab.hip   one image over several GPUs: row slabs (peer copies in one process, RCCL or a
-//                  caller-supplied transport with one process per GPU)
+//   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
+//                  for both forms, which differ in the transport only (peer copies in one process,
+//                  RCCL or a caller-supplied transport with one process per GPU)
 // The library is built with -fvisibility=hidden; only the C ABI of include/deff_amd.h is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -329,6 +331,50 @@ struct SweepPlan {
     // (input); own_lo / own_h are what the planner resolved (output, passed to the kernels)
     int band_lo = 0, band_h = 0, own_lo = 0, own_h = 0;
 };
+
+// The reference's stopping rule (JacobiGPU): Deff is evaluated at every check, and the loop goes on while its relative
+// change since the previous check exceeds tol.  One per image of deff_solve_batch, per slot of deff_solve_stream and per
+// row-slab solve.
+struct JacobiCheck {
+    double deffNew = 1, deffOld = 5, change = 100.0, conv = 0;      // cuh:1171-1173
+    int64_t checks = 0;
+    void update(double deff)
+    {
+        deffNew = deff;
+        change = (deffOld - deffNew) / (deffOld);                   // cuh:1265
+        deffOld = deffNew;
+        conv = change;                                              // cuh:1275
+        ++checks;
+    }
+    bool more(double tol) const { return tol < fabs(change); }     // cuh:1232
+    // deff_raw: the value at the last check (cuh:1309)
+    deff_result result(int64_t iters, float loop_ms) const { return deff_result{iters, checks, deffNew, conv, loop_ms}; }
+};
+
+// The sweeps from `iter` up to and including the next check -- the sweep with 0-based index k is followed by a check iff
+// k % check_every == 0 (cuh:1243) -- or, when no check comes before max_iter, up to max_iter.
+struct CheckStep {
+    int64_t next_check, sweeps;
+    bool check;
+};
+static inline CheckStep check_step(int64_t iter, int64_t max_iter, int64_t check_every)
+{
+    const int64_t next_check = ((iter + check_every - 1) / check_every) * check_every;
+    const bool check = next_check < max_iter;
+    return CheckStep{next_check, check ? next_check - iter + 1 : max_iter - iter, check};
+}
+
+// Deff from the wall fluxes of an image's ny rows, summed on the host in row order like the reference (cuh:1258-1263).
+static inline double deff_of_fluxes(const double *L, const double *R, int ny, double CL, double CR)
+{
+    double Q1 = 0, Q2 = 0;
+    for (int j = 0; j < ny; ++j) {
+        Q1 += L[j];
+        Q2 += R[j];
+    }
+    const double qAvg = (Q1 + Q2) / (2.0 * ny);
+    return qAvg / ((CR - CL));
+}
 
 // api_core.hip
 void reset_batch_state(deff_ctx *c);
