@@ -97,6 +97,10 @@ try {
     TRY(cg_table(c, tab));
     const CgGeom g = cg_geometry(c);
     const size_t items = (size_t)g.per_img * c->nimg;
+    c->cg_plan_kr = g.kr;
+    c->cg_plan_ntx = g.ntx;
+    c->cg_plan_items = (int)g.per_img;
+    c->cg_plan_restarts = 0;
     TRY(cg_buffers(c, items));
     HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), sizeof(double) * CG_DOUBLES, hipMemcpyHostToDevice, c->stream));
 
@@ -143,6 +147,7 @@ try {
             HIP_TRY(hipStreamSynchronize(c->stream));
             if (flags[1] == 0) break;
             ++rounds;
+            c->cg_plan_restarts = rounds;
         }
         for (int64_t i = 0; i < check_every; ++i, ++k) {
             double *p_in = c->cg_p[k & 1], *p_out = c->cg_p[(k + 1) & 1];

@@ -306,6 +306,10 @@ try {
     else if (!strcmp(key, "tb_aged")) *value = c->plan_aged;
     else if (!strcmp(key, "tb_rank_misses")) *value = c->tb_rank_misses;
     else if (!strcmp(key, "tb_rank_lost")) *value = c->tb_rank_lost;
+    else if (!strcmp(key, "cg_kr")) *value = c->cg_plan_kr;
+    else if (!strcmp(key, "cg_strips")) *value = c->cg_plan_ntx;
+    else if (!strcmp(key, "cg_items")) *value = c->cg_plan_items;
+    else if (!strcmp(key, "cg_restarts")) *value = c->cg_plan_restarts;
     else return fail(DEFF_EINVAL, "unknown plan key '%s'", key);
     return DEFF_OK;
 }

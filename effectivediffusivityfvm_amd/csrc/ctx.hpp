@@ -219,6 +219,8 @@ struct deff_ctx {
     void *cg_scal = nullptr;                     // CgScal per image
     unsigned *cg_flags = nullptr;                // [0] admissibility, [1] images restarted by a true-residual round
     hipEvent_t cg_ev0 = nullptr, cg_ev1 = nullptr;
+    int cg_plan_kr = 0, cg_plan_ntx = 0, cg_plan_items = 0;   // deff_get_plan "cg_kr" / "cg_strips" / "cg_items" of the last deff_solve_cg
+    int cg_plan_restarts = 0;                    // ... and its true-residual rounds that restarted an image ("cg_restarts")
 };
 
 static inline int use_device(const deff_ctx *c)

@@ -98,7 +98,9 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
 /* what the last launch plan of the temporally blocked kernel chose: "tb_T", "tb_LY" (rows per chunk),
  * "tb_strips", "tb_chunks_per_image", "tb_blocks" (workgroups launched), "tb_impl", "tb_R", "tb_resident" (1: the
  * passes of a batch run as one resident launch), "tb_fallbacks" (resident intervals that gave up and were redone with
- * one launch per pass); 0 before any sweep */
+ * one launch per pass); 0 before any sweep.  Of the last deff_solve_cg (0 before one): "cg_kr" (rows per work item),
+ * "cg_strips" (strips of 128 columns), "cg_items" (work items per image) and "cg_restarts" (true-residual rounds that
+ * sent an image back into the iteration) */
 int deff_get_plan(deff_ctx *ctx, const char *key, int *value);
 
 /* ---- image -> phases: replaces the mask->D loops cuh:1988-2000 (2-phase),
@@ -161,7 +163,9 @@ int deff_solve_batch(deff_ctx *ctx, double omega, double tol, int64_t max_iter, 
  * the images' flags every check_every iterations only; the results do not depend on it); the residual is then
  * recomputed from x and the iteration restarted if it misses rtol.  Decoupled rows (four zero links and b = 0: cells
  * outside the mesh, ImpSolid / FloodFill rows, a phase with D = 0) get x = 0 -- where the Jacobi loop of a 2-phase
- * system with Ds = 0 gives NaN, CG gives a finite field.  DEFF_EINVAL: row-slab contexts, systems without a row
+ * system with Ds = 0 gives NaN, CG gives a finite field.  A right-hand side of zero (||b|| = 0): a field with A x = 0
+ * returns at once with rel_residual 0, converged; any other field has rel_residual = inf, iterates to max_iter (the
+ * stop test ||r|| <= rtol * 0 never holds) and returns not converged with a finite field.  DEFF_EINVAL: row-slab contexts, systems without a row
  * dictionary or explicit-only ones (a wall link into the neighbouring row), and systems that are not symmetric (a link
  * between two active cells that differs from its partner, an active row with A0 <= 0); nothing is changed then. */
 typedef struct deff_cg_result {

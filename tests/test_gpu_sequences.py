@@ -8,9 +8,17 @@ outliving the field it ran under) lives BETWEEN calls.  Here every seed draws ~3
 1), solve (small MAX_ITER / check interval: stops by tolerance, by MAX_ITER on and between checks), wall fluxes, residual,
 field read-back, and changes of kernel / sweeps per pass / tile form / launch mode in between.  After every call that returns
 numbers they are compared with the oracle's: fields, sweep counts, Deff and conv bit for bit, the residual as
-oracle_binding.assert_residual does."""
+oracle_binding.assert_residual does.
+
+With `with_cg` the draw also holds deff_solve_cg (small and large max_iter, two tolerances, two check intervals).  CG is not
+the reference's algorithm, so its field is not the oracle's: it is checked by its own residual, its Deff and wall fluxes bit
+for bit against the oracle's flux evaluation of the field read back, and then the model ADOPTS that field -- every later
+sweep, solve, flux and residual has to match the oracle bit for bit from there, which is what shows that CG left the Jacobi
+tables, the plans, the frozen-image bookkeeping and the field ping-pong as it found them."""
 import numpy as np
 import pytest
+
+from test_cg_host import residual_np
 
 pytestmark = pytest.mark.gpu
 
@@ -60,7 +68,7 @@ class Model:
         return np.concatenate(arrs, axis=0)
 
 
-def run_sequence(pkg, ob, seed):
+def run_sequence(pkg, ob, seed, with_cg=False):
     rng = np.random.default_rng(seed)
     nx, ny = SHAPES[rng.integers(len(SHAPES))]
     B = int(rng.choice([1, 1, 3]))
@@ -80,6 +88,8 @@ def run_sequence(pkg, ob, seed):
                 ops += ["init", "set_field"]
                 if m.x is not None:
                     ops += ["sweeps", "sweeps", "solve", "solve", "flux", "get", "residual"]
+                    if with_cg:
+                        ops += ["cg", "cg"]
             op = ops[rng.integers(len(ops))]
             if op == "image":
                 m.new_image()
@@ -138,6 +148,35 @@ def run_sequence(pkg, ob, seed):
                     assert (res[i].iters, res[i].deff_raw, res[i].conv) == (it, deff, conv), (seed, log, i)
                     m.x[i] = x
                 fields_equal()
+            elif op == "cg":
+                rtol = float(rng.choice([1e-6, 1e-10]))
+                max_iter = int(rng.choice([0, 3, 100000]))
+                ce = int(rng.choice([1, 64]))
+                log.append(f"cg {rtol} {max_iter} {ce}")
+                try:
+                    res = s.solve_cg(rtol=rtol, max_iter=max_iter, check_every=ce)
+                except pkg.DeffError as e:
+                    # the one refusal these sequences can meet: three pixel classes or a D plane drawn cell by cell can give more
+                    # distinct rows than a dictionary holds (LUT_MAX_ROWS = 512 with the zero row, lut_layout.hpp), and CG runs on
+                    # the dictionary form only; nothing is changed then
+                    rows = np.unique(np.column_stack([np.concatenate(m.A), np.concatenate(m.b)]), axis=0)
+                    assert e.code == -1 and "no row dictionary" in str(e) and len(rows) > 511, (seed, log, e, len(rows))
+                    log[-1] += " refused"
+                    fields_equal()
+                    continue
+                res = [res] if B == 1 else res
+                got = s.get_field()
+                for i in range(B):
+                    x = got[i * ny:(i + 1) * ny].copy()
+                    rn = residual_np(m.A[i], m.b[i], x, nx, ny)
+                    assert res[i].iters <= max_iter and res[i].converged == (res[i].rel_residual <= rtol), (seed, log, i)
+                    if res[i].converged:                     # the additive term: test_gpu_cg.py::assert_honest
+                        assert rn <= rtol * (1 + 1e-6) + 1e-13, (seed, log, i, rn)
+                    elif rn >= 1e-6:                         # two float64 evaluations of a residual far above their rounding
+                        assert abs(res[i].rel_residual - rn) <= 1e-9 * rn, (seed, log, i, res[i].rel_residual, rn)
+                    want, L, R = ob.flux_deff(x, m.D[i], m.CL, m.CR)
+                    assert res[i].deff_raw == want and np.array_equal(res[i].MFL, L) and np.array_equal(res[i].MFR, R), (seed, log, i)
+                    m.x[i] = x
             elif op == "flux":
                 d, MFL, MFR = s.flux()
                 d = [d] if B == 1 else list(d)
@@ -166,6 +205,11 @@ def run_sequence(pkg, ob, seed):
 @pytest.mark.parametrize("seed", range(40))
 def test_random_call_sequences_match_the_oracle(pkg, oracle, seed):
     run_sequence(pkg, oracle, 1000 + seed)
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_random_call_sequences_with_cg(pkg, oracle, seed):
+    run_sequence(pkg, oracle, 2000 + seed, with_cg=True)
 
 
 def run_slab_sequence(pkg, ob, seed):
