@@ -135,6 +135,8 @@ try {
     for (void *p : cg_bufs) if (p) (void)hipFree(p);
     if (c->cg_ev0) (void)hipEventDestroy(c->cg_ev0);
     if (c->cg_ev1) (void)hipEventDestroy(c->cg_ev1);
+    if (c->resid_ev0) (void)hipEventDestroy(c->resid_ev0);
+    if (c->resid_ev1) (void)hipEventDestroy(c->resid_ev1);
     if (c->q_host) (void)hipHostFree(c->q_host);
     if (c->chain_counted) resident_chain_ctx_destroyed(c->device);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

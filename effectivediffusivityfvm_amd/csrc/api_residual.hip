@@ -30,17 +30,28 @@ static int residual_buffers(deff_ctx *c, size_t partials)
     return DEFF_OK;
 }
 
+// Opens the timed window of a call that asked for `ms` (the slot variant never does): the residual's own event pair, so a
+// residual taken inside a solve loop's callback leaves the loop's ev0 / ev1 -- and with them loop_ms -- alone.
+static int residual_start(deff_ctx *c, const float *ms)
+{
+    if (!ms) return DEFF_OK;
+    if (!c->resid_ev0) HIP_TRY(hipEventCreate(&c->resid_ev0));
+    if (!c->resid_ev1) HIP_TRY(hipEventCreate(&c->resid_ev1));
+    HIP_TRY(hipEventRecord(c->resid_ev0, c->stream));
+    return DEFF_OK;
+}
+
 // sums -> means: R / (numCols * numRows), cuh:491
 static int residual_finish(deff_ctx *c, size_t per_img, int nimg, double *r, float *ms)
 {
     double *out = c->resid + per_img * nimg;
     hipLaunchKernelGGL(k_residual_final, dim3(nimg), dim3(1024), 0, c->stream, c->resid, per_img, out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    if (ms) HIP_TRY(hipEventRecord(c->resid_ev1, c->stream));
     std::vector<double> sums(nimg);
     HIP_TRY(hipMemcpyAsync(sums.data(), out, sizeof(double) * nimg, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, c->ev0, c->ev1));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, c->resid_ev0, c->resid_ev1));
     const double cells = (double)((int64_t)c->nxt * (int64_t)c->ny);
     for (int k = 0; k < nimg; ++k) r[k] = sums[k] / cells;
     return DEFF_OK;
@@ -81,7 +92,7 @@ static int residual_classes(deff_ctx *c, const double *x, const uint8_t *pix, in
     const ResTable tab = residual_table(c);
     const bool fast = c->ampX == 1 && c->ampY == 1 && (c->W % 2) == 0;
     const dim3 grid((unsigned)((tiles + 3) / 4));
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    TRY(residual_start(c, ms));
 #define LAUNCH_RES(P_, F_)                                                                                              \
     hipLaunchKernelGGL((k_residual_classes<P_, F_>), grid, dim3(256), 0, c->stream, x, pix, c->W, c->ampX,              \
                        c->ampY, c->nx, c->nxt, c->ny, nimg, ntx, cpi, kt, c->CL, c->CR, tab, c->resid)
@@ -106,6 +117,7 @@ extern "C" int deff_residual_slot(deff_ctx *c, int slot, double *r)
 try {
     TRY(residual_common(c, r));
     if (slot < 0 || slot >= c->nimg) return fail(DEFF_EINVAL, "bad slot");
+    TRY(resident_check(c));                                        // settled already inside the stream's callback: a no-op there
     const double *x = c->x[(c->masked || c->in_stream) ? c->buf_of[slot] : c->cur] + (size_t)slot * c->n_img;
     return residual_classes(c, x, c->pix + (size_t)slot * c->W * c->H, 1, r, nullptr);
 }
@@ -123,7 +135,7 @@ try {
     double *dD = (double *)c->scratch;
     if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(dD, 0, sizeof(double) * c->n, c->stream));
     TRY(rows_h2d(c, dD, D, (size_t)c->rows));
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    TRY(residual_start(c, ms));
     hipLaunchKernelGGL(k_residual_plane, dim3((unsigned)(c->rows * segs)), dim3(256), 0, c->stream, c->x[c->cur], dD, c->nx,
                        c->nxt, c->ny, c->nimg, segs, c->dx, c->dy, CL, CR, c->resid);
     HIP_TRY(hipGetLastError());

@@ -221,6 +221,11 @@ struct deff_ctx {
     hipEvent_t cg_ev0 = nullptr, cg_ev1 = nullptr;
     int cg_plan_kr = 0, cg_plan_ntx = 0, cg_plan_items = 0;   // deff_get_plan "cg_kr" / "cg_strips" / "cg_items" of the last deff_solve_cg
     int cg_plan_restarts = 0;                    // ... and its true-residual rounds that restarted an image ("cg_restarts")
+
+    // deff_residual / deff_residual_D time themselves with their own pair, created by the first call that asks for `ms`:
+    // ev0 / ev1 belong to the solve loops alone, which read them at every check and may call the residual in between
+    // (a deff_set_progress or deff_image_done_fn callback)
+    hipEvent_t resid_ev0 = nullptr, resid_ev1 = nullptr;
 };
 
 static inline int use_device(const deff_ctx *c)

@@ -370,9 +370,7 @@ static bool solve_3phase_group(Session &S, const std::vector<Image> &ims, const 
     CK(deff_set_image(S.ctx, stack.data(), ims[0].W, ims[0].H, o.MeshIncreaseX, o.MeshIncreaseY));
     CK(deff_init_linear(S.ctx, o.CLeft, o.CRight));
     std::vector<deff_result> res(B);
-    int stage_no = 1;
-    for (double g = 10; g < DCG; g *= 10, ++stage_no) {              // JacobiGPUPreCond stages, cuh:2184-2326
-        if (o.verbose == 1) std::printf("Pre-Cond Stage %d: DCG = %1.3e\n", stage_no, g);
+    for (double g = 10; g < DCG; g *= 10) {                          // JacobiGPUPreCond stages, cuh:2184-2326
         CK(deff_assemble_3phase(S.ctx, DCS, DCF, g, grid.data(), o.CLeft, o.CRight));
         CK(deff_solve_batch(S.ctx, 2.0 / 3.0, o.ConvergeCriteria * 10, g_precond_maxiter, 10000, res.data(), nullptr, nullptr));
         for (int k = 0; k < B; ++k) rows[k].stages.push_back((long)res[k].iters);
@@ -385,7 +383,17 @@ static bool solve_3phase_group(Session &S, const std::vector<Image> &ims, const 
         rows[k].deff = res[k].deff_raw / DCF;                        // cuh:2370
         rows[k].conv = res[k].conv;
         rows[k].seconds = res[k].loop_ms / 1000.0 / B;               // final stage only (cuh:1147), shared by the group
-        if (o.verbose == 1) std::printf("Number%dDCF = %g, Deff %g\n", k, DCF, rows[k].deff);
+        if (o.verbose == 1) {
+            // the lines BatchSim3Phase prints for ONE image (cuh:2277, :2313, :2364, :2376), image after image as its loop does:
+            // the images of a group pass every stage together, so their lines are printed once the group is through
+            size_t q = 0;
+            for (double g = 10; g < DCG; g *= 10, ++q) {
+                std::printf("Pre-Cond Stage %d: DCG = %1.3e\n", (int)q + 1, g);
+                std::printf("Iterations taken = %ld\n", rows[k].stages[q]);
+            }
+            std::printf("Iterations taken = %ld\n", rows[k].iters);
+            std::printf("DCF = %g, Deff %g\n", DCF, rows[k].deff);
+        }
     }
     std::vector<double> rr(B);
     CK(deff_residual(S.ctx, rr.data(), nullptr));
@@ -612,7 +620,6 @@ static void stream_done(void *user, int64_t id, int slot, const deff_result *r)
     row.iters = (long)r->iters;
     row.stages.push_back((long)r->iters);
     row.seconds = r->loop_ms / 1000.0;                           // stream time when the image stopped
-    if (o.verbose == 1) std::printf("Number%dDCF = %g, Deff %g\n", (int)id, o.DCfluid, row.deff);
     if (deff_residual_slot(st.ctx, slot, &row.residual) != DEFF_OK) row.residual = NAN;
     progress_append(*st.sh->progress_path, (int)id, row);
     if (st.sh->want_field) {
@@ -711,7 +718,11 @@ int main(int argc, char **argv)
             if (!(g_cg_rtol >= 0.0) || !std::isfinite(g_cg_rtol)) { std::fprintf(stderr, "deff2d: --cg-rtol R (R >= 0)\n"); return 2; }
         }
         else if (s == "-h" || s == "--help") {
-            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R]\n");
+            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R]\n"
+                        "The Time column (seconds of device time, hipEvent): RunBatch 0 -- the solve loops of the image (3 phases: the final\n"
+                        "stage only, as the reference's JacobiGPUPreCond adds nothing to it); RunBatch 1, 2 phases -- the time from the\n"
+                        "start of the image's stream of slots to the check that retired the image, so it grows along a stream;\n"
+                        "RunBatch 1, 3 phases -- the final stage's loop divided by the number of images solved together.\n");
             return 0;
         } else if (!s.empty() && s[0] != '-') input = s;
         else { std::fprintf(stderr, "deff2d: unknown argument %s\n", s.c_str()); return 2; }
@@ -891,6 +902,13 @@ int main(int argc, char **argv)
         for (std::thread &t : pool) t.join();
     }
     if (failed.load()) return 1;
+    if (streaming && o.verbose == 1)
+        // BatchSim's two lines per image (cuh:2011-2021), in image order like the reference's loop: the slots retire their
+        // images in any order (and the prefetch threads deliver them in any order), so they are printed here, not on retirement
+        for (int k = 0; k < count; ++k) {
+            std::printf("Iterations taken = %ld\n", rows[(size_t)k].iters);
+            std::printf("Number%dDCF = %g, Deff %g\n", k, o.DCfluid, rows[(size_t)k].deff);
+        }
     write_csv(o, rows);                                              // after ALL images, like the reference (cuh:2051)
     if (!json.empty()) write_json(json, o, rows);
     return 0;

@@ -403,3 +403,22 @@ def ref_jacobi(A, b, x0, D, CL, CR, tol, max_iter, DCfluid=1.0, tmpdir=None, pre
     iters = struct.unpack("l", raw[:8])[0]
     v = np.frombuffer(raw[8:], dtype=np.float64)
     return iters, float(v[0]), float(v[1]), v[3:3 + n].reshape(ny, nx).copy(), v[3 + n:3 + n + ny].copy(), v[3 + n + ny:3 + n + 2 * ny].copy(), float(v[2])
+
+
+# ---- oracle/_ref/ref_on_seam: the reference's WHOLE PROGRAM -- main, readInputFile, the four drivers, FloodFill, the CSV / CMAP
+# writers, its own text -- with INTEGRATION.md section A applied (oracle/Makefile, SEAM_CUT), linked against libdeff_amd.so
+# through reference_seam.hpp.  Reads input.txt and the images from its working directory; needs a GPU to solve. -------------
+REF_ON_SEAM = os.path.join(ORACLE_DIR, "_ref", "ref_on_seam")
+
+
+def have_ref_on_seam():
+    return os.access(REF_ON_SEAM, os.X_OK)
+
+
+def run_ref_on_seam(cwd, timeout):
+    """One run of the patched reference program in `cwd` (the reference's main takes no arguments and reads ./input.txt).
+    The environment is inherited untouched; stdin is /dev/null, so a getchar() left anywhere returns at once instead of
+    waiting.  Returns the CompletedProcess (text mode; returncode < 0 = ended by that signal); a run that exceeds `timeout`
+    raises subprocess.TimeoutExpired after the child was killed."""
+    return subprocess.run([REF_ON_SEAM], cwd=str(cwd), stdin=subprocess.DEVNULL, capture_output=True, text=True,
+                          timeout=timeout)
