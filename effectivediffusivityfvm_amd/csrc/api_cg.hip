@@ -4,6 +4,7 @@
 // stay as they are (the "fma" knob does not apply here: CG's arithmetic is written-order FP64 only).
 #include "ctx.hpp"
 #include "kernels_cg.hpp"
+#include "kernels_cg_image.hpp"
 #include <vector>
 
 // true-residual rounds that may restart the recurrence of a finished image (each round costs one pass and a synchronisation)
@@ -101,6 +102,11 @@ try {
     c->cg_plan_ntx = g.ntx;
     c->cg_plan_items = (int)g.per_img;
     c->cg_plan_restarts = 0;
+    // on chip (tuning "cg_onchip"): an image whose arrays fit one compute unit's LDS and registers iterates there, one
+    // launch per check_every iterations instead of four per iteration; larger images keep the streaming kernels
+    const bool onchip = c->cg_onchip && (size_t)c->nx * c->ny <= (size_t)CGI_CELLS;
+    c->cg_plan_impl = onchip ? 2 : 1;
+    if (onchip && !c->cg_cus) HIP_TRY(hipDeviceGetAttribute(&c->cg_cus, hipDeviceAttributeMultiprocessorCount, c->device));
     TRY(cg_buffers(c, items));
     HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), sizeof(double) * CG_DOUBLES, hipMemcpyHostToDevice, c->stream));
 
@@ -148,6 +154,15 @@ try {
             if (flags[1] == 0) break;
             ++rounds;
             c->cg_plan_restarts = rounds;
+        }
+        if (onchip) {
+            // up to check_every iterations of every running image, p in cg_p[0] throughout (the streaming loop below starts
+            // every call at cg_p[0] with the restart flag set, so the two forms never read each other's p)
+            hipLaunchKernelGGL(k_cg_image, dim3((unsigned)std::min(c->nimg, c->cg_cus)), dim3(CGI_THREADS), 0, c->stream,
+                               c->cg_tab, c->lut_nrows, c->code, x, c->cg_r, c->cg_p[0], sc, c->nx, c->ny, c->nimg,
+                               (long long)check_every, tol2, (long long)max_iter);
+            HIP_TRY(hipGetLastError());
+            continue;
         }
         for (int64_t i = 0; i < check_every; ++i, ++k) {
             double *p_in = c->cg_p[k & 1], *p_out = c->cg_p[(k + 1) & 1];

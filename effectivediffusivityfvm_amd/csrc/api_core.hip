@@ -284,6 +284,10 @@ try {
     else if (!strcmp(key, "tb_rank_w1")) c->tb_rank_w[1] = value;
     else if (!strcmp(key, "tb_rank_w2")) c->tb_rank_w[2] = value;
     else if (!strcmp(key, "tb_rank_wall")) c->tb_rank_wall = value;
+    else if (!strcmp(key, "cg_onchip")) {
+        if (value > 1) return fail(DEFF_EINVAL, "cg_onchip takes 0 (streaming kernels) or 1 (small images iterate on one compute unit each)");
+        c->cg_onchip = value;
+    }
     else return fail(DEFF_EINVAL, "unknown tuning key '%s'", key);
     return DEFF_OK;
 }
@@ -312,6 +316,7 @@ try {
     else if (!strcmp(key, "cg_strips")) *value = c->cg_plan_ntx;
     else if (!strcmp(key, "cg_items")) *value = c->cg_plan_items;
     else if (!strcmp(key, "cg_restarts")) *value = c->cg_plan_restarts;
+    else if (!strcmp(key, "cg_impl")) *value = c->cg_plan_impl;
     else return fail(DEFF_EINVAL, "unknown plan key '%s'", key);
     return DEFF_OK;
 }

@@ -221,6 +221,10 @@ struct deff_ctx {
     hipEvent_t cg_ev0 = nullptr, cg_ev1 = nullptr;
     int cg_plan_kr = 0, cg_plan_ntx = 0, cg_plan_items = 0;   // deff_get_plan "cg_kr" / "cg_strips" / "cg_items" of the last deff_solve_cg
     int cg_plan_restarts = 0;                    // ... and its true-residual rounds that restarted an image ("cg_restarts")
+    // tuning "cg_onchip": 1 = images of at most 16 384 cells (pitch x ny) iterate on one compute unit each (kernels_cg_image.hpp);
+    // 0 (default) = the streaming kernels for every size.  cg_plan_impl: what the last deff_solve_cg ran, 1 streaming, 2 on chip
+    int cg_onchip = 0, cg_plan_impl = 0;
+    int cg_cus = 0;                              // compute units of the device (workgroups of an on-chip launch)
 
     // deff_residual / deff_residual_D time themselves with their own pair, created by the first call that asks for `ms`:
     // ev0 / ev1 belong to the solve loops alone, which read them at every check and may call the residual in between

@@ -120,6 +120,7 @@ static int64_t g_precond_maxiter = 1000000;
 static int g_prefetch_threads = 2;
 static bool g_solver_cg = false;   // --solver cg
 static double g_cg_rtol = 1e-10;   // --cg-rtol
+static int g_cg_batch = 0;         // --cg-batch B: 2-phase batch mode solves runs of up to B equally sized images in one stack
 
 struct Session {                   // one solver context, re-created only when the mesh / batch size changes
     deff_ctx *ctx = nullptr;
@@ -685,6 +686,7 @@ int main(int argc, char **argv)
     int device = 0, batch_size = 0;
     std::vector<int> devices;
     std::string progress_path;
+    bool cg_batch_given = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         if (s == "--device" && a + 1 < argc) device = std::atoi(argv[++a]);
@@ -717,8 +719,20 @@ int main(int argc, char **argv)
             g_cg_rtol = std::strtod(argv[++a], nullptr);
             if (!(g_cg_rtol >= 0.0) || !std::isfinite(g_cg_rtol)) { std::fprintf(stderr, "deff2d: --cg-rtol R (R >= 0)\n"); return 2; }
         }
+        else if (s == "--cg-batch" && a + 1 < argc) {
+            char *end = nullptr;
+            const long v = std::strtol(argv[++a], &end, 10);
+            if (end == argv[a] || *end || v < 0 || v > 1000000) {
+                std::fprintf(stderr, "deff2d: --cg-batch B (an integer >= 0; 0 = one image at a time)\n");
+                return 2;
+            }
+            g_cg_batch = (int)v;
+            cg_batch_given = true;
+        }
         else if (s == "-h" || s == "--help") {
-            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R]\n"
+            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B]\n"
+                        "--cg-batch B (with --solver cg, RunBatch 1, 2 phases): runs of up to B consecutive, equally sized images are solved\n"
+                        "together in one stack, an image of at most 16 384 cells on one compute unit each; 0 (default) = one image at a time.\n"
                         "The Time column (seconds of device time, hipEvent): RunBatch 0 -- the solve loops of the image (3 phases: the final\n"
                         "stage only, as the reference's JacobiGPUPreCond adds nothing to it); RunBatch 1, 2 phases -- the time from the\n"
                         "start of the image's stream of slots to the check that retired the image, so it grows along a stream;\n"
@@ -726,6 +740,10 @@ int main(int argc, char **argv)
             return 0;
         } else if (!s.empty() && s[0] != '-') input = s;
         else { std::fprintf(stderr, "deff2d: unknown argument %s\n", s.c_str()); return 2; }
+    }
+    if (cg_batch_given && !g_solver_cg) {
+        std::fprintf(stderr, "deff2d: --cg-batch needs --solver cg\n");
+        return 2;
     }
     Options o;
     std::string err;
@@ -737,9 +755,12 @@ int main(int argc, char **argv)
                              "CG iteration and are not offered\n");
         return 2;
     }
+    const bool cg_batched = g_solver_cg && o.BatchFlag && o.nPhase == 2 && g_cg_batch >= 2;
     if (g_solver_cg && o.BatchFlag && batch_size > 1)
-        std::fprintf(stderr, "deff2d: note: --solver cg solves one image at a time per worker (the stacked / streaming slots "
-                             "run the Jacobi loop only); --batch-size is ignored\n");
+        std::fprintf(stderr, "deff2d: note: --batch-size is ignored with --solver cg (the stacked / streaming slots run the Jacobi "
+                             "loop only): --cg-batch B solves B images of a 2-phase data set together\n");
+    if (g_cg_batch >= 2 && !cg_batched)
+        std::fprintf(stderr, "deff2d: note: --cg-batch applies to RunBatch 1 with 2 phases; one image at a time here\n");
     const int count = o.BatchFlag ? o.NumImg : 1;
     std::vector<Row> rows((size_t)count);
     const bool want_field = o.printCmap == 1 || !field_prefix.empty();
@@ -891,9 +912,80 @@ int main(int argc, char **argv)
             if (want_field) emit_field(k, field.data(), nx, ny);
         }
     };
+    // ---- --solver cg --cg-batch B (2-phase batch mode): runs of up to B consecutive, equally sized images from the prefetcher
+    // are one stack context each; with "cg_onchip" an image of at most 16 384 cells iterates on one compute unit, larger ones
+    // go through the same call and get the streaming kernels inside the library
+    auto cg_run = [&](Session &S, std::vector<Prepared> &run) -> bool {
+        const int B = (int)run.size(), W = run[0].im.W, H = run[0].im.H;
+        const int nx = W * o.MeshIncreaseX, ny = H * o.MeshIncreaseY;
+        if (!S.prepare(nx, ny, B)) return false;
+        CK(deff_set_tuning(S.ctx, "cg_onchip", 1));
+        std::vector<uint8_t> pix((size_t)B * W * H);
+        for (int q = 0; q < B; ++q) std::memcpy(pix.data() + (size_t)q * W * H, run[(size_t)q].im.pix.data(), (size_t)W * H);
+        CK(deff_set_image(S.ctx, pix.data(), W, H, o.MeshIncreaseX, o.MeshIncreaseY));
+        CK(deff_assemble_2phase(S.ctx, o.DCsolid, o.DCfluid, o.CLeft, o.CRight));
+        CK(deff_init_linear(S.ctx, o.CLeft, o.CRight));
+        std::vector<deff_cg_result> res((size_t)B);
+        CK(deff_solve_cg(S.ctx, g_cg_rtol, o.MAX_ITER, 512, res.data(), nullptr, nullptr));
+        std::vector<double> rr((size_t)B), fields;
+        CK(deff_residual(S.ctx, rr.data(), nullptr));
+        if (want_field) { fields.resize((size_t)nx * ny * B); CK(deff_get_field(S.ctx, fields.data())); }
+        for (int q = 0; q < B; ++q) {
+            const Prepared &p = run[(size_t)q];
+            Row &row = rows[(size_t)p.k];
+            row = Row();
+            row.name = image_name(p.k);
+            row.nElements = nx * ny;
+            row.porosity = p.porosity;
+            row.path = p.path;
+            row.deff = res[(size_t)q].deff_raw / o.DCfluid;          // cuh:2017
+            row.conv = res[(size_t)q].rel_residual;
+            row.iters = (long)res[(size_t)q].iters;
+            row.stages.push_back(row.iters);
+            row.seconds = res[(size_t)q].loop_ms / 1000.0 / B;       // the run's loop, shared by its images
+            row.residual = rr[(size_t)q];
+            if (o.verbose == 1) {
+                std::printf("Width = %d Height = %d Channel = %d\nPorosity = %g\n", p.im.W, p.im.H, p.im.nChannels, row.porosity);
+                std::printf("Iterations taken = %ld\nNumber%dDCF = %g, Deff %g\n", row.iters, p.k, o.DCfluid, row.deff);
+            }
+            progress_append(progress_path, p.k, row);
+            if (want_field) emit_field(p.k, fields.data() + (size_t)q * nx * ny, nx, ny);
+        }
+        return true;
+    };
+    auto cg_batch_worker = [&](int dev) {
+        Session S;
+        S.device = dev;
+        Prefetcher source(&shared, 64, g_prefetch_threads);
+        Prepared pending;
+        bool have_pending = false;
+        for (;;) {
+            std::vector<Prepared> run;
+            if (have_pending) { run.push_back(std::move(pending)); have_pending = false; }
+            bool end = false;
+            while ((int)run.size() < g_cg_batch) {
+                Prepared p = source.pop();
+                if (p.k < 0) { end = true; break; }
+                if (!run.empty() && (p.im.W != run[0].im.W || p.im.H != run[0].im.H)) {   // another size: the next run's first
+                    pending = std::move(p);
+                    have_pending = true;
+                    break;
+                }
+                run.push_back(std::move(p));
+            }
+            if (failed.load()) return;
+            if (!run.empty() && !cg_run(S, run)) { failed = true; return; }
+            if (end) return;
+        }
+    };
     const bool streaming = o.BatchFlag && o.nPhase == 2 && !g_solver_cg;   // slots of the Jacobi loop (cg: one image at a time)
     const bool grouped3 = o.BatchFlag && o.nPhase == 3 && !g_solver_cg;
-    auto run = [&](int dev) { if (streaming) stream_worker(dev); else if (grouped3) worker3(dev); else worker(dev); };
+    auto run = [&](int dev) {
+        if (streaming) stream_worker(dev);
+        else if (cg_batched) cg_batch_worker(dev);
+        else if (grouped3) worker3(dev);
+        else worker(dev);
+    };
     if (devices.size() <= 1 || count <= 1) {
         run(devices.empty() ? device : devices[0]);
     } else {

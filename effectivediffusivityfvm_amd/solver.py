@@ -82,9 +82,10 @@ class Solver:
         check(self._L.deff_set_tuning(self._ctx, key.encode(), int(value)))
 
     def plan(self):
-        """What the temporally blocked kernel's last launch plan chose (zeros before any sweep)."""
+        """What the temporally blocked kernel's last launch plan chose (zeros before any sweep), and "cg_impl": the form of
+        the last solve_cg (1 streaming kernels, 2 one image per compute unit: set_tuning("cg_onchip", 1); 0 before one)."""
         out = {}
-        for key in ("tb_T", "tb_LY", "tb_strips", "tb_chunks_per_image", "tb_blocks", "tb_impl", "tb_R", "tb_NW", "tb_resident", "tb_sym", "tb_ranked", "tb_aged"):
+        for key in ("tb_T", "tb_LY", "tb_strips", "tb_chunks_per_image", "tb_blocks", "tb_impl", "tb_R", "tb_NW", "tb_resident", "tb_sym", "tb_ranked", "tb_aged", "cg_impl"):
             v = C.c_int()
             check(self._L.deff_get_plan(self._ctx, key.encode(), C.byref(v)))
             out[key] = v.value

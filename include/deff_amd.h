@@ -85,6 +85,7 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  * dealt by the waves' age, 1 default), "dict" (harvest a row dictionary from explicit systems: 1 default),
  * "tb_impl" (1 streaming, 2 workgroup tiles), "tb_R", "tb_NW" (8 / 12 / 16 waves per
  *   tile: 12 = link-symmetric matrix rows in registers, 16 = tall resident tiles),
+ * "cg_onchip" (deff_solve_cg: 1 = images of at most 16 384 cells iterate on one compute unit each, see there),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
  *   run every pass between two checks in ONE launch, neighbouring tiles synchronised by flags: 1 = one launch per
  *   pass instead; a resident launch that cannot make progress -- another process holds part of the GPU -- gives up
@@ -99,8 +100,8 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * "tb_strips", "tb_chunks_per_image", "tb_blocks" (workgroups launched), "tb_impl", "tb_R", "tb_resident" (1: the
  * passes of a batch run as one resident launch), "tb_fallbacks" (resident intervals that gave up and were redone with
  * one launch per pass); 0 before any sweep.  Of the last deff_solve_cg (0 before one): "cg_kr" (rows per work item),
- * "cg_strips" (strips of 128 columns), "cg_items" (work items per image) and "cg_restarts" (true-residual rounds that
- * sent an image back into the iteration) */
+ * "cg_strips" (strips of 128 columns), "cg_items" (work items per image), "cg_restarts" (true-residual rounds that
+ * sent an image back into the iteration) and "cg_impl" (1 = streaming kernels, 2 = on chip) */
 int deff_get_plan(deff_ctx *ctx, const char *key, int *value);
 
 /* ---- image -> phases: replaces the mask->D loops cuh:1988-2000 (2-phase),
@@ -167,7 +168,14 @@ int deff_solve_batch(deff_ctx *ctx, double omega, double tol, int64_t max_iter, 
  * returns at once with rel_residual 0, converged; any other field has rel_residual = inf, iterates to max_iter (the
  * stop test ||r|| <= rtol * 0 never holds) and returns not converged with a finite field.  DEFF_EINVAL: row-slab contexts, systems without a row
  * dictionary or explicit-only ones (a wall link into the neighbouring row), and systems that are not symmetric (a link
- * between two active cells that differs from its partner, an active row with A0 <= 0); nothing is changed then. */
+ * between two active cells that differs from its partner, an active row with A0 <= 0); nothing is changed then.
+ * Tuning key "cg_onchip" (0 default: the streaming kernels, four launches per iteration): 1 = when an image of the context
+ * has at most 16 384 cells (row pitch x ny, the pitch being nx rounded up to even: 128 x 128, 8192 x 2, 2 x 8192 ...), every
+ * image is iterated by one workgroup that keeps x, r, p and the codes in one compute unit's registers and LDS; check_every
+ * iterations are then ONE launch, and a stack's images run side by side, one per compute unit.  Larger images keep the
+ * streaming kernels.  Same recurrence, stop rules, true-residual rounds and results as above (the dot products are summed
+ * in another fixed order, so the bits differ from the streaming form's; they do not depend on check_every or on the
+ * stack an image is in).  deff_get_plan "cg_impl" tells which form the last call ran: 1 = streaming, 2 = on chip. */
 typedef struct deff_cg_result {
     int64_t iters;         /* CG iterations of this image */
     double  rel_residual;  /* ||b - A x||_2 / ||b||_2 of the returned field, recomputed from x */

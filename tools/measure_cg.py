@@ -12,6 +12,15 @@ bench4096     bench.py's workload: synthetic 4096^2 (seed 12345), Ds 1e-3 (Jacob
               47 200 001 sweeps, 610 s -- not rerun)
 stack16x1024  16 synthetic 1024^2 images (seed 12345, images 0-15) in one stack context (Jacobi not run: image 0 is config2)
 shipped00042  the reference's shipped input.txt on 00042.jpg through `deff2d --solver cg` (Jacobi: profiles/r04_as_shipped_00042.json)
+onchip_config1   00000.jpg 128^2 in a one-image context: the streaming kernels ("cg_onchip" 0: the code path every earlier
+              revision runs) against the on-chip kernel ("cg_onchip" 1), alternating, 10 runs each at check_every 64 and 512
+onchip_stack256  256 synthetic 128^2 images (seed 12345, images 0-255) in one stack: the same comparison, --runs times each
+              at check_every 64 and 512; loop_ms, per-iteration time, ratio fastest streaming / slowest on-chip
+onchip_dataset   tools/measure_dataset.py's 128^2 JPEG set (--images N) through deff2d: --solver cg one image at a time (what
+              every earlier revision does) against --solver cg --cg-batch 1024, --runs times each, and the Jacobi streaming
+              slots once; images/s
+onchip_profile   k_cg_image's share of loop_ms from a `rocprofv3 --kernel-trace --stats` run of its own (a child process)
+  python tools/measure_cg.py --cases onchip_config1,onchip_stack256,onchip_dataset,onchip_profile --out profiles/cg_onchip_results.json
 The bytes model of one iteration is 68 B/cell; "model_us" is that traffic at 6.3 TB/s."""
 import argparse
 import json
@@ -92,6 +101,128 @@ def shipped00042(rtol):
             "jacobi_note": "profiles/r04_as_shipped_00042.json: 5 650 001 sweeps in all, final stage 0.984 s"}
 
 
+def onchip_pair(make, B, rtol, max_iter, runs, check_everys, only_onchip=False):
+    """Streaming kernels ("cg_onchip" 0: the code path every earlier revision runs) against one image per compute unit
+    ("cg_onchip" 1) on fresh contexts, the two forms alternating run by run, at the same check_every; per check_every the
+    runs, and the ratio fastest streaming / slowest on-chip loop_ms (the bar: > 1)."""
+    out = {}
+    for ce in check_everys:
+        rows = {"streaming": [], "onchip": []}
+        for _ in range(runs):
+            for label, on in (("streaming", 0), ("onchip", 1)):
+                if only_onchip and not on:
+                    continue
+                with make() as s:
+                    s.set_tuning("cg_onchip", on)
+                    s.init_linear(0.0, 1.0)
+                    rs = s.solve_cg(rtol=rtol, max_iter=max_iter, check_every=ce, fluxes=False)
+                    rs = rs if isinstance(rs, list) else [rs]
+                    assert s.plan_value("cg_impl") == 1 + on and all(r.converged for r in rs)
+                    its = [int(r.iters) for r in rs]
+                    rows[label].append({"loop_ms": rs[0].loop_ms, "max_iters": max(its), "mean_iters": sum(its) / B,
+                                        "per_iter_us": 1e3 * rs[0].loop_ms / max(its), "deff_raw_image0": rs[0].deff_raw})
+        if not only_onchip:
+            slow_new = max(r["loop_ms"] for r in rows["onchip"])
+            fast_old = min(r["loop_ms"] for r in rows["streaming"])
+            rows["slowest_onchip_ms"], rows["fastest_streaming_ms"] = slow_new, fast_old
+            rows["ratio_fastest_streaming_over_slowest_onchip"] = fast_old / slow_new
+        out[f"check_every_{ce}"] = rows
+    return out
+
+
+def onchip_stack256(rtol, max_iter, runs, only_onchip):
+    n, B = 128, 256
+
+    def make():
+        s = pkg.Solver(n, n, nimg=B)
+        s.synth_image(12345, 0)
+        s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+        return s
+    return {"mesh": [n, n], "nimg": B, "rtol": rtol, **onchip_pair(make, B, rtol, max_iter, runs, (512,) if only_onchip else (64, 512), only_onchip)}
+
+
+def onchip_config1(rtol, max_iter, runs):
+    """One image (00000.jpg, 128^2): short loops (milliseconds), so 10 alternating runs of each form per check_every."""
+    pix = np.load(os.path.join(ROOT, "tests", "golden", "img00000_pix_stb.npy"))
+    ny, nx = pix.shape
+
+    def make():
+        s = pkg.Solver(nx, ny)
+        s.set_image(pix)
+        s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+        return s
+    return {"mesh": [nx, ny], "nimg": 1, "rtol": rtol, **onchip_pair(make, 1, rtol, max_iter, max(runs, 10), (64, 512))}
+
+
+def onchip_profile(rtol):
+    """The on-chip kernel's share of loop_ms: one on-chip solve of the 256-image stack in a child process of its own under
+    `rocprofv3 --kernel-trace --stats` (check_every 512), k_cg_image's total duration against that run's loop_ms."""
+    import csv
+    import glob
+    with tempfile.TemporaryDirectory() as d:
+        run = os.path.join(d, "run.json")
+        p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(d, "prof"), "-o", "run", "--",
+                            sys.executable,
+                            os.path.abspath(__file__), "--cases", "onchip_stack256", "--runs", "1", "--only-onchip", "--rtol", repr(rtol),
+                            "--out", run], capture_output=True, text=True, timeout=600)
+        if p.returncode != 0 or not os.path.exists(run):
+            return {"error": (p.stderr or p.stdout)[-1500:]}
+        row = json.load(open(run))["onchip_stack256"]["check_every_512"]["onchip"][0]
+        out = {"loop_ms": row["loop_ms"], "max_iters": row["max_iters"], "kernels": {}}
+        files = glob.glob(os.path.join(d, "prof", "**", "*kernel_stats*.csv"), recursive=True)
+        trace = glob.glob(os.path.join(d, "prof", "**", "*kernel_trace*.csv"), recursive=True)
+        if files:
+            for k in csv.DictReader(open(files[0])):
+                out["kernels"][k["Name"].split("(")[0]] = {"calls": int(k["Calls"]), "total_ms": float(k["TotalDurationNs"]) / 1e6}
+        elif trace:                                                  # no stats table: add the trace's durations up
+            for k in csv.DictReader(open(trace[0])):
+                e = out["kernels"].setdefault(k["Kernel_Name"].split("(")[0], {"calls": 0, "total_ms": 0.0})
+                e["calls"] += 1
+                e["total_ms"] += (int(k["End_Timestamp"]) - int(k["Start_Timestamp"])) / 1e6
+        else:
+            return {**out, "error": "no kernel stats written", "files": [os.path.relpath(f, d) for f in
+                                                                          glob.glob(os.path.join(d, "prof", "**", "*"), recursive=True)][:20]}
+        img = [v for n_, v in out["kernels"].items() if "k_cg_image" in n_]
+        if img:
+            out["k_cg_image_ms"] = img[0]["total_ms"]
+            out["k_cg_image_share_of_loop"] = img[0]["total_ms"] / row["loop_ms"]
+            out["k_cg_image_us_per_iteration"] = 1e3 * img[0]["total_ms"] / row["max_iters"]
+    return out
+
+
+def onchip_dataset(rtol, runs, images):
+    """tools/measure_dataset.py's images (8 x 8-pixel grains, seed 0) and input file, through the driver."""
+    from PIL import Image
+    exe = os.path.join(ROOT, "effectivediffusivityfvm_amd", "deff2d")
+    S = 128
+    out = {"image_size": S, "images": images, "cg_rtol": rtol, "runs": {}}
+    with tempfile.TemporaryDirectory() as d:
+        rng = np.random.default_rng(0)
+        for k in range(images):
+            f = np.kron(rng.random((S // 8, S // 8)), np.ones((8, 8)))
+            Image.fromarray(np.where(f < rng.uniform(0.45, 0.75), 0, 255).astype(np.uint8)).save(os.path.join(d, f"{k:05d}.jpg"), quality=95)
+        open(os.path.join(d, "input.txt"), "w").write(
+            "Input File:\nPhases: 2\nDs: 1e-3\nDf: 1\nMeshAmpX: 1\nMeshAmpY: 1\nCR: 1\nCL: 0\nOutputName: out.csv\n"
+            f"printCMap: 0\nConvergence: 1e-6\nMaxIter: 5e5\nVerbose: 0\nRunBatch: 1\nNumImages: {images}\n")
+        cg = ["--solver", "cg", "--cg-rtol", repr(rtol)]
+        for label, extra, n in (("cg_one_at_a_time", cg, runs), ("cg_batch_1024", cg + ["--cg-batch", "1024"], runs), ("jacobi_streaming", [], 1)):
+            rows = []
+            for q in range(n):
+                t0 = time.perf_counter()
+                p = subprocess.run([exe, "input.txt", "--json", f"{label}{q}.json"] + extra, cwd=d, capture_output=True, text=True, timeout=1200)
+                dt = time.perf_counter() - t0
+                assert p.returncode == 0, p.stderr
+                res = json.load(open(os.path.join(d, f"{label}{q}.json")))["results"]
+                rows.append({"seconds": dt, "images_per_s": len(res) / dt, "mean_iterations": sum(x["iterations"] for x in res) / len(res),
+                             "mean_Deff": sum(x["Deff"] for x in res) / len(res)})
+            out["runs"][label] = rows
+    slow_new = min(r["images_per_s"] for r in out["runs"]["cg_batch_1024"])
+    fast_old = max(r["images_per_s"] for r in out["runs"]["cg_one_at_a_time"])
+    out["slowest_batched_images_per_s"], out["fastest_one_at_a_time_images_per_s"] = slow_new, fast_old
+    out["speedup_slowest_new_over_fastest_old"] = slow_new / fast_old
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="config1,config2,bench4096,stack16x1024,shipped00042")
@@ -99,6 +230,9 @@ def main():
     ap.add_argument("--max-iter", type=int, default=2_000_000)
     ap.add_argument("--no-jacobi", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--images", type=int, default=1024)
+    ap.add_argument("--only-onchip", action="store_true")
     a = ap.parse_args()
     jac = not a.no_jacobi
     out = {"rtol": a.rtol, "bytes_per_cell_model": BYTES_PER_CELL, "hbm_TBs_model": HBM_TBS}
@@ -116,6 +250,14 @@ def main():
             out[case] = synth_case(1024, 16, a.rtol, a.max_iter, False)
         elif case == "shipped00042":
             out[case] = shipped00042(a.rtol)
+        elif case == "onchip_stack256":
+            out[case] = onchip_stack256(a.rtol, a.max_iter, a.runs, a.only_onchip)
+        elif case == "onchip_config1":
+            out[case] = onchip_config1(a.rtol, a.max_iter, a.runs)
+        elif case == "onchip_profile":
+            out[case] = onchip_profile(a.rtol)
+        elif case == "onchip_dataset":
+            out[case] = onchip_dataset(a.rtol, a.runs, a.images)
         else:
             raise SystemExit(f"unknown case {case}")
         out[case]["case_wall_s"] = time.perf_counter() - t0
