@@ -1311,6 +1311,7 @@ static int stream_load_slot(deff_ctx *c, int slot, const uint8_t *pix_host)
     HIP_TRY(hipGetLastError());
     c->buf_of[slot] = (uint8_t)c->cur;
     c->links_sym = 0;                                  // new codes in this slot
+    c->have_explicit = false;                          // ... and coefficient planes, if any, that belong to the image before
     return DEFF_OK;
 }
 
@@ -1360,6 +1361,10 @@ try {
     HIP_TRY(hipMemsetAsync(c->code, 0, sizeof(uint16_t) * c->n, c->stream));      // empty slots: zero rows
     HIP_TRY(hipMemsetAsync(c->x[0], 0, sizeof(double) * c->n, c->stream));
     HIP_TRY(hipMemsetAsync(c->x[1], 0, sizeof(double) * c->n, c->stream));
+    // ... and zero wall diffusivities and pixels, so that their Deff is 0 and not what the allocation held
+    HIP_TRY(hipMemsetAsync(c->Dl, 0, sizeof(double) * c->rows, c->stream));
+    HIP_TRY(hipMemsetAsync(c->Dr, 0, sizeof(double) * c->rows, c->stream));
+    HIP_TRY(hipMemsetAsync(c->pix, 0, (size_t)W * H * B, c->stream));
     reset_batch_state(c);
 
     struct Slot { bool live = false; int64_t id = -1, iters = 0; JacobiCheck chk; };
@@ -1455,6 +1460,11 @@ try {
             }
         }
         TRY(refill());                                 // newcomers start with the sweep that precedes the next check
+        // the explicit / scalar kernels read coefficient planes, not codes: assemble them again with the new images' rows
+        if ((pl.kernel == DEFF_KERNEL_EXPLICIT || pl.kernel == DEFF_KERNEL_SCALAR) && !c->have_explicit) {
+            pl = SweepPlan();
+            TRY(plan_sweeps(c, omega, &pl));
+        }
         // new images, new codes: the symmetric short-cut of the tall tiles is re-verified, not carried over
         if (pl.impl == 2 && pl.tile->NW == WGL_WAVES && c->tb_sym != 2 && c->links_sym == 0) {
             TRY(check_links_symmetric(c));
@@ -1464,8 +1474,12 @@ try {
             if (c->links_sym != 1) { pl = SweepPlan(); TRY(plan_sweeps(c, omega, &pl)); }   // (never for the native assembly)
         }
     }
-    TRY(resident_check(c));                            // nothing unchecked outlives the stream's mask and slots
-    c->masked = false;
+    // What the context holds from here on (deff_amd.h): slot k = the last image that ran in it, its system and its final
+    // field.  A slot that retired while others kept sweeping is frozen in the buffer it stopped in, and that is x[cur] only
+    // if the flips since then are even: bring every slot's newest field into x[cur] (consolidate() settles the last resident
+    // interval first; it acts only under a mask, and the stream's last mask may already be gone) before buf_of is forgotten.
+    c->masked = true;
+    TRY(consolidate(c));
     reset_batch_state(c);
     return DEFF_OK;
 }
@@ -1481,7 +1495,8 @@ DEFF_API_CATCH
 
 // Diagnostics: time-stamp every wave tile of ONE temporally blocked pass (100 MHz wall clock ticks).
 // out[2*k], out[2*k+1] = start, end of wave tile k; *ntiles = number of tiles (call with out = NULL
-// to size the buffer).  Advances the field by one pass.
+// to size the buffer; that call leaves the field alone).  Advances the field by one pass = T sweeps; by THREE passes =
+// 3 * T sweeps when the plan is resident (workgroup tiles, "tb_resident" = 1), whose stamps cover three passes.
 extern "C" int deff_debug_tb_stamps(deff_ctx *c, double omega, unsigned long long *out, int *ntiles)
 try {
     if (!c || !ntiles) return fail(DEFF_EINVAL, "NULL argument");

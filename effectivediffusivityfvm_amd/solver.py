@@ -15,7 +15,7 @@ OMEGA_REFERENCE = 2.0 / 3.0     # updateX_SOR, Deff2D.cuh:72
 
 
 class SolveResult:
-    __slots__ = ("iters", "checks", "deff_raw", "conv", "loop_ms", "MFL", "MFR", "field")
+    __slots__ = ("iters", "checks", "deff_raw", "conv", "loop_ms", "MFL", "MFR", "field", "slot")
 
     def __repr__(self):
         return (f"SolveResult(iters={self.iters}, checks={self.checks}, deff_raw={self.deff_raw!r}, "
@@ -208,7 +208,8 @@ class Solver:
                      want_fields=False, ampX=1, ampY=1):
         """Dataset generation: `images` is any iterable of uint8 (H, W) arrays of one size; the nimg
         slots of this context are kept full (a finished image's slot is refilled with the next one).
-        Returns a list with one SolveResult per image, in input order (plus .field when want_fields)."""
+        Returns a list with one SolveResult per image, in input order, with .slot = the slot the image ran in (plus .field
+        when want_fields).  Afterwards slot k of the context holds the last image that ran in it, with its final field."""
         it = iter(images)
         H, W = self.ny // ampY, self.nx // ampX
         results = {}
@@ -239,6 +240,7 @@ class Solver:
                 out = SolveResult()
                 out.iters, out.checks, out.deff_raw, out.conv, out.loop_ms = r.iters, r.checks, r.deff_raw, r.conv, r.loop_ms
                 out.MFL = out.MFR = None
+                out.slot = int(slot)
                 if want_fields:
                     x = np.empty((self.ny, self.nx), dtype=np.float64)
                     check(self._L.deff_get_slot_field(self._ctx, slot, x))

@@ -194,6 +194,16 @@ int deff_solve_cg(deff_ctx *ctx, double rtol, int64_t max_iter, int64_t check_ev
  *   may be called from inside it to fetch the image's final field */
 typedef int (*deff_next_image_fn)(void *user, int slot, uint8_t *pix, int64_t *image_id);
 typedef void (*deff_image_done_fn)(void *user, int64_t image_id, int slot, const deff_result *res);
+/* After DEFF_OK the context is an ordinary stack context: slot k holds the last image that ran in it (the slot `done` reported
+ * for it), the 2-phase system of this call's Ds, Df, CL, CR, and that image's FINAL field, whatever buffer the image was
+ * frozen in while other slots kept sweeping.  A slot that never received an image (fewer images than slots) holds pixels
+ * of 0, zero rows, zero wall diffusivities and a zero field (Deff 0): it reads 0 and its Deff and residual are finite.  That
+ * is a place holder, not the system of an image: what later sweeps make of such a slot depends on the kernel (the kernels
+ * that read row codes keep it at 0, the ones that read coefficient planes rebuild them from the pixels of 0) and is
+ * unspecified until deff_set_image and an assembly give the slot an image.  Every later call behaves as on a stack assembled
+ * that way by hand: deff_get_field, deff_get_slot_field, deff_flux, deff_residual, deff_residual_slot, deff_sweeps,
+ * deff_solve_batch, deff_solve_cg, deff_device_field, a new image and re-assembly.  The same holds when no sweep ran at all
+ * (max_iter <= 0, or tol >= 100, the change the stopping rule is seeded with): the fields are then the linear guesses. */
 int deff_solve_stream(deff_ctx *ctx, int W, int H, int ampX, int ampY, double Ds, double Df, double CL,
                       double CR, double omega, double tol, int64_t max_iter, int64_t check_every,
                       deff_next_image_fn next, deff_image_done_fn done, void *user);
@@ -283,7 +293,11 @@ int deff_slab_rank_solve(deff_slab_rank *s, double omega, double tol, int64_t ma
                          int64_t check_every, deff_result *out, double *MFL, double *MFR);
 
 /* diagnostics: per wave tile of one temporally blocked pass of the streaming kernel two words -- the wall-clock (100 MHz) start,
- * and duration (low 32 bits) | HW_ID[15:0] << 32 | XCC_ID << 48 (where it ran); resident tiles: 12 wall-clock stamps per tile */
+ * and duration (low 32 bits) | HW_ID[15:0] << 32 | XCC_ID << 48 (where it ran); resident tiles: 12 wall-clock stamps per tile.
+ * out = NULL: only *ntiles (the number of word PAIRS out must hold) is set and the field is left alone.  Otherwise the field
+ * ADVANCES: by one pass = T sweeps (deff_get_plan "tb_T"), or by three passes = 3 * T sweeps when the plan is resident
+ * ("tb_impl" = 2 and "tb_resident" = 1: the 12 stamps of a resident tile cover three passes).  DEFF_ESTATE, field unchanged,
+ * when the sweeps do not resolve to DEFF_KERNEL_MATFREE_TB. */
 int deff_debug_tb_stamps(deff_ctx *ctx, double omega, unsigned long long *out, int *ntiles);
 
 /* raw device pointers for zero-copy interop (torch tensors, RCCL): current field, and the byte

@@ -43,15 +43,10 @@ class Model:
         self.kind = None                                     # "2p" / "3p" / "D": how the current system was assembled
 
     def new_image(self):
-        p = self.rng.uniform(0.3, 0.7)
-        vals = np.array([0, 30, 120, 199, 201, 255], dtype=np.uint8)
-        if self.rng.random() < 0.5:
-            self.pix = [np.where(self.rng.random((self.ny, self.nx)) < p, 0, 255).astype(np.uint8) for _ in range(self.B)]
-        else:
-            self.pix = [self.rng.choice(vals, size=(self.ny, self.nx)) for _ in range(self.B)]
+        self.pix = draw_images(self.rng, self.nx, self.ny, self.B)
         self.kind = None
 
-    def assemble(self, kind, Ds, Df, Dg, CL, CR):
+    def assemble(self, kind, Ds, Df, Dg, CL, CR, D=None):
         ob = self.ob
         self.CL, self.CR, self.kind = CL, CR, kind
         if kind == "2p":
@@ -59,8 +54,7 @@ class Model:
         elif kind == "3p":
             self.D = [ob.fill_D_3phase(p, Df, Ds, Dg) for p in self.pix]
         else:
-            levels = np.array([Ds, Df, Dg, 0.5 * (Ds + Df)])
-            self.D = [levels[self.rng.integers(0, 4, size=(self.ny, self.nx))] for _ in range(self.B)]
+            self.D = D if D is not None else draw_D_planes(self.rng, self.nx, self.ny, self.B, Ds, Df, Dg)
         sys_ = [ob.discretize(D, CL, CR) for D in self.D]
         self.A, self.b = [s[0] for s in sys_], [s[1] for s in sys_]
 
@@ -68,38 +62,266 @@ class Model:
         return np.concatenate(arrs, axis=0)
 
 
-def run_sequence(pkg, ob, seed, with_cg=False):
+def draw_images(rng, nx, ny, count):
+    p = rng.uniform(0.3, 0.7)
+    vals = np.array([0, 30, 120, 199, 201, 255], dtype=np.uint8)
+    if rng.random() < 0.5:
+        return [np.where(rng.random((ny, nx)) < p, 0, 255).astype(np.uint8) for _ in range(count)]
+    return [rng.choice(vals, size=(ny, nx)) for _ in range(count)]
+
+
+def draw_D_planes(rng, nx, ny, count, Ds, Df, Dg):
+    levels = np.array([Ds, Df, Dg, 0.5 * (Ds + Df)])
+    return [levels[rng.integers(0, 4, size=(ny, nx))] for _ in range(count)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The draw.  It depends on the generator and on three facts of the model's state (how the system was assembled, whether there
+# is a field, the stack size) -- never on what the GPU returns -- so it is separate from the execution: run_sequence() below
+# executes it against a context and the oracle, tests/test_sequences_host.py replays it without a GPU and counts what the
+# seeds reach.  Every option defaults to off, and with all of them off the generator is consumed exactly as before they
+# existed: the seeds 1000-1039 and 2000-2023 draw the sequences they always drew.
+#
+#   onchip   the tune draw may set "cg_onchip"; after every cg the form that ran (deff_get_plan "cg_impl") is asserted
+#   stream   deff_solve_stream of B ... 3B+1 images on a stack (B >= 2); the model becomes what deff_amd.h says the context holds
+#   ptr      deff_synchronize + deff_device_field, read with the HIP runtime's own hipMemcpy: pitch, pad column, every cell
+#   slot     deff_get_slot_field of a random slot outside any callback
+#   stamps   deff_debug_tb_stamps: sizing call, real call, the field advances by T (3 T on a resident plan) sweeps
+#   fma      the tuning key "fma" as a per-context choice, drawn once per seed before the first guess
+
+ONCHIP_LIMIT = 16384                                         # cells (row pitch x ny) one compute unit holds: deff_amd.h, "cg_onchip"
+SOLVE_TOL, SOLVE_MAX_ITER, SOLVE_CE = [1e-2, 1e-4, 1e-12], [1, 7, 100, 101, 130, 301], [7, 50, 100]
+ASSEMBLE_D = [(1e-3, 1.0, 10.0), (1e-2, 1.0, 50.0), (0.1, 2.0, 7.0)]
+ASSEMBLE_C = [(0.0, 1.0), (0.25, 0.75)]
+
+
+def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30, onchip=False, stream=False, ptr=False,
+                  slot=False, stamps=False, fma=False):
+    """Generator of (op, arguments...) tuples; the first is ("open", nx, ny, B, fma) and the second the first image."""
+    assert not (fma and with_cg)                             # CG's arithmetic has no contracted form to compare with
     rng = np.random.default_rng(seed)
-    nx, ny = SHAPES[rng.integers(len(SHAPES))]
-    B = int(rng.choice([1, 1, 3]))
-    m = Model(ob, nx, ny, B, rng)
+    nx, ny = shapes[rng.integers(len(shapes))]
+    B = int(rng.choice(list(stacks)))
+    use_fma = int(rng.integers(2)) if fma else 0
+    yield ("open", nx, ny, B, use_fma)
+    yield ("image", draw_images(rng, nx, ny, B))
+    kind, have_x = None, False
+    for step in range(steps):
+        ops = ["image", "assemble", "tune"]
+        if kind is not None:
+            ops += ["init", "set_field"]
+            if have_x:
+                ops += ["sweeps", "sweeps", "solve", "solve", "flux", "get", "residual"]
+                if with_cg:
+                    ops += ["cg", "cg"]
+                if onchip:
+                    ops += ["cg", "cg"]                      # (the seeds of the two forms are there for CG)
+                if ptr:
+                    ops += ["ptr"]
+                if slot:
+                    ops += ["slot"]
+                if stamps:
+                    ops += ["stamps"]
+        if stream and B >= 2:
+            ops += ["stream"]
+        op = ops[rng.integers(len(ops))]
+        if op == "image":
+            yield ("image", draw_images(rng, nx, ny, B))
+            kind = None
+        elif op == "assemble":
+            kind = ["2p", "2p", "3p", "D"][rng.integers(4)]
+            Ds, Df, Dg = ASSEMBLE_D[rng.integers(3)]
+            CL, CR = ASSEMBLE_C[rng.integers(2)]
+            yield ("assemble", kind, Ds, Df, Dg, CL, CR, draw_D_planes(rng, nx, ny, B, Ds, Df, Dg) if kind == "D" else None)
+        elif op == "tune":
+            what = rng.integers(9 if onchip else 5)         # (the key is drawn as often as the four blocked-pass keys together)
+            if what == 0:
+                yield ("tune", "tb_T", int(rng.choice([0, 2, 4, 8])))
+            elif what == 1:
+                yield ("tune", "tb_impl", int(rng.choice([0, 1, 2])))
+            elif what == 2:
+                yield ("tune", "tb_launch", int(rng.choice([0, 1])))
+            elif what == 3:
+                yield ("tune", "flux_reduce", int(rng.choice([0, 1])))
+            elif what == 4:
+                yield ("kernel", ["auto", "matfree_tb", "explicit", "matfree"][rng.integers(4)] if kind == "2p" else "auto")
+            else:
+                yield ("tune", "cg_onchip", int(rng.choice([0, 1, 1])))
+        elif op == "init":
+            yield ("init",)
+            have_x = True
+        elif op == "set_field":
+            yield ("set_field", [rng.random((ny, nx)) for _ in range(B)])
+            have_x = True
+        elif op == "sweeps":
+            k = int(rng.choice([1, 3, 8, 17, 40, 64]))
+            omega, kern = [(2.0 / 3.0, 0), (1.0, 1)][rng.integers(2)]
+            yield ("sweeps", k, omega, kern)
+        elif op == "solve":
+            tol = float(rng.choice(SOLVE_TOL))
+            max_iter = int(rng.choice(SOLVE_MAX_ITER))
+            ce = int(rng.choice(SOLVE_CE))
+            # what reads the stack after the solve.  Images of a stack stop at different sweeps and stay frozen in the buffer
+            # they stopped in until a reader consolidates them; deff_get_field is one such reader, and with "ptr" / "slot" the
+            # other two take its place in some solves: deff_device_field (consolidates itself) and deff_get_slot_field of
+            # every slot (reads each slot where it froze and leaves the stack as it is for the next call)
+            readers = ["get"] + (["ptr"] if ptr else []) + (["slot"] if slot else [])
+            yield ("solve", tol, max_iter, ce, readers[rng.integers(len(readers))] if len(readers) > 1 else "get")
+        elif op == "cg":
+            rtol = float(rng.choice([1e-6, 1e-10]))
+            max_iter = int(rng.choice([0, 3, 100000]))
+            yield ("cg", rtol, max_iter, int(rng.choice([1, 64])))
+        elif op == "stream":
+            count = int(rng.integers(B, 3 * B + 2))
+            imgs = draw_images(rng, nx, ny, count)
+            Ds, Df, _ = ASSEMBLE_D[rng.integers(3)]
+            CL, CR = ASSEMBLE_C[rng.integers(2)]
+            tol = float(rng.choice(SOLVE_TOL))
+            max_iter = int(rng.choice(SOLVE_MAX_ITER))
+            yield ("stream", imgs, Ds, Df, CL, CR, tol, max_iter, int(rng.choice(SOLVE_CE)))
+            kind, have_x = "2p", True
+        elif op == "slot":
+            yield ("slot", int(rng.integers(B)))
+        elif op == "stamps":
+            omega, kern = [(2.0 / 3.0, 0), (1.0, 1)][rng.integers(2)]
+            yield ("stamps", omega, kern)
+        else:
+            yield (op,)                                      # flux, get, residual, ptr: no arguments
+
+
+def stream_schedule(iters, B, max_iter, check_every):
+    """deff_solve_stream's bookkeeping on iteration counts alone (iters[i] = sweeps image i runs: oracle.jacobi's count).  All
+    slots share the check points; a free slot takes the next image one sweep before a check; an image leaves at the check
+    that stops it, or where it reaches max_iter between two checks.  Returns (slot of every image, the sweep count of the
+    stream at which it retired, the stream's last sweep)."""
+    n = len(iters)
+    slot_of, retired = [None] * n, [None] * n
+    live = {}                                                # slot -> [image, sweeps done]
+    nxt = t = 0
+
+    def refill():
+        nonlocal nxt
+        for k in range(B):
+            if k not in live and nxt < n:
+                live[k] = [nxt, 0]
+                slot_of[nxt] = k
+                nxt += 1
+
+    def advance(nsw):
+        nonlocal t
+        t += nsw
+        for k in list(live):
+            live[k][1] += nsw
+
+    def retire_done():
+        for k in list(live):
+            i, done = live[k]
+            assert done <= iters[i]
+            if done == iters[i]:
+                retired[i] = t
+                del live[k]
+
+    refill()
+    while live:
+        advance(1)
+        retire_done()                                        # the check
+        left = check_every - 1
+        while left > 0 and live:
+            seg = min([left] + [max_iter - done for _, done in live.values()])
+            if seg > 0:
+                advance(seg)
+                left -= seg
+            retire_done()                                    # max_iter between two checks
+        refill()
+    return slot_of, retired, t
+
+
+def device_rows(ptr, rows, pitch_bytes):
+    """rows x (pitch_bytes / 8) doubles from a device pointer, copied by the HIP runtime the library itself runs on (the one
+    already mapped into this process: a second copy of the runtime would not know the pointer)."""
+    import ctypes as C
+    path = None
+    with open("/proc/self/maps") as f:
+        for line in f:
+            if "libamdhip64" in line:
+                path = line.split()[-1]
+                break
+    assert path, "no HIP runtime mapped into this process"
+    hip = C.CDLL(path)
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipMemcpy.restype = C.c_int
+    assert pitch_bytes % 8 == 0
+    out = np.full((rows, pitch_bytes // 8), np.nan)
+    rc = hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), out.nbytes, 2)     # hipMemcpyDeviceToHost
+    assert rc == 0, rc
+    return out
+
+
+def expected_cg_impl(nx, ny, onchip_key):
+    return 2 if onchip_key == 1 and (nx + (nx & 1)) * ny <= ONCHIP_LIMIT else 1
+
+
+def tb_stamps(s, omega):
+    """deff_debug_tb_stamps: the sizing call, then the stamping one.  -> (pairs of the sizing call, pairs of the real call,
+    the words)."""
+    import ctypes as C
+    from effectivediffusivityfvm_amd import _capi
+    L = _capi.load()
+    n0 = C.c_int(-1)
+    _capi.check(L.deff_debug_tb_stamps(s._ctx, omega, None, C.byref(n0)))
+    buf = np.zeros(2 * n0.value, dtype=np.uint64)
+    n1 = C.c_int(-1)
+    _capi.check(L.deff_debug_tb_stamps(s._ctx, omega, buf.ctypes.data_as(C.c_void_p), C.byref(n1)))
+    return n0.value, n1.value, buf
+
+
+def run_sequence(pkg, ob, seed, with_cg=False, **options):
+    draw = draw_sequence(seed, with_cg=with_cg, **options)
+    _, nx, ny, B, use_fma = next(draw)
+    flavour = "fma" if use_fma else None
+    m = Model(ob, nx, ny, B, None)
     log = []
+    onchip_key = 0
     with pkg.Solver(nx, ny, nimg=B) as s:
         def fields_equal():
             got = s.get_field()
             for k in range(B):
                 assert np.array_equal(got[k * ny:(k + 1) * ny], m.x[k]), (seed, log, "field of image %d" % k)
 
-        m.new_image()
+        def device_field_equal():
+            # the pointer is taken on a settled context and the context is settled again before the copy below, which runs on
+            # the null stream: the context's stream does not wait for that one, and deff_device_field may have enqueued the
+            # copies that bring frozen images of a stack into the current buffer
+            s.synchronize()
+            p, pitch = s.device_field_ptr()
+            s.synchronize()
+            assert pitch == 8 * (nx + (nx & 1)), (seed, log, pitch)
+            got = device_rows(p, B * ny, pitch)
+            for k in range(B):
+                assert np.array_equal(got[k * ny:(k + 1) * ny, :nx], m.x[k]), (seed, log, "device field of image %d" % k)
+            if nx & 1:                                       # the pad cell holds 0 and is not part of the mesh (deff_amd.h)
+                assert np.array_equal(got[:, nx], np.zeros(B * ny)), (seed, log, "pad column", got[:, nx][got[:, nx] != 0][:4])
+
+        def slot_field_equal(k):
+            from effectivediffusivityfvm_amd import _capi
+            x = np.empty((ny, nx))
+            _capi.check(_capi.load().deff_get_slot_field(s._ctx, k, x))
+            assert np.array_equal(x, m.x[k]), (seed, log, "field of slot %d" % k)
+
+        if use_fma:
+            s.set_tuning("fma", 1)
+            log.append("fma 1")
+        m.pix = next(draw)[1]
         s.set_image(np.stack(m.pix))
-        for step in range(30):
-            ops = ["image", "assemble", "tune"]
-            if m.kind is not None:
-                ops += ["init", "set_field"]
-                if m.x is not None:
-                    ops += ["sweeps", "sweeps", "solve", "solve", "flux", "get", "residual"]
-                    if with_cg:
-                        ops += ["cg", "cg"]
-            op = ops[rng.integers(len(ops))]
+        for op, *args in draw:
             if op == "image":
-                m.new_image()
+                m.pix, m.kind = args[0], None
                 s.set_image(np.stack(m.pix))
                 log.append("image")
             elif op == "assemble":
-                kind = ["2p", "2p", "3p", "D"][rng.integers(4)]
-                Ds, Df, Dg = [(1e-3, 1.0, 10.0), (1e-2, 1.0, 50.0), (0.1, 2.0, 7.0)][rng.integers(3)]
-                CL, CR = [(0.0, 1.0), (0.25, 0.75)][rng.integers(2)]
-                m.assemble(kind, Ds, Df, Dg, CL, CR)
+                kind, Ds, Df, Dg, CL, CR, D = args
+                m.assemble(kind, Ds, Df, Dg, CL, CR, D)
+                m.phases = (Ds, Df, Dg)
                 if kind == "2p":
                     s.assemble_2phase(Ds, Df, CL, CR)
                 elif kind == "3p":
@@ -109,50 +331,50 @@ def run_sequence(pkg, ob, seed, with_cg=False):
                     s.assemble_from_D(m.stacked(m.D), CL, CR)
                 log.append(f"assemble {kind} {Ds} {Df} {CL}")
             elif op == "tune":
-                what = rng.integers(5)
-                if what == 0:
-                    v = int(rng.choice([0, 2, 4, 8])); s.set_tuning("tb_T", v); log.append(f"tb_T {v}")
-                elif what == 1:
-                    v = int(rng.choice([0, 1, 2])); s.set_tuning("tb_impl", v); log.append(f"tb_impl {v}")
-                elif what == 2:
-                    v = int(rng.choice([0, 1])); s.set_tuning("tb_launch", v); log.append(f"tb_launch {v}")
-                elif what == 3:
-                    v = int(rng.choice([0, 1])); s.set_tuning("flux_reduce", v); log.append(f"flux_reduce {v}")
-                else:
-                    k = ["auto", "matfree_tb", "explicit", "matfree"][rng.integers(4)] if m.kind == "2p" else "auto"
-                    s.set_kernel(k); log.append(f"kernel {k}")
+                key, v = args
+                s.set_tuning(key, v)
+                if key == "cg_onchip":
+                    onchip_key = v
+                log.append(f"{key} {v}")
+            elif op == "kernel":
+                s.set_kernel(args[0]); log.append(f"kernel {args[0]}")
             elif op == "init":
                 s.init_linear(m.CL, m.CR)
-                m.x = [ob.linear_guess(nx, ny, m.CL, m.CR) for _ in range(B)]
+                m.x = [ob.linear_guess(nx, ny, m.CL, m.CR, flavour=flavour) for _ in range(B)]
                 log.append("init")
             elif op == "set_field":
-                m.x = [rng.random((ny, nx)) for _ in range(B)]
+                m.x = args[0]
                 s.set_field(m.stacked(m.x))
                 log.append("set_field")
             elif op == "sweeps":
-                k = int(rng.choice([1, 3, 8, 17, 40, 64]))
-                omega, kern = [(2.0 / 3.0, 0), (1.0, 1)][rng.integers(2)]
+                k, omega, kern = args
                 s.sweeps(k, omega)
-                m.x = [ob.sweeps(m.A[i], m.b[i], m.x[i], k, kernel=kern, omega=omega) for i in range(B)]
+                m.x = [ob.sweeps(m.A[i], m.b[i], m.x[i], k, kernel=kern, omega=omega, flavour=flavour) for i in range(B)]
                 log.append(f"sweeps {k} {omega:.3f}")
                 fields_equal()
             elif op == "solve":
-                tol = float(rng.choice([1e-2, 1e-4, 1e-12]))
-                max_iter = int(rng.choice([1, 7, 100, 101, 130, 301]))
-                ce = int(rng.choice([7, 50, 100]))
+                tol, max_iter, ce, reader = args
                 res = s.solve(tol, max_iter, check_every=ce)
                 res = [res] if B == 1 else res
                 log.append(f"solve {tol} {max_iter} {ce}")
                 for i in range(B):
-                    it, deff, conv, x, MFL, MFR = ob.jacobi(m.A[i], m.b[i], m.x[i], m.D[i], m.CL, m.CR, tol, max_iter, check_every=ce)
+                    it, deff, conv, x, MFL, MFR = ob.jacobi(m.A[i], m.b[i], m.x[i], m.D[i], m.CL, m.CR, tol, max_iter, check_every=ce,
+                                                            flavour=flavour)
                     assert (res[i].iters, res[i].deff_raw, res[i].conv) == (it, deff, conv), (seed, log, i)
                     m.x[i] = x
-                fields_equal()
+                if reader == "ptr":
+                    log[-1] += " then ptr"
+                    device_field_equal()
+                elif reader == "slot":
+                    log[-1] += " then slots"
+                    for k in range(B):
+                        slot_field_equal(k)
+                else:
+                    fields_equal()
             elif op == "cg":
-                rtol = float(rng.choice([1e-6, 1e-10]))
-                max_iter = int(rng.choice([0, 3, 100000]))
-                ce = int(rng.choice([1, 64]))
+                rtol, max_iter, ce = args
                 log.append(f"cg {rtol} {max_iter} {ce}")
+                before = m.stacked(m.x)
                 try:
                     res = s.solve_cg(rtol=rtol, max_iter=max_iter, check_every=ce)
                 except pkg.DeffError as e:
@@ -164,8 +386,30 @@ def run_sequence(pkg, ob, seed, with_cg=False):
                     log[-1] += " refused"
                     fields_equal()
                     continue
+                if options.get("onchip"):
+                    assert s.plan_value("cg_impl") == expected_cg_impl(nx, ny, onchip_key), (seed, log, onchip_key)
+                    log[-1] += " impl %d" % expected_cg_impl(nx, ny, onchip_key)
                 res = [res] if B == 1 else res
                 got = s.get_field()
+                if options.get("onchip"):
+                    # nothing of the context's history is in the result: a fresh context with the same system, the same field
+                    # and the same form gives the same bits -- under the OTHER check interval, which the results do not depend
+                    # on (deff_amd.h); the forms share cg_p[0], the per-image scalars and the restart flag between calls
+                    with pkg.Solver(nx, ny, nimg=B) as f:
+                        f.set_tuning("cg_onchip", onchip_key)
+                        f.set_image(np.stack(m.pix))
+                        if m.kind == "2p":
+                            f.assemble_2phase(m.phases[0], m.phases[1], m.CL, m.CR)
+                        elif m.kind == "3p":
+                            f.assemble_3phase(*m.phases, m.CL, m.CR)
+                        else:
+                            f.assemble_from_D(m.stacked(m.D), m.CL, m.CR)
+                        f.set_field(before)
+                        res_f = f.solve_cg(rtol=rtol, max_iter=max_iter, check_every=1 if ce == 64 else 64)
+                        res_f = [res_f] if B == 1 else res_f
+                        assert f.plan_value("cg_impl") == s.plan_value("cg_impl")
+                        assert [(r.iters, r.rel_residual, r.deff_raw) for r in res_f] == [(r.iters, r.rel_residual, r.deff_raw) for r in res], (seed, log)
+                        assert np.array_equal(f.get_field(), got), (seed, log, "CG on a fresh context")
                 for i in range(B):
                     x = got[i * ny:(i + 1) * ny].copy()
                     rn = residual_np(m.A[i], m.b[i], x, nx, ny)
@@ -196,6 +440,64 @@ def run_sequence(pkg, ob, seed, with_cg=False):
                         ob.assert_residual(got[i], m.x[i], m.D[i], m.CL, m.CR)
                     except AssertionError as e:
                         raise AssertionError((seed, log, i, e.args))
+            elif op == "stream":
+                # the model step of deff_solve_stream: every image is a one-image run of the reference loop from the linear
+                # guess, and afterwards slot k is an ordinary image of the stack -- the last one that ran there, the call's
+                # 2-phase system, that image's final field (deff_amd.h)
+                imgs, Ds, Df, CL, CR, tol, max_iter, ce = args
+                log.append(f"stream {len(imgs)} {Ds} {Df} {CL} {tol} {max_iter} {ce}")
+                res = s.solve_stream(imgs, Ds, Df, CL, CR, tol, max_iter, check_every=ce, want_fields=True)
+                assert len(res) == len(imgs)
+                want = []
+                for i, pix in enumerate(imgs):
+                    D = ob.fill_D_2phase(pix, Df, Ds)
+                    A, b = ob.discretize(D, CL, CR)
+                    it, deff, conv, x, _, _ = ob.jacobi(A, b, ob.linear_guess(nx, ny, CL, CR, flavour=flavour), D, CL, CR, tol, max_iter,
+                                                        check_every=ce, flavour=flavour)
+                    assert (res[i].iters, res[i].deff_raw, res[i].conv) == (it, deff, conv), (seed, log, i)
+                    assert np.array_equal(res[i].field, x), (seed, log, "stream image %d" % i)
+                    want.append((D, A, b, x))
+                slot_of, retired, end = stream_schedule([r.iters for r in res], B, max_iter, ce)
+                assert [r.slot for r in res] == slot_of, (seed, log, [r.slot for r in res], slot_of)
+                last = {k: i for i, k in enumerate(slot_of)}                     # the last image of every slot
+                assert sorted(last) == list(range(B))
+                log[-1] += " early %s" % [k for k in range(B) if retired[last[k]] < end]
+                m.pix = [imgs[last[k]] for k in range(B)]
+                m.D, m.A, m.b = ([want[last[k]][j] for k in range(B)] for j in range(3))
+                m.x = [want[last[k]][3] for k in range(B)]
+                m.CL, m.CR, m.kind, m.phases = CL, CR, "2p", (Ds, Df, None)
+                fields_equal()
+            elif op == "ptr":
+                log.append("ptr")
+                device_field_equal()
+            elif op == "slot":
+                log.append(f"slot {args[0]}")
+                slot_field_equal(args[0])
+            elif op == "stamps":
+                omega, kern = args
+                log.append(f"stamps {omega:.3f}")
+                try:
+                    n0, n1, words = tb_stamps(s, omega)
+                except pkg.DeffError as e:
+                    assert e.code == -5 and "not on the temporally blocked kernel" in str(e), (seed, log, e)
+                    assert s.kernel_in_use() != "matfree_tb", (seed, log)
+                    log[-1] += " refused"
+                    fields_equal()
+                    continue
+                assert s.kernel_in_use() == "matfree_tb", (seed, log)
+                p = s.plan()
+                resident = p["tb_impl"] == 2 and p["tb_resident"] == 1
+                # where a tile's first clock lies: streaming form 2 words per wave tile; workgroup tiles T + 4 words per tile,
+                # resident ones 12 (the last pair may be half padding)
+                per = 2 if p["tb_impl"] == 1 else 12 if resident else p["tb_T"] + 4
+                starts = words[:len(words) // per * per:per]
+                assert n0 == n1 and n0 > 0 and len(starts) > 0 and np.all(starts != 0), (seed, log, n0, n1, p, np.flatnonzero(starts == 0)[:8])
+                nsw = p["tb_T"] * (3 if resident else 1)
+                log[-1] += f" T {p['tb_T']} sweeps {nsw}"
+                m.x = [ob.sweeps(m.A[i], m.b[i], m.x[i], nsw, kernel=kern, omega=omega, flavour=flavour) for i in range(B)]
+                fields_equal()
+            else:
+                raise AssertionError(op)
         if m.x is not None:
             fields_equal()
         assert s.plan_value("tb_fallbacks") == 0
@@ -210,6 +512,127 @@ def test_random_call_sequences_match_the_oracle(pkg, oracle, seed):
 @pytest.mark.parametrize("seed", range(24))
 def test_random_call_sequences_with_cg(pkg, oracle, seed):
     run_sequence(pkg, oracle, 2000 + seed, with_cg=True)
+
+
+# The rest of the ABI, each group of options on its own seeds (tests/test_sequences_host.py counts what these seeds reach).
+# Shapes of the on-chip seeds: most fit one compute unit (row pitch x ny <= 16 384: an odd width, and 128 x 128 exactly at the
+# limit), (130, 128) and (256, 130) do not and keep the streaming kernels whatever the key says.
+ONCHIP_SHAPES = [(64, 48), (97, 41), (128, 128), (40, 300), (130, 70), (33, 21), (130, 128), (256, 130)]
+ABI_SHAPES = [(64, 48), (130, 70), (97, 41), (256, 130), (40, 300), (129, 200)]
+ONCHIP_SEEDS = dict(first=3000, count=48, with_cg=True, shapes=ONCHIP_SHAPES, steps=40, onchip=True)
+STREAM_SEEDS = dict(first=4000, count=48, shapes=ABI_SHAPES, stacks=(2, 3, 4), stream=True, ptr=True, slot=True, stamps=True)
+FMA_SEEDS = dict(first=6000, count=24, shapes=ABI_SHAPES, stacks=(1, 2, 3), stream=True, ptr=True, slot=True, stamps=True, fma=True)
+
+
+def seed_options(group):
+    return {k: v for k, v in group.items() if k not in ("first", "count")}
+
+
+@pytest.mark.parametrize("seed", range(ONCHIP_SEEDS["count"]))
+def test_random_call_sequences_with_both_cg_forms(pkg, oracle, seed):
+    run_sequence(pkg, oracle, ONCHIP_SEEDS["first"] + seed, **seed_options(ONCHIP_SEEDS))
+
+
+@pytest.mark.parametrize("seed", range(STREAM_SEEDS["count"]))
+def test_random_call_sequences_with_streams_pointers_slots_and_stamps(pkg, oracle, seed):
+    run_sequence(pkg, oracle, STREAM_SEEDS["first"] + seed, **seed_options(STREAM_SEEDS))
+
+
+@pytest.mark.parametrize("seed", range(FMA_SEEDS["count"]))
+def test_random_call_sequences_with_contracted_arithmetic(pkg, oracle, seed):
+    run_sequence(pkg, oracle, FMA_SEEDS["first"] + seed, **seed_options(FMA_SEEDS))
+
+
+def test_cg_ignores_the_fma_key(pkg, oracle):
+    """api_cg.hip: "the fma knob does not apply here".  Both CG forms on a context with fma = 1 give the bits of one with
+    fma = 0 -- iterations, residual, Deff, wall fluxes and field -- from the same caller's field (the linear guess itself is
+    the one thing the key changes before a CG call, so it is not used here)."""
+    nx, ny = 97, 41
+    pix = oracle.synth_mask(nx, ny, 777, 0)
+    x0 = np.random.default_rng(5).random((ny, nx))
+    for onchip_key in (0, 1):
+        got = []
+        for fma in (0, 1):
+            with pkg.Solver(nx, ny) as s:
+                s.set_tuning("fma", fma)
+                s.set_tuning("cg_onchip", onchip_key)
+                s.set_image(pix)
+                s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+                s.set_field(x0)
+                r = s.solve_cg(rtol=1e-10, max_iter=100000)
+                assert r.converged and s.plan_value("cg_impl") == 1 + onchip_key
+                got.append((r.iters, r.rel_residual, r.deff_raw, r.MFL.copy(), r.MFR.copy(), s.get_field()))
+        a, b = got
+        assert a[:3] == b[:3] and all(np.array_equal(u, v) for u, v in zip(a[3:], b[3:])), (onchip_key, a[:3], b[:3])
+
+
+@pytest.mark.parametrize("launch,T", [(0, 4), (0, 8), (1, 4), (1, 8)])     # workgroup tiles exist for passes of 4 and 8
+def test_stamps_advance_one_pass_or_three_on_a_resident_plan(pkg, oracle, launch, T):
+    """deff_debug_tb_stamps by construction on both kinds of plan, so that the 3 T of deff_amd.h does not rest on what the
+    seeds happen to draw: workgroup tiles of a small stack are resident under tb_launch 0 (the field advances by three
+    passes) and one launch per pass under tb_launch 1 (one pass)."""
+    nx, ny, B = 97, 41, 2
+    rng = np.random.default_rng(11 + T)
+    pix = [np.where(rng.random((ny, nx)) < 0.5, 0, 255).astype(np.uint8) for _ in range(B)]
+    x0 = [rng.random((ny, nx)) for _ in range(B)]
+    with pkg.Solver(nx, ny, nimg=B, kernel="matfree_tb") as s:
+        s.set_tuning("tb_impl", 2); s.set_tuning("tb_launch", launch); s.set_tuning("tb_T", T)
+        s.set_image(np.stack(pix))
+        s.assemble_2phase(1e-2, 1.0, 0.0, 1.0)
+        s.set_field(np.concatenate(x0, axis=0))
+        n0, n1, words = tb_stamps(s, 2.0 / 3.0)
+        p = s.plan()
+        assert (p["tb_impl"], p["tb_T"], p["tb_resident"]) == (2, T, 1 - launch), p
+        per = 12 if p["tb_resident"] else T + 4
+        assert n0 == n1 > 0 and np.all(words[:len(words) // per * per:per] != 0), (n0, n1)
+        got = s.get_field()
+        for k in range(B):
+            A, b = oracle.discretize(oracle.fill_D_2phase(pix[k], 1.0, 1e-2), 0.0, 1.0)
+            assert np.array_equal(got[k * ny:(k + 1) * ny], oracle.sweeps(A, b, x0[k], T * (3 if p["tb_resident"] else 1))), (p, k)
+        assert s.plan_value("tb_fallbacks") == 0
+
+
+@pytest.mark.parametrize("reader", ["ptr", "slots"])
+def test_device_field_and_slot_reads_of_a_stack_with_frozen_images(pkg, oracle, reader):
+    """A batch solve leaves an image that stopped early in the buffer it stopped in.  deff_device_field has to bring it into
+    the buffer it hands out, and deff_get_slot_field has to read it where it is and leave the stack as it found it -- with
+    no deff_get_field in between, which would do the work for them.  One image of three stops at its second check (parallel
+    stripes: the wall fluxes settle after one sweep), the others run to max_iter, on the single-sweep kernel (one buffer flip
+    per sweep) for two consecutive max_iter: both parities of the flips after the early stop."""
+    nx, ny, B, ce = 97, 41, 3, 10
+    rng = np.random.default_rng(99)
+    pix = [np.where(rng.random((ny, nx)) < p, 0, 255).astype(np.uint8) for p in (0.45, 0.5, 0.6)]
+    pix[1][:] = 255
+    pix[1][:10, :] = 0
+    for max_iter in (ce + 2, ce + 3):
+        want, iters, sys_ = [], [], []
+        for k in range(B):
+            D = oracle.fill_D_2phase(pix[k], 1.0, 1e-2)
+            A, b = oracle.discretize(D, 0.25, 0.75)
+            it, _, _, x, _, _ = oracle.jacobi(A, b, oracle.linear_guess(nx, ny, 0.25, 0.75), D, 0.25, 0.75, 1e-6, max_iter, check_every=ce)
+            want.append(x); iters.append(it); sys_.append((A, b))
+        assert iters == [max_iter, ce + 1, max_iter]
+        with pkg.Solver(nx, ny, nimg=B, kernel="matfree") as s:
+            s.set_image(np.stack(pix))
+            s.assemble_2phase(1e-2, 1.0, 0.25, 0.75)
+            s.init_linear(0.25, 0.75)
+            res = s.solve(1e-6, max_iter, check_every=ce)
+            assert [r.iters for r in res] == iters
+            if reader == "ptr":
+                p, pitch = s.device_field_ptr()
+                s.synchronize()
+                got = device_rows(p, B * ny, pitch)[:, :nx]
+            else:
+                from effectivediffusivityfvm_amd import _capi
+                got = np.empty((B * ny, nx))
+                for k in range(B):
+                    _capi.check(_capi.load().deff_get_slot_field(s._ctx, k, got[k * ny:(k + 1) * ny]))
+            for k in range(B):
+                assert np.array_equal(got[k * ny:(k + 1) * ny], want[k]), (max_iter, k)
+            s.sweeps(3)                                      # and the stack goes on from every image's final field
+            got = s.get_field()
+            for k in range(B):
+                assert np.array_equal(got[k * ny:(k + 1) * ny], oracle.sweeps(sys_[k][0], sys_[k][1], want[k], 3)), (max_iter, k)
 
 
 def run_slab_sequence(pkg, ob, seed):
