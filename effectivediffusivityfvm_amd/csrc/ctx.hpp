@@ -2,8 +2,12 @@
 // helpers, the internal entry points that cross files and the reference's stopping rule
 // (JacobiCheck, check_step, deff_of_fluxes), which every Jacobi solve loop uses.
 //   api_core.hip   library, context lifecycle, image, assembly (native / from D / imported), field
-//   api_solve.hip  row dictionary, launch plans, sweeps, wall fluxes, the solve loops (one image,
-//                  batch, streaming batch)
+//   api_dict.hip   the row dictionary harvested from an explicit system
+//   api_sweep.hip  everything that plans or launches a sweep: the planner, the dealt tiles, the resident-launch
+//                  protocol, the launchers, deff_sweeps; the streaming and single-sweep kernels
+//   tiles_8wave.hip, tiles_tall.hip, tiles_12wave.hip
+//                  the workgroup-tile kernels, one family each, listed for the planner (tile_kernels.hpp)
+//   api_solve.hip  wall fluxes and the Jacobi solve loops (one image, batch, streaming batch); no sweep kernel
 //   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
@@ -161,7 +165,7 @@ struct deff_ctx {
     // passes between two checks are ONE launch whose tiles keep their matrix rows and owned cells in registers and wait
     // for their neighbours only.  Tuning key "tb_launch": 0 = resident passes whenever the tiles are co-resident (default:
     // the grid fits the chip by the occupancy query, resident launches of one process are chained per device,
-    // api_solve.hip, so that two of them never share the chip, and every wait is bounded); 1 = never (one launch per pass).
+    // api_sweep.hip, so that two of them never share the chip, and every wait is bounded); 1 = never (one launch per pass).
     // What the process cannot rule out -- another PROCESS on the same GPU, a CU mask -- ends in a bounded wait running
     // out; the solve then restores the field it had when the interval's first resident launch was enqueued, redoes the
     // interval with one launch per pass and stays in that mode (res_fallbacks counts these; deff_get_plan "tb_fallbacks").
@@ -188,13 +192,13 @@ struct deff_ctx {
     bool chain_counted = false;                  // this context is counted among its device's users of the resident chain's event
     int fma = 0;                                 // contracted arithmetic (kernels_sweep.hpp), opt-in
     int tb_xmajor = 1;                           // wave-tile numbering of the temporally blocked kernel
-    // Streaming kernel, chunk heights by service order (deal_ranked_tiles, api_solve.hip): 0 = equal chunks, 1 = dealt tiles.
+    // Streaming kernel, chunk heights by service order (deal_ranked_tiles, api_sweep.hip): 0 = equal chunks, 1 = dealt tiles.
     // tb_rank_w: the relative speed (per mille) of a SIMD's oldest / second / youngest wave, tb_rank_wall: what a row of a wall strip
     // costs, per mille of an inner strip's (its waves look up b as well)
-    int tb_tall_deal = 1;                        // tall tiles: rows dealt by the waves' age where a kernel for it exists (api_solve.hip, TILES)
+    int tb_tall_deal = 1;                        // tall tiles: rows dealt by the waves' age where a kernel for it exists (tiles_tall.hip)
     int plan_aged = 0;
-    int tb_sym_age = 1;                          // 12-wave tiles: the shapes with a row less for the youngest waves (api_solve.hip, TILES)
-    int tb_sym_shape = 0;                        // tests: 1-based index into the 12-wave shapes of T = 8 in TILES (0: the planner's choice)
+    int tb_sym_age = 1;                          // 12-wave tiles: the shapes with a row less for the youngest waves (tiles_12wave.hip)
+    int tb_sym_shape = 0;                        // tests: 1-based index into the 12-wave shapes of T = 8 in TILES_12WAVE (0: the planner's choice)
     int tb_ranked = 1;
     int tb_rank_w[3] = {460, 325, 215};
     int tb_rank_wall = 1100;
@@ -335,7 +339,7 @@ struct SweepPlan {
     bool guard = false;                                   // streaming kernel: the reference's non-zero link test
     double omega = 0;                                     // as given to plan_sweeps (omw = 1 - omega)
     int impl = 1;                                         // 1 = streaming kernel, 2 = workgroup tiles
-    const TileKernel *tile = nullptr;                     // impl 2: the tile's kernels, waves and rows (api_solve.hip, TILES)
+    const TileKernel *tile = nullptr;                     // impl 2: the tile's kernels, waves and rows (tile_kernels.hpp)
     const int4 *dealt = nullptr;                          // streaming kernel: dealt tiles (chunk heights by service order), or none
     bool resident = false;                                // impl 2 only: all passes of a batch in one launch (k_sweep_wgres)
     // rows the plan updates: band_h > 0 restricts it to the band [band_lo, band_lo + band_h) of the context's owned rows
@@ -395,20 +399,24 @@ void build_lut_rows(deff_ctx *c, double Ds, double Df, double CL, double CR);
 int upload_lut(deff_ctx *c, double omega);
 int consolidate(deff_ctx *c);
 int explicit_from_image(deff_ctx *c);
-// api_solve.hip
+// api_dict.hip
+int ensure_dictionary(deff_ctx *c);                      // harvest the row dictionary of an explicit system, if allowed
+// api_sweep.hip
 int default_tb_T(const deff_ctx *c);
 int clamp_tb_T(int T);
 int default_tb_impl(const deff_ctx *c);
 int plan_sweeps(deff_ctx *c, double omega, SweepPlan *pl);
+// a stream has put new images into slots: plan again, or verify again, what the plan took from the old codes
+int replan_for_new_codes(deff_ctx *c, double omega, SweepPlan *pl);
 void enqueue_sweep(deff_ctx *c, const SweepPlan &pl);
 int enqueue_tb_pass(deff_ctx *c, const SweepPlan &pl);
 int launch_tb_pass(deff_ctx *c, const SweepPlan &pl);    // the same launch without flipping x[cur]
-int dealt_watch(deff_ctx *c);
-int ensure_dictionary(deff_ctx *c);                      // harvest the row dictionary of an explicit system, if allowed                            // after a synchronisation: is the dispatch order the dealt tiles assume?
+int dealt_watch(deff_ctx *c);                            // after a synchronisation: is the dispatch order the dealt tiles assume?
 int enqueue_sweeps(deff_ctx *c, const SweepPlan &pl, int64_t n);   // stops at the first launch that fails
 // did a resident launch give up waiting?  (synchronises if one is pending; on an abort the interval is redone with one
 // launch per pass and the context stays in that mode)
 int resident_check(deff_ctx *c);
 void resident_chain_ctx_created(int device);
 void resident_chain_ctx_destroyed(int device);
+// api_solve.hip
 int flux_rows(deff_ctx *c, bool need_rows = true);

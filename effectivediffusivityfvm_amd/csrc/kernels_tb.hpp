@@ -216,7 +216,7 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
     // tiles end at 71 / 89 / 108 us of one T = 8 launch at 4096^2, by wave slot.  Evening that out with s_setprio -- a
     // rotating priority per group of steps -- brought +2...4 %: served in turn the three waves issue less in total than served
     // oldest-first.  What is kept is the other way round: the service order stays and the TILES differ, the oldest wave of a
-    // SIMD getting the tallest chunk -- `dealt` below, deal_ranked_tiles in api_solve.hip: +6...8 %.)
+    // SIMD getting the tallest chunk -- `dealt` below, deal_ranked_tiles in api_sweep.hip: +6...8 %.)
     // One group of three steps (input rows r, r+1, r+2).  TRIM = the group may contain levels whose
     // output row this chunk does not need: sweep t needs rows from max(mesh top, ry0 - (T - t)) on, and
     // produces row rr - t at the step that reads row rr, so for the first 2T steps of a chunk (T at the
@@ -326,7 +326,7 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(cons
     // written by lane 0 after the tile and read by nobody on the device
     const unsigned long long t_begin = stamps ? wall_clock64() : 0ull;
     if (dealt) {
-        // Dealt tiles (one tile per wave; plan_streaming / deal_ranked_tiles in api_solve.hip): wave `wave` of workgroup
+        // Dealt tiles (one tile per wave; plan_streaming / deal_ranked_tiles in api_sweep.hip): wave `wave` of workgroup
         // blockIdx.x runs the chunk the host wrote at dealt[4 * blockIdx.x + wave] = (strip | image << 16, first row, rows, stamp index) --
         // chunk heights then follow the order in which a SIMD serves its waves.  rows = 0: nothing for this wave.
         const int4 d = dealt[(size_t)blockIdx.x * 4u + (unsigned)wave];

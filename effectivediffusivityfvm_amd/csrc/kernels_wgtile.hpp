@@ -344,35 +344,6 @@ __global__ __launch_bounds__(WGT_WAVES * 64, 2) void k_sweep_wgtile(const double
 constexpr int WGL_WAVES = 16;
 constexpr int wgl_rows_owned(int T, int R) { return WGL_WAVES * R - 2 * T; }
 
-// Is the system behind (dictionary, codes) link-symmetric the way wgl_sweeps' short-cut needs it?  For every cell: the E link
-// of an even column equals, bit for bit, the W link of the odd column next to it (a lane's two cells), and the N link of a
-// row equals the S link of the row above it in the same image.  The native assemblies are (fvm_row: a face has one
-// harmonic mean); a dictionary harvested from somebody's matrix need not be.  Raises *flag on the first mismatch.
-__global__ __launch_bounds__(256) void k_links_symmetric(const double *__restrict__ lut_g, const uint16_t *__restrict__ code,
-                                                         int nx, int rows, int ny, int nrows, unsigned *flag)
-{
-    __shared__ double lut[LUT_DOUBLES];
-    load_lut(lut, lut_g, nrows);
-    constexpr int PS = LUT_PLANE_STRIDE * 8;
-    const size_t n = (size_t)nx * rows;
-    bool bad = false;
-    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (size_t)gridDim.x * 256) {
-        const int r = (int)(p / nx), c = (int)(p - (size_t)r * nx);
-        const char *me = reinterpret_cast<const char *>(lut) + code[p];
-        if (!(c & 1) && c + 1 < nx) {
-            const char *east = reinterpret_cast<const char *>(lut) + code[p + 1];
-            bad |= __double_as_longlong(*reinterpret_cast<const double *>(me + 2 * PS)) !=
-                   __double_as_longlong(*reinterpret_cast<const double *>(east + PS));
-        }
-        if (r % ny != 0) {
-            const char *north = reinterpret_cast<const char *>(lut) + code[p - nx];
-            bad |= __double_as_longlong(*reinterpret_cast<const double *>(me + 4 * PS)) !=
-                   __double_as_longlong(*reinterpret_cast<const double *>(north + 3 * PS));
-        }
-    }
-    if (bad) atomicOr(flag, 1u);
-}
-
 // SYM = the system is link-symmetric (compile-time: both row loops in one kernel cost the tall tiles their registers --
 // 2048^2 fell from 950 to 470 G with a run-time flag).
 template <int T, int R, bool FMA, bool GUARD, bool WALL, bool SYM>
@@ -525,7 +496,7 @@ __device__ __forceinline__ void wgl_sweeps(double2 (&xr)[R], const unsigned *cod
 // workgroup, 168 VGPRs) hold a tile.  A link belongs to a face: the W link of a lane's second cell IS the E link of its
 // first, and the N links of a row ARE the S links of the row above it, which the same wave holds (row 0 of a wave keeps
 // its own N links: 4 VGPRs per wave).  Same values, so the same bits -- provided the system at hand really is
-// link-symmetric, which k_links_symmetric verifies on the device per assembly (api_solve.hip, plan key tb_sym), exactly as
+// link-symmetric, which k_links_symmetric verifies on the device per assembly (api_sweep.hip, plan key tb_sym), exactly as
 // for the tall tiles' 7-lookup rows.  What it buys: an FP64 instruction issues every ~5.0 clocks from three waves of a SIMD
 // against ~6.1 from two (tools/ubench), and a tile of 12 x R rows has the shape of an 8-wave tile of 1.5 R rows:
 // one 1024^2 image is 9 x 24 tiles of 12 x 5 rows (44 owned) instead of 9 x 26 of 8 x 7 (40 owned).
@@ -688,7 +659,7 @@ __device__ __forceinline__ void wgs_sweeps(double2 (&xr)[R], const WgsCoef<R> &k
 //   boundary orders it after everything before.  `base` grows by npass from launch to launch, so stale flags are always
 //   smaller than anything waited for.
 // Forward progress: the host launches at most as many workgroups as the occupancy query says are co-resident and never
-// two resident kernels of one process on one device at a time (api_solve.hip), and every wait is bounded -- a lane that
+// two resident kernels of one process on one device at a time (api_sweep.hip), and every wait is bounded -- a lane that
 // has polled for WGR_TIMEOUT of the 100 MHz wall clock, or that sees *abort_flag set, raises *abort_flag and its workgroup
 // returns; so does, within one poll, every workgroup waiting anywhere.  The host checks the flag at its next
 // synchronisation, restores the field the interval started from and redoes it with one launch per pass (resident_check).
@@ -784,7 +755,7 @@ __device__ __forceinline__ void wgres_body(double *lut, double2 (&edge)[2][NW][2
     const int ry0 = own0 + (bty - img * cpi) * ly;
     const int ry1 = min(ry0 + ly, own0 + own_h);
     // a tall tile keeps no rows above the first row of its image (there is no halo beyond a wall): its 16R rows then reach
-    // T rows further down, which is what lets ONE tile hold a whole 128-row image (api_solve.hip, wgl_row_tiles)
+    // T rows further down, which is what lets ONE tile hold a whole 128-row image (api_sweep.hip, wgl_row_tiles)
     const int w0 = (TALL ? max(ry0 - T, row_lo) : ry0 - T) + first;
     const int ld_lo = max(ry0 - T, row_lo), ld_hi = min(ry1 + T, row_hi);
     const int col = tx * WOUT - shift + 2 * lane;

@@ -1,5 +1,5 @@
 """Dealt tiles of the streaming kernel (round 4): chunk heights follow the order in which a SIMD serves its waves
-(deal_ranked_tiles, api_solve.hip) -- a table of (strip, first row, rows) per wave replaces the equal chunks.  Whatever the
+(deal_ranked_tiles, api_sweep.hip) -- a table of (strip, first row, rows) per wave replaces the equal chunks.  Whatever the
 table says, every row must be swept exactly once: the results are the oracle's and those of equal chunks, bit for bit, for
 ragged shapes, both pass lengths, skewed weights, many and few chunks per strip."""
 import numpy as np

@@ -12,13 +12,14 @@ import pytest
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "effectivediffusivityfvm_amd", "csrc")
+SWEEP_UNITS = ("tiles_tall", "tiles_8wave", "tiles_12wave", "api_sweep")     # csrc/Makefile: the units that hold sweep kernels
 
 
 def remarks_of(unit):
     """The compiler's resource remarks of one translation unit: from the in-tree build if it is up to date (the Makefile keeps
     them as build/<unit>.usage.txt), else from a compile of its own."""
     kept = os.path.join(CSRC, "build", unit + ".usage.txt")
-    sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
+    sources = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f == unit + ".hip" or f.endswith(".hpp")]   # (the Makefile's rule)
     if os.path.exists(kept) and os.path.getsize(kept) > 0 and os.path.getmtime(kept) >= max(os.path.getmtime(f) for f in sources):
         return open(kept, errors="replace").read()
     r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -32,7 +33,7 @@ def remarks_of(unit):
 @pytest.fixture(scope="module")
 def usage():
     out, cur = {}, None
-    for line in remarks_of("api_solve").splitlines():
+    for line in "\n".join(remarks_of(unit) for unit in SWEEP_UNITS).splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             cur = out.setdefault(m.group(1), {})
@@ -77,7 +78,7 @@ def test_streaming_blocked_kernel_keeps_its_waves(usage):
 
 
 def test_experiment_kernels_are_not_in_the_library(usage):
-    """The paired-wave form and the A/B branches of round 3 live in tools/experiments/, not in the shipped translation unit."""
+    """The paired-wave form and the A/B branches of round 3 live in tools/experiments/, not in the shipped translation units."""
     assert not [k for k in usage if "matfree_tb2" in k]
 
 
