@@ -1,10 +1,12 @@
-// api_cg.hip -- deff_solve_cg: Jacobi-preconditioned conjugate gradients to a residual tolerance (kernels_cg.hpp).  Not the
+// api_cg.hip -- deff_solve_cg: Jacobi-preconditioned conjugate gradients to a residual tolerance (kernels_cg.hpp), and
+// deff_solve_cg_stream: the same solve through the refilled slots of a stack (kernels_cg_stream.hpp, second half).  Not the
 // reference's algorithm: it reaches the same discrete fixed point (same A, b, wall-flux Deff) as the weighted Jacobi loop of
 // deff_solve, in far fewer iterations.  Nothing of the Jacobi path is touched: its tables (lut, c0 plane), plans and knobs
 // stay as they are (the "fma" knob does not apply here: CG's arithmetic is written-order FP64 only).
 #include "ctx.hpp"
 #include "kernels_cg.hpp"
 #include "kernels_cg_image.hpp"
+#include "kernels_cg_stream.hpp"
 #include <vector>
 
 // true-residual rounds that may restart the recurrence of a finished image (each round costs one pass and a synchronisation)
@@ -191,6 +193,289 @@ try {
         out[i].loop_ms = ms;
         out[i].converged = hs[i].rel <= rtol;
     }
+    return DEFF_OK;
+}
+DEFF_API_CATCH
+
+// ---- deff_solve_cg_stream -----------------------------------------------------------------------------------------------
+//
+// The slot life cycle of deff_solve_stream around the CG iteration: every slot of a stack context iterates its own image,
+// stops by its own rule on the device, has its true residual checked (and is sent back, up to CG_MAX_RESTARTS times, when it
+// misses rtol) and is refilled with the next image -- while the other slots go on.  Per image the arithmetic is that of a
+// one-image deff_solve_cg from the linear guess (kernels_cg_stream.hpp, "Determinism").
+//
+// The GPU does not wait for the host: the iteration work of interval i + 1 (one k_cg_image launch, or check_every x 4
+// streaming launches) is enqueued BEFORE the host looks at the slot states interval i left behind; those arrive through an
+// asynchronous copy into pinned memory and an event.  A slot found stopped is frozen (every iteration kernel skips it), so
+// its true-residual round, flux, `done` callback, upload and entry kernels queue up behind interval i + 1 and the slot
+// rejoins at interval i + 2; until then the snapshots still show its old state and are not read for it (`valid_from`).
+// Launches and waits per interval do not depend on how many slots retire or enter: the slot-list kernels take them all.
+
+namespace {
+
+struct CgsBuffers {                                    // views into c->cgs_dev / c->cgs_pin
+    int *d_fin, *d_rounds, *d_new;                     // device: the round's list, restart rounds per slot, the entering list
+    uint8_t *d_pix;                                    // ... followed by the entering images' pixels (one H2D copy for both)
+    int *h_fin, *h_new;
+    uint8_t *h_pix;
+    CgScal *h_snap[2];
+    unsigned *h_flags[2];
+    CgScal *h_round;
+    double *h_q;
+};
+
+size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+int cgs_buffers(deff_ctx *c, size_t npix, CgsBuffers *b)
+{
+    const size_t B = (size_t)c->nimg;
+    const size_t stage = round16(sizeof(int) * B + npix * B);
+    const size_t dev = round16(sizeof(int) * B) * 2 + stage;
+    const size_t snap = sizeof(CgScal) * B + 16;
+    const size_t pin = round16(sizeof(int) * B) + stage + 2 * snap + sizeof(CgScal) * B + sizeof(double) * 2 * B;
+    if (c->cgs_dev_bytes < dev) {
+        if (c->cgs_dev) { HIP_TRY(hipFree(c->cgs_dev)); c->cgs_dev = nullptr; c->cgs_dev_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->cgs_dev, dev));
+        c->cgs_dev_bytes = dev;
+    }
+    if (c->cgs_pin_bytes < pin) {
+        if (c->cgs_pin) { HIP_TRY(hipHostFree(c->cgs_pin)); c->cgs_pin = nullptr; c->cgs_pin_bytes = 0; }
+        HIP_TRY(hipHostMalloc(&c->cgs_pin, pin));
+        c->cgs_pin_bytes = pin;
+    }
+    for (hipEvent_t &e : c->cgs_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    char *d = (char *)c->cgs_dev, *h = (char *)c->cgs_pin;
+    b->d_fin = (int *)d;
+    b->d_rounds = (int *)(d + round16(sizeof(int) * B));
+    b->d_new = (int *)(d + 2 * round16(sizeof(int) * B));
+    b->d_pix = (uint8_t *)(b->d_new + B);
+    b->h_fin = (int *)h;
+    b->h_new = (int *)(h + round16(sizeof(int) * B));
+    b->h_pix = (uint8_t *)(b->h_new + B);
+    h += round16(sizeof(int) * B) + stage;
+    for (int k = 0; k < 2; ++k) {
+        b->h_snap[k] = (CgScal *)h;
+        b->h_flags[k] = (unsigned *)(h + sizeof(CgScal) * B);
+        h += snap;
+    }
+    b->h_round = (CgScal *)h;
+    b->h_q = (double *)(h + sizeof(CgScal) * B);
+    return DEFF_OK;
+}
+
+}  // namespace
+
+extern "C" int deff_solve_cg_stream(deff_ctx *c, int W, int H, int ampX, int ampY, double Ds, double Df, double CL, double CR,
+                                    double rtol, int64_t max_iter, int64_t check_every, deff_next_image_fn next,
+                                    deff_cg_image_done_fn done, void *user)
+try {
+    if (!c || !next || !done) return fail(DEFF_EINVAL, "NULL argument");
+    if (!(rtol >= 0.0) || !std::isfinite(rtol)) return fail(DEFF_EINVAL, "deff_solve_cg_stream: rtol must be finite and >= 0");
+    if (max_iter < 0) return fail(DEFF_EINVAL, "deff_solve_cg_stream: negative max_iter");
+    if (check_every < 1) return fail(DEFF_EINVAL, "check_every must be >= 1");
+    if (c->slab) return fail(DEFF_EINVAL, "deff_solve_cg_stream: not for row-slab contexts");
+    TRY(use_device(c));
+    TRY(resident_check(c));                                          // an unchecked resident interval is settled under the OLD system
+    // the table first: a refusal leaves the context's dictionary as it was
+    std::vector<double> tab;
+    {
+        std::vector<double> rows0 = c->lut_rows;
+        const int nrows0 = c->lut_nrows;
+        const bool allb0 = c->lut_allb;
+        const double omega0 = c->lut_omega;
+        build_lut_rows(c, Ds, Df, CL, CR);
+        int rc = cg_table(c, tab);
+        if (rc == DEFF_OK) rc = image_shape(c, W, H, ampX, ampY);
+        if (rc != DEFF_OK) {
+            c->lut_rows.swap(rows0); c->lut_nrows = nrows0; c->lut_allb = allb0; c->lut_omega = omega0;
+            return rc;
+        }
+    }
+    TRY(ensure_walls(c));
+    TRY(dev_alloc(&c->code, c->n));
+    TRY(dev_alloc(&c->q, (size_t)2 * c->nimg));
+    const int B = c->nimg;
+    const size_t npix = (size_t)W * H;
+    c->CL = CL; c->CR = CR; c->Ds = Ds; c->Df = Df;
+    c->phase_mode = 2; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = 0.0;
+    c->have_image = true; c->have_walls = true; c->have_matfree = true; c->have_explicit = false;
+    c->wrap_links = false;
+    c->links_sym = 0;
+    c->dict_tried = false; c->have_field = true;
+    c->q_valid = false;
+    reset_batch_state(c);                                            // every slot's field lives in x[cur], now and afterwards
+    double *x = c->x[c->cur];
+    HIP_TRY(hipMemsetAsync(c->code, 0, sizeof(uint16_t) * c->n, c->stream));      // empty slots: zero rows, as deff_solve_stream
+    HIP_TRY(hipMemsetAsync(c->x[0], 0, sizeof(double) * c->n, c->stream));
+    HIP_TRY(hipMemsetAsync(c->x[1], 0, sizeof(double) * c->n, c->stream));
+    HIP_TRY(hipMemsetAsync(c->Dl, 0, sizeof(double) * c->rows, c->stream));
+    HIP_TRY(hipMemsetAsync(c->Dr, 0, sizeof(double) * c->rows, c->stream));
+    HIP_TRY(hipMemsetAsync(c->pix, 0, npix * B, c->stream));
+
+    CgGeom g = cg_geometry(c);
+    const size_t items = (size_t)g.per_img * B;
+    c->cg_plan_kr = g.kr;
+    c->cg_plan_ntx = g.ntx;
+    c->cg_plan_items = (int)g.per_img;
+    c->cg_plan_restarts = 0;
+    const bool onchip = c->cg_onchip && (size_t)c->nx * c->ny <= (size_t)CGI_CELLS;
+    c->cg_plan_impl = onchip ? 2 : 1;
+    if (onchip && !c->cg_cus) HIP_TRY(hipDeviceGetAttribute(&c->cg_cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    TRY(cg_buffers(c, items));
+    CgsBuffers bf;
+    TRY(cgs_buffers(c, npix, &bf));
+    int64_t launches = 0, waits = 0, intervals = 0;
+    c->cgs_intervals = c->cgs_launches = c->cgs_waits = 0;
+    auto figures = [&] {
+        c->cgs_intervals = (int)std::min<int64_t>(intervals, INT32_MAX);
+        c->cgs_launches = (int)std::min<int64_t>(launches, INT32_MAX);
+        c->cgs_waits = (int)std::min<int64_t>(waits, INT32_MAX);
+    };
+    // whatever way the call ends, nothing of it is left in flight (the pinned buffers and `tab` are read by queued copies)
+    struct Leave {
+        deff_ctx *c;
+        ~Leave() { (void)hipStreamSynchronize(c->stream); c->in_stream = false; }
+    } leave{c};
+    c->in_stream = true;                                             // deff_get_slot_field / deff_residual_slot: buf_of[] is current
+
+    CgScal *sc = (CgScal *)c->cg_scal;
+    // every slot parked (done = 4: no image) until an entry check starts it
+    for (int k = 0; k < B; ++k) { bf.h_snap[0][k] = CgScal(); bf.h_snap[0][k].done = 4; }
+    HIP_TRY(hipMemcpyAsync(sc, bf.h_snap[0], sizeof(CgScal) * B, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(bf.d_rounds, 0, sizeof(int) * B, c->stream));
+    HIP_TRY(hipMemsetAsync(c->cg_flags, 0, sizeof(unsigned) * 2, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), sizeof(double) * CG_DOUBLES, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                        // h_snap[0] is a snapshot buffer from here on
+    ++waits;
+
+    const double tol2 = rtol * rtol;
+    const dim3 grid((unsigned)((items + 3) / 4)), fin((unsigned)B);
+    double *part = c->cg_part, *part_rz = c->cg_part + items, *part_rr = c->cg_part + 2 * items;
+    struct Slot { bool live = false; int64_t id = -1, valid_from = 0; };
+    std::vector<Slot> S(B);
+    bool more = true;
+    int n_live = 0;
+    int64_t k_it = 0;                                                // streaming iterations enqueued (parity of the p buffers)
+
+    // r = b - A x and the check of `n` listed slots (the list is on the device)
+    auto resid_check = [&](const int *d_list, int n, int mode) -> int {
+        CgGeom gl = g;
+        gl.nimg = n;
+        hipLaunchKernelGGL(k_cgs_resid, dim3((unsigned)(((size_t)g.per_img * n + 3) / 4)), dim3(256), 0, c->stream, c->cg_tab,
+                           c->lut_nrows, c->code, x, c->cg_r, gl, d_list, part);
+        hipLaunchKernelGGL(k_cgs_check, dim3((unsigned)n), dim3(CG_FIN), 0, c->stream, part, g.per_img, sc, d_list, bf.d_rounds,
+                           tol2, (long long)max_iter, mode, CG_MAX_RESTARTS);
+        HIP_TRY(hipGetLastError());
+        launches += 2;
+        return DEFF_OK;
+    };
+    // every free slot takes the next image: pixels and list go up in ONE copy, the slots rejoin at interval `from`
+    auto enter = [&](int64_t from) -> int {
+        int n = 0;
+        for (int k = 0; k < B && more; ++k) {
+            if (S[k].live) continue;
+            int64_t id = -1;
+            const int got = next(user, k, bf.h_pix + (size_t)n * npix, &id);
+            if (got < 0) return fail(DEFF_EINVAL, "image source reported an error");
+            if (got == 0) { more = false; break; }
+            bf.h_new[n++] = k;
+            S[k].live = true; S[k].id = id; S[k].valid_from = from;
+            ++n_live;
+        }
+        if (!n) return DEFF_OK;
+        HIP_TRY(hipMemcpyAsync(bf.d_new, bf.h_new, sizeof(int) * B + (size_t)n * npix, hipMemcpyHostToDevice, c->stream));
+        const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>(64, (c->n_img + 1023) / 1024));
+        hipLaunchKernelGGL(k_cgs_enter, dim3(gx, (unsigned)n), dim3(256), 0, c->stream, bf.d_pix, bf.d_new, W, H, ampX, ampY,
+                           c->nx, c->nxt, c->ny, Df, Ds, CL, CR, c->fma, c->pix, c->code, c->Dl, c->Dr, x);
+        hipLaunchKernelGGL(k_cgs_admissible, dim3(gx, (unsigned)n), dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code,
+                           c->nx, c->ny, bf.d_new, c->cg_flags);
+        HIP_TRY(hipGetLastError());
+        launches += 2;
+        return resid_check(bf.d_new, n, 0);
+    };
+    // the iteration work of one interval, then the slots' states on their way to the host
+    auto interval = [&](int64_t i) -> int {
+        if (onchip) {
+            hipLaunchKernelGGL(k_cg_image, dim3((unsigned)std::min(B, c->cg_cus)), dim3(CGI_THREADS), 0, c->stream, c->cg_tab,
+                               c->lut_nrows, c->code, x, c->cg_r, c->cg_p[0], sc, c->nx, c->ny, B, (long long)check_every, tol2,
+                               (long long)max_iter);
+            launches += 1;
+        } else {
+            for (int64_t q = 0; q < check_every; ++q, ++k_it) {
+                double *p_in = c->cg_p[k_it & 1], *p_out = c->cg_p[(k_it + 1) & 1];
+                hipLaunchKernelGGL(k_cg_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->cg_r, p_in, p_out,
+                                   sc, g, part);
+                hipLaunchKernelGGL(k_cg_alpha, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc);
+                hipLaunchKernelGGL(k_cg_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x,
+                                   c->cg_r, sc, g, part_rz, part_rr);
+                hipLaunchKernelGGL(k_cg_beta, fin, dim3(CG_FIN), 0, c->stream, part_rz, part_rr, g.per_img, sc, tol2,
+                                   (long long)max_iter);
+            }
+            launches += 4 * check_every;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(bf.h_snap[i & 1], sc, sizeof(CgScal) * B, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(bf.h_flags[i & 1], c->cg_flags, sizeof(unsigned) * 2, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(c->cgs_ev[i & 1], c->stream));
+        return DEFF_OK;
+    };
+
+    HIP_TRY(hipEventRecord(c->cg_ev0, c->stream));
+    TRY(enter(0));
+    if (n_live > 0) TRY(interval(0));
+    for (int64_t i = 0; n_live > 0; ++i) {
+        TRY(interval(i + 1));                                        // the GPU's next work, before the host handles interval i
+        HIP_TRY(hipEventSynchronize(c->cgs_ev[i & 1]));
+        ++waits;
+        ++intervals;
+        figures();
+        if (bf.h_flags[i & 1][0])
+            return fail(DEFF_EINVAL, "deff_solve_cg_stream: the system of an image is not symmetric (a link between two active "
+                                     "cells differs from its partner, or an active row links out of its image)");
+        int n_fin = 0;
+        for (int k = 0; k < B; ++k)
+            if (S[k].live && i >= S[k].valid_from && bf.h_snap[i & 1][k].done != 0) bf.h_fin[n_fin++] = k;
+        if (!n_fin) continue;
+        // the stopped slots' true residual (an image that misses rtol goes on), their fluxes, and both back in one wait
+        HIP_TRY(hipMemcpyAsync(bf.d_fin, bf.h_fin, sizeof(int) * n_fin, hipMemcpyHostToDevice, c->stream));
+        TRY(resid_check(bf.d_fin, n_fin, 1));
+        hipLaunchKernelGGL(k_cgs_flux, dim3((unsigned)n_fin), dim3(256), 0, c->stream, x, c->Dl, c->Dr, c->nx, c->nxt, c->ny,
+                           c->rows, c->dx, CL, CR, bf.d_fin, c->flux_reduce == 2 ? 1 : 0, c->mf, c->q);
+        HIP_TRY(hipGetLastError());
+        launches += 1;
+        HIP_TRY(hipMemcpyAsync(bf.h_round, sc, sizeof(CgScal) * B, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(bf.h_q, c->q, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipEventRecord(c->cg_ev1, c->stream));
+        HIP_TRY(hipEventSynchronize(c->cg_ev1));
+        ++waits;
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->cg_ev0, c->cg_ev1));
+        for (int q = 0; q < n_fin; ++q) {
+            const int k = bf.h_fin[q];
+            const CgScal &s = bf.h_round[k];
+            if (s.done == 0) {                                       // restarted: back in the iteration from interval i + 2
+                S[k].valid_from = i + 2;
+                ++c->cg_plan_restarts;
+                continue;
+            }
+            deff_cg_result res;
+            res.iters = s.iters;
+            res.rel_residual = s.rel;
+            const double qAvg = (bf.h_q[2 * k] + bf.h_q[2 * k + 1]) / (2.0 * c->ny);      // deff_flux's expressions
+            res.deff_raw = qAvg / ((CR - CL));
+            res.loop_ms = ms;
+            res.converged = s.rel <= rtol;
+            S[k].live = false;
+            --n_live;
+            done(user, S[k].id, k, &res);                            // the slot's field is readable (deff_get_slot_field)
+        }
+        TRY(enter(i + 2));
+        figures();
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));                        // the interval enqueued ahead found every slot stopped
+    ++waits;
+    figures();
     return DEFF_OK;
 }
 DEFF_API_CATCH

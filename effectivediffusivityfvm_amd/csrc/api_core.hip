@@ -135,6 +135,9 @@ try {
     for (void *p : cg_bufs) if (p) (void)hipFree(p);
     if (c->cg_ev0) (void)hipEventDestroy(c->cg_ev0);
     if (c->cg_ev1) (void)hipEventDestroy(c->cg_ev1);
+    if (c->cgs_dev) (void)hipFree(c->cgs_dev);
+    if (c->cgs_pin) (void)hipHostFree(c->cgs_pin);
+    for (hipEvent_t e : c->cgs_ev) if (e) (void)hipEventDestroy(e);
     if (c->resid_ev0) (void)hipEventDestroy(c->resid_ev0);
     if (c->resid_ev1) (void)hipEventDestroy(c->resid_ev1);
     if (c->q_host) (void)hipHostFree(c->q_host);
@@ -317,6 +320,9 @@ try {
     else if (!strcmp(key, "cg_items")) *value = c->cg_plan_items;
     else if (!strcmp(key, "cg_restarts")) *value = c->cg_plan_restarts;
     else if (!strcmp(key, "cg_impl")) *value = c->cg_plan_impl;
+    else if (!strcmp(key, "cgs_intervals")) *value = c->cgs_intervals;
+    else if (!strcmp(key, "cgs_launches")) *value = c->cgs_launches;
+    else if (!strcmp(key, "cgs_waits")) *value = c->cgs_waits;
     else return fail(DEFF_EINVAL, "unknown plan key '%s'", key);
     return DEFF_OK;
 }

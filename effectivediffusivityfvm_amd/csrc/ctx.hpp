@@ -8,7 +8,7 @@
 //   tiles_8wave.hip, tiles_tall.hip, tiles_12wave.hip
 //                  the workgroup-tile kernels, one family each, listed for the planner (tile_kernels.hpp)
 //   api_solve.hip  wall fluxes and the Jacobi solve loops (one image, batch, streaming batch); no sweep kernel
-//   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg)
+//   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg) and through refilled slots (deff_solve_cg_stream)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
 //                  RCCL or a caller-supplied transport with one process per GPU)
@@ -229,6 +229,13 @@ struct deff_ctx {
     // 0 (default) = the streaming kernels for every size.  cg_plan_impl: what the last deff_solve_cg ran, 1 streaming, 2 on chip
     int cg_onchip = 0, cg_plan_impl = 0;
     int cg_cus = 0;                              // compute units of the device (workgroups of an on-chip launch)
+    // deff_solve_cg_stream (api_cg.hip, kernels_cg_stream.hpp), allocated by the first one.  cgs_dev: the round's slot list,
+    // the slots' restart rounds, and the staging area -- the entering slots' list followed by their pixels --; cgs_pin: the
+    // pinned mirror of the two lists and the pixels, two snapshots of the slots' CgScal + flags, and a round's results
+    void *cgs_dev = nullptr, *cgs_pin = nullptr;
+    size_t cgs_dev_bytes = 0, cgs_pin_bytes = 0;
+    hipEvent_t cgs_ev[2] = {nullptr, nullptr};   // a snapshot has arrived
+    int cgs_intervals = 0, cgs_launches = 0, cgs_waits = 0;   // deff_get_plan: figures of the last stream
 
     // deff_residual / deff_residual_D time themselves with their own pair, created by the first call that asks for `ms`:
     // ev0 / ev1 belong to the solve loops alone, which read them at every check and may call the residual in between

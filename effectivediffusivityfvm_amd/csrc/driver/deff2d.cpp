@@ -121,6 +121,7 @@ static int g_prefetch_threads = 2;
 static bool g_solver_cg = false;   // --solver cg
 static double g_cg_rtol = 1e-10;   // --cg-rtol
 static int g_cg_batch = 0;         // --cg-batch B: 2-phase batch mode solves runs of up to B equally sized images in one stack
+static int g_cg_stream = 0;        // --cg-stream B: ... keeps B slots full instead (deff_solve_cg_stream)
 
 struct Session {                   // one solver context, re-created only when the mesh / batch size changes
     deff_ctx *ctx = nullptr;
@@ -611,16 +612,17 @@ static int stream_next(void *user, int /*slot*/, uint8_t *pix, int64_t *id)
     return stream_emit(st, p, pix, id);
 }
 
-static void stream_done(void *user, int64_t id, int slot, const deff_result *r)
+// an image of a stream has retired in `slot`: its row (conv = what the solver's stopping rule looked at), the residual of its
+// field, the progress line and, where asked for, the field itself
+static void stream_finish_row(StreamState &st, int64_t id, int slot, double deff_raw, double conv, int64_t iters, double loop_ms)
 {
-    StreamState &st = *(StreamState *)user;
     const Options &o = *st.sh->o;
     Row &row = (*st.sh->rows)[(size_t)id];
-    row.deff = r->deff_raw / o.DCfluid;                          // cuh:2017
-    row.conv = r->conv;
-    row.iters = (long)r->iters;
-    row.stages.push_back((long)r->iters);
-    row.seconds = r->loop_ms / 1000.0;                           // stream time when the image stopped
+    row.deff = deff_raw / o.DCfluid;                             // cuh:2017
+    row.conv = conv;
+    row.iters = (long)iters;
+    row.stages.push_back((long)iters);
+    row.seconds = loop_ms / 1000.0;                              // stream time when the image stopped
     if (deff_residual_slot(st.ctx, slot, &row.residual) != DEFF_OK) row.residual = NAN;
     progress_append(*st.sh->progress_path, (int)id, row);
     if (st.sh->want_field) {
@@ -628,6 +630,17 @@ static void stream_done(void *user, int64_t id, int slot, const deff_result *r)
         std::vector<double> x((size_t)nx * ny);
         if (deff_get_slot_field(st.ctx, slot, x.data()) == DEFF_OK) (*st.sh->emit)((int)id, x.data(), nx, ny);
     }
+}
+
+static void stream_done(void *user, int64_t id, int slot, const deff_result *r)
+{
+    stream_finish_row(*(StreamState *)user, id, slot, r->deff_raw, r->conv, r->iters, r->loop_ms);
+}
+
+// --cg-stream: an image of deff_solve_cg_stream has retired (the row as --solver cg reports it: conv = the relative residual)
+static void cg_stream_done(void *user, int64_t id, int slot, const deff_cg_result *r)
+{
+    stream_finish_row(*(StreamState *)user, id, slot, r->deff_raw, r->rel_residual, r->iters, r->loop_ms);
 }
 
 // One line per finished image: index and every field of its row, doubles as hex floats (exact).
@@ -686,7 +699,7 @@ int main(int argc, char **argv)
     int device = 0, batch_size = 0;
     std::vector<int> devices;
     std::string progress_path;
-    bool cg_batch_given = false;
+    bool cg_batch_given = false, cg_stream_given = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         if (s == "--device" && a + 1 < argc) device = std::atoi(argv[++a]);
@@ -729,10 +742,22 @@ int main(int argc, char **argv)
             g_cg_batch = (int)v;
             cg_batch_given = true;
         }
+        else if (s == "--cg-stream" && a + 1 < argc) {
+            char *end = nullptr;
+            const long v = std::strtol(argv[++a], &end, 10);
+            if (end == argv[a] || *end || v < 0 || v > 1000000) {
+                std::fprintf(stderr, "deff2d: --cg-stream B (an integer >= 0; 0 = one image at a time)\n");
+                return 2;
+            }
+            g_cg_stream = (int)v;
+            cg_stream_given = true;
+        }
         else if (s == "-h" || s == "--help") {
-            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B]\n"
+            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B] [--cg-stream B]\n"
                         "--cg-batch B (with --solver cg, RunBatch 1, 2 phases): runs of up to B consecutive, equally sized images are solved\n"
                         "together in one stack, an image of at most 16 384 cells on one compute unit each; 0 (default) = one image at a time.\n"
+                        "--cg-stream B (with --solver cg, RunBatch 1, 2 phases; not with --cg-batch): B slots are kept full instead -- a slot\n"
+                        "whose image has converged is refilled with the next image of its size while the others go on iterating.\n"
                         "The Time column (seconds of device time, hipEvent): RunBatch 0 -- the solve loops of the image (3 phases: the final\n"
                         "stage only, as the reference's JacobiGPUPreCond adds nothing to it); RunBatch 1, 2 phases -- the time from the\n"
                         "start of the image's stream of slots to the check that retired the image, so it grows along a stream;\n"
@@ -743,6 +768,14 @@ int main(int argc, char **argv)
     }
     if (cg_batch_given && !g_solver_cg) {
         std::fprintf(stderr, "deff2d: --cg-batch needs --solver cg\n");
+        return 2;
+    }
+    if (cg_stream_given && !g_solver_cg) {
+        std::fprintf(stderr, "deff2d: --cg-stream needs --solver cg\n");
+        return 2;
+    }
+    if (cg_stream_given && cg_batch_given) {
+        std::fprintf(stderr, "deff2d: --cg-stream and --cg-batch exclude each other\n");
         return 2;
     }
     Options o;
@@ -758,9 +791,12 @@ int main(int argc, char **argv)
     const bool cg_batched = g_solver_cg && o.BatchFlag && o.nPhase == 2 && g_cg_batch >= 2;
     if (g_solver_cg && o.BatchFlag && batch_size > 1)
         std::fprintf(stderr, "deff2d: note: --batch-size is ignored with --solver cg (the stacked / streaming slots run the Jacobi "
-                             "loop only): --cg-batch B solves B images of a 2-phase data set together\n");
+                             "loop only): --cg-batch B solves B images of a 2-phase data set together, --cg-stream B keeps B slots full\n");
     if (g_cg_batch >= 2 && !cg_batched)
         std::fprintf(stderr, "deff2d: note: --cg-batch applies to RunBatch 1 with 2 phases; one image at a time here\n");
+    const bool cg_streamed = g_solver_cg && o.BatchFlag && o.nPhase == 2 && g_cg_stream >= 2;
+    if (g_cg_stream >= 2 && !cg_streamed)
+        std::fprintf(stderr, "deff2d: note: --cg-stream applies to RunBatch 1 with 2 phases; one image at a time here\n");
     const int count = o.BatchFlag ? o.NumImg : 1;
     std::vector<Row> rows((size_t)count);
     const bool want_field = o.printCmap == 1 || !field_prefix.empty();
@@ -795,10 +831,11 @@ int main(int argc, char **argv)
 
     // ---- 2-phase batch mode: streaming slots (deff_solve_stream) --------------------------------
     Shared shared{&o, &rows, &done, &next_index, &failed, count, want_field, &emit_field, &progress_path, image_name};
-    auto stream_worker = [&](int dev) {
+    // (cg: --solver cg --cg-stream B -- the same slots around deff_solve_cg_stream, B of them, with "cg_onchip")
+    auto stream_worker = [&](int dev, bool cg) {
         StreamState st;
         st.sh = &shared;
-        Prefetcher source(&shared, 8, g_prefetch_threads);
+        Prefetcher source(&shared, cg ? 64 : 8, g_prefetch_threads);
         st.source = &source;
         for (;;) {
             if (!st.have_pending) {                              // first image of the next stream fixes its size
@@ -818,7 +855,9 @@ int main(int argc, char **argv)
             // rule lives in the library: deff_recommended_batch)
             const long long per_dev = (count + (long long)std::max<size_t>(1, devices.size()) - 1) / (long long)std::max<size_t>(1, devices.size());
             int slots = 1;
-            if (batch_size > 0) {
+            if (cg) {
+                slots = g_cg_stream;
+            } else if (batch_size > 0) {
                 slots = (int)std::min<long long>(std::min<long long>(batch_size, std::max<long long>(1, per_dev)), 4096);
             } else if (deff_recommended_batch(dev, nx, ny, std::max<long long>(1, per_dev), &slots) != DEFF_OK) {
                 std::fprintf(stderr, "deff2d: %s\n", deff_last_error());
@@ -826,14 +865,19 @@ int main(int argc, char **argv)
                 return;
             }
             if (deff_create_batch(dev, nx, ny, slots, &st.ctx) != DEFF_OK ||
-                deff_set_tuning(st.ctx, "fma", g_contracted) != DEFF_OK) {
+                deff_set_tuning(st.ctx, "fma", g_contracted) != DEFF_OK ||
+                (cg && deff_set_tuning(st.ctx, "cg_onchip", 1) != DEFF_OK)) {
                 std::fprintf(stderr, "deff2d: %s\n", deff_last_error());
+                deff_destroy(st.ctx);
+                st.ctx = nullptr;
                 failed = true;
                 return;
             }
-            const int rc = deff_solve_stream(st.ctx, st.W, st.H, o.MeshIncreaseX, o.MeshIncreaseY, o.DCsolid, o.DCfluid,
-                                             o.CLeft, o.CRight, 2.0 / 3.0, o.ConvergeCriteria, o.MAX_ITER, 10000, stream_next,
-                                             stream_done, &st);
+            const int rc = cg ? deff_solve_cg_stream(st.ctx, st.W, st.H, o.MeshIncreaseX, o.MeshIncreaseY, o.DCsolid, o.DCfluid,
+                                                     o.CLeft, o.CRight, g_cg_rtol, o.MAX_ITER, 64, stream_next, cg_stream_done, &st)
+                              : deff_solve_stream(st.ctx, st.W, st.H, o.MeshIncreaseX, o.MeshIncreaseY, o.DCsolid, o.DCfluid,
+                                                  o.CLeft, o.CRight, 2.0 / 3.0, o.ConvergeCriteria, o.MAX_ITER, 10000, stream_next,
+                                                  stream_done, &st);
             deff_destroy(st.ctx);
             st.ctx = nullptr;
             if (rc != DEFF_OK) {
@@ -981,7 +1025,7 @@ int main(int argc, char **argv)
     const bool streaming = o.BatchFlag && o.nPhase == 2 && !g_solver_cg;   // slots of the Jacobi loop (cg: one image at a time)
     const bool grouped3 = o.BatchFlag && o.nPhase == 3 && !g_solver_cg;
     auto run = [&](int dev) {
-        if (streaming) stream_worker(dev);
+        if (streaming || cg_streamed) stream_worker(dev, cg_streamed);
         else if (cg_batched) cg_batch_worker(dev);
         else if (grouped3) worker3(dev);
         else worker(dev);
@@ -994,7 +1038,7 @@ int main(int argc, char **argv)
         for (std::thread &t : pool) t.join();
     }
     if (failed.load()) return 1;
-    if (streaming && o.verbose == 1)
+    if ((streaming || cg_streamed) && o.verbose == 1)
         // BatchSim's two lines per image (cuh:2011-2021), in image order like the reference's loop: the slots retire their
         // images in any order (and the prefetch threads deliver them in any order), so they are printed here, not on retirement
         for (int k = 0; k < count; ++k) {

@@ -24,7 +24,7 @@ class SolveResult:
 
 class CGResult:
     """deff_solve_cg of one image: CG iterations, ||b - A x|| / ||b|| recomputed from the returned field, its Deff (not / Df)."""
-    __slots__ = ("iters", "rel_residual", "deff_raw", "converged", "loop_ms", "MFL", "MFR")
+    __slots__ = ("iters", "rel_residual", "deff_raw", "converged", "loop_ms", "MFL", "MFR", "field", "slot")
 
     def __repr__(self):
         return (f"CGResult(iters={self.iters}, rel_residual={self.rel_residual!r}, deff_raw={self.deff_raw!r}, "
@@ -252,6 +252,60 @@ class Solver:
         nxt, dn = _capi.NEXT_IMAGE_FN(_next), _capi.IMAGE_DONE_FN(_done)
         rc = self._L.deff_solve_stream(self._ctx, W, H, ampX, ampY, Ds, Df, CL, CR, omega, tol, int(max_iter),
                                        int(check_every), nxt, dn, None)
+        if errors:
+            raise errors[0]
+        check(rc)
+        return [results[k] for k in range(counter[0])]
+
+    def solve_cg_stream(self, images, Ds, Df, CL, CR, rtol=1e-10, max_iter=1_000_000, check_every=64, want_fields=False,
+                        ampX=1, ampY=1):
+        """solve_stream with conjugate gradients (deff_solve_cg_stream): every image of the iterable is solved to
+        ||b - A x|| <= rtol ||b|| from the linear guess, exactly as a one-image solve_cg would, in whichever slot is free.
+        Returns a list with one CGResult per image, in input order, with .slot (plus .field when want_fields; MFL / MFR are
+        None).  Afterwards slot k of the context holds the last image that ran in it, with its final field."""
+        it = iter(images)
+        H, W = self.ny // ampY, self.nx // ampX
+        results = {}
+        counter = [0]
+        errors = []
+
+        def _next(_user, _slot, pix_ptr, id_ptr):
+            try:
+                img = next(it)
+            except StopIteration:
+                return 0
+            except Exception as e:          # noqa: BLE001 - reported to the C side as an error code
+                errors.append(e)
+                return -1
+            a = np.ascontiguousarray(img, dtype=np.uint8)
+            if a.shape != (H, W):
+                errors.append(ValueError(f"image {counter[0]} is {a.shape}, expected {(H, W)}"))
+                return -1
+            C.memmove(pix_ptr, a.ctypes.data, a.size)
+            id_ptr[0] = counter[0]
+            counter[0] += 1
+            return 1
+
+        def _done(_user, image_id, slot, res_ptr):
+            # an exception raised inside a ctypes callback is swallowed: record it, re-raise after the call
+            try:
+                r = res_ptr[0]
+                out = CGResult()
+                out.iters, out.rel_residual, out.deff_raw = r.iters, r.rel_residual, r.deff_raw
+                out.converged, out.loop_ms = bool(r.converged), r.loop_ms
+                out.MFL = out.MFR = None
+                out.slot = int(slot)
+                if want_fields:
+                    x = np.empty((self.ny, self.nx), dtype=np.float64)
+                    check(self._L.deff_get_slot_field(self._ctx, slot, x))
+                    out.field = x
+                results[int(image_id)] = out
+            except Exception as e:          # noqa: BLE001
+                errors.append(e)
+
+        nxt, dn = _capi.NEXT_IMAGE_FN(_next), _capi.CG_IMAGE_DONE_FN(_done)
+        rc = self._L.deff_solve_cg_stream(self._ctx, W, H, ampX, ampY, Ds, Df, CL, CR, float(rtol), int(max_iter),
+                                          int(check_every), nxt, dn, None)
         if errors:
             raise errors[0]
         check(rc)

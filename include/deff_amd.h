@@ -101,7 +101,8 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * passes of a batch run as one resident launch), "tb_fallbacks" (resident intervals that gave up and were redone with
  * one launch per pass); 0 before any sweep.  Of the last deff_solve_cg (0 before one): "cg_kr" (rows per work item),
  * "cg_strips" (strips of 128 columns), "cg_items" (work items per image), "cg_restarts" (true-residual rounds that
- * sent an image back into the iteration) and "cg_impl" (1 = streaming kernels, 2 = on chip) */
+ * sent an image back into the iteration) and "cg_impl" (1 = streaming kernels, 2 = on chip); of the last
+ * deff_solve_cg_stream, which also sets the "cg_" keys: "cgs_intervals", "cgs_launches", "cgs_waits" (see there) */
 int deff_get_plan(deff_ctx *ctx, const char *key, int *value);
 
 /* ---- image -> phases: replaces the mask->D loops cuh:1988-2000 (2-phase),
@@ -208,6 +209,34 @@ int deff_solve_stream(deff_ctx *ctx, int W, int H, int ampX, int ampY, double Ds
                       double CR, double omega, double tol, int64_t max_iter, int64_t check_every,
                       deff_next_image_fn next, deff_image_done_fn done, void *user);
 int deff_get_slot_field(deff_ctx *ctx, int slot, double *x /* nx*ny */);
+/* Conjugate gradients through refilled slots (dataset generation with converged fields): the slot life cycle of
+ * deff_solve_stream around the iteration of deff_solve_cg.  Batch contexts, native 2-phase system; `next` as above.  Every image
+ * is solved exactly as a one-image deff_solve_cg call would solve it from the linear guess (deff_init_linear): the same
+ * recurrence, the same stop per image (||r|| <= rtol ||b||, max_iter, breakdown), the same true-residual round at its end with
+ * up to 8 restart rounds per image; rel_residual is recomputed from the field, converged derived from it, deff_raw is the
+ * slot's deff_flux value, loop_ms the hipEvent time from the start of the call to the check that retired the image.  The
+ * results (bits) do not depend on check_every, on the number of slots or on the slot and neighbours an image had.  With the
+ * tuning key "cg_onchip" 1, images of at most 16 384 cells iterate on one compute unit each; everything else runs the
+ * streaming kernels (deff_get_plan "cg_impl": 2 / 1).
+ *   The device does not wait for the host: the iterations of the next check interval (check_every of them) are enqueued before
+ * the host reads what the last one left; a slot found stopped is frozen until its true-residual round, flux, `done`, the next
+ * image's upload and entry have run behind that interval, and rejoins with the interval after it.  Launches and host waits per
+ * interval do not grow with the number of slots that retire or enter.  (An interval in which a slot retires still has a turn
+ * of the host that the device waits for: the wait for the round comes behind the interval already enqueued, and `done`, `next`
+ * and the upload run before the interval after it is enqueued.)  deff_get_plan, of the last stream: "cgs_intervals",
+ * "cgs_launches" = kernel launches enqueued, "cgs_waits" = host waits on the device.
+ *   done(user, image_id, slot, result): once per image; deff_get_slot_field and deff_residual_slot work for `slot` inside it.
+ *   DEFF_EINVAL before `next` is ever called: NULL callbacks, rtol negative or not finite, max_iter < 0, check_every < 1, a
+ * row-slab context, an image that does not match the mesh, a table that is not admissible (an active row without a finite
+ * A0 > 0, e.g. Df < 0 or not finite; the rule is deff_solve_cg's, so Df = 0 or Ds = 0 is admitted: that phase's rows are
+ * decoupled and its cells get x = 0).  A `next` that returns < 0: DEFF_EINVAL.  The symmetry of an entering slot's system is checked on the
+ * device and reported (DEFF_EINVAL) with the next look at the slots.
+ *   After DEFF_OK the context is an ordinary stack context, as after deff_solve_stream: slot k holds the last image that ran in
+ * it, its system and its final field; slots that never received an image hold the zero place holder described above. */
+typedef void (*deff_cg_image_done_fn)(void *user, int64_t image_id, int slot, const deff_cg_result *res);
+int deff_solve_cg_stream(deff_ctx *ctx, int W, int H, int ampX, int ampY, double Ds, double Df, double CL, double CR,
+                         double rtol, int64_t max_iter, int64_t check_every,
+                         deff_next_image_fn next, deff_cg_image_done_fn done, void *user);
 /* optional observer called on the host after every convergence check with
  * (iter of the checked sweep, Deff, signed change): what the reference prints under
  * Verbose (cuh:1267-1271).  NULL removes it. */

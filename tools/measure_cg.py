@@ -21,6 +21,13 @@ onchip_dataset   tools/measure_dataset.py's 128^2 JPEG set (--images N) through 
               slots once; images/s
 onchip_profile   k_cg_image's share of loop_ms from a `rocprofv3 --kernel-trace --stats` run of its own (a child process)
   python tools/measure_cg.py --cases onchip_config1,onchip_stack256,onchip_dataset,onchip_profile --out profiles/cg_onchip_results.json
+stream_library   --images N (4096) synthetic 128^2 images, host pixels, upload included, whole-call wall clock: (a) consecutive
+              deff_solve_cg stacks of B = deff_recommended_batch images with "cg_onchip" 1 at check_every 64 and 512 (what
+              --cg-batch does) against (b) deff_solve_cg_stream through B slots at check_every 64; the forms alternate run by
+              run on fresh contexts; CU-busy share = sum of iterations x --per-iter-us / (wall x min(B, compute units))
+stream_profile   where the stream's time goes: a `rocprofv3 --kernel-trace --stats` run of its own (a child process) of the stream alone
+stream_driver    tools/measure_dataset.py's JPEG set through deff2d: --solver cg --cg-batch 1024 against --cg-stream B, alternating
+  python tools/measure_cg.py --cases stream_library,stream_driver --images 4096 --out profiles/cg_stream_results.json
 The bytes model of one iteration is 68 B/cell; "model_us" is that traffic at 6.3 TB/s."""
 import argparse
 import json
@@ -223,6 +230,143 @@ def onchip_dataset(rtol, runs, images):
     return out
 
 
+def synth_pixels(n, first, count, seed=12345):
+    """k_synth_mask on the host: images first .. first + count - 1 of the n x n sequence, (count, n, n) uint8."""
+    M = np.uint64(0xFFFFFFFFFFFFFFFF)
+    with np.errstate(over="ignore"):
+        z = (np.uint64(seed) * np.uint64(0x100000001B3) + np.arange(first * n * n, (first + count) * n * n, dtype=np.uint64)) & M
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return np.where(z >> np.uint64(63), 255, 0).astype(np.uint8).reshape(count, n, n)
+
+
+def stream_library(rtol, max_iter, runs, images, per_iter_us, only_stream=False):
+    import torch                                                     # before the library is loaded: one HIP runtime for both
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = 128
+    B = pkg.recommended_batch(n, n, images)
+    pix = synth_pixels(n, 0, images)
+    busy = min(B, cus)                                               # compute units an on-chip launch can keep busy
+    out = {"mesh": [n, n], "images": images, "slots": B, "compute_units": cus, "rtol": rtol, "per_iter_us_model": per_iter_us,
+           "runs": {}}
+
+    def row(wall, iters):
+        return {"wall_s": wall, "images_per_s": images / wall, "mean_iters": sum(iters) / len(iters), "max_iters": max(iters),
+                "cu_busy_share": sum(iters) * per_iter_us * 1e-6 / (wall * busy)}
+
+    def stacks(ce):
+        t0 = time.perf_counter()
+        iters = []
+        with pkg.Solver(n, n, nimg=B) as s:
+            s.set_tuning("cg_onchip", 1)
+            for k in range(0, images - images % B, B):
+                s.set_image(pix[k:k + B])
+                s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+                s.init_linear(0.0, 1.0)
+                rs = s.solve_cg(rtol=rtol, max_iter=max_iter, check_every=ce, fluxes=False)
+                assert all(r.converged for r in rs) and s.plan_value("cg_impl") == 2
+                iters += [int(r.iters) for r in rs]
+        rest = images % B                                            # the last, shorter stack gets a context of its own, as in the driver
+        if rest:
+            with pkg.Solver(n, n, nimg=rest) as s:
+                s.set_tuning("cg_onchip", 1)
+                s.set_image(pix[images - rest:])
+                s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+                s.init_linear(0.0, 1.0)
+                rs = s.solve_cg(rtol=rtol, max_iter=max_iter, check_every=ce, fluxes=False)
+                rs = rs if isinstance(rs, list) else [rs]
+                iters += [int(r.iters) for r in rs]
+        return row(time.perf_counter() - t0, iters)
+
+    def stream(ce):
+        t0 = time.perf_counter()
+        with pkg.Solver(n, n, nimg=B) as s:
+            s.set_tuning("cg_onchip", 1)
+            rs = s.solve_cg_stream(pix, 1e-3, 1.0, 0.0, 1.0, rtol=rtol, max_iter=max_iter, check_every=ce)
+            assert all(r.converged for r in rs) and s.plan_value("cg_impl") == 2
+            fig = {k: s.plan_value(k) for k in ("cgs_intervals", "cgs_launches", "cgs_waits")}
+        return {**row(time.perf_counter() - t0, [int(r.iters) for r in rs]), **fig}
+
+    forms = (("stacks_ce64", lambda: stacks(64)), ("stacks_ce512", lambda: stacks(512)), ("stream_ce64", lambda: stream(64)))
+    for _ in range(runs):
+        for label, fn in forms[2:] if only_stream else forms:
+            out["runs"].setdefault(label, []).append(fn())
+    if only_stream:
+        return out
+    slow_new = max(r["wall_s"] for r in out["runs"]["stream_ce64"])
+    fast_old = min(r["wall_s"] for k in ("stacks_ce64", "stacks_ce512") for r in out["runs"][k])
+    out["slowest_stream_s"], out["fastest_stacks_s"] = slow_new, fast_old
+    out["ratio_fastest_stacks_over_slowest_stream"] = fast_old / slow_new
+    return out
+
+
+def stream_profile(rtol, images):
+    """Where the stream's time goes: one stream_library run of the stream alone in a child process of its own under
+    `rocprofv3 --kernel-trace --stats` (no counters in the same run); per kernel the calls and the total duration, next to
+    that run's wall clock (which includes the context's creation and the tracer's own cost per launch)."""
+    import csv
+    import glob
+    with tempfile.TemporaryDirectory() as d:
+        run = os.path.join(d, "run.json")
+        p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(d, "prof"), "-o", "run", "--",
+                            sys.executable, os.path.abspath(__file__), "--cases", "stream_library", "--runs", "1", "--only-stream",
+                            "--images", str(images), "--rtol", repr(rtol), "--out", run], capture_output=True, text=True, timeout=600)
+        if p.returncode != 0 or not os.path.exists(run):
+            return {"error": (p.stderr or p.stdout)[-1500:]}
+        row = json.load(open(run))["stream_library"]["runs"]["stream_ce64"][0]
+        out = {"run": row, "kernels": {}}
+        files = glob.glob(os.path.join(d, "prof", "**", "*kernel_stats*.csv"), recursive=True)
+        trace = glob.glob(os.path.join(d, "prof", "**", "*kernel_trace*.csv"), recursive=True)
+        if files:
+            for k in csv.DictReader(open(files[0])):
+                out["kernels"][k["Name"].split("(")[0]] = {"calls": int(k["Calls"]), "total_ms": float(k["TotalDurationNs"]) / 1e6}
+        elif trace:
+            for k in csv.DictReader(open(trace[0])):
+                e = out["kernels"].setdefault(k["Kernel_Name"].split("(")[0], {"calls": 0, "total_ms": 0.0})
+                e["calls"] += 1
+                e["total_ms"] += (int(k["End_Timestamp"]) - int(k["Start_Timestamp"])) / 1e6
+        else:
+            return {**out, "error": "no kernel stats written"}
+        out["kernels_total_ms"] = sum(v["total_ms"] for v in out["kernels"].values())
+        out["kernels_share_of_wall"] = out["kernels_total_ms"] / (1e3 * row["wall_s"])
+    return out
+
+
+def stream_driver(rtol, runs, images):
+    """tools/measure_dataset.py's images through the driver: --cg-batch 1024 (the parent's way) against --cg-stream B."""
+    from PIL import Image
+    exe = os.path.join(ROOT, "effectivediffusivityfvm_amd", "deff2d")
+    S = 128
+    B = pkg.recommended_batch(S, S, images)
+    out = {"image_size": S, "images": images, "cg_rtol": rtol, "slots": B, "runs": {}}
+    with tempfile.TemporaryDirectory() as d:
+        rng = np.random.default_rng(0)
+        for k in range(images):
+            f = np.kron(rng.random((S // 8, S // 8)), np.ones((8, 8)))
+            Image.fromarray(np.where(f < rng.uniform(0.45, 0.75), 0, 255).astype(np.uint8)).save(os.path.join(d, f"{k:05d}.jpg"), quality=95)
+        open(os.path.join(d, "input.txt"), "w").write(
+            "Input File:\nPhases: 2\nDs: 1e-3\nDf: 1\nMeshAmpX: 1\nMeshAmpY: 1\nCR: 1\nCL: 0\nOutputName: out.csv\n"
+            f"printCMap: 0\nConvergence: 1e-6\nMaxIter: 5e5\nVerbose: 0\nRunBatch: 1\nNumImages: {images}\n")
+        cg = ["--solver", "cg", "--cg-rtol", repr(rtol)]
+        for q in range(runs):
+            for label, extra in (("cg_batch_1024", ["--cg-batch", "1024"]), ("cg_stream", ["--cg-stream", str(B)])):
+                t0 = time.perf_counter()
+                p = subprocess.run([exe, "input.txt", "--json", f"{label}{q}.json"] + cg + extra, cwd=d, capture_output=True, text=True, timeout=1200)
+                dt = time.perf_counter() - t0
+                assert p.returncode == 0, p.stderr
+                res = json.load(open(os.path.join(d, f"{label}{q}.json")))["results"]
+                out["runs"].setdefault(label, []).append(
+                    {"seconds": dt, "images_per_s": len(res) / dt, "mean_iterations": sum(x["iterations"] for x in res) / len(res),
+                     "mean_Deff": sum(x["Deff"] for x in res) / len(res)})
+    slow_new = max(r["seconds"] for r in out["runs"]["cg_stream"])
+    fast_old = min(r["seconds"] for r in out["runs"]["cg_batch_1024"])
+    out["slowest_stream_s"], out["fastest_batch_s"] = slow_new, fast_old
+    out["ratio_fastest_batch_over_slowest_stream"] = fast_old / slow_new
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="config1,config2,bench4096,stack16x1024,shipped00042")
@@ -233,6 +377,8 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--only-onchip", action="store_true")
+    ap.add_argument("--only-stream", action="store_true")
+    ap.add_argument("--per-iter-us", type=float, default=11.1, help="k_cg_image per iteration (onchip_profile), for the CU-busy share")
     a = ap.parse_args()
     jac = not a.no_jacobi
     out = {"rtol": a.rtol, "bytes_per_cell_model": BYTES_PER_CELL, "hbm_TBs_model": HBM_TBS}
@@ -258,6 +404,12 @@ def main():
             out[case] = onchip_profile(a.rtol)
         elif case == "onchip_dataset":
             out[case] = onchip_dataset(a.rtol, a.runs, a.images)
+        elif case == "stream_library":
+            out[case] = stream_library(a.rtol, a.max_iter, a.runs, a.images, a.per_iter_us, a.only_stream)
+        elif case == "stream_profile":
+            out[case] = stream_profile(a.rtol, a.images)
+        elif case == "stream_driver":
+            out[case] = stream_driver(a.rtol, a.runs, a.images)
         else:
             raise SystemExit(f"unknown case {case}")
         out[case]["case_wall_s"] = time.perf_counter() - t0
