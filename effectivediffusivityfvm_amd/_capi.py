@@ -25,7 +25,7 @@ SYMBOLS = [
     "deff_slab_group_create", "deff_slab_group_destroy", "deff_slab_group_layout", "deff_slab_group_set_tuning", "deff_slab_group_get_plan",
     "deff_slab_group_set_image", "deff_slab_group_synth_image", "deff_slab_group_assemble_2phase",
     "deff_slab_group_init_linear", "deff_slab_group_set_field", "deff_slab_group_get_field",
-    "deff_slab_group_sweeps", "deff_slab_group_flux", "deff_slab_group_solve",
+    "deff_slab_group_sweeps", "deff_slab_group_flux", "deff_slab_group_solve", "deff_slab_group_solve_cg", "deff_slab_rank_solve_cg",
     "deff_rccl_unique_id", "deff_slab_rank_create", "deff_slab_rank_create_custom", "deff_slab_rank_destroy", "deff_slab_rank_layout",
     "deff_slab_rank_window", "deff_slab_rank_context", "deff_slab_rank_set_tuning", "deff_slab_rank_set_image_window",
     "deff_slab_rank_synth_image", "deff_slab_rank_assemble_3phase", "deff_slab_group_assemble_3phase", "deff_slab_rank_get_field", "deff_slab_rank_sweeps", "deff_slab_rank_solve",
@@ -135,6 +135,8 @@ def load():
     L.deff_slab_group_flux.argtypes = [ctx, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
     L.deff_slab_group_solve.argtypes = [ctx, C.c_double, C.c_double, C.c_int64, C.c_int64, C.POINTER(Result),
                                         C.c_void_p, C.c_void_p]
+    L.deff_slab_group_solve_cg.argtypes = [ctx, C.c_double, C.c_int64, C.c_int64, C.POINTER(CGResultC), C.c_void_p, C.c_void_p]
+    L.deff_slab_rank_solve_cg.argtypes = [ctx, C.c_double, C.c_int64, C.c_int64, C.POINTER(CGResultC), C.c_void_p, C.c_void_p]
     L.deff_rccl_unique_id.argtypes = [C.c_char_p]
     L.deff_slab_rank_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(ctx)]
     L.deff_slab_rank_create_custom.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, HOST_EXCHANGE_FN,

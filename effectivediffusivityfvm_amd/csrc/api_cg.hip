@@ -1,5 +1,6 @@
 // api_cg.hip -- deff_solve_cg: Jacobi-preconditioned conjugate gradients to a residual tolerance (kernels_cg.hpp), and
-// deff_solve_cg_stream: the same solve through the refilled slots of a stack (kernels_cg_stream.hpp, second half).  Not the
+// deff_solve_cg_stream: the same solve through the refilled slots of a stack (kernels_cg_stream.hpp, second half); at the end
+// the steps of one row slab of deff_slab_*_solve_cg (kernels_cg_slab.hpp; the loop over the slabs is in api_slab.hip).  Not the
 // reference's algorithm: it reaches the same discrete fixed point (same A, b, wall-flux Deff) as the weighted Jacobi loop of
 // deff_solve, in far fewer iterations.  Nothing of the Jacobi path is touched: its tables (lut, c0 plane), plans and knobs
 // stay as they are (the "fma" knob does not apply here: CG's arithmetic is written-order FP64 only).
@@ -7,10 +8,12 @@
 #include "kernels_cg.hpp"
 #include "kernels_cg_image.hpp"
 #include "kernels_cg_stream.hpp"
+#include "kernels_cg_slab.hpp"
+#include "cg_slab.hpp"
 #include <vector>
 
-// true-residual rounds that may restart the recurrence of a finished image (each round costs one pass and a synchronisation)
-static constexpr int CG_MAX_RESTARTS = 8;
+// (CG_MAX_RESTARTS, cg_slab.hpp: true-residual rounds that may restart the recurrence of a finished image; each round costs
+// one pass and a synchronisation)
 
 // CG table from the host dictionary: planes A0, 1/A0, aW, aE, aS, aN, b; decoupled rows (four zero links, b == 0) stay all
 // zeros.  An active row must have a finite positive A0 with a normal 1/A0 and finite links and b.
@@ -39,8 +42,11 @@ static int cg_table(const deff_ctx *c, std::vector<double> &t)
     return DEFF_OK;
 }
 
+// rows per work item of an image of `ntx` strips and ny rows: ~8 192 items per image, 2..16 rows each
+static int cg_rows_per_item(int ntx, int ny) { return (int)std::max(2L, std::min(16L, (long)ntx * ny / 8192)); }
+
 // Work items of one image: strips of 128 columns x kr rows, kr chosen from (nx, ny) alone so that an image of a stack is cut
-// (and its sums ordered) exactly like a one-image context's; ~8 192 items per image, 2..16 rows each.
+// (and its sums ordered) exactly like a one-image context's.
 static CgGeom cg_geometry(const deff_ctx *c)
 {
     CgGeom g;
@@ -48,8 +54,7 @@ static CgGeom cg_geometry(const deff_ctx *c)
     g.ny = c->ny;
     g.nimg = c->nimg;
     g.ntx = (c->nx + CG_COLS - 1) / CG_COLS;
-    const long want = (long)g.ntx * c->ny / 8192;
-    g.kr = (int)std::max(2L, std::min(16L, want));
+    g.kr = cg_rows_per_item(g.ntx, c->ny);
     g.cpi = (c->ny + g.kr - 1) / g.kr;
     g.per_img = (unsigned)((size_t)g.ntx * g.cpi);
     return g;
@@ -85,7 +90,8 @@ try {
     if (max_iter < 0) return fail(DEFF_EINVAL, "deff_solve_cg: negative max_iter");
     if (check_every < 1) return fail(DEFF_EINVAL, "check_every must be >= 1");
     if (c->slab)
-        return fail(DEFF_EINVAL, "deff_solve_cg: not for row-slab contexts (CG over row slabs needs an all-reduce per iteration)");
+        return fail(DEFF_EINVAL, "deff_solve_cg: not for row-slab contexts (CG over row slabs sums over all slabs: call "
+                                 "deff_slab_group_solve_cg or deff_slab_rank_solve_cg)");
     if (!c->have_field) return fail(DEFF_ESTATE, "no field: call deff_init_linear() or deff_set_field()");
     if (!c->have_walls) return fail(DEFF_ESTATE, "wall diffusivities unknown (needed for Deff)");
     if (c->wrap_links)
@@ -274,7 +280,9 @@ try {
     if (!(rtol >= 0.0) || !std::isfinite(rtol)) return fail(DEFF_EINVAL, "deff_solve_cg_stream: rtol must be finite and >= 0");
     if (max_iter < 0) return fail(DEFF_EINVAL, "deff_solve_cg_stream: negative max_iter");
     if (check_every < 1) return fail(DEFF_EINVAL, "check_every must be >= 1");
-    if (c->slab) return fail(DEFF_EINVAL, "deff_solve_cg_stream: not for row-slab contexts");
+    if (c->slab)
+        return fail(DEFF_EINVAL, "deff_solve_cg_stream: not for row-slab contexts (one image over row slabs: "
+                                 "deff_slab_group_solve_cg or deff_slab_rank_solve_cg)");
     TRY(use_device(c));
     TRY(resident_check(c));                                          // an unchecked resident interval is settled under the OLD system
     // the table first: a refusal leaves the context's dictionary as it was
@@ -479,3 +487,152 @@ try {
     return DEFF_OK;
 }
 DEFF_API_CATCH
+
+// ---- conjugate gradients over row slabs: the steps of one slab (cg_slab.hpp; the loop is slab_solve_cg, api_slab.hip) -----
+
+static_assert(SLCG_SLOT == CG_SLAB_SLOT, "gather slot width");
+
+static CgSlabGeom slcg_geom(const CgSlab &s)
+{
+    const deff_ctx *c = s.c;
+    return CgSlabGeom{c->nx, s.ntx, s.kr, c->own_lo, c->own_h, s.m_lo, s.m_hi, s.items};
+}
+
+// what deff_solve_cg asks of a context, for one slab; the table on success
+static int slcg_admit(deff_ctx *c, std::vector<double> &tab)
+{
+    if (!c->have_field) return fail(DEFF_ESTATE, "no field: call init_linear or set_field on the slabs");
+    if (!c->have_walls) return fail(DEFF_ESTATE, "wall diffusivities unknown (needed for Deff)");
+    if (c->wrap_links)
+        return fail(DEFF_EINVAL, "CG over row slabs: the system links a wall column to the neighbouring row (explicit-only system)");
+    if (!c->have_matfree && c->have_explicit) TRY(ensure_dictionary(c));
+    if (!c->have_matfree)
+        return fail(DEFF_EINVAL, "CG over row slabs: the slab's system has no row dictionary (too many distinct rows, or "
+                                 "dictionaries disabled): CG runs on the matrix-free form only");
+    return cg_table(c, tab);
+}
+
+int slcg_setup(CgSlab *s, double rtol, int64_t max_iter)
+{
+    deff_ctx *c = s->c;
+    TRY(use_device(c));
+    s->refusal.clear();
+    s->status = DEFF_OK;
+    std::vector<double> tab;
+    int rc = slcg_admit(c, tab);
+    // geometry: kr and the strips from the whole image, the items from this slab's owned rows
+    s->ntx = (c->nx + CG_COLS - 1) / CG_COLS;
+    s->kr = cg_rows_per_item(s->ntx, c->mesh_ny);
+    s->items = (unsigned)((size_t)s->ntx * ((c->own_h + s->kr - 1) / s->kr));
+    s->m_lo = std::max(0, c->dom_lo);
+    s->m_hi = std::min(c->rows, c->dom_lo + c->mesh_ny);
+    s->tol2 = rtol * rtol;
+    s->max_iter = (long long)max_iter;
+    s->k = 0;
+    // the work vectors only once the host's checks have passed (the check on the device needs the table and the flags there)
+    if (rc == DEFF_OK) rc = cg_buffers(c, s->items);
+    if (rc == DEFF_EHIP) return rc;
+    if (rc != DEFF_OK) { s->refusal = g_err; s->status = rc; }
+    if (rc == DEFF_OK) {
+        HIP_TRY(hipMemsetAsync(c->cg_flags, 0, sizeof(unsigned) * 2, c->stream));
+        // pageable source: the copy has left `tab` when the call returns
+        HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), sizeof(double) * CG_DOUBLES, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        hipLaunchKernelGGL(k_slcg_admissible, dim3(grid_for((size_t)c->nx * (s->m_hi - s->m_lo), 2048)), dim3(256), 0, c->stream,
+                           c->cg_tab, c->lut_nrows, c->code, c->nx, s->m_lo, s->m_hi, c->dom_lo >= 0 ? 1 : 0,
+                           c->dom_lo + c->mesh_ny <= c->rows ? 1 : 0, c->cg_flags);
+    }
+    // the host's verdict travels as 1 - status (>= 2; 0 and 1 are the device's): the flags are not read then, and may not exist
+    static_assert(DEFF_OK == 0 && DEFF_EINVAL < 0 && DEFF_ESTATE < 0 && DEFF_ENOMEM < 0, "verdict encoding");
+    hipLaunchKernelGGL(k_slcg_verdict, dim3(1), dim3(1), 0, c->stream, c->cg_flags, rc == DEFF_OK ? 0.0 : (double)(1 - rc),
+                       slcg_slot(*s, 2, s->me));
+    HIP_TRY(hipGetLastError());
+    return DEFF_OK;
+}
+
+void slcg_commit(CgSlab *s)
+{
+    deff_ctx *c = s->c;
+    c->cg_plan_kr = s->kr;
+    c->cg_plan_ntx = s->ntx;
+    c->cg_plan_items = (int)s->items;
+    c->cg_plan_restarts = 0;
+    c->cg_plan_impl = 1;
+}
+
+int slcg_dir(CgSlab *s)
+{
+    deff_ctx *c = s->c;
+    const CgSlabGeom g = slcg_geom(*s);
+    double *p_in = c->cg_p[s->k & 1], *p_out = c->cg_p[(s->k + 1) & 1];
+    hipLaunchKernelGGL(k_slcg_dir, dim3((g.items + 3) / 4), dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->cg_r, p_in,
+                       p_out, (const CgScal *)c->cg_scal, g, c->cg_part);
+    if (s->nslabs > 1)
+        hipLaunchKernelGGL(k_slcg_sum, dim3(1), dim3(CG_FIN), 0, c->stream, c->cg_part, g.items, 1, (size_t)0, 1,
+                           slcg_slot(*s, 0, s->me));
+    HIP_TRY(hipGetLastError());
+    return DEFF_OK;
+}
+
+int slcg_alpha_update(CgSlab *s)
+{
+    deff_ctx *c = s->c;
+    const CgSlabGeom g = slcg_geom(*s);
+    double *p = c->cg_p[(s->k + 1) & 1];
+    double *part_rz = c->cg_part + g.items, *part_rr = c->cg_part + 2 * (size_t)g.items;
+    hipLaunchKernelGGL(k_slcg_alpha, dim3(1), dim3(CG_FIN), 0, c->stream, c->cg_part, g.items, slcg_slot(*s, 0, 0), s->nslabs, s->me,
+                       (CgScal *)c->cg_scal);
+    hipLaunchKernelGGL(k_slcg_update, dim3((g.items + 3) / 4), dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p,
+                       c->x[c->cur], c->cg_r, (const CgScal *)c->cg_scal, g, part_rz, part_rr);
+    if (s->nslabs > 1)
+        hipLaunchKernelGGL(k_slcg_sum, dim3(1), dim3(CG_FIN), 0, c->stream, part_rz, g.items, 1, (size_t)g.items, 2,
+                           slcg_slot(*s, 1, s->me));
+    HIP_TRY(hipGetLastError());
+    ++s->k;
+    return DEFF_OK;
+}
+
+int slcg_beta(CgSlab *s)
+{
+    deff_ctx *c = s->c;
+    double *part_rz = c->cg_part + s->items, *part_rr = c->cg_part + 2 * (size_t)s->items;
+    hipLaunchKernelGGL(k_slcg_beta, dim3(1), dim3(CG_FIN), 0, c->stream, part_rz, part_rr, s->items, slcg_slot(*s, 1, 0), s->nslabs,
+                       s->me, (CgScal *)c->cg_scal, s->tol2, s->max_iter);
+    HIP_TRY(hipGetLastError());
+    return DEFF_OK;
+}
+
+int slcg_resid(CgSlab *s)
+{
+    deff_ctx *c = s->c;
+    const CgSlabGeom g = slcg_geom(*s);
+    hipLaunchKernelGGL(k_slcg_resid, dim3((g.items + 3) / 4), dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->x[c->cur],
+                       c->cg_r, g, c->cg_part);
+    if (s->nslabs > 1)
+        hipLaunchKernelGGL(k_slcg_sum, dim3(1), dim3(CG_FIN), 0, c->stream, c->cg_part, g.items, 3, (size_t)1, 3,
+                           slcg_slot(*s, 2, s->me));
+    HIP_TRY(hipGetLastError());
+    return DEFF_OK;
+}
+
+int slcg_check(CgSlab *s, int mode, int allow_restart)
+{
+    deff_ctx *c = s->c;
+    if (mode == 1) HIP_TRY(hipMemsetAsync(c->cg_flags + 1, 0, sizeof(unsigned), c->stream));
+    hipLaunchKernelGGL(k_slcg_check, dim3(1), dim3(CG_FIN), 0, c->stream, c->cg_part, s->items, slcg_slot(*s, 2, 0), s->nslabs, s->me,
+                       (CgScal *)c->cg_scal, s->tol2, s->max_iter, mode, allow_restart, c->cg_flags + 1);
+    HIP_TRY(hipGetLastError());
+    return DEFF_OK;
+}
+
+int slcg_read(CgSlab *s, CgSlabState *out)
+{
+    deff_ctx *c = s->c;
+    CgScal h;
+    unsigned flag = 0;
+    HIP_TRY(hipMemcpyAsync(&h, c->cg_scal, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&flag, c->cg_flags + 1, sizeof flag, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out = CgSlabState{h.iters, h.rel, h.done, flag};
+    return DEFF_OK;
+}

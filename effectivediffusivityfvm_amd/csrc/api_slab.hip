@@ -4,6 +4,7 @@
 
 #include <functional>
 
+#include "cg_slab.hpp"
 #include "ctx.hpp"
 
 // ====================================================================== row slabs ==
@@ -41,6 +42,11 @@ struct Slab {
     hipStream_t xs = nullptr;
     hipEvent_t bnd = nullptr, halo = nullptr;
     SlabPass plT, pl1;                        // passes of T sweeps and of one sweep (slab_plans)
+    // conjugate gradients (slab_solve_cg), made by the first one: the solve's state, the gathered sums on the device and
+    // the event "this slab's rows and its gather slot are written"
+    CgSlab cg;
+    double *cg_all = nullptr;
+    hipEvent_t cg_ev = nullptr;
 };
 
 // The slabs one call drives and how their halo rows travel: a group's N slabs with peer copies, or a rank's one slab
@@ -51,6 +57,12 @@ struct SlabSet {
     int n;
     int overlap;                              // slab_overlap as it applies to these slabs
     std::function<int(int r, hipStream_t xs)> exchange;
+    // what conjugate gradients need beyond it (slab_solve_cg), each enqueued on slab r's stream behind the neighbours' cg_ev:
+    int total = 1, first = 0;                 // slabs of the image, and which of them s[0] is
+    // the row of buf(slab) next to each neighbour goes into that neighbour's adjacent halo row (and theirs into r's)
+    std::function<int(int r, double *(*buf)(const Slab &))> send_row;
+    std::function<int(int r, int phase)> gather;          // every slab's CG_SLAB_SLOT doubles of `phase` into every slab's cg_all
+    std::function<int(int r)> settle;                     // r's stream waits until its neighbours have taken what `exchange` moves
 };
 
 // overlap: 0 = never split, 1 = split when it pays (a slab of >= 16 Mi cells: three launches + the stream hand-overs
@@ -142,6 +154,8 @@ static void slab_close(Slab &s)
     if (s.xs) { (void)hipStreamSynchronize(s.xs); (void)hipStreamDestroy(s.xs); }
     if (s.bnd) (void)hipEventDestroy(s.bnd);
     if (s.halo) (void)hipEventDestroy(s.halo);
+    if (s.cg_ev) (void)hipEventDestroy(s.cg_ev);
+    if (s.cg_all) (void)hipFree(s.cg_all);
     deff_destroy(s.c);
     s.c = nullptr;
 }
@@ -320,6 +334,172 @@ static int slab_solve(const SlabSet &set, const std::function<int(double *deff_r
     float ms = 0;
     TRY(slab_elapsed(set, &ms));
     *out = chk.result(iter, ms);
+    return DEFF_OK;
+}
+
+// ------------------------------------------------------------ conjugate gradients over the slabs --
+//
+// deff_solve_cg's loop (api_cg.hip) with the image's rows on several slabs: kernels_cg_slab.hpp has the dependency argument.
+// Per iteration and slab: dir + slab sum | gather A | alpha, update + slab sums | one row of r to each neighbour, gather B |
+// beta.  Every slab holds the same scalars bit for bit and freezes itself on the device; the host enqueues check_every
+// iterations on every slab without waiting and then reads slab 0's state (set.s[0]: in the rank form, this rank's own).
+// Between slabs only events order the work (cg_ev: "my rows and my slot are written"), recorded for all slabs before any
+// slab waits for one.  The three gather phases have buffers of their own, so a slab's next sum never overwrites a slot a
+// copy still reads: the gather in between is a barrier among all slabs ("Row slabs").
+
+static double *slab_cg_r(const Slab &s) { return s.c->cg_r; }
+
+// the 8-row exchange of the current field, as after a pass: every halo row of every slab holds the neighbours' rows
+static int slab_exchange_field(const SlabSet &set)
+{
+    for (int r = 0; r < set.n; ++r) {
+        TRY(use_device(set.s[r].c));
+        HIP_TRY(hipEventRecord(set.s[r].bnd, set.s[r].c->stream));
+    }
+    for (int r = 0; r < set.n; ++r) {
+        Slab &s = set.s[r];
+        TRY(use_device(s.c));
+        TRY(set.exchange(r, s.c->stream));
+        HIP_TRY(hipEventRecord(s.halo, s.c->stream));
+    }
+    for (int r = 0; r < set.n; ++r) { TRY(use_device(set.s[r].c)); TRY(set.settle(r)); }
+    return DEFF_OK;
+}
+
+static int slab_cg_record(const SlabSet &set, int r)
+{
+    HIP_TRY(hipEventRecord(set.s[r].cg_ev, set.s[r].c->stream));
+    return DEFF_OK;
+}
+
+static int slab_solve_cg(const SlabSet &set, const std::function<int(double *deff_raw)> &flux, double rtol, int64_t max_iter,
+                         int64_t check_every, deff_cg_result *out)
+{
+    const bool multi = set.total > 1;
+    const size_t all_n = (size_t)CG_SLAB_PHASES * set.total * CG_SLAB_SLOT;
+    for (int r = 0; r < set.n; ++r) {
+        Slab &s = set.s[r];
+        TRY(use_device(s.c));
+        // x[cur] as it stands is the guess: a slab context is one image (nothing to consolidate) and never sweeps with
+        // resident launches (resident_allowed), so this settles nothing today and stays right if that changes
+        TRY(resident_check(s.c));
+        if (!s.cg_all) {
+            HIP_TRY(hipMalloc((void **)&s.cg_all, sizeof(double) * all_n));
+            HIP_TRY(hipMemsetAsync(s.cg_all, 0, sizeof(double) * all_n, s.c->stream));
+            HIP_TRY(hipEventCreateWithFlags(&s.cg_ev, hipEventDisableTiming));
+        }
+        s.cg.c = s.c;
+        s.cg.nslabs = set.total;
+        s.cg.me = set.first + r;
+        s.cg.all = s.cg_all;
+        TRY(slcg_setup(&s.cg, rtol, max_iter));
+        TRY(slab_cg_record(set, r));
+    }
+    // the verdicts, gathered like a sum: every slab (every rank) sees them all and refuses or goes on with the others
+    std::vector<double> verdict((size_t)set.total * CG_SLAB_SLOT);
+    for (int r = 0; r < set.n; ++r) {
+        Slab &s = set.s[r];
+        TRY(use_device(s.c));
+        if (multi) TRY(set.gather(r, 2));
+        HIP_TRY(hipMemcpyAsync(verdict.data(), slcg_slot(s.cg, 2, 0), sizeof(double) * verdict.size(), hipMemcpyDeviceToHost,
+                               s.c->stream));
+        HIP_TRY(hipStreamSynchronize(s.c->stream));
+    }
+    for (int q = 0; q < set.total; ++q) {
+        const double v = verdict[(size_t)q * CG_SLAB_SLOT];
+        if (v == 0.0) continue;
+        if (v == 1.0)
+            return fail(DEFF_EINVAL, "CG over row slabs: the system is not symmetric (slab %d: a link between two active cells "
+                                     "differs from its partner, or an active row links out of the image)", q);
+        // the status of that slab's own checks, as deff_solve_cg gives it (slcg_setup: v = 1 - status)
+        const int code = 1 - (int)v, r = q - set.first;
+        const int status = code == DEFF_ESTATE || code == DEFF_ENOMEM ? code : DEFF_EINVAL;
+        if (r >= 0 && r < set.n && !set.s[r].cg.refusal.empty())
+            return fail(status, "CG over row slabs, slab %d: %s", q, std::string(set.s[r].cg.refusal).c_str());
+        return fail(status, "CG over row slabs: slab %d cannot run it (its rank reports why)", q);
+    }
+    for (int r = 0; r < set.n; ++r) slcg_commit(&set.s[r].cg);
+
+    deff_ctx *c0 = set.s[0].c;
+    TRY(use_device(c0));
+    HIP_TRY(hipEventRecord(c0->ev0, c0->stream));
+    // r = b - A x and its check on every slab: x's halo rows first, r's adjacent halo row afterwards
+    auto residual_round = [&](int mode, int allow) -> int {
+        if (multi) TRY(slab_exchange_field(set));
+        for (int r = 0; r < set.n; ++r) {
+            TRY(use_device(set.s[r].c));
+            TRY(slcg_resid(&set.s[r].cg));
+            TRY(slab_cg_record(set, r));
+        }
+        for (int r = 0; r < set.n; ++r) {
+            TRY(use_device(set.s[r].c));
+            if (multi) { TRY(set.send_row(r, slab_cg_r)); TRY(set.gather(r, 2)); }
+            TRY(slcg_check(&set.s[r].cg, mode, allow));
+        }
+        return DEFF_OK;
+    };
+    // the one host wait of an interval: slab 0's scalars (every slab's are the same bits), every slab's stream idle
+    CgSlabState st;
+    auto look = [&]() -> int {
+        TRY(use_device(c0));
+        TRY(slcg_read(&set.s[0].cg, &st));
+        for (int r = 1; r < set.n; ++r) { TRY(use_device(set.s[r].c)); HIP_TRY(hipStreamSynchronize(set.s[r].c->stream)); }
+        return DEFF_OK;
+    };
+    TRY(residual_round(0, 0));
+    int rounds = 0;
+    for (;;) {
+        TRY(look());
+        if (st.done) {
+            // the recurrence's residual drifts from b - A x: recompute it; a solve whose true residual misses rtol goes on
+            TRY(residual_round(1, rounds < CG_MAX_RESTARTS));
+            TRY(look());
+            if (!st.restarted) break;
+            ++rounds;
+            for (int r = 0; r < set.n; ++r) set.s[r].c->cg_plan_restarts = rounds;
+        }
+        for (int64_t i = 0; i < check_every; ++i) {
+            for (int r = 0; r < set.n; ++r) {
+                TRY(use_device(set.s[r].c));
+                TRY(slcg_dir(&set.s[r].cg));
+                if (multi) TRY(slab_cg_record(set, r));
+            }
+            // every slab's wait on the others' dir is enqueued before any slab records its update: a wait binds to the
+            // event's latest record, and behind a neighbour's newer one the updates would run one slab after another
+            if (multi)
+                for (int r = 0; r < set.n; ++r) { TRY(use_device(set.s[r].c)); TRY(set.gather(r, 0)); }
+            for (int r = 0; r < set.n; ++r) {
+                TRY(use_device(set.s[r].c));
+                TRY(slcg_alpha_update(&set.s[r].cg));
+                if (multi) TRY(slab_cg_record(set, r));
+            }
+            for (int r = 0; r < set.n; ++r) {
+                TRY(use_device(set.s[r].c));
+                if (multi) { TRY(set.send_row(r, slab_cg_r)); TRY(set.gather(r, 1)); }
+                TRY(slcg_beta(&set.s[r].cg));
+            }
+        }
+    }
+    // an ordinary slab set again: the last round wrote zeros on decoupled cells, so the field's halo rows travel once more
+    if (multi) TRY(slab_exchange_field(set));
+    float ms = 0;
+    TRY(slab_elapsed(set, &ms));
+    double deff = 0;
+    TRY(flux(&deff));
+    out->iters = st.iters;
+    out->rel_residual = st.rel;
+    out->deff_raw = deff;
+    out->loop_ms = ms;
+    out->converged = st.rel <= rtol;
+    return DEFF_OK;
+}
+
+static int cg_arguments(const void *obj, const deff_cg_result *out, double rtol, int64_t max_iter, int64_t check_every)
+{
+    if (!obj || !out) return fail(DEFF_EINVAL, "NULL argument");
+    if (!(rtol >= 0.0) || !std::isfinite(rtol)) return fail(DEFF_EINVAL, "CG over row slabs: rtol must be finite and >= 0");
+    if (max_iter < 0) return fail(DEFF_EINVAL, "CG over row slabs: negative max_iter");
+    if (check_every < 1) return fail(DEFF_EINVAL, "check_every must be >= 1");
     return DEFF_OK;
 }
 
@@ -521,6 +701,71 @@ try {
 }
 DEFF_API_CATCH
 
+// The group's transports for conjugate gradients, all on slab r's own stream behind the other slabs' cg_ev.
+static int group_send_row(deff_slab_group *g, int r, double *(*buf)(const Slab &))
+{
+    const Slab &me = g->slabs[r];
+    deff_ctx *c = me.c;
+    const size_t bytes = sizeof(double) * c->nx;
+    if (r > 0) {                                                   // halo row above <- last own row of slab r-1
+        const Slab &u = g->slabs[r - 1];
+        HIP_TRY(hipStreamWaitEvent(c->stream, u.cg_ev, 0));
+        HIP_TRY(hipMemcpyPeerAsync(buf(me) + (size_t)(c->own_lo - 1) * c->nx, c->device,
+                                   buf(u) + (size_t)(u.c->own_lo + u.c->own_h - 1) * c->nx, u.c->device, bytes, c->stream));
+    }
+    if (r + 1 < (int)g->slabs.size()) {                            // halo row below <- first own row of slab r+1
+        const Slab &d = g->slabs[r + 1];
+        HIP_TRY(hipStreamWaitEvent(c->stream, d.cg_ev, 0));
+        HIP_TRY(hipMemcpyPeerAsync(buf(me) + (size_t)(c->own_lo + c->own_h) * c->nx, c->device,
+                                   buf(d) + (size_t)d.c->own_lo * c->nx, d.c->device, bytes, c->stream));
+    }
+    return DEFF_OK;
+}
+
+static int group_gather(deff_slab_group *g, int r, int phase)
+{
+    const Slab &me = g->slabs[r];
+    for (int q = 0; q < (int)g->slabs.size(); ++q) {
+        if (q == r) continue;
+        const Slab &o = g->slabs[q];
+        HIP_TRY(hipStreamWaitEvent(me.c->stream, o.cg_ev, 0));
+        HIP_TRY(hipMemcpyPeerAsync(slcg_slot(me.cg, phase, q), me.c->device, slcg_slot(o.cg, phase, q), o.c->device,
+                                   sizeof(double) * CG_SLAB_SLOT, me.c->stream));
+    }
+    return DEFF_OK;
+}
+
+// slab r goes on only when its neighbours' copies out of its rows are done (their `halo`)
+static int group_settle(deff_slab_group *g, int r)
+{
+    if (r > 0) HIP_TRY(hipStreamWaitEvent(g->slabs[r].c->stream, g->slabs[r - 1].halo, 0));
+    if (r + 1 < (int)g->slabs.size()) HIP_TRY(hipStreamWaitEvent(g->slabs[r].c->stream, g->slabs[r + 1].halo, 0));
+    return DEFF_OK;
+}
+
+static SlabSet cg_slabs_of(deff_slab_group *g)
+{
+    SlabSet set = slabs_of(g);
+    set.total = (int)g->slabs.size();
+    set.first = 0;
+    set.send_row = [g](int r, double *(*buf)(const Slab &)) { return group_send_row(g, r, buf); };
+    set.gather = [g](int r, int phase) { return group_gather(g, r, phase); };
+    set.settle = [g](int r) { return group_settle(g, r); };
+    return set;
+}
+
+extern "C" int deff_slab_group_solve_cg(deff_slab_group *g, double rtol, int64_t max_iter, int64_t check_every,
+                                        deff_cg_result *out, double *MFL, double *MFR)
+try {
+    TRY(cg_arguments(g, out, rtol, max_iter, check_every));
+    TRY(slab_solve_cg(cg_slabs_of(g), [g](double *deff_raw) { return group_flux(g, deff_raw); }, rtol, max_iter, check_every,
+                      out));
+    if (MFL) memcpy(MFL, g->mfl.data(), sizeof(double) * g->NY);
+    if (MFR) memcpy(MFR, g->mfr.data(), sizeof(double) * g->NY);
+    return DEFF_OK;
+}
+DEFF_API_CATCH
+
 extern "C" int deff_slab_group_set_tuning(deff_slab_group *g, const char *key, int value)
 try {
     if (!g) return fail(DEFF_EINVAL, "group is NULL");
@@ -557,6 +802,7 @@ struct deff_slab_rank {
     deff_host_allgather_fn gather = nullptr;
     void *user = nullptr;
     std::vector<double> h_send_up, h_send_dn, h_recv_up, h_recv_dn, h_pack;
+    std::vector<double> h_cg_all;                    // ... and the gathered sums of conjugate gradients
     int overlap = 1;
 };
 
@@ -831,6 +1077,92 @@ try {
     if (!s || !out) return fail(DEFF_EINVAL, "NULL argument");
     TRY(slab_solve(slabs_of(s), [s](double *deff_raw) { return rank_flux(s, deff_raw); }, omega, tol, max_iter,
                    check_every, out));
+    if (MFL) memcpy(MFL, s->mfl.data(), sizeof(double) * s->NY);
+    if (MFR) memcpy(MFR, s->mfr.data(), sizeof(double) * s->NY);
+    return DEFF_OK;
+}
+DEFF_API_CATCH
+
+// The rank's transports for conjugate gradients, on the context's stream.  RCCL: a grouped ncclSend / ncclRecv of one row
+// per neighbour and an in-place ncclAllGather of the slots, no host wait.  Custom: host staged through the caller's
+// callbacks (`exchange` with count = row pitch, `allgather` with count = CG_SLAB_SLOT), which waits every time.
+static int rank_send_row(deff_slab_rank *s, double *(*buf)(const Slab &))
+{
+    deff_ctx *c = s->slab.c;
+    const size_t row = (size_t)c->nx;
+    double *b = buf(s->slab);
+    const bool up = s->rank > 0, dn = s->rank + 1 < s->nranks;
+    double *top_own = b + (size_t)c->own_lo * row, *bot_own = b + (size_t)(c->own_lo + c->own_h - 1) * row;
+    double *top_halo = b + (size_t)(c->own_lo - 1) * row, *bot_halo = b + (size_t)(c->own_lo + c->own_h) * row;
+    if (s->xchg) {
+        if (up) HIP_TRY(hipMemcpyAsync(s->h_send_up.data(), top_own, sizeof(double) * row, hipMemcpyDeviceToHost, c->stream));
+        if (dn) HIP_TRY(hipMemcpyAsync(s->h_send_dn.data(), bot_own, sizeof(double) * row, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (s->xchg(s->user, up ? s->h_send_up.data() : nullptr, up ? s->h_recv_up.data() : nullptr,
+                    dn ? s->h_send_dn.data() : nullptr, dn ? s->h_recv_dn.data() : nullptr, row) != 0)
+            return fail(DEFF_ECOMM, "custom row exchange failed");
+        if (up) HIP_TRY(hipMemcpyAsync(top_halo, s->h_recv_up.data(), sizeof(double) * row, hipMemcpyHostToDevice, c->stream));
+        if (dn) HIP_TRY(hipMemcpyAsync(bot_halo, s->h_recv_dn.data(), sizeof(double) * row, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));                // the host buffers are reused by the next exchange
+        return DEFF_OK;
+    }
+    NCCL_TRY(ncclGroupStart());                                  // (a failure inside still closes the group: rank_exchange)
+    ncclResult_t first = ncclSuccess;
+    const char *what = "";
+    auto step = [&](ncclResult_t r, const char *name) { if (first == ncclSuccess && r != ncclSuccess) { first = r; what = name; } };
+    if (up) {
+        step(ncclSend(top_own, row, ncclDouble, s->rank - 1, s->comm, c->stream), "ncclSend(up)");
+        step(ncclRecv(top_halo, row, ncclDouble, s->rank - 1, s->comm, c->stream), "ncclRecv(up)");
+    }
+    if (dn) {
+        step(ncclSend(bot_own, row, ncclDouble, s->rank + 1, s->comm, c->stream), "ncclSend(down)");
+        step(ncclRecv(bot_halo, row, ncclDouble, s->rank + 1, s->comm, c->stream), "ncclRecv(down)");
+    }
+    const ncclResult_t end = ncclGroupEnd();
+    if (first != ncclSuccess) return fail(DEFF_ECOMM, "%s failed: %s", what, ncclGetErrorString(first));
+    if (end != ncclSuccess) return fail(DEFF_ECOMM, "ncclGroupEnd failed: %s", ncclGetErrorString(end));
+    return DEFF_OK;
+}
+
+static int rank_gather(deff_slab_rank *s, int phase)
+{
+    deff_ctx *c = s->slab.c;
+    const CgSlab &cg = s->slab.cg;
+    if (s->gather) {
+        s->h_cg_all.resize((size_t)(s->nranks + 1) * CG_SLAB_SLOT);
+        double *mine = s->h_cg_all.data() + (size_t)s->nranks * CG_SLAB_SLOT;
+        HIP_TRY(hipMemcpyAsync(mine, slcg_slot(cg, phase, s->rank), sizeof(double) * CG_SLAB_SLOT, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (s->gather(s->user, mine, s->h_cg_all.data(), (size_t)CG_SLAB_SLOT) != 0)
+            return fail(DEFF_ECOMM, "custom all-gather of the CG sums failed");
+        HIP_TRY(hipMemcpyAsync(slcg_slot(cg, phase, 0), s->h_cg_all.data(), sizeof(double) * CG_SLAB_SLOT * s->nranks,
+                               hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return DEFF_OK;
+    }
+    NCCL_TRY(ncclAllGather(slcg_slot(cg, phase, s->rank), slcg_slot(cg, phase, 0), (size_t)CG_SLAB_SLOT, ncclDouble, s->comm,
+                           c->stream));
+    return DEFF_OK;
+}
+
+static SlabSet cg_slabs_of(deff_slab_rank *s)
+{
+    SlabSet set = slabs_of(s);
+    set.total = s->nranks;
+    set.first = s->rank;
+    set.send_row = [s](int, double *(*buf)(const Slab &)) { return rank_send_row(s, buf); };
+    set.gather = [s](int, int phase) { return rank_gather(s, phase); };
+    set.settle = [](int) { return DEFF_OK; };                    // a rank's sends are in its own stream's order
+    return set;
+}
+
+// Collective, like deff_slab_rank_solve: every rank calls it with the same arguments and gets the same result.
+extern "C" int deff_slab_rank_solve_cg(deff_slab_rank *s, double rtol, int64_t max_iter, int64_t check_every,
+                                       deff_cg_result *out, double *MFL, double *MFR)
+try {
+    TRY(cg_arguments(s, out, rtol, max_iter, check_every));
+    TRY(slab_solve_cg(cg_slabs_of(s), [s](double *deff_raw) { return rank_flux(s, deff_raw); }, rtol, max_iter, check_every,
+                      out));
     if (MFL) memcpy(MFL, s->mfl.data(), sizeof(double) * s->NY);
     if (MFR) memcpy(MFR, s->mfr.data(), sizeof(double) * s->NY);
     return DEFF_OK;

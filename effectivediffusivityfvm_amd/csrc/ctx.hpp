@@ -8,10 +8,12 @@
 //   tiles_8wave.hip, tiles_tall.hip, tiles_12wave.hip
 //                  the workgroup-tile kernels, one family each, listed for the planner (tile_kernels.hpp)
 //   api_solve.hip  wall fluxes and the Jacobi solve loops (one image, batch, streaming batch); no sweep kernel
-//   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg) and through refilled slots (deff_solve_cg_stream)
+//   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg) and through refilled slots (deff_solve_cg_stream);
+//                  every CG kernel, the slab forms included: their launches for one slab (cg_slab.hpp)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
-//                  RCCL or a caller-supplied transport with one process per GPU)
+//                  RCCL or a caller-supplied transport with one process per GPU); conjugate gradients over the slabs
+//                  (slab_solve_cg: the loop and what travels between slabs)
 // The library is built with -fvisibility=hidden; only the C ABI of include/deff_amd.h is exported.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -10,12 +10,13 @@
 //
 //   deff2d [input.txt] [--device N | --devices 0,1,..] [--json results.json] [--field-bin prefix] [--batch-size B]
 //          [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K]
-//          [--solver jacobi|cg] [--cg-rtol R]
+//          [--solver jacobi|cg] [--cg-rtol R] [--cg-slabs]
 // --solver cg: every solve of a one-GPU image runs preconditioned conjugate gradients to ||b - A x|| <= R ||b||
 // (deff_solve_cg, R = --cg-rtol, default 1e-10) instead of the reference's Jacobi loop; the 3-phase continuation
 // stages keep their structure.  The CSV columns stay: iterations = CG iterations, converge = the final relative
-// residual.  Row slabs (--devices with RunBatch 0) refuse it; batch mode then solves one image at a time per worker
-// instead of in stacked slots.
+// residual.  Row slabs (--devices with RunBatch 0) refuse it unless --cg-slabs is given (deff_slab_group_solve_cg: the
+// dot products are then summed slab by slab, so the result agrees with the one-GPU solve to rounding, not bit for
+// bit); batch mode then solves one image at a time per worker instead of in stacked slots.
 // --arith contracted: products fused into adds the way a compiler contracts the reference's expressions
 // (kernels_sweep.hpp); default is the reference's written operation order.
 //
@@ -121,6 +122,7 @@ static int g_prefetch_threads = 2;
 static bool g_solver_cg = false;   // --solver cg
 static double g_cg_rtol = 1e-10;   // --cg-rtol
 static int g_cg_batch = 0;         // --cg-batch B: 2-phase batch mode solves runs of up to B equally sized images in one stack
+static bool g_cg_slabs = false;    // --cg-slabs: --solver cg on row slabs (deff_slab_group_solve_cg)
 static int g_cg_stream = 0;        // --cg-stream B: ... keeps B slots full instead (deff_solve_cg_stream)
 
 struct Session {                   // one solver context, re-created only when the mesh / batch size changes
@@ -203,6 +205,19 @@ struct Slabs {
     const std::vector<int> &devices;
     deff_slab_group *g = nullptr;
     ~Slabs() { deff_slab_group_destroy(g); }
+    // --solver cg --cg-slabs: deff_slab_group_solve_cg in place of the Jacobi loop, reported like solve_cg above
+    int solve_cg(int64_t max_iter, deff_result *r)
+    {
+        deff_cg_result c;
+        const int rc = deff_slab_group_solve_cg(g, g_cg_rtol, max_iter, 64, &c, nullptr, nullptr);
+        if (rc != DEFF_OK) return rc;
+        r->iters = c.iters;
+        r->checks = 0;
+        r->deff_raw = c.deff_raw;
+        r->conv = c.rel_residual;
+        r->loop_ms = c.loop_ms;
+        return DEFF_OK;
+    }
     bool open(const Image &im, const Options &o, int nx, int ny)
     {
         CK(deff_slab_group_create((int)devices.size(), devices.data(), nx, ny, &g));
@@ -219,6 +234,7 @@ struct Slabs {
     bool assemble(const Options &o, double DCF) { CK(deff_slab_group_assemble_2phase(g, o.DCsolid, DCF, o.CLeft, o.CRight)); return true; }
     bool solve(const Options &o, double *, deff_result *r)
     {
+        if (g_solver_cg) { CK(solve_cg(o.MAX_ITER, r)); return true; }
         CK(deff_slab_group_solve(g, 2.0 / 3.0, o.ConvergeCriteria, o.MAX_ITER, 10000, r, nullptr, nullptr));
         return true;
     }
@@ -231,6 +247,7 @@ struct Slabs {
     }
     bool solve_with(const Options &, double tol, int64_t max_iter, bool, double *, deff_result *r)
     {
+        if (g_solver_cg) { CK(solve_cg(max_iter, r)); return true; }
         CK(deff_slab_group_solve(g, 2.0 / 3.0, tol, max_iter, 10000, r, nullptr, nullptr));
         return true;
     }
@@ -752,8 +769,11 @@ int main(int argc, char **argv)
             g_cg_stream = (int)v;
             cg_stream_given = true;
         }
+        else if (s == "--cg-slabs") g_cg_slabs = true;
         else if (s == "-h" || s == "--help") {
-            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B] [--cg-stream B]\n"
+            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B] [--cg-stream B] [--cg-slabs]\n"
+                        "--cg-slabs (with --solver cg, RunBatch 0 and --devices a,b,...): conjugate gradients over the row slabs; the dot\n"
+                        "products are summed slab by slab, so the result agrees with the one-GPU solve to rounding, not bit for bit.\n"
                         "--cg-batch B (with --solver cg, RunBatch 1, 2 phases): runs of up to B consecutive, equally sized images are solved\n"
                         "together in one stack, an image of at most 16 384 cells on one compute unit each; 0 (default) = one image at a time.\n"
                         "--cg-stream B (with --solver cg, RunBatch 1, 2 phases; not with --cg-batch): B slots are kept full instead -- a slot\n"
@@ -774,6 +794,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "deff2d: --cg-stream needs --solver cg\n");
         return 2;
     }
+    if (g_cg_slabs && !g_solver_cg) {
+        std::fprintf(stderr, "deff2d: --cg-slabs needs --solver cg\n");
+        return 2;
+    }
     if (cg_stream_given && cg_batch_given) {
         std::fprintf(stderr, "deff2d: --cg-stream and --cg-batch exclude each other\n");
         return 2;
@@ -783,9 +807,13 @@ int main(int argc, char **argv)
     if (!deff::read_input_file(input.c_str(), &o, &err)) { std::fprintf(stderr, "deff2d: %s\n", err.c_str()); return 1; }
     if (o.verbose == 1) deff::print_options(o);
 
-    if (g_solver_cg && !o.BatchFlag && devices.size() >= 2) {
-        std::fprintf(stderr, "deff2d: --solver cg runs on one GPU: row slabs (--devices with RunBatch 0) need an all-reduce per "
-                             "CG iteration and are not offered\n");
+    if (g_cg_slabs && (o.BatchFlag || devices.size() < 2)) {
+        std::fprintf(stderr, "deff2d: --cg-slabs needs a row-slab run: RunBatch 0 and --devices with two or more entries\n");
+        return 2;
+    }
+    if (g_solver_cg && !g_cg_slabs && !o.BatchFlag && devices.size() >= 2) {
+        std::fprintf(stderr, "deff2d: --solver cg runs on one GPU by default: over row slabs (--devices with RunBatch 0) it sums its "
+                             "dot products slab by slab and agrees with the one-GPU solve to rounding only; ask for it with --cg-slabs\n");
         return 2;
     }
     const bool cg_batched = g_solver_cg && o.BatchFlag && o.nPhase == 2 && g_cg_batch >= 2;

@@ -31,6 +31,20 @@ class CGResult:
                 f"converged={self.converged}, loop_ms={self.loop_ms:.3f})")
 
 
+def _slab_solve_cg(fn, handle, ny, rtol, max_iter, check_every, fluxes):
+    """deff_slab_group_solve_cg / deff_slab_rank_solve_cg -> CGResult with the image's NY wall fluxes."""
+    res = CGResultC()
+    MFL = np.zeros(ny)
+    MFR = np.zeros(ny)
+    check(fn(handle, float(rtol), int(max_iter), int(check_every), C.byref(res),
+             MFL.ctypes.data_as(C.c_void_p) if fluxes else None, MFR.ctypes.data_as(C.c_void_p) if fluxes else None))
+    out = CGResult()
+    out.iters, out.rel_residual, out.deff_raw = res.iters, res.rel_residual, res.deff_raw
+    out.converged, out.loop_ms = bool(res.converged), res.loop_ms
+    out.MFL, out.MFR = MFL, MFR
+    return out
+
+
 def recommended_batch(nx, ny, images, device=0):
     """Slots a stack Solver(nx, ny, nimg=...) should have to solve `images` images (deff_recommended_batch)."""
     n = C.c_int()
@@ -405,6 +419,12 @@ class SlabGroup:
             out.append(d)
         return out
 
+    def plan_value(self, slab, key):
+        """One figure of slab `slab`'s last plan (deff_slab_group_get_plan), e.g. "cg_kr", "cg_items"."""
+        v = C.c_int()
+        check(self._L.deff_slab_group_get_plan(self._g, int(slab), key.encode(), C.byref(v)))
+        return v.value
+
     def set_image(self, pix):
         pix = np.ascontiguousarray(pix, dtype=np.uint8)
         assert pix.shape == (self.ny, self.nx)
@@ -462,6 +482,11 @@ class SlabGroup:
         out.deff_raw, out.conv, out.loop_ms = res.deff_raw, res.conv, res.loop_ms
         out.MFL, out.MFR = MFL, MFR
         return out
+
+    def solve_cg(self, rtol=1e-10, max_iter=1_000_000, check_every=64, fluxes=True):
+        """Conjugate gradients over the slabs from the current field to ||b - A x|| <= rtol ||b|| (deff_slab_group_solve_cg):
+        Solver.solve_cg for an image spread over row slabs.  One slab: the bits of Solver.solve_cg."""
+        return _slab_solve_cg(self._L.deff_slab_group_solve_cg, self._g, self.ny, rtol, max_iter, check_every, fluxes)
 
 
 def rccl_unique_id():
@@ -618,6 +643,15 @@ class SlabRank:
         out.deff_raw, out.conv, out.loop_ms = res.deff_raw, res.conv, res.loop_ms
         out.MFL, out.MFR = MFL, MFR
         return out
+
+    def solve_cg(self, rtol=1e-10, max_iter=1_000_000, check_every=64, fluxes=True):
+        """SlabGroup.solve_cg, collective over the ranks (deff_slab_rank_solve_cg): every rank gets the same CGResult."""
+        return _slab_solve_cg(self._L.deff_slab_rank_solve_cg, self._s, self.ny, rtol, max_iter, check_every, fluxes)
+
+    def plan_value(self, key):
+        v = C.c_int()
+        check(self._L.deff_get_plan(self._ctx, key.encode(), C.byref(v)))
+        return v.value
 
 
 def load_jpeg_gray(path):

@@ -167,7 +167,8 @@ int deff_solve_batch(deff_ctx *ctx, double omega, double tol, int64_t max_iter, 
  * outside the mesh, ImpSolid / FloodFill rows, a phase with D = 0) get x = 0 -- where the Jacobi loop of a 2-phase
  * system with Ds = 0 gives NaN, CG gives a finite field.  A right-hand side of zero (||b|| = 0): a field with A x = 0
  * returns at once with rel_residual 0, converged; any other field has rel_residual = inf, iterates to max_iter (the
- * stop test ||r|| <= rtol * 0 never holds) and returns not converged with a finite field.  DEFF_EINVAL: row-slab contexts, systems without a row
+ * stop test ||r|| <= rtol * 0 never holds) and returns not converged with a finite field.  DEFF_EINVAL: row-slab contexts (one image
+ * over row slabs: deff_slab_group_solve_cg / deff_slab_rank_solve_cg below), systems without a row
  * dictionary or explicit-only ones (a wall link into the neighbouring row), and systems that are not symmetric (a link
  * between two active cells that differs from its partner, an active row with A0 <= 0); nothing is changed then.
  * Tuning key "cg_onchip" (0 default: the streaming kernels, four launches per iteration): 1 = when an image of the context
@@ -285,6 +286,27 @@ int deff_slab_group_sweeps(deff_slab_group *g, int64_t n, double omega, float *m
 int deff_slab_group_flux(deff_slab_group *g, double *deff_raw, double *MFL, double *MFR);
 int deff_slab_group_solve(deff_slab_group *g, double omega, double tol, int64_t max_iter,
                           int64_t check_every, deff_result *out, double *MFL, double *MFR);
+/* deff_solve_cg for the image the slabs hold: the current field is the guess and the solution is written into it; the same
+ * recurrence, the same stop rules decided on the device (||r|| <= rtol ||b||, max_iter, breakdown), the same true-residual
+ * round at the end with up to 8 restart rounds; rel_residual is recomputed from the field and `converged` derived from it;
+ * deff_raw / MFL / MFR (NY each, may be NULL) are deff_slab_group_flux of the returned field; loop_ms is slab 0's stream time
+ * with the other slabs waited for.  Same argument checks and the same admissibility rules (a row dictionary in every slab,
+ * no wall link into the neighbouring row, finite A0 > 0, symmetric links -- checked on the device over each slab's rows):
+ * DEFF_EINVAL otherwise, DEFF_ESTATE for a slab without a field or without wall diffusivities, as deff_solve_cg gives them.
+ * Every slab's verdict is gathered before anything is written, so all slabs refuse or none; on a refusal no slab's field
+ * is changed and deff_slab_group_get_plan reports what it reported before the call.
+ *   Each slab iterates its own rows with slab forms of the streaming kernels.  Per iteration one row of the residual
+ * travels to each neighbouring slab and every slab's partial dot products -- reduced per slab in a fixed order -- are
+ * gathered and added in slab order ((S0 + S1) + S2) + ... by every slab, so all slabs hold the same alpha, beta and stop
+ * decision bit for bit.  The results are deterministic and do not depend on check_every, on the transport or on the group /
+ * rank form.  With ONE slab they are the bits of deff_solve_cg on a plain context.  With more, the dot products are
+ * grouped by slab: the field agrees with the one-context solve to rounding, not bit for bit (as the on-chip form does).
+ * The tuning key "cg_onchip" has no effect.  deff_slab_group_get_plan, per slab: "cg_kr" and "cg_strips" (from the whole
+ * image, the same on every slab), "cg_items" (this slab's work items), "cg_restarts", "cg_impl" = 1.
+ *   After DEFF_OK the group is an ordinary slab set: all 8 halo rows of every slab's current field hold the neighbours'
+ * rows, as after deff_slab_group_set_field. */
+int deff_slab_group_solve_cg(deff_slab_group *g, double rtol, int64_t max_iter, int64_t check_every,
+                             deff_cg_result *out /* [1] */, double *MFL, double *MFR);
 
 /* ---- row slabs, one process per GPU: same slabs, RCCL transport (grouped ncclSend/ncclRecv of the
  * 8-row halo blocks between neighbour ranks once per blocked pass; ncclAllGather of the per-row
@@ -320,6 +342,17 @@ int deff_slab_rank_get_field(deff_slab_rank *s, double *x_own);
 int deff_slab_rank_sweeps(deff_slab_rank *s, int64_t n, double omega, float *ms);
 int deff_slab_rank_solve(deff_slab_rank *s, double omega, double tol, int64_t max_iter,
                          int64_t check_every, deff_result *out, double *MFL, double *MFR);
+/* deff_slab_group_solve_cg, one process per slab; collective like deff_slab_rank_solve: every rank calls it with the same
+ * arguments and gets the same result, bit for bit that of a group of as many slabs.  RCCL: per iteration a grouped
+ * ncclSend / ncclRecv of one row per neighbour and two ncclAllGather of 3 doubles per rank, on the context's stream, with
+ * no host wait inside an interval of check_every iterations.  Custom transport: `exchange` with count = the row pitch (nx
+ * rounded up to even) and `allgather` with count = 3, host staged, waiting every time (tests, portability).
+ *   A refusal (DEFF_EINVAL, DEFF_ESTATE) and a failed allocation of the work vectors (DEFF_ENOMEM) on any rank travel with
+ * the first all-gather, and every rank returns that status.  A rank on which a HIP or RCCL call or a custom callback fails
+ * returns at once (DEFF_EHIP, DEFF_ECOMM) and takes no further part: the other ranks then wait in their next collective,
+ * as in deff_slab_rank_solve, and the caller has to tear the communicator down. */
+int deff_slab_rank_solve_cg(deff_slab_rank *s, double rtol, int64_t max_iter, int64_t check_every,
+                            deff_cg_result *out, double *MFL, double *MFR);
 
 /* diagnostics: per wave tile of one temporally blocked pass of the streaming kernel two words -- the wall-clock (100 MHz) start,
  * and duration (low 32 bits) | HW_ID[15:0] << 32 | XCC_ID << 48 (where it ran); resident tiles: 12 wall-clock stamps per tile.

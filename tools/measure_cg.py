@@ -28,6 +28,10 @@ stream_library   --images N (4096) synthetic 128^2 images, host pixels, upload i
 stream_profile   where the stream's time goes: a `rocprofv3 --kernel-trace --stats` run of its own (a child process) of the stream alone
 stream_driver    tools/measure_dataset.py's JPEG set through deff2d: --solver cg --cg-batch 1024 against --cg-stream B, alternating
   python tools/measure_cg.py --cases stream_library,stream_driver --images 4096 --out profiles/cg_stream_results.json
+slabs4096     bench4096's image and rtol: one context (deff_solve_cg) against 1, 2 and 4 row slabs on ONE GPU
+              (deff_slab_group_solve_cg), the four forms alternating, --runs rounds; iterations to rtol, loop_ms, time per
+              iteration.  One slab = what the slab kernels cost; 2 and 4 = the exchange and the gathers per iteration
+  python tools/measure_cg.py --cases slabs4096 --runs 2 --out profiles/cg_slabs_results.json
 The bytes model of one iteration is 68 B/cell; "model_us" is that traffic at 6.3 TB/s."""
 import argparse
 import json
@@ -68,6 +72,28 @@ def synth_case(n, nimg, rtol, max_iter, jacobi):
             s.init_linear(0.0, 1.0)
             rj = s.solve(1e-6, 50_000_000)
             out["jacobi"] = {"sweeps": rj.iters, "deff_raw": rj.deff_raw, "loop_ms": rj.loop_ms}
+    return out
+
+
+def slabs4096(rtol, max_iter, runs, n=4096):
+    forms = [("one_context", 0), ("slabs1", 1), ("slabs2", 2), ("slabs4", 4)]
+    rows = {name: [] for name, _ in forms}
+    for _ in range(runs):
+        for name, k in forms:
+            s = pkg.Solver(n, n) if k == 0 else pkg.SlabGroup(n, n, [0] * k)
+            with s:
+                s.synth_image(12345, 0)
+                s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+                s.init_linear(0.0, 1.0)
+                t0 = time.perf_counter()
+                r = s.solve_cg(rtol=rtol, max_iter=max_iter, fluxes=False)
+                row = cg_row(r, n * n)
+                row["wall_s"] = time.perf_counter() - t0
+                rows[name].append(row)
+    out = {"mesh": [n, n], "rtol": rtol, "runs": runs, "forms": rows}
+    base = min(r["per_iter_us"] for r in rows["one_context"])
+    out["per_iter_us_best"] = {name: min(r["per_iter_us"] for r in rows[name]) for name, _ in forms}
+    out["per_iter_over_one_context"] = {name: v / base for name, v in out["per_iter_us_best"].items()}
     return out
 
 
@@ -406,6 +432,8 @@ def main():
             out[case] = onchip_dataset(a.rtol, a.runs, a.images)
         elif case == "stream_library":
             out[case] = stream_library(a.rtol, a.max_iter, a.runs, a.images, a.per_iter_us, a.only_stream)
+        elif case == "slabs4096":
+            out[case] = slabs4096(a.rtol, a.max_iter, a.runs)
         elif case == "stream_profile":
             out[case] = stream_profile(a.rtol, a.images)
         elif case == "stream_driver":
