@@ -87,6 +87,7 @@ static int slab_pass_plans(deff_ctx *c, double omega, int T_override, int overla
         pl[k]->band_lo = lo[k];
         pl[k]->band_h = h[k];
         TRY(plan_sweeps(c, omega, pl[k]));
+        if (pl[k]->kernel != DEFF_KERNEL_MATFREE_TB) return fail(DEFF_ESTATE, "row-slab mode needs the temporally blocked kernel");
     }
     return DEFF_OK;
 }

@@ -606,6 +606,7 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
         nmax = std::max(nmax, std::max(q.n[0], std::max(q.n[1], q.n[2])));
     }
     if ((long)3 * c->nimg * ntx * nmax >= (1L << 30)) return DEFF_OK;
+    int tallest = 0;                                              // rows of the tallest chunk dealt (tb_window_fits below)
     const size_t entries = (size_t)resident * 4 + 1;              // + the word the waves count their misplacements in (kernels_tb.hpp)
     {
         std::vector<int4> &tab = c->tb_dealt_host;
@@ -620,6 +621,7 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
             ry0 += q * sp.ly[r];
             int rows_here = std::min(sp.ly[r], own_hi - ry0);
             if (r == 2 && q == sp.n[2] - 1) rows_here = own_hi - ry0;              // the youngest rank's last chunk takes what rounding left over
+            tallest = std::max(tallest, rows_here);
             return make_int4(tx | (img << 16), ry0, rows_here > 0 ? rows_here : 0, (int)((unsigned)(((r * c->nimg + img) * ntx + tx) * nmax + q) | ((unsigned)r << 30)));
         };
         for (int r = 0; r < 3; ++r) {
@@ -652,6 +654,8 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
                 }
             }
         }
+        // (the kernel's 32-bit row offsets; a table that fails is not uploaded and equal chunks, checked in turn, take over)
+        if (!tb_window_fits(c->nx, tallest, T)) return DEFF_OK;
         if (c->tb_dealt_cap < entries) {
             TRY(resident_check(c));
             if (c->tb_dealt) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->tb_dealt)); c->tb_dealt = nullptr; }
@@ -706,6 +710,11 @@ static int plan_streaming(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int own
         if (!LY) LY = own_h;
     }
     if (LY > own_h) LY = own_h;
+    // The streaming kernel addresses a chunk's rows through 32-bit buffer offsets from the chunk's own window (tb_strip,
+    // kernels_tb.hpp): (LY + 2 T) rows x nx doubles must stay below 2 GiB, the offset that marks a lane as outside.  A chunk
+    // that could not fit (a quarter of a million cells per row and more, times a tall chunk) is not launched: the context
+    // sweeps with the single-sweep matrix-free kernel, as contexts too small for a blocked pass do.
+    if (!tb_window_fits(c->nx, LY, T)) { pl->kernel = DEFF_KERNEL_MATFREE; return DEFF_OK; }
     pl->LY = LY;
     pl->tcpi = (own_h + LY - 1) / LY;
     pl->tgy = pl->tcpi * c->nimg;
@@ -811,6 +820,7 @@ static int plan_blocked_pass(deff_ctx *c, SweepPlan *pl)
         if (pl->resident) TRY(ensure_resident_buffers(c, (long)pl->ntx * pl->tgy));
     } else {
         TRY(plan_streaming(c, pl, T, own_lo, own_h));
+        if (pl->kernel != DEFF_KERNEL_MATFREE_TB) return DEFF_OK;     // (a chunk window the kernel cannot address: single sweeps)
     }
     record_plan(c, pl);
     return DEFF_OK;

@@ -93,6 +93,7 @@ __device__ __forceinline__ double tb_cell(const double *lut, unsigned off, doubl
 // chains interleave and every FP64 instruction has another between itself and its consumer.  Same operations, same order
 // per cell, same bits.
 // the matrix rows of a lane's two cells
+constexpr int TB_STAGE_FENCE = 0x4;                             // sched_barrier mask: SALU may cross, nothing else
 struct TbCoef {
     double c0[2], aW[2], aE[2], aS[2], aN[2], b[2];
 };
@@ -112,21 +113,32 @@ __device__ __forceinline__ void tb_lookup(const double *lut, unsigned o0, unsign
         else k.b[h] = 0.0;
     }
 }
-template <bool FMA>
+// PINNED = the stages stay in the order written (a fence between them that only scalar instructions may cross): see tb_strip
+template <bool FMA, bool PINNED = false>
 __device__ __forceinline__ double2 tb_apply(const TbCoef &k, double2 vC, double xw0, double xe1, double2 vS, double2 vN, double omw)
 {
+    auto stage = []() __attribute__((always_inline)) {
+        if constexpr (PINNED) __builtin_amdgcn_sched_barrier(TB_STAGE_FENCE);
+    };
     double s0 = k.aW[0] * xw0, s1 = k.aW[1] * vC.x;
+    stage();
     s0 = mul_add<FMA>(k.aE[0], vC.y, s0); s1 = mul_add<FMA>(k.aE[1], xe1, s1);
+    stage();
     s0 = mul_add<FMA>(k.aS[0], vS.x, s0); s1 = mul_add<FMA>(k.aS[1], vS.y, s1);
+    stage();
     s0 = mul_add<FMA>(k.aN[0], vN.x, s0); s1 = mul_add<FMA>(k.aN[1], vN.y, s1);
+    stage();
     s0 = k.b[0] - s0; s1 = k.b[1] - s1;
+    stage();
     double2 o;
     if constexpr (FMA) {
         s0 = k.c0[0] * s0; s1 = k.c0[1] * s1;
+        stage();
         o.x = __builtin_fma(omw, vC.x, s0); o.y = __builtin_fma(omw, vC.y, s1);
     } else {
         const double m0 = omw * vC.x, m1 = omw * vC.y;
         s0 = k.c0[0] * s0; s1 = k.c0[1] * s1;
+        stage();
         o.x = m0 + s0; o.y = m1 + s1;
     }
     return o;
@@ -148,6 +160,20 @@ __device__ __forceinline__ double2 tb_pair(const double *lut, unsigned o0, unsig
 }
 
 
+// Raw buffer access to the rows (see tb_strip).  A lane offset of TB_LANE_OUT lies beyond every descriptor: the host only
+// launches chunks whose window -- (rows + 2 T) rows of nx doubles -- stays below 2 GiB (tb_window_fits, checked by
+// plan_streaming), so every in-range offset, lane part plus row part, is below it and 32-bit offset arithmetic cannot wrap.
+typedef unsigned int tb_u4 __attribute__((ext_vector_type(4)));
+constexpr unsigned TB_LANE_OUT = 0x80000000u;
+constexpr bool tb_window_fits(int nx, int rows, int T)
+{
+    return ((long long)rows + 2 * T) * nx * 8 < (long long)TB_LANE_OUT;
+}
+template <class P> __device__ __forceinline__ __amdgpu_buffer_rsrc_t tb_rsrc(P *p, unsigned bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(static_cast<const void *>(p)), 0, (int)bytes, 0x00020000);
+}
+
 // One strip x chunk: the whole row pipeline of a wave (2 cells per lane, 128 columns).
 // Geometry (array rows): the mesh of this image is rows [row_lo, row_lo+ny) -- rows outside it
 // are "outside the mesh" even if another image of a batch lives there, and row_lo is negative
@@ -157,7 +183,7 @@ __device__ __forceinline__ double2 tb_pair(const double *lut, unsigned o0, unsig
 // The code is deliberately written with double2 values and named slots: an array-of-scalars formulation of the same
 // dataflow made hipcc hoist the lookups to 204 VGPRs.  Everything that was measured on this function and dropped --
 // pipelined lookups, 4 cells per lane, skewed levels, cooperating strips, one lookup per face, LDS-DMA prefetch, fences
-// elsewhere, buffer addressing, a pair of waves per tile -- is recorded with its numbers in DESIGN.md section 4 and
+// elsewhere, a pair of waves per tile -- is recorded with its numbers in DESIGN.md section 4 and
 // profiles/r03_tb_ab_kbench.log; the variants themselves are tools/experiments/r03_tb_variants.patch.
 template <int T, bool GUARD, bool WALL, bool FMA>
 __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__restrict__ code,
@@ -187,6 +213,22 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
     const bool st_x = in_x && (col >= out_lo) && (col < out_hi);
     const double2 zero = make_double2(0.0, 0.0);
 
+    // Rows travel through raw buffer descriptors: address = descriptor base (this wave's window, a wave-uniform 64-bit add)
+    // + lane offset (one loop-invariant VGPR per array) + row offset (an SGPR).  The hardware's range check does the masking:
+    // a lane outside the mesh (loads) or outside [out_lo, out_hi) (stores) carries TB_LANE_OUT, beyond the end of any window,
+    // and a row outside the window takes a descriptor of zero bytes (at row offset 0) -- such loads return 0 for x and for the
+    // codes, such stores are dropped.  No per-lane 64-bit address, no select, no branch around a store; an address outside
+    // the window cannot be formed.  The windows: x and the codes, rows [r_begin, min(r_end, row_hi)); xnew, rows [ry0, ry1).
+    const int win_hi = min(r_end, row_hi);
+    const unsigned xrow = (unsigned)nx * 8u, crow = (unsigned)nx * 2u;                 // bytes per row (tb_window_fits: no overflow below)
+    const unsigned lrows = (unsigned)max(win_hi - r_begin, 0), srows = (unsigned)max(ry1 - ry0, 0);
+    const double *const xwin = x + (ptrdiff_t)r_begin * nx;
+    const uint16_t *const cwin = code + (ptrdiff_t)r_begin * nx;
+    double *const swin = xnew + (ptrdiff_t)ry0 * nx;
+    const unsigned vo_x = in_x ? (unsigned)col * 8u : TB_LANE_OUT;
+    const unsigned vo_c = in_x ? (unsigned)col * 2u : TB_LANE_OUT;
+    const unsigned vo_s = st_x ? (unsigned)col * 8u : TB_LANE_OUT;
+
     double2 w[T][3];                               // w[t]: 3 newest rows of sweep t
     unsigned cw[T + 1];                            // cw[t]: the two 16-bit codes of row rr-t
 #pragma unroll
@@ -194,21 +236,24 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
 #pragma unroll
     for (int t = 0; t <= T; ++t) cw[t] = 0u;
 
-    // prefetch the first group of three rows
-    double2 nx_x[3];
-    unsigned nx_c[3];
-    auto fetch = [&](const int rr, double2 &vx_out, unsigned &vc_out) __attribute__((always_inline)) {
-        const bool ok = in_x && rr >= row_lo && rr < row_hi && rr < r_end;
-        const size_t p = (size_t)(ok ? rr : 0) * nx + (ok ? col : 0);
-        // the loads are issued UNCONDITIONALLY (the address is clamped into the array) and the value is
-        // selected afterwards: with `ok ? load : 0` hipcc branches around the loads, no longer knows how
-        // many are in flight, and waits with vmcnt(0) right after issuing the next group's loads --
-        // i.e. no prefetch at all (found by removing the loads / the store: +23 % / +30 %)
-        const double2 vx = ld2(x + p);
-        const unsigned vc = *reinterpret_cast<const uint32_t *>(code + p);
-        vx_out = ok ? vx : zero;
-        vc_out = ok ? vc : 0u;                                               // rows / lanes outside the mesh: zero row
+    // (rr >= r_begin for every row asked for: the loops below start there and only go down)
+    auto fetch = [&](const int rr, tb_u4 &vx_out, unsigned &vc_out) __attribute__((always_inline)) {
+        const bool ok = rr < win_hi;                                                  // wave-uniform
+        const unsigned k = ok ? (unsigned)(rr - r_begin) : 0u;
+        vx_out = __builtin_amdgcn_raw_buffer_load_b128(tb_rsrc(xwin, ok ? lrows * xrow : 0u), (int)vo_x, (int)(k * xrow), 0);
+        vc_out = __builtin_amdgcn_raw_buffer_load_b32(tb_rsrc(cwin, ok ? lrows * crow : 0u), (int)vo_c, (int)(k * crow), 0);
     };
+    auto store = [&](const int rt, const double2 o) __attribute__((always_inline)) {
+        const bool go = rt >= ry0 && rt < ry1;                                        // wave-uniform
+        const unsigned k = go ? (unsigned)(rt - ry0) : 0u;
+        tb_u4 v;
+        __builtin_memcpy(&v, &o, 16);
+        __builtin_amdgcn_raw_buffer_store_b128(v, tb_rsrc(swin, go ? srows * xrow : 0u), (int)vo_s, (int)(k * xrow), 0);
+    };
+    // Three rows are always in flight: row rr + 3 is asked for at the top of the step that consumes row rr, into the
+    // registers that row has just left (nx_*[rr % 3 by position in the group]).
+    tb_u4 nx_x[3];                                 // (kept as loaded, 16 bytes: two doubles)
+    unsigned nx_c[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) fetch(r_begin + k, nx_x[k], nx_c[k]);
 
@@ -227,13 +272,6 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
     // read only through zero links or not at all.
     auto group = [&](const int r, auto trim_tag) __attribute__((always_inline)) {
         constexpr bool TRIM = decltype(trim_tag)::value;
-        double2 cur_x[3];
-        unsigned cur_c[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { cur_x[k] = nx_x[k]; cur_c[k] = nx_c[k]; }
-        // issue the next group's loads before working on this one
-#pragma unroll
-        for (int k = 0; k < 3; ++k) fetch(r + 3 + k, nx_x[k], nx_c[k]);      // unconditional loads, see above
 #pragma unroll
         for (int ph = 0; ph < 3; ++ph) {
             const int rr = r + ph;                 // input row of this step
@@ -241,8 +279,24 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
             const int sN = (ph + 1) % 3, sC = (ph + 2) % 3, sS = ph;
 #pragma unroll
             for (int t = T; t >= 1; --t) cw[t] = cw[t - 1];
-            cw[0] = cur_c[ph];
-            w[0][sS] = cur_x[ph];
+            // Row rr, asked for three steps ago, is consumed HERE, behind the previous step's last level fence, by register moves
+            // the compiler cannot place elsewhere or fold away (moves, not loads: the loads stay the compiler's, and so does
+            // counting them).  Written as plain copies, the copies are coalesced with the loop-carried registers: hipcc then
+            // copies the loaded rows at the loop's end, or inside level 1 of the next step, and waits for loads it issued one
+            // step or ~50 instructions earlier.  CDNA counts loads and stores in one vmcnt, in issue order; with no branch in
+            // the loop the compiler knows what is in flight and waits in front of these moves with a counted vmcnt(4...6): rows
+            // rr + 1 and rr + 2 and the stores of the last two steps stay in flight.  tests/test_tb_stream_isa.py holds the
+            // emitted loop to that: one branch, no wait that forces a store younger than one step (none with vmcnt 0), first
+            // read of a row at least two steps after its load, no select, no 64-bit address arithmetic.
+            {
+                double lo, hi;
+                __builtin_memcpy(&lo, &nx_x[ph], 8);
+                __builtin_memcpy(&hi, reinterpret_cast<const char *>(&nx_x[ph]) + 8, 8);
+                asm volatile("v_mov_b64 %0, %3\n\tv_mov_b64 %1, %4\n\tv_mov_b32 %2, %5"
+                             : "=&v"(w[0][sS].x), "=&v"(w[0][sS].y), "=&v"(cw[0])
+                             : "v"(lo), "v"(hi), "v"(nx_c[ph]));
+            }
+            fetch(rr + 3, nx_x[ph], nx_c[ph]);
 #pragma unroll
             for (int t = 1; t <= T; ++t) {
                 const int rt = rr - t;             // row produced by sweep t in this step
@@ -256,22 +310,22 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
                 const double xw0 = from_lane_below(vC.y);
                 const double xe1 = from_lane_above(vC.x);
                 const unsigned o0 = cw[t] & 0xFFFFu, o1 = cw[t] >> 16;
-                const double2 o = tb_pair<GUARD, WALL, FMA>(lut, o0, o1, vC, xw0, xe1, vS, vN, omw);
-                if (t == T && ph == 2) {
-                    // CDNA counts loads and stores in one vmcnt and lets stores complete out of order, so
-                    // "the prefetched rows have arrived" can only be expressed as vmcnt(0), which also
-                    // waits for every store in flight.  Ask for the prefetched group HERE, before the
-                    // group's last store goes out: the two stores then in flight are a step old (acked),
-                    // whereas at the top of the next group the wait would sit right behind a fresh store
-                    // (measured by deleting the store: +21..30 %).
-                    asm volatile("" :: "v"(nx_x[0].x), "v"(nx_x[0].y), "v"(nx_x[1].x), "v"(nx_x[1].y), "v"(nx_x[2].x),
-                                 "v"(nx_x[2].y), "v"(nx_c[0]), "v"(nx_c[1]), "v"(nx_c[2]));
+                double2 o;
+                if constexpr (GUARD) {
+                    o = tb_pair<GUARD, WALL, FMA>(lut, o0, o1, vC, xw0, xe1, vS, vN, omw);
+                } else {
+                    // The lookups first, then the arithmetic stage by stage, both cells side by side, as written: left to
+                    // itself inside a level the scheduler -- short of registers at 3 waves per SIMD -- runs one cell's chain
+                    // to its end before it starts the other's (each FP64 instruction then waits for the one before it).
+                    // That it did not do so before was an accident of a register pressure ABOVE the budget, which made it
+                    // give the schedule up and keep the source order; the fences say it.
+                    TbCoef k;
+                    tb_lookup<WALL>(lut, o0, o1, k);
+                    __builtin_amdgcn_sched_barrier(TB_STAGE_FENCE);
+                    o = tb_apply<FMA, true>(k, vC, xw0, xe1, vS, vN, omw);
                 }
-                if (t < T) {
-                    w[t][sS] = o;
-                } else if (st_x && rt >= ry0 && rt < ry1) {
-                    st2(xnew + (size_t)rt * nx + col, o);
-                }
+                if (t < T) w[t][sS] = o;
+                else store(rt, o);
                 // keep the scheduler from pulling the next sweeps' table lookups up here: left
                 // alone it hoists them all (180-250 VGPRs, 1-2 waves per SIMD); with the fence a
                 // step keeps ~120 VGPRs and 4 waves per SIMD hide the LDS latency instead
@@ -283,6 +337,15 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
     int r = r_begin;
     for (; r < r_begin + TRIMMED && r < r_end; r += 3) group(r, TbTag<true>{});
     for (; r < r_end; r += 3) group(r, TbTag<false>{});
+}
+
+// Does strip tx read a wall column?  The first and the last strip do; with the older placement (shift = HW) so does the
+// last but one when the last strip holds at most HW columns of the mesh: the wall column then lies in its halo, and the
+// sweeps it recomputes there need b (226 columns, T = 8: strip 1 reads columns 104...231).  Never so with shift = 0.
+template <int T> __device__ __forceinline__ bool tb_wall_strip(int tx, int ntx, int shift, int nx)
+{
+    constexpr int HW = (T + 1) & ~1;
+    return tx == 0 || tx == ntx - 1 || tx * (TB_COLS - 2 * HW) - shift + TB_COLS >= nx;
 }
 
 // grid: persistent workgroups of 4 waves.  Wave tiles (strip tx, chunk ty) are numbered
@@ -340,7 +403,7 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(cons
         const int tx = d.x & 0xFFFF, img = d.x >> 16;      // image of a stack
         if (active && !active[img]) return;
         const int row_lo = dom_lo + img * img_stride, own_hi = own_lo + img * img_stride + own_h;
-        if (allb || tx == 0 || tx == ntx - 1)
+        if (allb || tb_wall_strip<T>(tx, ntx, shift, nx))
             tb_strip<T, GUARD, true, FMA>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
         else
             tb_strip<T, GUARD, false, FMA>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
@@ -369,7 +432,7 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(cons
 
         // b is read only where it can be non-zero: strips holding a wall column, or everywhere for a
         // harvested dictionary whose right-hand side is not confined to the walls
-        if (allb || tx == 0 || tx == ntx - 1)
+        if (allb || tb_wall_strip<T>(tx, ntx, shift, nx))
             tb_strip<T, GUARD, true, FMA>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
         else
             tb_strip<T, GUARD, false, FMA>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
