@@ -128,6 +128,7 @@ try {
     if (c->q) (void)hipFree(c->q);
     if (c->resid) (void)hipFree(c->resid);
     if (c->tb_dealt) (void)hipFree(c->tb_dealt);
+    if (c->tb_chain_nbrs) (void)hipFree(c->tb_chain_nbrs);
     if (c->res_flags) (void)hipFree(c->res_flags);
     if (c->res_abort) (void)hipFree(c->res_abort);
     if (c->res_backup) (void)hipFree(c->res_backup);
@@ -280,6 +281,7 @@ try {
     else if (!strcmp(key, "tb_wall_halo")) c->tb_wall_halo = value > 2 ? 2 : value;
     else if (!strcmp(key, "tb_wg")) c->tb_wg = (value + 7) / 8 * 8;
     else if (!strcmp(key, "tb_ranked")) { c->tb_ranked = value ? 1 : 0; c->tb_rank_lost = 0; }
+    else if (!strcmp(key, "tb_chain")) c->tb_chain = value ? 1 : 0;
     else if (!strcmp(key, "tb_tall_deal")) c->tb_tall_deal = value ? 1 : 0;
     else if (!strcmp(key, "tb_sym_age")) c->tb_sym_age = value ? 1 : 0;
     else if (!strcmp(key, "tb_sym_shape")) c->tb_sym_shape = value;
@@ -312,6 +314,7 @@ try {
     else if (!strcmp(key, "tb_NW")) *value = c->plan_NW;
     else if (!strcmp(key, "tb_fallbacks")) *value = c->res_fallbacks;
     else if (!strcmp(key, "tb_ranked")) *value = c->plan_ranked;
+    else if (!strcmp(key, "tb_chain")) *value = c->plan_chain;
     else if (!strcmp(key, "tb_aged")) *value = c->plan_aged;
     else if (!strcmp(key, "tb_rank_misses")) *value = c->tb_rank_misses;
     else if (!strcmp(key, "tb_rank_lost")) *value = c->tb_rank_lost;

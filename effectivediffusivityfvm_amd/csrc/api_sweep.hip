@@ -4,6 +4,7 @@
 // See ctx.hpp for the file map, DESIGN.md section 4 for the design.
 #include "ctx.hpp"
 #include "tile_kernels.hpp"
+#include "tb_chain.hpp"
 #include <map>
 #include <mutex>
 
@@ -17,6 +18,9 @@ template <int... T> static constexpr auto streaming_passes()
     return std::array{by_flags([](auto f, auto g) { return k_sweep_matfree_tb<T, decltype(f)::value, decltype(g)::value>; })...};
 }
 static constexpr auto STREAMING = streaming_passes<1, 2, 4, 6, 8>();
+// ... and its chained form, [2 fma + guard]: dealt tiles exist for T = 8 only (plan_streaming)
+static constexpr auto STREAMING_CHAIN = by_flags([](auto f, auto g) { return k_sweep_matfree_tb_chain<8, decltype(f)::value, decltype(g)::value>; });
+static_assert(TB_CHAIN_NB == TB_CHAIN_MAXN && TB_CHAIN_COLS == TB_COLS && sizeof(TbChainTile) == sizeof(int4), "tb_chain.hpp and kernels_tb.hpp disagree");
 static int tb_index(int T) { return T == 1 ? 0 : T == 2 ? 1 : T == 4 ? 2 : T == 6 ? 3 : 4; }
 
 // The first workgroup tile (tile_kernels.hpp) that pred accepts: 8-wave, tall, 12-wave tiles, each list in its order.
@@ -122,6 +126,17 @@ static hipError_t launch_resident(deff_ctx *c, const SweepPlan &pl, double *xa, 
     std::lock_guard<std::mutex> lock(g_res_mu);
     hipError_t e = resident_chain_begin(c);
     if (e != hipSuccess) return e;
+    if (pl.impl == 1) {
+        // chained streaming passes: the dealt tiles, one wave each, flags by table slot
+        unsigned *miss = reinterpret_cast<unsigned *>(c->tb_dealt + c->tb_dealt_miss_at);
+        hipLaunchKernelGGL(STREAMING_CHAIN[2 * pl.fma + pl.guard], dim3(pl.tblocks), dim3(256), 0, c->stream, lut, code, xa, xb, nx, ny,
+                           img_stride, dom_lo, own_lo, own_h, ntx, allb, nrows, shift, omw, pl.dealt, pl.nbrs, miss, npass, flags, base,
+                           abort_flag, stamps);
+        e = hipPeekAtLastError();
+        if (e != hipSuccess) return e;
+        c->tb_dealt_waves += (int64_t)pl.tblocks * 4;
+        return resident_chain_end(c);
+    }
     hipLaunchKernelGGL(pl.tile->kernel, dim3(pl.tblocks), dim3(pl.tile->threads()), 0, c->stream, lut, code, xa,
                        xb, nx, ny, img_stride, dom_lo, own_lo, own_h, cpi, ly, mask, ntx, gy, xmajor, allb, nrows, shift,
                        omw, npass, flags, base, abort_flag, xbytes, stall_tile, stamps);
@@ -541,6 +556,7 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
         pl->tgy = pl->tcpi * c->nimg;
         pl->tgx = (ntx * pl->tgy + 3) / 4;
         pl->tblocks = resident;
+        pl->nbrs = c->tb_chain_fits ? c->tb_chain_nbrs : nullptr;
         *dealt = true;
     };
     if (c->tb_dealt && key == c->tb_dealt_key) { fill_plan(); return DEFF_OK; }
@@ -663,7 +679,22 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
             c->tb_dealt_cap = entries;
         }
         HIP_TRY(hipMemcpyAsync(c->tb_dealt, tab.data(), entries * sizeof(int4), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));                                   // (pageable source; once per plan change)
+        // who waits for whom if this table's passes are chained (tb_chain.hpp: from the geometry, by rectangle intersection);
+        // uploaded beside the table as slot + 1, 0 = none.  A table whose lists do not fit is not chained.
+        std::vector<int> lists;
+        const TbChainGeom geom{c->nx, T, pl->shift, ntx, c->ny, c->dom_lo, c->mesh_ny, own_lo, own_h};
+        c->tb_chain_fits = tb_chain_lists(geom, reinterpret_cast<const TbChainTile *>(tab.data()), entries - 1, &lists);
+        std::vector<unsigned> up(lists.size());
+        if (c->tb_chain_fits) {
+            for (size_t k = 0; k < lists.size(); ++k) up[k] = (unsigned)(lists[k] + 1);
+            if (c->tb_chain_nbrs_cap < up.size()) {
+                if (c->tb_chain_nbrs) { HIP_TRY(hipFree(c->tb_chain_nbrs)); c->tb_chain_nbrs = nullptr; }   // (nothing in flight: resident_check above or a first table)
+                HIP_TRY(hipMalloc((void **)&c->tb_chain_nbrs, up.size() * sizeof(unsigned)));
+                c->tb_chain_nbrs_cap = up.size();
+            }
+            HIP_TRY(hipMemcpyAsync(c->tb_chain_nbrs, up.data(), up.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));                                   // (pageable sources; once per plan change)
         c->tb_dealt_key = key;
         c->tb_dealt_LY = st[ntx / 2].ly[1];
         c->tb_dealt_nmax = nmax;
@@ -675,10 +706,21 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
     return DEFF_OK;
 }
 
+// Where chained passes are the default.  Measured against the parent build (profiles/r06_tb_chain_ab.log):
+// one 4096^2 image (16 Mi cells, a pass of ~100 us) +2.7 %; 8192^2 and 64 x 1024^2 (64 Mi cells, passes of ~430 us) -2...-5 %
+// -- a launch boundary is worth ~9 us + the tail whatever the size, the tiles' waits and the coherent rows cost in
+// proportion to the pass.  Nothing was measured between the two, so the rule stops at what won.
+static bool chain_pays(const deff_ctx *c)
+{
+    return c->n <= ((size_t)1 << 24);
+}
+
 static int plan_streaming(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int own_h)
 {
     pl->impl = 1;
     pl->resident = false;
+    pl->chained = false;
+    pl->nbrs = nullptr;
     pl->guard = c->lut_guard;                          // the reference's non-zero link test matters only when a phase cannot diffuse
     int resident = c->tb_wg;
     if (!resident) {
@@ -690,6 +732,15 @@ static int plan_streaming(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int own
     if (c->tb_ranked && !c->tb_rank_lost && !c->tb_LY && !c->tb_wg && pl->band_h == 0 && !c->slab && T == 8 && !c->masked) {
         bool dealt = false;
         TRY(deal_ranked_tiles(c, pl, T, own_lo, own_h, resident, &dealt));
+        // chained passes: on the conditions of the resident tiles (a whole context, 32-bit offsets, the caller has not asked
+        // for one launch per pass, no earlier fallback) when the neighbour lists fit and where it was measured to win
+        if (dealt) pl->chained = pl->nbrs && c->tb_chain && resident_allowed(c, pl) && chain_pays(c);
+        if (pl->chained) {
+            // every wave of the grid must be on the chip for the whole launch: by the chained kernel's own occupancy
+            int at_once = 0;
+            TRY(resident_blocks(c, STREAMING_CHAIN[2 * pl->fma + pl->guard], 256, &at_once));
+            if (at_once < pl->tblocks) pl->chained = false;
+        }
         if (dealt) return DEFF_OK;
     }
     int LY = c->tb_LY;
@@ -735,6 +786,7 @@ static void record_plan(deff_ctx *c, const SweepPlan *pl)
     c->plan_NW = pl->impl == 2 ? pl->tile->NW : 0;
     c->plan_resident = pl->impl == 2 && pl->resident ? 1 : 0;
     c->plan_ranked = pl->impl == 1 && pl->dealt ? 1 : 0;
+    c->plan_chain = pl->impl == 1 && pl->chained ? 1 : 0;
     c->plan_aged = pl->impl == 2 && pl->tile->aged() ? 1 : 0;
 }
 
@@ -821,6 +873,7 @@ static int plan_blocked_pass(deff_ctx *c, SweepPlan *pl)
     } else {
         TRY(plan_streaming(c, pl, T, own_lo, own_h));
         if (pl->kernel != DEFF_KERNEL_MATFREE_TB) return DEFF_OK;     // (a chunk window the kernel cannot address: single sweeps)
+        if (pl->chained) TRY(ensure_resident_buffers(c, (long)pl->tblocks * 4));    // one flag per wave of the grid
     }
     record_plan(c, pl);
     return DEFF_OK;
@@ -968,6 +1021,7 @@ int launch_tb_pass(deff_ctx *c, const SweepPlan &pl)
     return DEFF_OK;
 }
 
+// (workgroup tiles, or the chained form of the streaming kernel)
 // All whole passes of n sweeps as resident launches of up to 4 096 passes (tens of milliseconds each); *n is reduced by
 // the sweeps enqueued.  In front of the first resident launch since the abort flag was last looked at, the field is copied
 // aside: the restart point if a launch gives up (resident_check).
@@ -1001,7 +1055,7 @@ static int launch_resident_passes(deff_ctx *c, const SweepPlan &pl, int64_t *n)
         np -= chunk;
         *n -= (int64_t)chunk * pl.T;
         c->res_redo += (int64_t)chunk * pl.T;
-        ++c->last_launches;
+        c->last_launches += pl.impl == 1 ? chunk : 1;              // a chained launch counts its passes (deff_last_launches)
     }
     return DEFF_OK;
 }
@@ -1009,13 +1063,18 @@ static int launch_resident_passes(deff_ctx *c, const SweepPlan &pl, int64_t *n)
 // n sweeps: as many T-sweep passes as fit, the rest one at a time.  Stops at the first launch that fails.
 int enqueue_sweeps(deff_ctx *c, const SweepPlan &pl, int64_t n)
 {
-    if (pl.kernel == DEFF_KERNEL_MATFREE_TB && pl.impl == 2 && pl.resident && !c->tb_resident) {
+    // (a stack some of whose images have stopped since the plan was made -- deff_solve_batch keeps its plan -- goes on with one
+    // launch per pass on the same table: that kernel leaves frozen images alone, a chain has no mask)
+    const bool chained = pl.kernel == DEFF_KERNEL_MATFREE_TB && pl.impl == 1 && pl.chained && !c->masked;
+    if (((pl.kernel == DEFF_KERNEL_MATFREE_TB && pl.impl == 2 && pl.resident) || chained) && !c->tb_resident) {
         // the context fell back to one launch per pass (resident_check) after this plan was made
         SweepPlan again;
         TRY(plan_sweeps(c, pl.omega, &again));
-        if (again.resident) return fail(DEFF_ESTATE, "internal: plan still resident after the fallback");
+        if (again.resident || again.chained) return fail(DEFF_ESTATE, "internal: plan still resident after the fallback");
         return enqueue_sweeps(c, again, n);
     }
+    // chained streaming passes: two passes or more go through the resident launches' machinery (a single pass gains nothing)
+    if (chained && n >= 2 * pl.T) TRY(launch_resident_passes(c, pl, &n));
     // (while resident launches are in flight unchecked, whatever follows them is part of what a fallback must redo)
     if (pl.kernel == DEFF_KERNEL_MATFREE_TB && pl.impl == 2 && pl.resident && n >= (pl.tile->pass ? 2 : 1) * pl.T)
         TRY(launch_resident_passes(c, pl, &n));
@@ -1062,8 +1121,10 @@ try {
     // streaming form: 2 stamps per wave tile; workgroup-tile form: T + 4 per tile, flattened -- *ntiles is always
     // the number of PAIRS the buffer must hold
     // (resident launches stamp 12 clocks per tile whatever T: entry + 3 passes x {neighbours seen, halo in, swept, published})
-    const bool res_stamps = pl.impl == 2 && pl.resident;
-    const int n = res_stamps ? (pl.ntx * pl.tgy * 12 + 1) / 2 : pl.impl == 2 ? (pl.ntx * pl.tgy * (pl.T + 4) + 1) / 2 : pl.ntx * pl.tgy;
+    // (chained streaming launches: 8 clocks per tile -- entry, where, 3 passes x {neighbours seen, swept} --, 3 passes as well)
+    const bool chain_stamps = pl.impl == 1 && pl.chained;
+    const bool res_stamps = (pl.impl == 2 && pl.resident) || chain_stamps;
+    const int n = chain_stamps ? pl.ntx * pl.tgy * 4 : res_stamps ? (pl.ntx * pl.tgy * 12 + 1) / 2 : pl.impl == 2 ? (pl.ntx * pl.tgy * (pl.T + 4) + 1) / 2 : pl.ntx * pl.tgy;
     *ntiles = n;
     if (!out) return DEFF_OK;
     HIP_TRY(hipMalloc((void **)&c->tb_stamps, sizeof(unsigned long long) * 2 * n));

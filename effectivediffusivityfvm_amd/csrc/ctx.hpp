@@ -214,6 +214,14 @@ struct deff_ctx {
     int tb_rank_misses = 0, tb_rank_lost = 0;    // last count read; 1 = the dispatch order is not the assumed one: equal chunks from now on
     int tb_dealt_LY = 0, tb_dealt_nmax = 0;      // ... and what deff_get_plan reports of it (an inner strip's middle rank; most chunks per rank)
     int plan_ranked = 0;
+    // Chained streaming passes (k_sweep_matfree_tb_chain, kernels_tb.hpp): the passes between two checks as ONE launch of the
+    // dealt tiles, each tile waiting only for its neighbours (tb_chain.hpp).  Tuning key "tb_chain": 0 = one launch per pass.
+    // Runs through the resident launches' machinery: flags, restart copy, abort word, fallback (which clears tb_resident).
+    int tb_chain = 1;
+    int plan_chain = 0;                          // the last plan chained its passes
+    unsigned *tb_chain_nbrs = nullptr;           // device: TB_CHAIN_MAXN neighbour slots (+ 1; 0 = none) per entry of tb_dealt
+    size_t tb_chain_nbrs_cap = 0;
+    bool tb_chain_fits = false;                  // the current table's lists fit (else it is not chained)
     int64_t last_launches = 0;                   // sweep-kernel launches of the last deff_sweeps()/deff_solve()
 
     // conjugate gradients (api_cg.hip): work vectors, CG table, per-image scalars and the loop's own event pair, allocated
@@ -351,6 +359,8 @@ struct SweepPlan {
     const TileKernel *tile = nullptr;                     // impl 2: the tile's kernels, waves and rows (tile_kernels.hpp)
     const int4 *dealt = nullptr;                          // streaming kernel: dealt tiles (chunk heights by service order), or none
     bool resident = false;                                // impl 2 only: all passes of a batch in one launch (k_sweep_wgres)
+    bool chained = false;                                 // impl 1, dealt tiles: all passes of a batch in one launch (k_sweep_matfree_tb_chain)
+    const unsigned *nbrs = nullptr;                       //   ... and the tiles' neighbour lists
     // rows the plan updates: band_h > 0 restricts it to the band [band_lo, band_lo + band_h) of the context's owned rows
     // (input); own_lo / own_h are what the planner resolved (output, passed to the kernels)
     int band_lo = 0, band_h = 0, own_lo = 0, own_h = 0;

@@ -185,7 +185,11 @@ template <class P> __device__ __forceinline__ __amdgpu_buffer_rsrc_t tb_rsrc(P *
 // pipelined lookups, 4 cells per lane, skewed levels, cooperating strips, one lookup per face, LDS-DMA prefetch, fences
 // elsewhere, a pair of waves per tile -- is recorded with its numbers in DESIGN.md section 4 and
 // profiles/r03_tb_ab_kbench.log; the variants themselves are tools/experiments/r03_tb_variants.patch.
-template <int T, bool GUARD, bool WALL, bool FMA>
+// XAUX = the cache-policy (aux) bits of the x-row accesses -- the row loads of the prologue and of the loop, and the xnew
+// stores; 0 = plain (k_sweep_matfree_tb), 16 = sc1 (device-coherent: k_sweep_matfree_tb_chain, whose tiles read their
+// neighbours' rows of the same launch).  The code loads stay plain.  In the one-pass kernel sc1 rows measured -0.3 +- 0.3 us
+// per 107 us launch: profiles/r06_tb_chain_ab.log.
+template <int T, bool GUARD, bool WALL, bool FMA, int XAUX = 0>
 __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__restrict__ code,
                                          const double *__restrict__ x, double *__restrict__ xnew, int nx,
                                          int ny, int row_lo, int own_hi, int tx, int ntx, int shift, int ry0, int LY,
@@ -240,7 +244,7 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
     auto fetch = [&](const int rr, tb_u4 &vx_out, unsigned &vc_out) __attribute__((always_inline)) {
         const bool ok = rr < win_hi;                                                  // wave-uniform
         const unsigned k = ok ? (unsigned)(rr - r_begin) : 0u;
-        vx_out = __builtin_amdgcn_raw_buffer_load_b128(tb_rsrc(xwin, ok ? lrows * xrow : 0u), (int)vo_x, (int)(k * xrow), 0);
+        vx_out = __builtin_amdgcn_raw_buffer_load_b128(tb_rsrc(xwin, ok ? lrows * xrow : 0u), (int)vo_x, (int)(k * xrow), XAUX);
         vc_out = __builtin_amdgcn_raw_buffer_load_b32(tb_rsrc(cwin, ok ? lrows * crow : 0u), (int)vo_c, (int)(k * crow), 0);
     };
     auto store = [&](const int rt, const double2 o) __attribute__((always_inline)) {
@@ -248,7 +252,7 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
         const unsigned k = go ? (unsigned)(rt - ry0) : 0u;
         tb_u4 v;
         __builtin_memcpy(&v, &o, 16);
-        __builtin_amdgcn_raw_buffer_store_b128(v, tb_rsrc(swin, go ? srows * xrow : 0u), (int)vo_s, (int)(k * xrow), 0);
+        __builtin_amdgcn_raw_buffer_store_b128(v, tb_rsrc(swin, go ? srows * xrow : 0u), (int)vo_s, (int)(k * xrow), XAUX);
     };
     // Three rows are always in flight: row rr + 3 is asked for at the top of the step that consumes row rr, into the
     // registers that row has just left (nx_*[rr % 3 by position in the group]).
@@ -357,6 +361,11 @@ template <int T> __device__ __forceinline__ bool tb_wall_strip(int tx, int ntx, 
 // [own_lo + k*img_stride, ... + own_h).  Batch: dom_lo = own_lo = 0, own_h = img_stride = ny.
 // Row slab (one image): dom_lo = -(first array row's global index), ny = global height,
 // own_lo = halo depth, own_h = rows owned by this rank.
+// (measurement switch: -DTB_ROWS_AUX=16 builds the dealt path of this kernel with device-coherent rows, to be timed against
+// the plain build in one process -- tools/build_variant.sh; never set by the Makefile)
+#ifndef TB_ROWS_AUX
+#define TB_ROWS_AUX 0
+#endif
 template <int T, bool FMA, bool GUARD>
 __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(const double *__restrict__ lut_g,
                                                           const uint16_t *__restrict__ code,
@@ -404,9 +413,9 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(cons
         if (active && !active[img]) return;
         const int row_lo = dom_lo + img * img_stride, own_hi = own_lo + img * img_stride + own_h;
         if (allb || tb_wall_strip<T>(tx, ntx, shift, nx))
-            tb_strip<T, GUARD, true, FMA>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
+            tb_strip<T, GUARD, true, FMA, TB_ROWS_AUX>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
         else
-            tb_strip<T, GUARD, false, FMA>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
+            tb_strip<T, GUARD, false, FMA, TB_ROWS_AUX>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
         if (stamps && lane == 0) {
             const unsigned long long where = (unsigned long long)(__builtin_amdgcn_s_getreg(0xF804) & 0xFFFFu) |
                                              ((unsigned long long)(__builtin_amdgcn_s_getreg(0xF814) & 0xFu) << 16);
@@ -444,6 +453,105 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(cons
             stamps[2 * (size_t)wt + 1] = ((wall_clock64() - t_begin) & 0xFFFFFFFFull) | (where << 32);
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Flags between the tiles of ONE launch: shared by the chained streaming kernel below and the resident workgroup tiles
+// (kernels_wgtile.hpp, where the protocol and its history are described).  A flag holds the number of passes its tile has
+// published; a tile's data is stored device-coherently (aux bit sc1), acknowledged, and only then counted.
+constexpr unsigned long long WGR_TIMEOUT = 200000000ull;       // 2 s of the 100 MHz wall clock
+constexpr int WGR_FLAG_STRIDE = 64;                            // unsigneds between two tiles' flags: one 256-byte block each, so that
+                                                               // ~2 000 polling lanes do not queue on a handful of cache lines
+constexpr int WGR_SC1 = 16;                                    // aux bit 4 of the raw buffer intrinsics on gfx94x/gfx950
+
+// One lane waits until *flag has reached `want` (signed difference: the count may wrap).  Bounded: a lane that has polled for
+// WGR_TIMEOUT, or that sees *abort_flag set, raises *abort_flag and returns true -- so does, within 32 polls, every lane
+// waiting anywhere; the caller then leaves the kernel (the host redoes the interval, resident_check in api_sweep.hip).
+__device__ __forceinline__ bool wgr_wait_flag(const unsigned *flag, unsigned want, unsigned *abort_flag)
+{
+    const unsigned long long t0 = wall_clock64();
+    unsigned polls = 0;
+    while ((int)(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
+        __builtin_amdgcn_s_sleep(1);
+        if ((++polls & 31u) == 0u &&
+            (__hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || wall_clock64() - t0 > WGR_TIMEOUT)) {
+            __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return true;
+        }
+    }
+    return false;
+}
+
+// Chained passes: `npass` passes of the dealt tiles in ONE launch.  The grid is exactly the co-resident one (three workgroups
+// per CU, one tile per wave: deal_ranked_tiles), so every tile is on the chip for the whole launch and a launch boundary --
+// a chip-wide barrier that leaves every SIMD on two waves, then one, then none until the slowest tile of the chip has ended --
+// is replaced by what the next pass really needs: the tiles whose rows a tile's window reads, and those that still read the
+// rows it is about to overwrite (nbrs: up to TB_CHAIN_NB table slots per wave, each + 1, 0 = none; tb_chain.hpp computes them on the
+// host from the same geometry as tb_strip).  Pass p reads xa and writes xb when p is even, the other way round when odd.
+//   before pass p > 0   lanes 0...TB_CHAIN_NB-1 poll one neighbour's flag each until it reads base + p;
+//   after pass p        (not the last: the end of the launch publishes that) the wave waits for its stores' acknowledgement
+//                       and lane 0 stores base + p + 1 to its own flag.
+// Waves are independent: no workgroup barrier after the dictionary load.  The rows travel device-coherently (tb_strip's XAUX =
+// sc1) from the first pass on, the codes -- constant -- through plain loads.  Same tiles, same arithmetic, same bits as
+// npass launches of k_sweep_matfree_tb on the same table.  `miss`: the dealt-slot miss counter (see k_sweep_matfree_tb).
+// stamps (tools/tb_stamps.py --chain): per tile 8 words -- entry, where it ran, then for passes 0...2 {neighbours seen, swept}.
+constexpr int TB_CHAIN_NB = 16;
+template <int T, bool FMA, bool GUARD>
+__global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb_chain(const double *__restrict__ lut_g,
+                                                          const uint16_t *__restrict__ code, double *xa, double *xb,
+                                                          int nx, int ny, int img_stride, int dom_lo, int own_lo,
+                                                          int own_h, int ntx, int allb, int nrows, int shift, double omw,
+                                                          const int4 *__restrict__ dealt, const unsigned *__restrict__ nbrs,
+                                                          unsigned *miss, int npass, unsigned *flags, unsigned base,
+                                                          unsigned *abort_flag, unsigned long long *stamps)
+{
+    static_assert(T >= 1 && T <= 8, "unsupported T");
+    __shared__ double lut[LUT_DOUBLES];
+    load_lut(lut, lut_g, nrows);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const size_t slot = (size_t)blockIdx.x * 4u + (unsigned)wave;
+    const int4 d = dealt[slot];
+    if (d.z <= 0) return;                                          // a wave without a tile: in nobody's list
+    if (lane == 0 && __builtin_amdgcn_s_getreg(0x1804) != ((unsigned)d.w >> 30)) atomicAdd(miss, 1u);
+    const int tx = d.x & 0xFFFF, img = d.x >> 16;
+    const int row_lo = dom_lo + img * img_stride, own_hi = own_lo + img * img_stride + own_h;
+    unsigned long long *st = stamps ? stamps + (size_t)(d.w & 0x3FFFFFFF) * 8u : nullptr;     // (wave-uniform; lane 0 writes)
+    if (st && lane == 0) {
+        st[0] = wall_clock64();
+        st[1] = (unsigned long long)(__builtin_amdgcn_s_getreg(0xF804) & 0xFFFFu) | ((unsigned long long)(__builtin_amdgcn_s_getreg(0xF814) & 0xFu) << 16);
+    }
+    auto passes = [&](auto wall_tag) __attribute__((always_inline)) {
+        constexpr bool WALL = decltype(wall_tag)::value;
+#pragma unroll 1
+        for (int p = 0; p < npass; ++p) {
+            if (p > 0) {
+                // (the list is read again in every pass rather than kept -- a register the row loop does not have --, through a
+                // descriptor of this wave's TB_CHAIN_NB entries: no per-lane address to keep either; lanes beyond it read 0)
+                const unsigned nb = __builtin_amdgcn_raw_buffer_load_b32(tb_rsrc(nbrs + slot * TB_CHAIN_NB, TB_CHAIN_NB * 4u), lane * 4, 0, 0);
+                bool bad = false;
+                if (nb != 0u) bad = wgr_wait_flag(flags + (size_t)(nb - 1u) * WGR_FLAG_STRIDE, base + (unsigned)p, abort_flag);
+                if (__builtin_amdgcn_ballot_w64(bad) != 0ull) return;       // wave-uniform: this wave gives up
+                // the rows are asked for after the flags were seen: the polls' values have arrived (the loop's exit depends on
+                // them) and the compiler moves no memory access across this line
+                asm volatile("" ::: "memory");
+            }
+            if (st && p < 3 && lane == 0) st[2 + 2 * p] = wall_clock64();
+            const double *src = (p & 1) ? xb : xa;
+            double *dst = (p & 1) ? xa : xb;
+            tb_strip<T, GUARD, WALL, FMA, WGR_SC1>(lut, code, src, dst, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
+            if (st && p < 3 && lane == 0) st[3 + 2 * p] = wall_clock64();
+            if (p + 1 < npass) {
+                // the stores acknowledged (written through to the coherence point), then the flag: spelled out, see wgres_body
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (lane == 0)
+                    __hip_atomic_store(flags + slot * WGR_FLAG_STRIDE, base + (unsigned)p + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    };
+    if (allb || tb_wall_strip<T>(tx, ntx, shift, nx)) passes(TbTag<true>{});
+    else passes(TbTag<false>{});
 }
 
 }  // namespace deff

@@ -677,9 +677,8 @@ __device__ __forceinline__ void wgs_sweeps(double2 (&xr)[R], const WgsCoef<R> &k
 // with all loads of a poll in flight together one 150 001-sweep solve came out WRONG on a quiet GPU while the short parity
 // tests passed: whether a 16-byte sc1 access is single-copy atomic against another XCD is nothing this library can
 // establish, so nothing here rests on it.  Flags after acknowledged stores stay.)
-constexpr unsigned long long WGR_TIMEOUT = 200000000ull;       // 2 s
-constexpr int WGR_FLAG_STRIDE = 64;                            // unsigneds between two tiles' flags: one 256-byte block each, so that
-                                                               // ~2 000 polling lanes do not queue on a handful of cache lines
+// (WGR_TIMEOUT, WGR_FLAG_STRIDE, WGR_SC1 and the bounded poll wgr_wait_flag are in kernels_tb.hpp: the chained streaming
+// kernel uses the same flags)
 
 // The field between passes of one launch travels through device-coherent accesses: 16-byte buffer loads / stores with
 // sc1 set (what an agent-scope relaxed atomic compiles to on gfx942/gfx950: the store is written through, the load is
@@ -688,7 +687,6 @@ constexpr int WGR_FLAG_STRIDE = 64;                            // unsigneds betw
 // 8-byte sc1 accesses of whole tiles 16.6 us (2.6 us of it the re-read: twice 8 MB from beyond L2); halo-only 16-byte
 // accesses: see DESIGN.md.
 typedef unsigned int wgr_u4 __attribute__((ext_vector_type(4)));
-constexpr int WGR_SC1 = 16;                                    // aux bit 4 of the raw buffer intrinsics on gfx94x/gfx950
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t wgr_rsrc(double *p, unsigned bytes)
 {
     return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)bytes, 0x00020000);
@@ -829,21 +827,7 @@ __device__ __forceinline__ void wgres_body(double *lut, double2 (&edge)[2][NW][2
             const bool last = p + 1 == npass;
             if (p > 0) {
                 int bad = 0;
-                if (nb >= 0) {
-                    const unsigned want = base + (unsigned)p;
-                    const unsigned long long t0 = wall_clock64();
-                    unsigned polls = 0;
-                    while ((int)(__hip_atomic_load(flags + (size_t)nb * WGR_FLAG_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-                        __builtin_amdgcn_s_sleep(1);
-                        if ((++polls & 31u) == 0u &&
-                            (__hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ||
-                             wall_clock64() - t0 > WGR_TIMEOUT)) {
-                            __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            bad = 1;
-                            break;
-                        }
-                    }
-                }
+                if (nb >= 0 && wgr_wait_flag(flags + (size_t)nb * WGR_FLAG_STRIDE, base + (unsigned)p, abort_flag)) bad = 1;
                 if (__syncthreads_or(bad)) return;                 // workgroup-uniform: decided by wave 0's polling lanes
                 if (st && p < 3) st[4 * p] = wall_clock64();
 #pragma unroll

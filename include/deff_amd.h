@@ -81,7 +81,9 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
 /* tuning knob; 0 restores the default.  Keys: "rows_explicit", "rows_matfree", "wg_matfree",
  * "nt_explicit", "serpentine", "tb_T" (sweeps per pass: 1,2,4,6,8), "tb_LY" (rows per chunk), "tb_wg",
  * "tb_xmajor", "tb_wall_halo", "tb_ranked" (streaming kernel: chunk heights by the service order of a SIMD's waves, 1 default;
- * weights "tb_rank_w0", "tb_rank_w1", "tb_rank_w2", "tb_rank_wall" per mille), "tb_tall_deal" / "tb_sym_age" (resident tiles: rows
+ * weights "tb_rank_w0", "tb_rank_w1", "tb_rank_w2", "tb_rank_wall" per mille), "tb_chain" (streaming kernel on dealt tiles: 1 default =
+ * the passes between two checks run as ONE launch, every tile waiting only for the tiles whose rows it reads or overwrites, under the
+ * rules of "tb_launch" below, fallback included; 0 = one launch per pass; deff_get_plan "tb_chain"), "tb_tall_deal" / "tb_sym_age" (resident tiles: rows
  * dealt by the waves' age, 1 default), "dict" (harvest a row dictionary from explicit systems: 1 default),
  * "tb_impl" (1 streaming, 2 workgroup tiles), "tb_R", "tb_NW" (8 / 12 / 16 waves per
  *   tile: 12 = link-symmetric matrix rows in registers, 16 = tall resident tiles),
@@ -98,7 +100,7 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
 int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
 /* what the last launch plan of the temporally blocked kernel chose: "tb_T", "tb_LY" (rows per chunk),
  * "tb_strips", "tb_chunks_per_image", "tb_blocks" (workgroups launched), "tb_impl", "tb_R", "tb_resident" (1: the
- * passes of a batch run as one resident launch), "tb_fallbacks" (resident intervals that gave up and were redone with
+ * passes of a batch run as one resident launch; workgroup tiles only), "tb_chain" (1: the streaming kernel chains its passes), "tb_fallbacks" (resident intervals that gave up and were redone with
  * one launch per pass); 0 before any sweep.  Of the last deff_solve_cg (0 before one): "cg_kr" (rows per work item),
  * "cg_strips" (strips of 128 columns), "cg_items" (work items per image), "cg_restarts" (true-residual rounds that
  * sent an image back into the iteration) and "cg_impl" (1 = streaming kernels, 2 = on chip); of the last
@@ -258,7 +260,9 @@ int deff_residual(deff_ctx *ctx, double *r /* [nimg] */, float *ms);
 int deff_residual_slot(deff_ctx *ctx, int slot, double *r);
 int deff_residual_D(deff_ctx *ctx, const double *D, double CL, double CR, double *r /* [nimg] */, float *ms);
 /* sweep-kernel launches issued by the last deff_sweeps()/deff_solve() and the sweeps one
- * temporally blocked launch performs (1 for the single-sweep kernels) */
+ * temporally blocked launch performs (1 for the single-sweep kernels).  A chained launch of the streaming kernel
+ * (deff_get_plan "tb_chain" = 1: several passes of *sweeps_per_pass sweeps in one launch) counts its PASSES, so that
+ * *launches stays nsweeps / T + nsweeps % T there and time / *launches stays the time of one pass. */
 int deff_last_launches(const deff_ctx *ctx, int64_t *launches, int *sweeps_per_pass);
 
 /* ---- row slabs: ONE image split over several GPUs (BASELINE config #4; nothing like it in the

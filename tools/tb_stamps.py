@@ -11,6 +11,8 @@ sys.path.insert(0, ROOT)
 import effectivediffusivityfvm_amd as pkg  # noqa: E402
 from effectivediffusivityfvm_amd import _capi  # noqa: E402
 
+CHAIN = "--chain" in sys.argv                                       # three chained passes in one launch (k_sweep_matfree_tb_chain)
+sys.argv = [a for a in sys.argv if a != "--chain"]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 with pkg.Solver(n, n) as s:
@@ -20,6 +22,10 @@ with pkg.Solver(n, n) as s:
         s.set_tuning(k, int(v))
     if os.environ.get("TB_RANKED") is not None:
         s.set_tuning("tb_ranked", int(os.environ["TB_RANKED"]))
+    try:
+        s.set_tuning("tb_chain", 1 if CHAIN else 0)                 # (one pass per launch unless asked: the stamps below are of ONE pass)
+    except Exception:
+        assert not CHAIN                                            # an older build of the library (DEFF_AMD_LIB): no such key, never chained
     s.synth_image(12345, 0)
     s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
     s.init_linear(0.0, 1.0)
@@ -29,6 +35,27 @@ with pkg.Solver(n, n) as s:
     _capi.check(L.deff_debug_tb_stamps(s._ctx, 2.0 / 3.0, None, C.byref(nt)))
     buf = np.zeros(2 * nt.value, dtype=np.uint64)
     _capi.check(L.deff_debug_tb_stamps(s._ctx, 2.0 / 3.0, buf.ctypes.data_as(C.c_void_p), C.byref(nt)))
+    if CHAIN:
+        # 8 words per tile: entry, where it ran, then for passes 0..2 {neighbours seen, swept}
+        assert s.plan_value("tb_chain") == 1 and s.plan_value("tb_fallbacks") == 0, "the plan is not chained"
+        w = buf.reshape(-1, 8)
+        w = w[w[:, 0] > 0].astype(np.int64)
+        t0 = w[:, 0].min()
+        seen = (w[:, 2::2] - t0) / 100.0                            # [tile, pass]: neighbours seen = the pass starts
+        swept = (w[:, 3::2] - t0) / 100.0                           #               the tile's last row is stored
+        simd = w[:, 1] >> 4
+        print(f"n={n} tiles={len(w)} chained launch of 3 passes, span {swept.max():.1f} us = {swept.max() / 3:.1f} us per pass")
+        for p in range(3):
+            q = np.percentile(swept[:, p], [0, 5, 50, 95, 100])
+            dur = swept[:, p] - seen[:, p]
+            line = f"  pass {p}: swept min {q[0]:6.1f} p5 {q[1]:6.1f} p50 {q[2]:6.1f} p95 {q[3]:6.1f} max {q[4]:6.1f} (spread p95-p5 {q[3] - q[1]:.1f}); sweep time mean {dur.mean():.1f}"
+            if p > 0:
+                wait = seen[:, p] - swept[:, p - 1]                 # stores acknowledged + flag + neighbours' flags seen
+                line += f"; wait before it mean {wait.mean():.2f} p50 {np.median(wait):.2f} p95 {np.percentile(wait, 95):.2f} max {wait.max():.2f}"
+            print(line)
+        last = np.array([swept[simd == k, 2].max() for k in np.unique(simd)])
+        print(f"  a SIMD's last wave ends pass 2: mean {last.mean():.1f} min {last.min():.1f} max {last.max():.1f} -> SIMD-time idle before the launch ends: {1 - last.mean() / swept.max():.3f} of 3 passes")
+        sys.exit(0)
     st = buf[0::2].astype(np.int64)
     dur_t = (buf[1::2] & np.uint64(0xFFFFFFFF)).astype(np.int64)
     where = (buf[1::2] >> np.uint64(32)).astype(np.int64)          # HW_ID[15:0] | XCC << 16
