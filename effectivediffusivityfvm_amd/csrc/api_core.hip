@@ -315,6 +315,8 @@ try {
     else if (!strcmp(key, "tb_fallbacks")) *value = c->res_fallbacks;
     else if (!strcmp(key, "tb_ranked")) *value = c->plan_ranked;
     else if (!strcmp(key, "tb_chain")) *value = c->plan_chain;
+    else if (!strcmp(key, "tb_chunk_min")) *value = c->plan_ranked ? c->tb_dealt_min : 0;   // dealt tiles: rows of the shortest / tallest chunk
+    else if (!strcmp(key, "tb_chunk_max")) *value = c->plan_ranked ? c->tb_dealt_max : 0;
     else if (!strcmp(key, "tb_aged")) *value = c->plan_aged;
     else if (!strcmp(key, "tb_rank_misses")) *value = c->tb_rank_misses;
     else if (!strcmp(key, "tb_rank_lost")) *value = c->tb_rank_lost;

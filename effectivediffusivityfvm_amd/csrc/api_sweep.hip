@@ -623,6 +623,7 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
     }
     if ((long)3 * c->nimg * ntx * nmax >= (1L << 30)) return DEFF_OK;
     int tallest = 0;                                              // rows of the tallest chunk dealt (tb_window_fits below)
+    int shortest = INT32_MAX;                                     // ... and of the shortest that has any (deff_get_plan "tb_chunk_min")
     const size_t entries = (size_t)resident * 4 + 1;              // + the word the waves count their misplacements in (kernels_tb.hpp)
     {
         std::vector<int4> &tab = c->tb_dealt_host;
@@ -638,6 +639,7 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
             int rows_here = std::min(sp.ly[r], own_hi - ry0);
             if (r == 2 && q == sp.n[2] - 1) rows_here = own_hi - ry0;              // the youngest rank's last chunk takes what rounding left over
             tallest = std::max(tallest, rows_here);
+            if (rows_here > 0) shortest = std::min(shortest, rows_here);
             return make_int4(tx | (img << 16), ry0, rows_here > 0 ? rows_here : 0, (int)((unsigned)(((r * c->nimg + img) * ntx + tx) * nmax + q) | ((unsigned)r << 30)));
         };
         for (int r = 0; r < 3; ++r) {
@@ -697,6 +699,8 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
         HIP_TRY(hipStreamSynchronize(c->stream));                                   // (pageable sources; once per plan change)
         c->tb_dealt_key = key;
         c->tb_dealt_LY = st[ntx / 2].ly[1];
+        c->tb_dealt_min = shortest == INT32_MAX ? 0 : shortest;
+        c->tb_dealt_max = tallest;
         c->tb_dealt_nmax = nmax;
         c->tb_dealt_miss_at = (size_t)resident * 4;
         c->tb_dealt_waves = 0;
@@ -712,7 +716,11 @@ static int deal_ranked_tiles(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int 
 // proportion to the pass.  Nothing was measured between the two, so the rule stops at what won.
 static bool chain_pays(const deff_ctx *c)
 {
+#ifdef TB_CHAIN_ALWAYS                                  // (measurement switch: chain every dealt plan; never set by the Makefile)
+    return c->n > 0;
+#else
     return c->n <= ((size_t)1 << 24);
+#endif
 }
 
 static int plan_streaming(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int own_h)
@@ -1021,6 +1029,13 @@ int launch_tb_pass(deff_ctx *c, const SweepPlan &pl)
     return DEFF_OK;
 }
 
+// Passes one resident launch may hold: ~25 ms (a pass of T sweeps takes about n * T / 0.9e12 s on these forms), between 64 and 4 096.
+static int64_t resident_pass_cap(const deff_ctx *c, const SweepPlan &pl)
+{
+    const double pass_s = (double)c->n * pl.T / 0.9e12;
+    return std::max<int64_t>(64, std::min<int64_t>(4096, (int64_t)(25e-3 / pass_s)));
+}
+
 // (workgroup tiles, or the chained form of the streaming kernel)
 // All whole passes of n sweeps as resident launches of up to 4 096 passes (tens of milliseconds each); *n is reduced by
 // the sweeps enqueued.  In front of the first resident launch since the abort flag was last looked at, the field is copied
@@ -1037,8 +1052,7 @@ static int launch_resident_passes(deff_ctx *c, const SweepPlan &pl, int64_t *n)
     }
     // a resident launch holds the whole chip until it ends: keep one to ~25 ms (a pass of T sweeps takes about n * T / 0.9e12 s
     // on these forms), between 64 and 4 096 passes -- the reference's 10 000-sweep interval is one launch up to ~1500^2
-    const double pass_s = (double)c->n * pl.T / 0.9e12;
-    const int64_t cap = std::max<int64_t>(64, std::min<int64_t>(4096, (int64_t)(25e-3 / pass_s)));
+    const int64_t cap = resident_pass_cap(c, pl);
     while (np > 0) {
         const int chunk = (int)(np < cap ? np : cap);
         if (c->res_epoch > (1u << 30)) {
@@ -1121,16 +1135,31 @@ try {
     // streaming form: 2 stamps per wave tile; workgroup-tile form: T + 4 per tile, flattened -- *ntiles is always
     // the number of PAIRS the buffer must hold
     // (resident launches stamp 12 clocks per tile whatever T: entry + 3 passes x {neighbours seen, halo in, swept, published})
-    // (chained streaming launches: 8 clocks per tile -- entry, where, 3 passes x {neighbours seen, swept} --, 3 passes as well)
+    // (chained streaming launches: two header words, then TB_CHAIN_STAMPS clocks per tile -- entry, where, 3 passes x six
+    // clocks, see k_sweep_matfree_tb_chain.  The caller writes the header into `out` before the call: out[0] = the first of the
+    // three passes to stamp, out[1] = the passes of the chain, 0 meaning out[0] + 3; the field advances by that many passes.
+    // The chain must be ONE launch -- see launch_resident_passes for how many passes that holds.)
     const bool chain_stamps = pl.impl == 1 && pl.chained;
     const bool res_stamps = (pl.impl == 2 && pl.resident) || chain_stamps;
-    const int n = chain_stamps ? pl.ntx * pl.tgy * 4 : res_stamps ? (pl.ntx * pl.tgy * 12 + 1) / 2 : pl.impl == 2 ? (pl.ntx * pl.tgy * (pl.T + 4) + 1) / 2 : pl.ntx * pl.tgy;
+    const int n = chain_stamps ? (TB_CHAIN_STAMP_HEAD + pl.ntx * pl.tgy * TB_CHAIN_STAMPS) / 2 : res_stamps ? (pl.ntx * pl.tgy * 12 + 1) / 2 : pl.impl == 2 ? (pl.ntx * pl.tgy * (pl.T + 4) + 1) / 2 : pl.ntx * pl.tgy;
     *ntiles = n;
     if (!out) return DEFF_OK;
     HIP_TRY(hipMalloc((void **)&c->tb_stamps, sizeof(unsigned long long) * 2 * n));
     HIP_TRY(hipMemsetAsync(c->tb_stamps, 0, sizeof(unsigned long long) * 2 * n, c->stream));
     int rc = DEFF_OK;
-    if (res_stamps) rc = enqueue_sweeps(c, pl, 3 * pl.T);                                  // k_sweep_wgres / wgsym: 12 stamps per tile, 3 passes
+    int64_t passes = 3;
+    if (chain_stamps) {
+        const unsigned long long first = out[0];
+        passes = out[1] ? (int64_t)out[1] : (int64_t)first + 3;
+        if (first > 4093ull || passes < (int64_t)first + 3 || passes > resident_pass_cap(c, pl)) {
+            (void)hipFree(c->tb_stamps);
+            c->tb_stamps = nullptr;
+            return fail(DEFF_EINVAL, "stamps of passes %llu ... + 2 of a chain of %lld: not one launch", first, (long long)passes);
+        }
+        HIP_TRY(hipMemcpyAsync(c->tb_stamps, out, sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));                                          // (`out` is the caller's, pageable)
+    }
+    if (res_stamps) rc = enqueue_sweeps(c, pl, passes * pl.T);                                  // k_sweep_wgres / wgsym: 12 stamps per tile, 3 passes
     else rc = enqueue_tb_pass(c, pl);
     if (rc != DEFF_OK) { (void)hipFree(c->tb_stamps); c->tb_stamps = nullptr; return rc; }
     hipError_t e = hipMemcpyAsync(out, c->tb_stamps, sizeof(unsigned long long) * 2 * n, hipMemcpyDeviceToHost, c->stream);

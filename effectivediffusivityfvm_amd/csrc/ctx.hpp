@@ -212,6 +212,7 @@ struct deff_ctx {
     int64_t tb_dealt_waves = 0;                  // waves launched on the current table
     int tb_dealt_looks = 0;                      // times the count was read (dealt_watch: the first three synchronisations)
     int tb_rank_misses = 0, tb_rank_lost = 0;    // last count read; 1 = the dispatch order is not the assumed one: equal chunks from now on
+    int tb_dealt_min = 0, tb_dealt_max = 0;      // rows of the shortest and of the tallest chunk of the table ("tb_chunk_min", "tb_chunk_max")
     int tb_dealt_LY = 0, tb_dealt_nmax = 0;      // ... and what deff_get_plan reports of it (an inner strip's middle rank; most chunks per rank)
     int plan_ranked = 0;
     // Chained streaming passes (k_sweep_matfree_tb_chain, kernels_tb.hpp): the passes between two checks as ONE launch of the

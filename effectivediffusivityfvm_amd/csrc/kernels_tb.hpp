@@ -34,6 +34,18 @@ namespace deff {
 
 constexpr int TB_COLS = 128;                                   // columns per wave strip (2 per lane)
 template <bool V> struct TbTag { static constexpr bool value = V; };   // compile-time flag for generic lambdas
+template <int V> struct TbInt { static constexpr int value = V; };     // compile-time index for generic lambdas
+// f(TbInt<G>{}) for G = FIRST ... N - 1, in order, until one returns false: straight-line code with one exit per call
+template <int FIRST, int N, class F> __device__ __forceinline__ void tb_each_until(F &&f)
+{
+    if constexpr (FIRST < N) {
+        if (f(TbInt<FIRST>{})) tb_each_until<FIRST + 1, N>(f);
+    }
+}
+// diagnostics of the chained kernel (tools/tb_stamps.py --chain): wall clocks taken inside tb_strip, kept in scalar registers
+struct TbMarks {
+    unsigned long long first_row, steady;          // first row consumed; entry into the steady-state loop
+};
 
 // lane i <- lane i-1 (lane 0 <- 0.0)
 __device__ __forceinline__ double from_lane_below(double v)
@@ -189,11 +201,20 @@ template <class P> __device__ __forceinline__ __amdgpu_buffer_rsrc_t tb_rsrc(P *
 // stores; 0 = plain (k_sweep_matfree_tb), 16 = sc1 (device-coherent: k_sweep_matfree_tb_chain, whose tiles read their
 // neighbours' rows of the same launch).  The code loads stay plain.  In the one-pass kernel sc1 rows measured -0.3 +- 0.3 us
 // per 107 us launch: profiles/r06_tb_chain_ab.log.
-template <int T, bool GUARD, bool WALL, bool FMA, int XAUX = 0>
+// `marks` (chained kernel only): two wall clocks for the tile stamps, read into scalar registers where they are taken.
+// (measurement switch: -DTB_STRAIGHT_RAMP=0 builds every tile with the generic trimmed groups, to be timed against the default
+// build in one process; never set by the Makefile)
+#ifndef TB_STRAIGHT_RAMP
+#define TB_STRAIGHT_RAMP 1
+#endif
+// RAMP = full-halo tiles cross their first steps as straight-line code (below).  Off in the loop over the tiles of a workgroup
+// that was dealt none (k_sweep_matfree_tb without a table): what the previous tile left in flight would reach this tile's
+// steady-state loop along the edge described below.
+template <int T, bool GUARD, bool WALL, bool FMA, int XAUX = 0, bool RAMP = true>
 __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__restrict__ code,
                                          const double *__restrict__ x, double *__restrict__ xnew, int nx,
                                          int ny, int row_lo, int own_hi, int tx, int ntx, int shift, int ry0, int LY,
-                                         int lane, double omw)
+                                         int lane, double omw, TbMarks *marks = nullptr)
 {
     // column halo rounded up to even so that odd T keeps the 16-B alignment of a lane's pair
     constexpr int HW = (T + 1) & ~1;
@@ -235,10 +256,7 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
 
     double2 w[T][3];                               // w[t]: 3 newest rows of sweep t
     unsigned cw[T + 1];                            // cw[t]: the two 16-bit codes of row rr-t
-#pragma unroll
-    for (int t = 0; t < T; ++t) { w[t][0] = zero; w[t][1] = zero; w[t][2] = zero; }
-#pragma unroll
-    for (int t = 0; t <= T; ++t) cw[t] = 0u;
+                                                   // (both zeroed where the generic trimmed groups start, see below)
 
     // (rr >= r_begin for every row asked for: the loops below start there and only go down)
     auto fetch = [&](const int rr, tb_u4 &vx_out, unsigned &vc_out) __attribute__((always_inline)) {
@@ -258,9 +276,44 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
     // registers that row has just left (nx_*[rr % 3 by position in the group]).
     tb_u4 nx_x[3];                                 // (kept as loaded, 16 bytes: two doubles)
     unsigned nx_c[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) fetch(r_begin + k, nx_x[k], nx_c[k]);
+    // (the first three rows are requested where the steps begin, below)
 
+    // One level of one step: row rt of sweep t from the three newest rows of sweep t - 1 (window slots sN, sC, sS).
+    auto level = [&](const int t, const int rt, const int sN, const int sC, const int sS) __attribute__((always_inline)) {
+        const double2 vN = w[t - 1][sN], vC = w[t - 1][sC], vS = w[t - 1][sS];
+        const double xw0 = from_lane_below(vC.y);
+        const double xe1 = from_lane_above(vC.x);
+        const unsigned o0 = cw[t] & 0xFFFFu, o1 = cw[t] >> 16;
+        double2 o;
+        if constexpr (GUARD) {
+            o = tb_pair<GUARD, WALL, FMA>(lut, o0, o1, vC, xw0, xe1, vS, vN, omw);
+        } else {
+            // The lookups first, then the arithmetic stage by stage, both cells side by side, as written: left to
+            // itself inside a level the scheduler -- short of registers at 3 waves per SIMD -- runs one cell's chain
+            // to its end before it starts the other's (each FP64 instruction then waits for the one before it).
+            // That it did not do so before was an accident of a register pressure ABOVE the budget, which made it
+            // give the schedule up and keep the source order; the fences say it.
+            TbCoef k;
+            tb_lookup<WALL>(lut, o0, o1, k);
+            __builtin_amdgcn_sched_barrier(TB_STAGE_FENCE);
+            o = tb_apply<FMA, true>(k, vC, xw0, xe1, vS, vN, omw);
+        }
+        if (t < T) w[t][sS] = o;
+        else store(rt, o);
+        // keep the scheduler from pulling the next sweeps' table lookups up here: left
+        // alone it hoists them all (180-250 VGPRs, 1-2 waves per SIMD); with the fence a
+        // step keeps ~120 VGPRs and 4 waves per SIMD hide the LDS latency instead
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // A requested row enters the window (slot sS of level 0) and its codes cw[0]: see the comment in `group`.
+    auto take = [&](const tb_u4 &vx, const unsigned vc, const int sS) __attribute__((always_inline)) {
+        double lo, hi;
+        __builtin_memcpy(&lo, &vx, 8);
+        __builtin_memcpy(&hi, reinterpret_cast<const char *>(&vx) + 8, 8);
+        asm volatile("v_mov_b64 %0, %3\n\tv_mov_b64 %1, %4\n\tv_mov_b32 %2, %5"
+                     : "=&v"(w[0][sS].x), "=&v"(w[0][sS].y), "=&v"(cw[0])
+                     : "v"(lo), "v"(hi), "v"(vc));
+    };
     // (Measured with the tile time stamps, tools/tb_stamps.py: waves sharing a SIMD are served oldest-first, so identical
     // tiles end at 71 / 89 / 108 us of one T = 8 launch at 4096^2, by wave slot.  Evening that out with s_setprio -- a
     // rotating priority per group of steps -- brought +2...4 %: served in turn the three waves issue less in total than served
@@ -292,14 +345,7 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
             // rr + 1 and rr + 2 and the stores of the last two steps stay in flight.  tests/test_tb_stream_isa.py holds the
             // emitted loop to that: one branch, no wait that forces a store younger than one step (none with vmcnt 0), first
             // read of a row at least two steps after its load, no select, no 64-bit address arithmetic.
-            {
-                double lo, hi;
-                __builtin_memcpy(&lo, &nx_x[ph], 8);
-                __builtin_memcpy(&hi, reinterpret_cast<const char *>(&nx_x[ph]) + 8, 8);
-                asm volatile("v_mov_b64 %0, %3\n\tv_mov_b64 %1, %4\n\tv_mov_b32 %2, %5"
-                             : "=&v"(w[0][sS].x), "=&v"(w[0][sS].y), "=&v"(cw[0])
-                             : "v"(lo), "v"(hi), "v"(nx_c[ph]));
-            }
+            take(nx_x[ph], nx_c[ph], sS);
             fetch(rr + 3, nx_x[ph], nx_c[ph]);
 #pragma unroll
             for (int t = 1; t <= T; ++t) {
@@ -310,36 +356,94 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
                         continue;
                     }
                 }
-                const double2 vN = w[t - 1][sN], vC = w[t - 1][sC], vS = w[t - 1][sS];
-                const double xw0 = from_lane_below(vC.y);
-                const double xe1 = from_lane_above(vC.x);
-                const unsigned o0 = cw[t] & 0xFFFFu, o1 = cw[t] >> 16;
-                double2 o;
-                if constexpr (GUARD) {
-                    o = tb_pair<GUARD, WALL, FMA>(lut, o0, o1, vC, xw0, xe1, vS, vN, omw);
-                } else {
-                    // The lookups first, then the arithmetic stage by stage, both cells side by side, as written: left to
-                    // itself inside a level the scheduler -- short of registers at 3 waves per SIMD -- runs one cell's chain
-                    // to its end before it starts the other's (each FP64 instruction then waits for the one before it).
-                    // That it did not do so before was an accident of a register pressure ABOVE the budget, which made it
-                    // give the schedule up and keep the source order; the fences say it.
-                    TbCoef k;
-                    tb_lookup<WALL>(lut, o0, o1, k);
-                    __builtin_amdgcn_sched_barrier(TB_STAGE_FENCE);
-                    o = tb_apply<FMA, true>(k, vC, xw0, xe1, vS, vN, omw);
-                }
-                if (t < T) w[t][sS] = o;
-                else store(rt, o);
-                // keep the scheduler from pulling the next sweeps' table lookups up here: left
-                // alone it hoists them all (180-250 VGPRs, 1-2 waves per SIMD); with the fence a
-                // step keeps ~120 VGPRs and 4 waves per SIMD hide the LDS latency instead
-                __builtin_amdgcn_sched_barrier(0);
+                level(t, rt, sN, sC, sS);
             }
         }
     };
     constexpr int TRIMMED = ((2 * T + 2) / 3) * 3;   // steps that may hold unneeded levels, rounded up to whole groups
     int r = r_begin;
-    for (; r < r_begin + TRIMMED && r < r_end; r += 3) group(r, TbTag<true>{});
+    if constexpr (!(RAMP && TB_STRAIGHT_RAMP)) {
+        // every tile through the generic trimmed groups
+#pragma unroll
+        for (int t = 0; t < T; ++t) { w[t][0] = zero; w[t][1] = zero; w[t][2] = zero; }
+#pragma unroll
+        for (int t = 0; t <= T; ++t) cw[t] = 0u;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fetch(r_begin + k, nx_x[k], nx_c[k]);
+        if (marks) marks->first_row = wall_clock64();                                  // (here: in front of the first group)
+        for (; r < r_begin + TRIMMED && r < r_end; r += 3) group(r, TbTag<true>{});
+    } else if (r >= r_end) {
+        return;                                    // no input row: an empty chunk
+    } else if (ry0 - T >= row_lo && r_end - r_begin > TRIMMED - 3) {
+        // The ramp of a tile whose window starts a full halo above its chunk -- every chunk but the topmost of a mesh: step j
+        // (input row r_begin + j) needs exactly the levels 1 ... j / 2 (the test of the trimmed groups, rt - t >= ry0 - T, with
+        // r_begin = ry0 - T), known when the code is written.  So the same TRIMMED steps are straight-line code: no branch
+        // around a level, no window slot zeroed -- level t first runs at step 2 t, when steps 2 t - 2 ... 2 t have written the
+        // three rows it reads -- and no test between the groups either: a chunk of one row already has 2 T + 1 input rows,
+        // more than TRIMMED - 3, so the loop over the trimmed groups runs them all (the second condition above says so for
+        // every T; a chunk too short for it, which no caller sends, would take the generic groups).  One basic block: the
+        // requests stay where they are written.
+        // And while the upper levels' windows are dead their registers hold rows: the prologue asks for RAMP_ROWS rows at
+        // once, steps 0, 1, 2 for three more, and the wave crosses the ramp -- a step holds few levels, a fraction of a
+        // memory round trip -- in one or two round trips of the device-coherent rows instead of one per group.  From row
+        // RAMP_ROWS on the rows travel as in the loop, three steps ahead through nx_*, which the loop finds as it expects them:
+        // rows r, r + 1, r + 2 of its first group in nx_*[0...2].  All requests go through `fetch`: inside the window, or
+        // answered by the descriptor of zero bytes.
+        constexpr int RAMP_ROWS = TRIMMED - 3 < 3 ? 3 : TRIMMED - 3 > 12 ? 12 : TRIMMED - 3;   // (T = 8: 12 of the 18; a multiple of 3)
+        constexpr int NEX = RAMP_ROWS > 3 ? RAMP_ROWS - 3 : 1;
+        tb_u4 ex_x[NEX];                           // rows 3 ... RAMP_ROWS - 1 of the window, as loaded
+        unsigned ex_c[NEX];
+        tb_each_until<0, RAMP_ROWS>([&](auto k_tag) __attribute__((always_inline)) {
+            constexpr int k = decltype(k_tag)::value;
+            if constexpr (k < 3) fetch(r_begin + k, nx_x[k], nx_c[k]);
+            else fetch(r_begin + k, ex_x[k - 3], ex_c[k - 3]);
+            return true;
+        });
+        auto ramp_step = [&](auto j_tag) __attribute__((always_inline)) {
+            constexpr int j = decltype(j_tag)::value, ph = j % 3;
+            constexpr int sN = (ph + 1) % 3, sC = (ph + 2) % 3, sS = ph;
+            const int rr = r_begin + j;
+#pragma unroll
+            for (int t = T; t >= 1; --t) cw[t] = cw[t - 1];
+            if constexpr (j >= 3 && j < RAMP_ROWS) take(ex_x[j - 3], ex_c[j - 3], sS);
+            else take(nx_x[ph], nx_c[ph], sS);
+            if constexpr (j < 3) fetch(rr + RAMP_ROWS, nx_x[ph], nx_c[ph]);
+            else if constexpr (j >= RAMP_ROWS) fetch(rr + 3, nx_x[ph], nx_c[ph]);
+            if constexpr (j == 0) {
+                if (marks) marks->first_row = wall_clock64();
+            }
+            tb_each_until<1, (j / 2 < T ? j / 2 : T) + 1>([&](auto t_tag) __attribute__((always_inline)) {
+                constexpr int t = decltype(t_tag)::value;
+                level(t, rr - t, sN, sC, sS);
+                return true;
+            });
+        };
+        tb_each_until<0, TRIMMED>([&](auto j_tag) __attribute__((always_inline)) {
+            ramp_step(j_tag);
+            return true;
+        });
+        r += TRIMMED;
+    } else {
+        // the top of a mesh (the first chunk of an image -- of every image of a stack -- and a slab whose window is clipped):
+        // which levels a step needs depends on where the mesh begins; skipped levels leave their slots as they are, zero
+        // (Both arms begin by requesting row r_begin, and the compiler lifts what they share in front of the branch.  The
+        // emitted control flow has an edge from there straight to the steady-state loop -- never taken, but the loop's waits
+        // are counted along it too, and a request in flight on it means vmcnt(0) in every round.  No load is lifted across
+        // this line.  For the same reason a caller must not arrive here with operations in flight that the compiler knows
+        // of: see RAMP.)
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int t = 0; t < T; ++t) { w[t][0] = zero; w[t][1] = zero; w[t][2] = zero; }
+#pragma unroll
+        for (int t = 0; t <= T; ++t) cw[t] = 0u;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fetch(r_begin + k, nx_x[k], nx_c[k]);
+        if (marks) marks->first_row = wall_clock64();                                  // (here: in front of the first group)
+        // (at least one group, as tested above: no way from the requests just made straight to the loop below, which would
+        // then have to wait for them in every round)
+        do { group(r, TbTag<true>{}); r += 3; } while (r < r_begin + TRIMMED && r < r_end);
+    }
+    if (marks) marks->steady = wall_clock64();
     for (; r < r_end; r += 3) group(r, TbTag<false>{});
 }
 
@@ -442,9 +546,9 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(cons
         // b is read only where it can be non-zero: strips holding a wall column, or everywhere for a
         // harvested dictionary whose right-hand side is not confined to the walls
         if (allb || tb_wall_strip<T>(tx, ntx, shift, nx))
-            tb_strip<T, GUARD, true, FMA>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
+            tb_strip<T, GUARD, true, FMA, 0, false>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
         else
-            tb_strip<T, GUARD, false, FMA>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
+            tb_strip<T, GUARD, false, FMA, 0, false>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
         if (stamps && lane == 0) {
             // end stamp: low 32 bits = duration in 10-ns ticks, bits 32...47 = HW_ID (wave slot, SIMD, CU, SE), 48...51 = XCC
             const unsigned long long where = (unsigned long long)(__builtin_amdgcn_s_getreg(0xF804) & 0xFFFFu) |
@@ -494,7 +598,11 @@ __device__ __forceinline__ bool wgr_wait_flag(const unsigned *flag, unsigned wan
 // Waves are independent: no workgroup barrier after the dictionary load.  The rows travel device-coherently (tb_strip's XAUX =
 // sc1) from the first pass on, the codes -- constant -- through plain loads.  Same tiles, same arithmetic, same bits as
 // npass launches of k_sweep_matfree_tb on the same table.  `miss`: the dealt-slot miss counter (see k_sweep_matfree_tb).
-// stamps (tools/tb_stamps.py --chain): per tile 8 words -- entry, where it ran, then for passes 0...2 {neighbours seen, swept}.
+// stamps (tools/tb_stamps.py --chain): word 0 of the buffer = the first pass to stamp (set by the host, so that three passes
+// DEEP in a chain can be looked at), word 1 unused; then TB_CHAIN_STAMPS words per tile -- entry, where it ran, and for the
+// passes first ... first + 2 {neighbours seen, first row consumed, steady-state loop entered, swept = last store issued,
+// stores acknowledged, flag published}.
+constexpr int TB_CHAIN_STAMPS = 20, TB_CHAIN_STAMP_HEAD = 2;
 constexpr int TB_CHAIN_NB = 16;
 template <int T, bool FMA, bool GUARD>
 __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb_chain(const double *__restrict__ lut_g,
@@ -517,7 +625,8 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb_chai
     if (lane == 0 && __builtin_amdgcn_s_getreg(0x1804) != ((unsigned)d.w >> 30)) atomicAdd(miss, 1u);
     const int tx = d.x & 0xFFFF, img = d.x >> 16;
     const int row_lo = dom_lo + img * img_stride, own_hi = own_lo + img * img_stride + own_h;
-    unsigned long long *st = stamps ? stamps + (size_t)(d.w & 0x3FFFFFFF) * 8u : nullptr;     // (wave-uniform; lane 0 writes)
+    unsigned long long *st = stamps ? stamps + TB_CHAIN_STAMP_HEAD + (size_t)(d.w & 0x3FFFFFFF) * TB_CHAIN_STAMPS : nullptr;     // (wave-uniform; lane 0 writes)
+    const int st_first = stamps ? (int)stamps[0] : 0;
     if (st && lane == 0) {
         st[0] = wall_clock64();
         st[1] = (unsigned long long)(__builtin_amdgcn_s_getreg(0xF804) & 0xFFFFu) | ((unsigned long long)(__builtin_amdgcn_s_getreg(0xF814) & 0xFu) << 16);
@@ -528,7 +637,9 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb_chai
         for (int p = 0; p < npass; ++p) {
             if (p > 0) {
                 // (the list is read again in every pass rather than kept -- a register the row loop does not have --, through a
-                // descriptor of this wave's TB_CHAIN_NB entries: no per-lane address to keep either; lanes beyond it read 0)
+                // descriptor of this wave's TB_CHAIN_NB entries: no per-lane address to keep either; lanes beyond it read 0.
+                // Asking for it one round trip earlier, in the shadow of the stores' acknowledgement below, was measured and
+                // bought nothing: DESIGN.md section 4, profiles/r07_tb_chain_boundary.log)
                 const unsigned nb = __builtin_amdgcn_raw_buffer_load_b32(tb_rsrc(nbrs + slot * TB_CHAIN_NB, TB_CHAIN_NB * 4u), lane * 4, 0, 0);
                 bool bad = false;
                 if (nb != 0u) bad = wgr_wait_flag(flags + (size_t)(nb - 1u) * WGR_FLAG_STRIDE, base + (unsigned)p, abort_flag);
@@ -537,16 +648,27 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb_chai
                 // them) and the compiler moves no memory access across this line
                 asm volatile("" ::: "memory");
             }
-            if (st && p < 3 && lane == 0) st[2 + 2 * p] = wall_clock64();
+            unsigned long long *sp = (st && p >= st_first && p < st_first + 3) ? st + 2 + 6 * (p - st_first) : nullptr;   // (wave-uniform)
+            if (sp && lane == 0) sp[0] = wall_clock64();
             const double *src = (p & 1) ? xb : xa;
             double *dst = (p & 1) ? xa : xb;
-            tb_strip<T, GUARD, WALL, FMA, WGR_SC1>(lut, code, src, dst, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
-            if (st && p < 3 && lane == 0) st[3 + 2 * p] = wall_clock64();
+            // (the two clocks are read whether or not anybody stamps: a wave-uniform test around them would cut the ramp's
+            // basic block in two, and the compiler sinks row requests across such a cut -- two scalar clock reads per pass)
+            TbMarks mk = {0ull, 0ull};
+            // (To the compiler: nothing is in flight here -- the wait behind the previous pass is inline assembly, which its
+            // count of the operations in flight does not read, and what it believes pending from there would reach the
+            // steady-state loop's waits along an edge of the emitted control flow that is never taken.  At run time the counter
+            // is at zero already: the polls' values have arrived, and they return behind everything older.)
+            __builtin_amdgcn_s_waitcnt(0x0F70);                        // vmcnt(0) alone
+            tb_strip<T, GUARD, WALL, FMA, WGR_SC1>(lut, code, src, dst, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw, &mk);
+            if (sp && lane == 0) { sp[1] = mk.first_row; sp[2] = mk.steady; sp[3] = wall_clock64(); }
             if (p + 1 < npass) {
                 // the stores acknowledged (written through to the coherence point), then the flag: spelled out, see wgres_body
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (sp && lane == 0) sp[4] = wall_clock64();
                 if (lane == 0)
                     __hip_atomic_store(flags + slot * WGR_FLAG_STRIDE, base + (unsigned)p + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (sp && lane == 0) sp[5] = wall_clock64();
             }
         }
     };

@@ -100,7 +100,7 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
 int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
 /* what the last launch plan of the temporally blocked kernel chose: "tb_T", "tb_LY" (rows per chunk),
  * "tb_strips", "tb_chunks_per_image", "tb_blocks" (workgroups launched), "tb_impl", "tb_R", "tb_resident" (1: the
- * passes of a batch run as one resident launch; workgroup tiles only), "tb_chain" (1: the streaming kernel chains its passes), "tb_fallbacks" (resident intervals that gave up and were redone with
+ * passes of a batch run as one resident launch; workgroup tiles only), "tb_chain" (1: the streaming kernel chains its passes), "tb_chunk_min" / "tb_chunk_max" (dealt tiles: rows of the shortest and of the tallest chunk), "tb_fallbacks" (resident intervals that gave up and were redone with
  * one launch per pass); 0 before any sweep.  Of the last deff_solve_cg (0 before one): "cg_kr" (rows per work item),
  * "cg_strips" (strips of 128 columns), "cg_items" (work items per image), "cg_restarts" (true-residual rounds that
  * sent an image back into the iteration) and "cg_impl" (1 = streaming kernels, 2 = on chip); of the last
@@ -363,7 +363,12 @@ int deff_slab_rank_solve_cg(deff_slab_rank *s, double rtol, int64_t max_iter, in
  * out = NULL: only *ntiles (the number of word PAIRS out must hold) is set and the field is left alone.  Otherwise the field
  * ADVANCES: by one pass = T sweeps (deff_get_plan "tb_T"), or by three passes = 3 * T sweeps when the plan is resident
  * ("tb_impl" = 2 and "tb_resident" = 1: the 12 stamps of a resident tile cover three passes).  DEFF_ESTATE, field unchanged,
- * when the sweeps do not resolve to DEFF_KERNEL_MATFREE_TB. */
+ * when the sweeps do not resolve to DEFF_KERNEL_MATFREE_TB.
+ *   A chained streaming plan ("tb_impl" = 1, "tb_chain" = 1) stamps three passes of ONE chained launch: two header words, then
+ * 20 per tile -- start, where it ran, and per pass six clocks (neighbours seen, first row consumed, steady-state loop entered,
+ * last store issued, stores acknowledged, flag published).  The caller sets the header in `out` before the call: out[0] = the
+ * first pass to stamp, out[1] = the passes of the chain (0: out[0] + 3); the field advances by that many passes.
+ * DEFF_EINVAL when so many passes are not one launch. */
 int deff_debug_tb_stamps(deff_ctx *ctx, double omega, unsigned long long *out, int *ntiles);
 
 /* raw device pointers for zero-copy interop (torch tensors, RCCL): current field, and the byte

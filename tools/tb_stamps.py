@@ -11,8 +11,15 @@ sys.path.insert(0, ROOT)
 import effectivediffusivityfvm_amd as pkg  # noqa: E402
 from effectivediffusivityfvm_amd import _capi  # noqa: E402
 
-CHAIN = "--chain" in sys.argv                                       # three chained passes in one launch (k_sweep_matfree_tb_chain)
+CHAIN = "--chain" in sys.argv                                       # chained passes in one launch (k_sweep_matfree_tb_chain)
 sys.argv = [a for a in sys.argv if a != "--chain"]
+# --deep FIRST PASSES: stamp passes FIRST ... FIRST + 2 of a chain of PASSES (default 60 of 150: the steady state of bench.py's
+# launch); --deep 0 3 is the start of a chain
+FIRST, PASSES = 60, 150
+if "--deep" in sys.argv:
+    k = sys.argv.index("--deep")
+    FIRST, PASSES = int(sys.argv[k + 1]), int(sys.argv[k + 2])
+    del sys.argv[k:k + 3]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 with pkg.Solver(n, n) as s:
@@ -30,31 +37,46 @@ with pkg.Solver(n, n) as s:
     s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
     s.init_linear(0.0, 1.0)
     s.sweeps(48)
+    if CHAIN:
+        s.sweeps(3 * 8 * PASSES)                                    # (the clocks of an idle chip: a chain right after start-up ran a fifth slower)
     L = _capi.load()
     nt = C.c_int()
     _capi.check(L.deff_debug_tb_stamps(s._ctx, 2.0 / 3.0, None, C.byref(nt)))
     buf = np.zeros(2 * nt.value, dtype=np.uint64)
+    if CHAIN:
+        buf[0], buf[1] = FIRST, PASSES                               # the header: first pass to stamp, passes of the chain
     _capi.check(L.deff_debug_tb_stamps(s._ctx, 2.0 / 3.0, buf.ctypes.data_as(C.c_void_p), C.byref(nt)))
     if CHAIN:
-        # 8 words per tile: entry, where it ran, then for passes 0..2 {neighbours seen, swept}
+        # two header words, then 20 words per tile: entry, where it ran, then for three passes {neighbours seen, first row
+        # consumed, steady-state loop entered, swept (last store issued), stores acknowledged, flag published}
         assert s.plan_value("tb_chain") == 1 and s.plan_value("tb_fallbacks") == 0, "the plan is not chained"
-        w = buf.reshape(-1, 8)
+        w = buf[2:].reshape(-1, 20)
         w = w[w[:, 0] > 0].astype(np.int64)
         t0 = w[:, 0].min()
-        seen = (w[:, 2::2] - t0) / 100.0                            # [tile, pass]: neighbours seen = the pass starts
-        swept = (w[:, 3::2] - t0) / 100.0                           #               the tile's last row is stored
+        ev = (w[:, 2:].reshape(len(w), 3, 6) - t0) / 100.0          # [tile, pass, event] in us
+        seen, first, steady, swept, acked, pub = (ev[:, :, k] for k in range(6))
         simd = w[:, 1] >> 4
-        print(f"n={n} tiles={len(w)} chained launch of 3 passes, span {swept.max():.1f} us = {swept.max() / 3:.1f} us per pass")
-        for p in range(3):
-            q = np.percentile(swept[:, p], [0, 5, 50, 95, 100])
-            dur = swept[:, p] - seen[:, p]
-            line = f"  pass {p}: swept min {q[0]:6.1f} p5 {q[1]:6.1f} p50 {q[2]:6.1f} p95 {q[3]:6.1f} max {q[4]:6.1f} (spread p95-p5 {q[3] - q[1]:.1f}); sweep time mean {dur.mean():.1f}"
-            if p > 0:
-                wait = seen[:, p] - swept[:, p - 1]                 # stores acknowledged + flag + neighbours' flags seen
-                line += f"; wait before it mean {wait.mean():.2f} p50 {np.median(wait):.2f} p95 {np.percentile(wait, 95):.2f} max {wait.max():.2f}"
-            print(line)
+        print(f"n={n} tiles={len(w)} chained launch of {PASSES} passes, stamped {FIRST}...{FIRST + 2}; pass {FIRST} starts at {seen[:, 0].min():.1f} us")
+        period = np.concatenate([seen[:, 1] - seen[:, 0], seen[:, 2] - seen[:, 1]])
+        print(f"  (a) period (a tile's start of a pass to its start of the next): mean {period.mean():.2f} p5 {np.percentile(period, 5):.2f} p50 {np.median(period):.2f} p95 {np.percentile(period, 95):.2f}")
+        sweep = swept - seen                                        # the whole of tb_strip
+        own = pub[:, :2] - swept[:, :2]                             # stores acknowledged + flag
+        wait = seen[:, 1:] - pub[:, :2]                             # list (unless it came with the acknowledgement) + polls + waiting
+        parts = (("first row (request -> consumed)", first - seen), ("ramp (first row -> steady loop)", steady - first),
+                 ("steady loop", swept - steady), ("sweep = the three", sweep), ("stores acknowledged", acked[:, :2] - swept[:, :2]),
+                 ("flag", pub[:, :2] - acked[:, :2]), ("until neighbours seen", wait))
+        for name, v in parts:
+            print(f"      {name:32s} mean {v.mean():6.2f} p5 {np.percentile(v, 5):6.2f} p50 {np.median(v):6.2f} p95 {np.percentile(v, 95):6.2f} max {v.max():6.2f}")
+        print(f"      sum of the means: sweep {sweep.mean():.2f} + own (acknowledged, flag) {own.mean():.2f} + until seen {wait.mean():.2f} = {sweep.mean() + own.mean() + wait.mean():.2f}")
+        # (b) the slowest tiles: is their own path what the period consists of?
+        slow = np.argsort(sweep.mean(axis=1))[::-1][:max(len(w) // 20, 1)]
+        ws, os_, ss = wait[slow], own[slow], sweep[slow]
+        print(f"  (b) slowest 5 % of tiles by sweep time ({len(slow)}): sweep mean {ss.mean():.2f} min {ss.min():.2f}; own mean {os_.mean():.2f}; until neighbours seen mean {ws.mean():.2f} p50 {np.median(ws):.2f} p95 {np.percentile(ws, 95):.2f} max {ws.max():.2f}")
+        print(f"      their first row {(first - seen)[slow].mean():.2f}, ramp {(steady - first)[slow].mean():.2f}, steady loop {(swept - steady)[slow].mean():.2f}; sweep + own + until seen = {ss.mean() + os_.mean() + ws.mean():.2f} against the period {period.mean():.2f}")
+        fast = np.argsort(sweep.mean(axis=1))[:max(len(w) // 20, 1)]
+        print(f"      fastest 5 %: sweep mean {sweep[fast].mean():.2f}; until neighbours seen mean {wait[fast].mean():.2f}")
         last = np.array([swept[simd == k, 2].max() for k in np.unique(simd)])
-        print(f"  a SIMD's last wave ends pass 2: mean {last.mean():.1f} min {last.min():.1f} max {last.max():.1f} -> SIMD-time idle before the launch ends: {1 - last.mean() / swept.max():.3f} of 3 passes")
+        print(f"  a SIMD's last wave ends pass {FIRST + 2}: mean {last.mean():.1f} min {last.min():.1f} max {last.max():.1f}")
         sys.exit(0)
     st = buf[0::2].astype(np.int64)
     dur_t = (buf[1::2] & np.uint64(0xFFFFFFFF)).astype(np.int64)
