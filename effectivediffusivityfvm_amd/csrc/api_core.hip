@@ -328,6 +328,8 @@ try {
     else if (!strcmp(key, "cgs_intervals")) *value = c->cgs_intervals;
     else if (!strcmp(key, "cgs_launches")) *value = c->cgs_launches;
     else if (!strcmp(key, "cgs_waits")) *value = c->cgs_waits;
+    else if (!strcmp(key, "res_kt")) *value = c->res_plan_kt;
+    else if (!strcmp(key, "res_items")) *value = c->res_plan_items;
     else return fail(DEFF_EINVAL, "unknown plan key '%s'", key);
     return DEFF_OK;
 }

@@ -100,6 +100,7 @@ static int residual_classes(deff_ctx *c, const double *x, const uint8_t *pix, in
     else { if (fast) LAUNCH_RES(3, true); else LAUNCH_RES(3, false); }
 #undef LAUNCH_RES
     HIP_TRY(hipGetLastError());
+    c->res_plan_kt = kt; c->res_plan_items = (int)per_img;       // deff_get_plan "res_kt" / "res_items": what was launched
     return residual_finish(c, per_img, nimg, r, ms);
 }
 
@@ -139,6 +140,7 @@ try {
     hipLaunchKernelGGL(k_residual_plane, dim3((unsigned)(c->rows * segs)), dim3(256), 0, c->stream, c->x[c->cur], dD, c->nx,
                        c->nxt, c->ny, c->nimg, segs, c->dx, c->dy, CL, CR, c->resid);
     HIP_TRY(hipGetLastError());
+    c->res_plan_kt = 0; c->res_plan_items = (int)per_img;        // no runs: one partial sum per row segment
     return residual_finish(c, per_img, c->nimg, r, ms);
 }
 DEFF_API_CATCH

@@ -117,6 +117,9 @@ struct deff_ctx {
     double *resid = nullptr;        // device: partial sums of the residual reduction + one sum per image
     size_t resid_cap = 0;
     int res_kt = 0;                 // tuning: tiles of 8 rows a wave of the residual kernel streams through (0 = planner)
+    // deff_get_plan "res_kt" / "res_items" of the last residual call that launched: the run length the class kernel used
+    // (planner, override and clip applied; 0 for deff_residual_D) and the partial sums k_residual_final adds per image
+    int res_plan_kt = 0, res_plan_items = 0;
 
     // wall data for the flux evaluation
     double *Dl = nullptr, *Dr = nullptr;

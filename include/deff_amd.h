@@ -88,6 +88,8 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  * "tb_impl" (1 streaming, 2 workgroup tiles), "tb_R", "tb_NW" (8 / 12 / 16 waves per
  *   tile: 12 = link-symmetric matrix rows in registers, 16 = tall resident tiles),
  * "cg_onchip" (deff_solve_cg: 1 = images of at most 16 384 cells iterate on one compute unit each, see there),
+ * "res_kt" (deff_residual / deff_residual_slot: tiles of 8 rows one wave streams through, a "run"; 0 = the planner's choice,
+ *   about 4 096 work items per launch; clipped to the image's tile rows; deff_get_plan "res_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
  *   run every pass between two checks in ONE launch, neighbouring tiles synchronised by flags: 1 = one launch per
  *   pass instead; a resident launch that cannot make progress -- another process holds part of the GPU -- gives up
@@ -104,7 +106,11 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * one launch per pass); 0 before any sweep.  Of the last deff_solve_cg (0 before one): "cg_kr" (rows per work item),
  * "cg_strips" (strips of 128 columns), "cg_items" (work items per image), "cg_restarts" (true-residual rounds that
  * sent an image back into the iteration) and "cg_impl" (1 = streaming kernels, 2 = on chip); of the last
- * deff_solve_cg_stream, which also sets the "cg_" keys: "cgs_intervals", "cgs_launches", "cgs_waits" (see there) */
+ * deff_solve_cg_stream, which also sets the "cg_" keys: "cgs_intervals", "cgs_launches", "cgs_waits" (see there).  Of the
+ * last deff_residual / deff_residual_slot / deff_residual_D that launched (0 before one; a refused call leaves them alone):
+ * "res_kt" (tiles of 8 rows per run as used: after the planner, the tuning key and the clip to the image's tile rows;
+ * 0 after deff_residual_D, which has no runs) and "res_items" (partial sums added per image by the final reduction:
+ * strips of 128 columns x ceil(tile rows / res_kt), or for deff_residual_D rows x segments of 256 columns) */
 int deff_get_plan(deff_ctx *ctx, const char *key, int *value);
 
 /* ---- image -> phases: replaces the mask->D loops cuh:1988-2000 (2-phase),
