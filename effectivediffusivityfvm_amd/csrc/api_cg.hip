@@ -1,4 +1,5 @@
-// api_cg.hip -- deff_solve_cg: Jacobi-preconditioned conjugate gradients to a residual tolerance (kernels_cg.hpp), and
+// api_cg.hip -- deff_solve_cg: Jacobi-preconditioned conjugate gradients to a residual tolerance (kernels_cg.hpp; on the
+// explicit coefficient planes for systems without a row dictionary, tuning key "cg_planes": kernels_cg_planes.hpp), and
 // deff_solve_cg_stream: the same solve through the refilled slots of a stack (kernels_cg_stream.hpp, second half); at the end
 // the steps of one row slab of deff_slab_*_solve_cg (kernels_cg_slab.hpp; the loop over the slabs is in api_slab.hip).  Not the
 // reference's algorithm: it reaches the same discrete fixed point (same A, b, wall-flux Deff) as the weighted Jacobi loop of
@@ -6,6 +7,7 @@
 // stay as they are (the "fma" knob does not apply here: CG's arithmetic is written-order FP64 only).
 #include "ctx.hpp"
 #include "kernels_cg.hpp"
+#include "kernels_cg_planes.hpp"
 #include "kernels_cg_image.hpp"
 #include "kernels_cg_stream.hpp"
 #include "kernels_cg_slab.hpp"
@@ -82,6 +84,14 @@ static int cg_buffers(deff_ctx *c, size_t items)
     return DEFF_OK;
 }
 
+// the plane form's own work vectors (kernels_cg_planes.hpp): 1 / a0 per cell and q = A p
+static int cgp_buffers(deff_ctx *c)
+{
+    TRY(dev_alloc(&c->cg_inv, c->n));
+    TRY(dev_alloc(&c->cg_q, c->n));
+    return DEFF_OK;
+}
+
 extern "C" int deff_solve_cg(deff_ctx *c, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out,
                              double *MFL, double *MFR)
 try {
@@ -98,34 +108,55 @@ try {
         return fail(DEFF_EINVAL, "deff_solve_cg: the system links a wall column to the neighbouring row (explicit-only system)");
     TRY(use_device(c));
     TRY(consolidate(c));                                             // every image's newest field in x[cur]
-    if (!c->have_matfree && c->have_explicit) TRY(ensure_dictionary(c));
-    if (!c->have_matfree)
-        return fail(DEFF_EINVAL, "deff_solve_cg: the system has no row dictionary (too many distinct rows, or dictionaries "
-                                 "disabled): CG runs on the matrix-free form only");
+    // the form: the row table, or (tuning "cg_planes") the explicit coefficient planes -- 2 = always, 1 = when the system has no
+    // dictionary after ensure_dictionary has had its try
+    bool planes = c->cg_planes == 2;
+    if (!planes) {
+        if (!c->have_matfree && c->have_explicit) TRY(ensure_dictionary(c));
+        if (!c->have_matfree) {
+            if (c->cg_planes != 1 || !c->have_explicit)
+                return fail(DEFF_EINVAL, "deff_solve_cg: the system has no row dictionary (too many distinct rows, or dictionaries "
+                                         "disabled): CG runs on the matrix-free form only (the tuning key \"cg_planes\" lets it "
+                                         "run on the coefficient planes)");
+            planes = true;
+        }
+    }
     std::vector<double> tab;
-    TRY(cg_table(c, tab));
+    if (planes) TRY(explicit_from_image(c));                         // a native system's planes; nothing to do for any other
+    else TRY(cg_table(c, tab));
     const CgGeom g = cg_geometry(c);
     const size_t items = (size_t)g.per_img * c->nimg;
+    // on chip (tuning "cg_onchip"): an image whose arrays fit one compute unit's LDS and registers iterates there, one
+    // launch per check_every iterations instead of four per iteration; larger images keep the streaming kernels
+    const bool onchip = !planes && c->cg_onchip && (size_t)c->nx * c->ny <= (size_t)CGI_CELLS;
+    if (onchip && !c->cg_cus) HIP_TRY(hipDeviceGetAttribute(&c->cg_cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    TRY(cg_buffers(c, items));
+    if (planes) TRY(cgp_buffers(c));
     c->cg_plan_kr = g.kr;
     c->cg_plan_ntx = g.ntx;
     c->cg_plan_items = (int)g.per_img;
     c->cg_plan_restarts = 0;
-    // on chip (tuning "cg_onchip"): an image whose arrays fit one compute unit's LDS and registers iterates there, one
-    // launch per check_every iterations instead of four per iteration; larger images keep the streaming kernels
-    const bool onchip = c->cg_onchip && (size_t)c->nx * c->ny <= (size_t)CGI_CELLS;
-    c->cg_plan_impl = onchip ? 2 : 1;
-    if (onchip && !c->cg_cus) HIP_TRY(hipDeviceGetAttribute(&c->cg_cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    TRY(cg_buffers(c, items));
-    HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), sizeof(double) * CG_DOUBLES, hipMemcpyHostToDevice, c->stream));
+    c->cg_plan_impl = planes ? 3 : onchip ? 2 : 1;
+    const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, c->b};
 
-    // admissibility: active links symmetric bit for bit, no link out of the image; nothing is changed on a refusal
+    // admissibility: active rows positive and finite (table form: cg_table above), active links symmetric bit for bit, no link
+    // out of the image; nothing is changed on a refusal
     unsigned flags[2] = {0, 0};
     HIP_TRY(hipMemsetAsync(c->cg_flags, 0, sizeof(unsigned) * 2, c->stream));
-    hipLaunchKernelGGL(k_cg_admissible, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code,
-                       c->nx, c->rows, c->ny, c->cg_flags);
+    if (planes)
+        hipLaunchKernelGGL(k_cgp_prepare, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, P, c->nx, c->rows, c->ny, c->cg_inv,
+                           c->cg_flags);
+    else {
+        HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), sizeof(double) * CG_DOUBLES, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_cg_admissible, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code,
+                           c->nx, c->rows, c->ny, c->cg_flags);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(flags, c->cg_flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flags[0] & CGP_FLAG_ROW)
+        return fail(DEFF_EINVAL, "deff_solve_cg: a matrix row is not admissible: an active row needs a finite A0 > 0 and finite "
+                                 "links");
     if (flags[0])
         return fail(DEFF_EINVAL, "deff_solve_cg: the system is not symmetric (a link between two active cells differs from "
                                  "its partner, or an active row links out of its image)");
@@ -137,7 +168,8 @@ try {
     CgScal *sc = (CgScal *)c->cg_scal;
     std::vector<CgScal> hs(c->nimg);
     auto true_residual = [&](int mode, int allow) -> int {
-        hipLaunchKernelGGL(k_cg_resid, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, x, c->cg_r, g, part);
+        if (planes) hipLaunchKernelGGL(k_cgp_resid, grid, dim3(256), 0, c->stream, P, c->cg_inv, x, c->cg_r, g, part);
+        else hipLaunchKernelGGL(k_cg_resid, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, x, c->cg_r, g, part);
         hipLaunchKernelGGL(k_cg_check, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc, tol2, (long long)max_iter, mode,
                            allow, c->cg_flags + 1);
         HIP_TRY(hipGetLastError());
@@ -174,11 +206,19 @@ try {
         }
         for (int64_t i = 0; i < check_every; ++i, ++k) {
             double *p_in = c->cg_p[k & 1], *p_out = c->cg_p[(k + 1) & 1];
-            hipLaunchKernelGGL(k_cg_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->cg_r, p_in, p_out,
-                               sc, g, part);
+            if (planes)
+                hipLaunchKernelGGL(k_cgp_dir, grid, dim3(256), 0, c->stream, P, c->cg_inv, c->cg_r, p_in, p_out, c->cg_q, sc, g,
+                                   part);
+            else
+                hipLaunchKernelGGL(k_cg_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->cg_r, p_in,
+                                   p_out, sc, g, part);
             hipLaunchKernelGGL(k_cg_alpha, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc);
-            hipLaunchKernelGGL(k_cg_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x, c->cg_r,
-                               sc, g, part_rz, part_rr);
+            if (planes)
+                hipLaunchKernelGGL(k_cgp_update, grid, dim3(256), 0, c->stream, c->cg_inv, p_out, c->cg_q, x, c->cg_r, sc, g,
+                                   part_rz, part_rr);
+            else
+                hipLaunchKernelGGL(k_cg_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x,
+                                   c->cg_r, sc, g, part_rz, part_rr);
             hipLaunchKernelGGL(k_cg_beta, fin, dim3(CG_FIN), 0, c->stream, part_rz, part_rr, g.per_img, sc, tol2,
                                (long long)max_iter);
         }

@@ -132,7 +132,7 @@ try {
     if (c->res_flags) (void)hipFree(c->res_flags);
     if (c->res_abort) (void)hipFree(c->res_abort);
     if (c->res_backup) (void)hipFree(c->res_backup);
-    void *cg_bufs[] = {c->cg_r, c->cg_p[0], c->cg_p[1], c->cg_tab, c->cg_part, c->cg_scal, c->cg_flags};
+    void *cg_bufs[] = {c->cg_r, c->cg_p[0], c->cg_p[1], c->cg_tab, c->cg_part, c->cg_scal, c->cg_flags, c->cg_inv, c->cg_q};
     for (void *p : cg_bufs) if (p) (void)hipFree(p);
     if (c->cg_ev0) (void)hipEventDestroy(c->cg_ev0);
     if (c->cg_ev1) (void)hipEventDestroy(c->cg_ev1);
@@ -292,6 +292,12 @@ try {
     else if (!strcmp(key, "cg_onchip")) {
         if (value > 1) return fail(DEFF_EINVAL, "cg_onchip takes 0 (streaming kernels) or 1 (small images iterate on one compute unit each)");
         c->cg_onchip = value;
+    }
+    else if (!strcmp(key, "cg_planes")) {
+        if (value > 2)
+            return fail(DEFF_EINVAL, "cg_planes takes 0 (CG on the row dictionary only), 1 (on the coefficient planes when the system "
+                                     "has no dictionary) or 2 (always on the coefficient planes)");
+        c->cg_planes = value;
     }
     else return fail(DEFF_EINVAL, "unknown tuning key '%s'", key);
     return DEFF_OK;

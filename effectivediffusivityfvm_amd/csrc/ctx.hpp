@@ -243,6 +243,11 @@ struct deff_ctx {
     // 0 (default) = the streaming kernels for every size.  cg_plan_impl: what the last deff_solve_cg ran, 1 streaming, 2 on chip
     int cg_onchip = 0, cg_plan_impl = 0;
     int cg_cus = 0;                              // compute units of the device (workgroups of an on-chip launch)
+    // tuning "cg_planes": deff_solve_cg on the explicit coefficient planes (kernels_cg_planes.hpp; cg_plan_impl 3) -- 1 = for a
+    // system that has no row dictionary, 2 = for every system (tests: the bits are the table form's); 0 (default) = never.
+    // cg_inv (1 / a0 per cell, 0 on decoupled cells) and cg_q (A p) are allocated by the first call that takes that form
+    int cg_planes = 0;
+    double *cg_inv = nullptr, *cg_q = nullptr;
     // deff_solve_cg_stream (api_cg.hip, kernels_cg_stream.hpp), allocated by the first one.  cgs_dev: the round's slot list,
     // the slots' restart rounds, and the staging area -- the entering slots' list followed by their pixels --; cgs_pin: the
     // pinned mirror of the two lists and the pixels, two snapshots of the slots' CgScal + flags, and a round's results

@@ -97,7 +97,8 @@ class Solver:
 
     def plan(self):
         """What the temporally blocked kernel's last launch plan chose (zeros before any sweep), and "cg_impl": the form of
-        the last solve_cg (1 streaming kernels, 2 one image per compute unit: set_tuning("cg_onchip", 1); 0 before one)."""
+        the last solve_cg (1 streaming kernels, 2 one image per compute unit: set_tuning("cg_onchip", 1), 3 on the coefficient
+        planes: set_tuning("cg_planes", 1 or 2); 0 before one)."""
         out = {}
         for key in ("tb_T", "tb_LY", "tb_strips", "tb_chunks_per_image", "tb_blocks", "tb_impl", "tb_R", "tb_NW", "tb_resident", "tb_sym", "tb_ranked", "tb_aged", "cg_impl"):
             v = C.c_int()
@@ -201,7 +202,12 @@ class Solver:
 
     def solve_cg(self, rtol=1e-10, max_iter=1_000_000, check_every=64, fluxes=True):
         """Jacobi-preconditioned conjugate gradients from the current field to ||b - A x|| <= rtol ||b|| (deff_solve_cg):
-        not the reference's algorithm, the same fixed point.  One image: a CGResult; a stack: a list, one per image."""
+        not the reference's algorithm, the same fixed point.  One image: a CGResult; a stack: a list, one per image.
+        A system without a row dictionary (a D plane that varies cell by cell, a caller's set_system, more distinct rows than
+        a dictionary holds, set_tuning("dict", 0)) is refused unless set_tuning("cg_planes", 1) lets the iteration read the
+        explicit coefficient planes; set_tuning("cg_planes", 2) takes that form for every system (the bits of the table
+        form where a dictionary exists).  plan_value("cg_impl") is 3 after such a call.  Explicit-only systems (a wall link
+        into the neighbouring row) and row slabs stay refused."""
         res = (CGResultC * self.nimg)()
         MFL = np.zeros(self.rows)
         MFR = np.zeros(self.rows)

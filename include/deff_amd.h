@@ -88,6 +88,8 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  * "tb_impl" (1 streaming, 2 workgroup tiles), "tb_R", "tb_NW" (8 / 12 / 16 waves per
  *   tile: 12 = link-symmetric matrix rows in registers, 16 = tall resident tiles),
  * "cg_onchip" (deff_solve_cg: 1 = images of at most 16 384 cells iterate on one compute unit each, see there),
+ * "cg_planes" (deff_solve_cg on the explicit coefficient planes: 1 = for a system without a row dictionary, 2 = always;
+ *   values above 2 are DEFF_EINVAL; see there),
  * "res_kt" (deff_residual / deff_residual_slot: tiles of 8 rows one wave streams through, a "run"; 0 = the planner's choice,
  *   about 4 096 work items per launch; clipped to the image's tile rows; deff_get_plan "res_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
@@ -105,7 +107,7 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * passes of a batch run as one resident launch; workgroup tiles only), "tb_chain" (1: the streaming kernel chains its passes), "tb_chunk_min" / "tb_chunk_max" (dealt tiles: rows of the shortest and of the tallest chunk), "tb_fallbacks" (resident intervals that gave up and were redone with
  * one launch per pass); 0 before any sweep.  Of the last deff_solve_cg (0 before one): "cg_kr" (rows per work item),
  * "cg_strips" (strips of 128 columns), "cg_items" (work items per image), "cg_restarts" (true-residual rounds that
- * sent an image back into the iteration) and "cg_impl" (1 = streaming kernels, 2 = on chip); of the last
+ * sent an image back into the iteration) and "cg_impl" (1 = streaming kernels, 2 = on chip, 3 = on the coefficient planes); of the last
  * deff_solve_cg_stream, which also sets the "cg_" keys: "cgs_intervals", "cgs_launches", "cgs_waits" (see there).  Of the
  * last deff_residual / deff_residual_slot / deff_residual_D that launched (0 before one; a refused call leaves them alone):
  * "res_kt" (tiles of 8 rows per run as used: after the planner, the tuning key and the clip to the image's tile rows;
@@ -185,7 +187,21 @@ int deff_solve_batch(deff_ctx *ctx, double omega, double tol, int64_t max_iter, 
  * iterations are then ONE launch, and a stack's images run side by side, one per compute unit.  Larger images keep the
  * streaming kernels.  Same recurrence, stop rules, true-residual rounds and results as above (the dot products are summed
  * in another fixed order, so the bits differ from the streaming form's; they do not depend on check_every or on the
- * stack an image is in).  deff_get_plan "cg_impl" tells which form the last call ran: 1 = streaming, 2 = on chip. */
+ * stack an image is in).  deff_get_plan "cg_impl" tells which form the last call ran: 1 = streaming, 2 = on chip.
+ * Tuning key "cg_planes" (0 default: as above, a system without a row dictionary is refused): the iteration reads the matrix
+ * from the explicit coefficient planes (a0, aW, aE, aS, aN, b per cell) instead of the row codes and the dictionary -- for a
+ * diffusivity that varies cell by cell (deff_assemble_from_D), a caller's own assembly (deff_set_system), more distinct rows
+ * than a dictionary holds, or a context with the tuning key "dict" 0.  1 = when the system has no dictionary after one has
+ * been looked for; a system that has one runs as above ("cg_onchip" included).  2 = for every system: a native system's
+ * planes are built from its image, the dictionary is neither looked for nor touched and "cg_onchip" has no effect; a system
+ * that has a dictionary gives the bits of the table form (same work items, expressions and summation order).  Everything
+ * said above holds for this form -- guess and solution in the field, the stop on the device, results independent of
+ * check_every, the true-residual rounds, rel_residual from the field, decoupled rows at x = 0, an image of a stack solved
+ * as alone -- and the system's admissibility is checked on the device before the field is touched (same refusals).
+ * deff_get_plan "cg_impl" = 3; "cg_kr", "cg_strips", "cg_items", "cg_restarts" keep their meaning.  The planes, the row
+ * dictionary and every plan of the Jacobi path are left as they are.  Still refused whatever the key: explicit-only systems
+ * (a wall link into the neighbouring row) and row-slab contexts; the key has no effect on deff_slab_*_solve_cg (a slab's
+ * system needs a dictionary) nor on deff_solve_cg_stream (a native 2-phase system always has one). */
 typedef struct deff_cg_result {
     int64_t iters;         /* CG iterations of this image */
     double  rel_residual;  /* ||b - A x||_2 / ||b||_2 of the returned field, recomputed from x */

@@ -32,6 +32,16 @@ slabs4096     bench4096's image and rtol: one context (deff_solve_cg) against 1,
               (deff_slab_group_solve_cg), the four forms alternating, --runs rounds; iterations to rtol, loop_ms, time per
               iteration.  One slab = what the slab kernels cost; 2 and 4 = the exchange and the gathers per iteration
   python tools/measure_cg.py --cases slabs4096 --runs 2 --out profiles/cg_slabs_results.json
+planes_iter    the plane form ("cg_planes", kernels_cg_planes.hpp) per iteration at 1024^2 and 4096^2, a fixed number of iterations
+              (rtol 0): a diffusivity drawn cell by cell (uniform 0.5 ... 2, assemble_from_D, key 1) and the native benchmark
+              image under key 2 next to key 0 in the same process, alternating, --runs times; against the bytes models
+              (136 B/cell on planes, 68 B/cell on the table) at 4.7 and 6.3 TB/s
+planes_to_rtol the per-cell D at 1024^2 to --rtol on planes, next to what such a system could do before: deff_solve on the
+              explicit kernel to tol 1e-6
+planes_profile the per-kernel split of the 4096^2 per-cell-D run: a `rocprofv3 --kernel-trace --stats` run of its own (a child
+              process); --stats-out keeps the table
+  python tools/measure_cg.py --cases planes_iter,planes_to_rtol,planes_profile --out profiles/cg_planes_results.json \
+                             --stats-out profiles/cg_planes_kernel_stats.csv
 The bytes model of one iteration is 68 B/cell; "model_us" is that traffic at 6.3 TB/s."""
 import argparse
 import json
@@ -393,6 +403,99 @@ def stream_driver(rtol, runs, images):
     return out
 
 
+PLANES_BYTES_PER_CELL = 136                                    # k_cgp_dir 80 + k_cgp_update 56 ("Planes")
+STREAM_TBS = (4.7, 6.3)                                         # the chip's measured read/write stream rates
+
+
+def planes_row(r, cells, bytes_per_cell):
+    per_it_us = 1e3 * r.loop_ms / max(1, r.iters)
+    model = {f"{t}": cells * bytes_per_cell / (t * 1e12) * 1e6 for t in STREAM_TBS}
+    return {"iters": int(r.iters), "loop_ms": r.loop_ms, "per_iter_us": per_it_us, "bytes_per_cell_model": bytes_per_cell,
+            "model_us_at_TBs": model, "per_iter_over_model": {t: per_it_us / v for t, v in model.items()},
+            "achieved_TBs_of_model_bytes": cells * bytes_per_cell / (per_it_us * 1e-6) / 1e12}
+
+
+def per_cell_D(n):
+    return np.random.default_rng(n).uniform(0.5, 2.0, (n, n))
+
+
+def planes_iter(runs, sizes=(1024, 4096)):
+    out = {}
+    for n in sizes:
+        iters = 400 if n <= 1024 else 100
+        rows = {"per_cell_D_planes": [], "native_table": [], "native_planes": []}
+        with pkg.Solver(n, n) as s:
+            s.set_tuning("cg_planes", 1)
+            s.assemble_from_D(per_cell_D(n), 0.0, 1.0)
+            for _ in range(runs + 1):                                # the first run allocates and warms up
+                s.init_linear(0.0, 1.0)
+                r = s.solve_cg(rtol=0.0, max_iter=iters, check_every=iters, fluxes=False)
+                assert s.plan_value("cg_impl") == 3 and r.iters == iters
+                rows["per_cell_D_planes"].append(planes_row(r, n * n, PLANES_BYTES_PER_CELL))
+        with pkg.Solver(n, n) as s:
+            s.synth_image(12345, 0)
+            s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+            for _ in range(runs + 1):
+                for key, name in ((0, "native_table"), (2, "native_planes")):
+                    s.set_tuning("cg_planes", key)
+                    s.init_linear(0.0, 1.0)
+                    r = s.solve_cg(rtol=0.0, max_iter=iters, check_every=iters, fluxes=False)
+                    assert s.plan_value("cg_impl") == (3 if key else 1) and r.iters == iters
+                    rows[name].append(planes_row(r, n * n, PLANES_BYTES_PER_CELL if key else BYTES_PER_CELL))
+        best = {k: min(x["per_iter_us"] for x in v[1:]) for k, v in rows.items()}
+        out[f"{n}x{n}"] = {"iterations_per_run": iters, "runs": {k: v[1:] for k, v in rows.items()}, "per_iter_us_best": best,
+                           "planes_over_table_native": best["native_planes"] / best["native_table"]}
+    return out
+
+
+def planes_to_rtol(rtol, max_iter, n=1024):
+    D = per_cell_D(n)
+    out = {"mesh": [n, n], "rtol": rtol}
+    with pkg.Solver(n, n) as s:
+        s.set_tuning("cg_planes", 1)
+        s.assemble_from_D(D, 0.0, 1.0)
+        for _ in range(2):
+            s.init_linear(0.0, 1.0)
+            t0 = time.perf_counter()
+            r = s.solve_cg(rtol=rtol, max_iter=max_iter, fluxes=False)
+            wall = time.perf_counter() - t0
+        assert s.plan_value("cg_impl") == 3
+        out["cg_planes"] = {**planes_row(r, n * n, PLANES_BYTES_PER_CELL), "rel_residual": r.rel_residual,
+                            "converged": bool(r.converged), "deff_raw": r.deff_raw, "wall_s": wall}
+        s.init_linear(0.0, 1.0)
+        t0 = time.perf_counter()
+        rj = s.solve(1e-6, 5_000_000)
+        out["jacobi_explicit_tol_1e-6"] = {"kernel": s.kernel_in_use(), "sweeps": rj.iters, "deff_raw": rj.deff_raw,
+                                           "loop_ms": rj.loop_ms, "wall_s": time.perf_counter() - t0,
+                                           "rel_residual_of_its_field": float(s.residual(D, 0.0, 1.0))}
+        out["deff_gap_jacobi_to_cg"] = abs(rj.deff_raw - r.deff_raw) / abs(r.deff_raw)
+        out["jacobi_loop_ms_over_cg_loop_ms"] = rj.loop_ms / r.loop_ms
+    return out
+
+
+def planes_profile(stats_out):
+    """The per-kernel split of the plane form at 4096^2 (per-cell D): one child process under rocprofv3 --kernel-trace --stats."""
+    import csv
+    import glob
+    with tempfile.TemporaryDirectory() as d:
+        run = os.path.join(d, "run.json")
+        p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(d, "prof"), "-o", "run", "--",
+                            sys.executable, os.path.abspath(__file__), "--cases", "planes_iter", "--runs", "1", "--only-planes-4096",
+                            "--out", run], capture_output=True, text=True, timeout=900)
+        if p.returncode != 0 or not os.path.exists(run):
+            return {"error": (p.stderr or p.stdout)[-1500:]}
+        files = glob.glob(os.path.join(d, "prof", "**", "*kernel_stats*.csv"), recursive=True)
+        if not files:
+            return {"error": "no kernel stats written"}
+        out = {"kernels": {}}
+        for k in csv.DictReader(open(files[0])):
+            out["kernels"][k["Name"].split("(")[0]] = {"calls": int(k["Calls"]), "total_ms": float(k["TotalDurationNs"]) / 1e6,
+                                                       "average_us": float(k["AverageNs"]) / 1e3, "percent": float(k["Percentage"])}
+        if stats_out:
+            shutil.copy(files[0], stats_out)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="config1,config2,bench4096,stack16x1024,shipped00042")
@@ -404,6 +507,8 @@ def main():
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--only-onchip", action="store_true")
     ap.add_argument("--only-stream", action="store_true")
+    ap.add_argument("--only-planes-4096", action="store_true")
+    ap.add_argument("--stats-out", default=None, help="planes_profile: where the kernel-stats table is kept")
     ap.add_argument("--per-iter-us", type=float, default=11.1, help="k_cg_image per iteration (onchip_profile), for the CU-busy share")
     a = ap.parse_args()
     jac = not a.no_jacobi
@@ -434,6 +539,12 @@ def main():
             out[case] = stream_library(a.rtol, a.max_iter, a.runs, a.images, a.per_iter_us, a.only_stream)
         elif case == "slabs4096":
             out[case] = slabs4096(a.rtol, a.max_iter, a.runs)
+        elif case == "planes_iter":
+            out[case] = planes_iter(a.runs, (4096,) if a.only_planes_4096 else (1024, 4096))
+        elif case == "planes_to_rtol":
+            out[case] = planes_to_rtol(a.rtol, a.max_iter)
+        elif case == "planes_profile":
+            out[case] = planes_profile(a.stats_out)
         elif case == "stream_profile":
             out[case] = stream_profile(a.rtol, a.images)
         elif case == "stream_driver":
