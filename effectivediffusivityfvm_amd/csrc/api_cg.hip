@@ -8,6 +8,7 @@
 #include "ctx.hpp"
 #include "kernels_cg.hpp"
 #include "kernels_cg_planes.hpp"
+#include "kernels_cg_fold.hpp"
 #include "kernels_cg_image.hpp"
 #include "kernels_cg_stream.hpp"
 #include "kernels_cg_slab.hpp"
@@ -81,6 +82,13 @@ static int cg_buffers(deff_ctx *c, size_t items)
         HIP_TRY(hipMalloc((void **)&c->cg_part, sizeof(double) * 3 * items));
         c->cg_part_cap = 3 * items;
     }
+    // arrival counters of the folded launches ("cg_fold"): one set for the direction launch, one for the update launch
+    const size_t ticks = 2 * cgf_ticks((unsigned)(items / std::max(1, c->nimg)), (size_t)c->nimg);
+    if (c->cg_tick_cap < ticks) {
+        if (c->cg_tick) { HIP_TRY(hipFree(c->cg_tick)); c->cg_tick = nullptr; c->cg_tick_cap = 0; }
+        HIP_TRY(hipMalloc((void **)&c->cg_tick, sizeof(unsigned) * ticks));
+        c->cg_tick_cap = ticks;
+    }
     return DEFF_OK;
 }
 
@@ -137,12 +145,17 @@ try {
     c->cg_plan_items = (int)g.per_img;
     c->cg_plan_restarts = 0;
     c->cg_plan_impl = planes ? 3 : onchip ? 2 : 1;
+    // two launches per iteration (tuning "cg_fold", kernels_cg_fold.hpp); the plane form's direction kernel loads ahead already
+    const int fold = onchip ? 0 : (planes && c->cg_fold == 2) ? 1 : c->cg_fold;
+    c->cg_plan_fold = fold;
     const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, c->b};
 
     // admissibility: active rows positive and finite (table form: cg_table above), active links symmetric bit for bit, no link
     // out of the image; nothing is changed on a refusal
     unsigned flags[2] = {0, 0};
     HIP_TRY(hipMemsetAsync(c->cg_flags, 0, sizeof(unsigned) * 2, c->stream));
+    // the counters start every call at 0: the last arriver's reset alone would not do after a call that ended early
+    HIP_TRY(hipMemsetAsync(c->cg_tick, 0, sizeof(unsigned) * 2 * cgf_ticks(g.per_img, (size_t)c->nimg), c->stream));
     if (planes)
         hipLaunchKernelGGL(k_cgp_prepare, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, P, c->nx, c->rows, c->ny, c->cg_inv,
                            c->cg_flags);
@@ -166,6 +179,7 @@ try {
     double *x = c->x[c->cur];
     double *part = c->cg_part, *part_rz = c->cg_part + items, *part_rr = c->cg_part + 2 * items;
     CgScal *sc = (CgScal *)c->cg_scal;
+    unsigned *tick_a = c->cg_tick, *tick_b = c->cg_tick + cgf_ticks(g.per_img, (size_t)c->nimg);
     std::vector<CgScal> hs(c->nimg);
     auto true_residual = [&](int mode, int allow) -> int {
         if (planes) hipLaunchKernelGGL(k_cgp_resid, grid, dim3(256), 0, c->stream, P, c->cg_inv, x, c->cg_r, g, part);
@@ -206,6 +220,20 @@ try {
         }
         for (int64_t i = 0; i < check_every; ++i, ++k) {
             double *p_in = c->cg_p[k & 1], *p_out = c->cg_p[(k + 1) & 1];
+            if (fold) {
+                if (planes) {
+                    hipLaunchKernelGGL(k_cgpf_dir, grid, dim3(256), 0, c->stream, P, c->cg_inv, c->cg_r, p_in, p_out, c->cg_q, sc,
+                                       g, part, tick_a);
+                    hipLaunchKernelGGL(k_cgpf_update, grid, dim3(256), 0, c->stream, c->cg_inv, p_out, c->cg_q, x, c->cg_r, sc, g,
+                                       part_rz, part_rr, tol2, (long long)max_iter, tick_b);
+                } else {
+                    hipLaunchKernelGGL(fold == 2 ? k_cgf_dir2 : k_cgf_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows,
+                                       c->code, c->cg_r, p_in, p_out, sc, g, part, tick_a);
+                    hipLaunchKernelGGL(k_cgf_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x,
+                                       c->cg_r, sc, g, part_rz, part_rr, tol2, (long long)max_iter, tick_b);
+                }
+                continue;
+            }
             if (planes)
                 hipLaunchKernelGGL(k_cgp_dir, grid, dim3(256), 0, c->stream, P, c->cg_inv, c->cg_r, p_in, p_out, c->cg_q, sc, g,
                                    part);
@@ -369,6 +397,8 @@ try {
     c->cg_plan_restarts = 0;
     const bool onchip = c->cg_onchip && (size_t)c->nx * c->ny <= (size_t)CGI_CELLS;
     c->cg_plan_impl = onchip ? 2 : 1;
+    const int fold = onchip ? 0 : c->cg_fold;
+    c->cg_plan_fold = fold;
     if (onchip && !c->cg_cus) HIP_TRY(hipDeviceGetAttribute(&c->cg_cus, hipDeviceAttributeMultiprocessorCount, c->device));
     TRY(cg_buffers(c, items));
     CgsBuffers bf;
@@ -393,6 +423,7 @@ try {
     HIP_TRY(hipMemcpyAsync(sc, bf.h_snap[0], sizeof(CgScal) * B, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(bf.d_rounds, 0, sizeof(int) * B, c->stream));
     HIP_TRY(hipMemsetAsync(c->cg_flags, 0, sizeof(unsigned) * 2, c->stream));
+    HIP_TRY(hipMemsetAsync(c->cg_tick, 0, sizeof(unsigned) * 2 * cgf_ticks(g.per_img, (size_t)B), c->stream));
     HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), sizeof(double) * CG_DOUBLES, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));                        // h_snap[0] is a snapshot buffer from here on
     ++waits;
@@ -452,6 +483,14 @@ try {
         } else {
             for (int64_t q = 0; q < check_every; ++q, ++k_it) {
                 double *p_in = c->cg_p[k_it & 1], *p_out = c->cg_p[(k_it + 1) & 1];
+                if (fold) {
+                    hipLaunchKernelGGL(fold == 2 ? k_cgf_dir2 : k_cgf_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows,
+                                       c->code, c->cg_r, p_in, p_out, sc, g, part, c->cg_tick);
+                    hipLaunchKernelGGL(k_cgf_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x,
+                                       c->cg_r, sc, g, part_rz, part_rr, tol2, (long long)max_iter,
+                                       c->cg_tick + cgf_ticks(g.per_img, (size_t)B));
+                    continue;
+                }
                 hipLaunchKernelGGL(k_cg_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->cg_r, p_in, p_out,
                                    sc, g, part);
                 hipLaunchKernelGGL(k_cg_alpha, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc);
@@ -460,7 +499,7 @@ try {
                 hipLaunchKernelGGL(k_cg_beta, fin, dim3(CG_FIN), 0, c->stream, part_rz, part_rr, g.per_img, sc, tol2,
                                    (long long)max_iter);
             }
-            launches += 4 * check_every;
+            launches += (fold ? 2 : 4) * check_every;
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(bf.h_snap[i & 1], sc, sizeof(CgScal) * B, hipMemcpyDeviceToHost, c->stream));
@@ -598,6 +637,7 @@ void slcg_commit(CgSlab *s)
     c->cg_plan_items = (int)s->items;
     c->cg_plan_restarts = 0;
     c->cg_plan_impl = 1;
+    c->cg_plan_fold = 0;                                             // row slabs: the gathers are a reduction of their own
 }
 
 int slcg_dir(CgSlab *s)

@@ -132,7 +132,7 @@ try {
     if (c->res_flags) (void)hipFree(c->res_flags);
     if (c->res_abort) (void)hipFree(c->res_abort);
     if (c->res_backup) (void)hipFree(c->res_backup);
-    void *cg_bufs[] = {c->cg_r, c->cg_p[0], c->cg_p[1], c->cg_tab, c->cg_part, c->cg_scal, c->cg_flags, c->cg_inv, c->cg_q};
+    void *cg_bufs[] = {c->cg_r, c->cg_p[0], c->cg_p[1], c->cg_tab, c->cg_part, c->cg_scal, c->cg_flags, c->cg_inv, c->cg_q, c->cg_tick};
     for (void *p : cg_bufs) if (p) (void)hipFree(p);
     if (c->cg_ev0) (void)hipEventDestroy(c->cg_ev0);
     if (c->cg_ev1) (void)hipEventDestroy(c->cg_ev1);
@@ -299,6 +299,12 @@ try {
                                      "has no dictionary) or 2 (always on the coefficient planes)");
         c->cg_planes = value;
     }
+    else if (!strcmp(key, "cg_fold")) {
+        if (value > 2)
+            return fail(DEFF_EINVAL, "cg_fold takes 0 (four launches per CG iteration), 1 (two: the per-image sums are taken by the "
+                                     "last workgroup to arrive) or 2 (as 1, the direction kernel loads a row ahead)");
+        c->cg_fold = value;
+    }
     else return fail(DEFF_EINVAL, "unknown tuning key '%s'", key);
     return DEFF_OK;
 }
@@ -331,6 +337,7 @@ try {
     else if (!strcmp(key, "cg_items")) *value = c->cg_plan_items;
     else if (!strcmp(key, "cg_restarts")) *value = c->cg_plan_restarts;
     else if (!strcmp(key, "cg_impl")) *value = c->cg_plan_impl;
+    else if (!strcmp(key, "cg_fold")) *value = c->cg_plan_fold;
     else if (!strcmp(key, "cgs_intervals")) *value = c->cgs_intervals;
     else if (!strcmp(key, "cgs_launches")) *value = c->cgs_launches;
     else if (!strcmp(key, "cgs_waits")) *value = c->cgs_waits;

@@ -248,6 +248,13 @@ struct deff_ctx {
     // cg_inv (1 / a0 per cell, 0 on decoupled cells) and cg_q (A p) are allocated by the first call that takes that form
     int cg_planes = 0;
     double *cg_inv = nullptr, *cg_q = nullptr;
+    // tuning "cg_fold": 1 = an iteration of the streaming forms is two launches, the image's last workgroup to arrive does what
+    // k_cg_alpha / k_cg_beta do (kernels_cg_fold.hpp); 2 = as 1, the table form's direction kernel with loads a row ahead;
+    // 0 (default) = four launches.  cg_plan_fold: what the last CG call ran.  cg_tick: the arrival counters of the two folded
+    // launches, per image its own and one per shard of items (kernels_cg_fold.hpp)
+    int cg_fold = 0, cg_plan_fold = 0;
+    unsigned *cg_tick = nullptr;
+    size_t cg_tick_cap = 0;
     // deff_solve_cg_stream (api_cg.hip, kernels_cg_stream.hpp), allocated by the first one.  cgs_dev: the round's slot list,
     // the slots' restart rounds, and the staging area -- the entering slots' list followed by their pixels --; cgs_pin: the
     // pinned mirror of the two lists and the pixels, two snapshots of the slots' CgScal + flags, and a round's results

@@ -124,6 +124,7 @@ static double g_cg_rtol = 1e-10;   // --cg-rtol
 static int g_cg_batch = 0;         // --cg-batch B: 2-phase batch mode solves runs of up to B equally sized images in one stack
 static bool g_cg_slabs = false;    // --cg-slabs: --solver cg on row slabs (deff_slab_group_solve_cg)
 static int g_cg_stream = 0;        // --cg-stream B: ... keeps B slots full instead (deff_solve_cg_stream)
+static int g_cg_fold = 0;          // --cg-fold N: the tuning key "cg_fold" of every context that runs CG
 
 struct Session {                   // one solver context, re-created only when the mesh / batch size changes
     deff_ctx *ctx = nullptr;
@@ -136,6 +137,7 @@ struct Session {                   // one solver context, re-created only when t
         ctx = nullptr;
         CK(deff_create_batch(device, nx_, ny_, nimg_, &ctx));
         CK(deff_set_tuning(ctx, "fma", g_contracted));
+        if (g_solver_cg) CK(deff_set_tuning(ctx, "cg_fold", g_cg_fold));
         nx = nx_; ny = ny_; nimg = nimg_;
         return true;
     }
@@ -716,7 +718,7 @@ int main(int argc, char **argv)
     int device = 0, batch_size = 0;
     std::vector<int> devices;
     std::string progress_path;
-    bool cg_batch_given = false, cg_stream_given = false;
+    bool cg_batch_given = false, cg_stream_given = false, cg_fold_given = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         if (s == "--device" && a + 1 < argc) device = std::atoi(argv[++a]);
@@ -769,15 +771,28 @@ int main(int argc, char **argv)
             g_cg_stream = (int)v;
             cg_stream_given = true;
         }
+        else if (s == "--cg-fold" && a + 1 < argc) {
+            char *end = nullptr;
+            const long v = std::strtol(argv[++a], &end, 10);
+            if (end == argv[a] || *end || v < 0 || v > 2) {
+                std::fprintf(stderr, "deff2d: --cg-fold N (0, 1 or 2)\n");
+                return 2;
+            }
+            g_cg_fold = (int)v;
+            cg_fold_given = true;
+        }
         else if (s == "--cg-slabs") g_cg_slabs = true;
         else if (s == "-h" || s == "--help") {
-            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B] [--cg-stream B] [--cg-slabs]\n"
+            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B] [--cg-stream B] [--cg-slabs] [--cg-fold N]\n"
                         "--cg-slabs (with --solver cg, RunBatch 0 and --devices a,b,...): conjugate gradients over the row slabs; the dot\n"
                         "products are summed slab by slab, so the result agrees with the one-GPU solve to rounding, not bit for bit.\n"
                         "--cg-batch B (with --solver cg, RunBatch 1, 2 phases): runs of up to B consecutive, equally sized images are solved\n"
                         "together in one stack, an image of at most 16 384 cells on one compute unit each; 0 (default) = one image at a time.\n"
                         "--cg-stream B (with --solver cg, RunBatch 1, 2 phases; not with --cg-batch): B slots are kept full instead -- a slot\n"
                         "whose image has converged is refilled with the next image of its size while the others go on iterating.\n"
+                        "--cg-fold N (with --solver cg): 1 = an iteration of the streaming CG kernels is two launches instead of four, the\n"
+                        "per-image sums are taken by the last workgroup to arrive; 2 = as 1, the direction kernel loads a row ahead; 0\n"
+                        "(default) = four launches.  The same results bit for bit; no effect on chip (--cg-batch) and on row slabs.\n"
                         "The Time column (seconds of device time, hipEvent): RunBatch 0 -- the solve loops of the image (3 phases: the final\n"
                         "stage only, as the reference's JacobiGPUPreCond adds nothing to it); RunBatch 1, 2 phases -- the time from the\n"
                         "start of the image's stream of slots to the check that retired the image, so it grows along a stream;\n"
@@ -792,6 +807,10 @@ int main(int argc, char **argv)
     }
     if (cg_stream_given && !g_solver_cg) {
         std::fprintf(stderr, "deff2d: --cg-stream needs --solver cg\n");
+        return 2;
+    }
+    if (cg_fold_given && !g_solver_cg) {
+        std::fprintf(stderr, "deff2d: --cg-fold needs --solver cg\n");
         return 2;
     }
     if (g_cg_slabs && !g_solver_cg) {
@@ -894,7 +913,8 @@ int main(int argc, char **argv)
             }
             if (deff_create_batch(dev, nx, ny, slots, &st.ctx) != DEFF_OK ||
                 deff_set_tuning(st.ctx, "fma", g_contracted) != DEFF_OK ||
-                (cg && deff_set_tuning(st.ctx, "cg_onchip", 1) != DEFF_OK)) {
+                (cg && deff_set_tuning(st.ctx, "cg_onchip", 1) != DEFF_OK) ||
+                (cg && deff_set_tuning(st.ctx, "cg_fold", g_cg_fold) != DEFF_OK)) {
                 std::fprintf(stderr, "deff2d: %s\n", deff_last_error());
                 deff_destroy(st.ctx);
                 st.ctx = nullptr;

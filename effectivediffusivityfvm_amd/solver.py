@@ -207,7 +207,10 @@ class Solver:
         a dictionary holds, set_tuning("dict", 0)) is refused unless set_tuning("cg_planes", 1) lets the iteration read the
         explicit coefficient planes; set_tuning("cg_planes", 2) takes that form for every system (the bits of the table
         form where a dictionary exists).  plan_value("cg_impl") is 3 after such a call.  Explicit-only systems (a wall link
-        into the neighbouring row) and row slabs stay refused."""
+        into the neighbouring row) and row slabs stay refused.
+        set_tuning("cg_fold", 1) makes an iteration of the streaming forms (cg_impl 1 and 3) two launches instead of four: the
+        per-image sums are taken by the last workgroup to arrive; 2 also lets the table form's direction kernel load a row
+        ahead.  The results are those of 0 bit for bit; plan_value("cg_fold") is what the last call ran (0 on chip)."""
         res = (CGResultC * self.nimg)()
         MFL = np.zeros(self.rows)
         MFR = np.zeros(self.rows)
@@ -282,7 +285,9 @@ class Solver:
         """solve_stream with conjugate gradients (deff_solve_cg_stream): every image of the iterable is solved to
         ||b - A x|| <= rtol ||b|| from the linear guess, exactly as a one-image solve_cg would, in whichever slot is free.
         Returns a list with one CGResult per image, in input order, with .slot (plus .field when want_fields; MFL / MFR are
-        None).  Afterwards slot k of the context holds the last image that ran in it, with its final field."""
+        None).  Afterwards slot k of the context holds the last image that ran in it, with its final field.
+        With set_tuning("cg_fold", 1 or 2) the streaming kernels run two launches per iteration, as in solve_cg (the same
+        bits; plan_value("cgs_launches") drops by two per enqueued iteration); images that iterate on chip are not affected."""
         it = iter(images)
         H, W = self.ny // ampY, self.nx // ampX
         results = {}

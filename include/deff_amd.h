@@ -90,6 +90,8 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  * "cg_onchip" (deff_solve_cg: 1 = images of at most 16 384 cells iterate on one compute unit each, see there),
  * "cg_planes" (deff_solve_cg on the explicit coefficient planes: 1 = for a system without a row dictionary, 2 = always;
  *   values above 2 are DEFF_EINVAL; see there),
+ * "cg_fold" (deff_solve_cg / deff_solve_cg_stream: 1 = two launches per iteration instead of four, 2 = as 1 with loads a row
+ *   ahead; values above 2 are DEFF_EINVAL; see deff_solve_cg),
  * "res_kt" (deff_residual / deff_residual_slot: tiles of 8 rows one wave streams through, a "run"; 0 = the planner's choice,
  *   about 4 096 work items per launch; clipped to the image's tile rows; deff_get_plan "res_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
@@ -107,7 +109,8 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * passes of a batch run as one resident launch; workgroup tiles only), "tb_chain" (1: the streaming kernel chains its passes), "tb_chunk_min" / "tb_chunk_max" (dealt tiles: rows of the shortest and of the tallest chunk), "tb_fallbacks" (resident intervals that gave up and were redone with
  * one launch per pass); 0 before any sweep.  Of the last deff_solve_cg (0 before one): "cg_kr" (rows per work item),
  * "cg_strips" (strips of 128 columns), "cg_items" (work items per image), "cg_restarts" (true-residual rounds that
- * sent an image back into the iteration) and "cg_impl" (1 = streaming kernels, 2 = on chip, 3 = on the coefficient planes); of the last
+ * sent an image back into the iteration), "cg_impl" (1 = streaming kernels, 2 = on chip, 3 = on the coefficient planes) and
+ * "cg_fold" (the fold the call ran: 0, 1 or 2, see the tuning key); of the last
  * deff_solve_cg_stream, which also sets the "cg_" keys: "cgs_intervals", "cgs_launches", "cgs_waits" (see there).  Of the
  * last deff_residual / deff_residual_slot / deff_residual_D that launched (0 before one; a refused call leaves them alone):
  * "res_kt" (tiles of 8 rows per run as used: after the planner, the tuning key and the clip to the image's tile rows;
@@ -201,7 +204,19 @@ int deff_solve_batch(deff_ctx *ctx, double omega, double tol, int64_t max_iter, 
  * deff_get_plan "cg_impl" = 3; "cg_kr", "cg_strips", "cg_items", "cg_restarts" keep their meaning.  The planes, the row
  * dictionary and every plan of the Jacobi path are left as they are.  Still refused whatever the key: explicit-only systems
  * (a wall link into the neighbouring row) and row-slab contexts; the key has no effect on deff_slab_*_solve_cg (a slab's
- * system needs a dictionary) nor on deff_solve_cg_stream (a native 2-phase system always has one). */
+ * system needs a dictionary) nor on deff_solve_cg_stream (a native 2-phase system always has one).
+ * Tuning key "cg_fold" (0 default: four launches per iteration -- two that stream over the field, two that run one
+ * workgroup per image to add its partial sums and set alpha / beta and the stop flags): 1 = two launches per iteration.
+ * Every work item counts itself in when its partial sum is stored, and the last workgroup to arrive for an image adds the
+ * image's partial sums, in the order the separate launch adds them, and does that launch's step; no workgroup waits for
+ * another.  2 = as 1, and the table form's direction kernel keeps the loads of a row ahead in flight (on the coefficient
+ * planes 2 means 1: that kernel loads ahead already).  Values above 2 are DEFF_EINVAL.  The results are those of 0 bit for
+ * bit -- fields, iteration counts, rel_residual, converged, deff_raw, the wall fluxes, "cg_kr", "cg_strips", "cg_items",
+ * "cg_restarts" -- for every system, stack and check_every.  The key applies to the streaming kernels of deff_solve_cg
+ * ("cg_impl" 1 and 3, plain and stack contexts) and of deff_solve_cg_stream, whose "cgs_launches" drops by two per enqueued
+ * iteration; it has no effect on the on-chip form ("cg_impl" 2) nor on row slabs (deff_slab_*_solve_cg: their gathers are
+ * a reduction of their own).  The start of a call and the true-residual rounds keep their own launches.
+ * deff_get_plan "cg_fold" tells what the last CG call ran: 0, 1 or 2; 0 when it ran on chip, and before any call. */
 typedef struct deff_cg_result {
     int64_t iters;         /* CG iterations of this image */
     double  rel_residual;  /* ||b - A x||_2 / ||b||_2 of the returned field, recomputed from x */

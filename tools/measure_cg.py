@@ -42,6 +42,13 @@ planes_profile the per-kernel split of the 4096^2 per-cell-D run: a `rocprofv3 -
               process); --stats-out keeps the table
   python tools/measure_cg.py --cases planes_iter,planes_to_rtol,planes_profile --out profiles/cg_planes_results.json \
                              --stats-out profiles/cg_planes_kernel_stats.csv
+fold_iter      the tuning key "cg_fold" (kernels_cg_fold.hpp) per iteration: keys 0 / 1 / 2 alternating in one process on one
+              context, a fixed number of iterations at rtol 0, --runs times each, best and spread; 00000.jpg 128^2, synthetic
+              1024^2 and 4096^2, the 16 x 1024^2 stack, a per-cell D at 1024^2 on planes (keys 0 / 1), 00042.jpg's final stage
+fold_profile   the per-kernel split of keys 0 / 1 / 2 at 1024^2 and at 4096^2: one `rocprofv3 --kernel-trace --stats` run of its
+              own per size (child processes); --stats-out keeps the two tables in one file
+  python tools/measure_cg.py --cases fold_iter,fold_profile --out profiles/cg_fold_results.json \
+                             --stats-out profiles/cg_fold_kernel_stats.csv
 The bytes model of one iteration is 68 B/cell; "model_us" is that traffic at 6.3 TB/s."""
 import argparse
 import json
@@ -496,6 +503,103 @@ def planes_profile(stats_out):
     return out
 
 
+def fold_workloads(only=None):
+    """(name, cells, bytes per cell of the model, iterations per run, keys, context with its system assembled)"""
+    def synth(n, nimg=1):
+        s = pkg.Solver(n, n, nimg=nimg)
+        s.synth_image(12345, 0)
+        s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+        return s
+
+    def config1_image():
+        pix = np.load(os.path.join(ROOT, "tests", "golden", "img00000_pix_stb.npy"))
+        s = pkg.Solver(pix.shape[1], pix.shape[0])
+        s.set_image(pix)
+        s.assemble_2phase(1e-3, 1.0, 0.0, 1.0)
+        return s
+
+    def per_cell(n):
+        s = pkg.Solver(n, n)
+        s.set_tuning("cg_planes", 1)
+        s.assemble_from_D(per_cell_D(n), 0.0, 1.0)
+        return s
+
+    def shipped_final_stage():
+        pix = pkg.load_jpeg_gray(os.path.join(ROOT, "tests", "golden", "00042.jpg"))
+        grid, _ = pkg.flood_fill((pix > 200).astype(np.uint32))
+        s = pkg.Solver(pix.shape[1], pix.shape[0])
+        s.set_image(pix)
+        s.assemble_3phase(0.0, 1.0, 1237500.0, 0.0, 1.0, grid)
+        return s
+
+    table = [("config1_128", 2000, (0, 1, 2), BYTES_PER_CELL, config1_image),
+             ("synth_1024", 400, (0, 1, 2), BYTES_PER_CELL, lambda: synth(1024)),
+             ("synth_4096", 100, (0, 1, 2), BYTES_PER_CELL, lambda: synth(4096)),
+             ("stack_16x1024", 100, (0, 1, 2), BYTES_PER_CELL, lambda: synth(1024, 16)),
+             ("per_cell_D_1024_planes", 400, (0, 1), PLANES_BYTES_PER_CELL, lambda: per_cell(1024)),
+             ("shipped_00042_final_stage", 200, (0, 1, 2), BYTES_PER_CELL, shipped_final_stage)]
+    return [w for w in table if only is None or w[0] in only]
+
+
+def fold_iter(runs, only=None):
+    out = {}
+    for name, iters, keys, bpc, make in fold_workloads(only):
+        with make() as s:
+            cells = s.nx * s.ny * s.nimg
+            rows = {k: [] for k in keys}
+            for _ in range(runs + 1):                                # the first round allocates and warms up
+                for k in keys:
+                    s.set_tuning("cg_fold", k)
+                    s.init_linear(0.0, 1.0)
+                    rs = s.solve_cg(rtol=0.0, max_iter=iters, check_every=iters, fluxes=False)
+                    r = rs[0] if isinstance(rs, list) else rs
+                    assert s.plan_value("cg_fold") == (min(k, 1) if s.plan_value("cg_impl") == 3 else k) and r.iters == iters
+                    rows[k].append(planes_row(r, cells, bpc))
+            per = {k: [x["per_iter_us"] for x in v[1:]] for k, v in rows.items()}
+            best = {k: min(v) for k, v in per.items()}
+            model = rows[keys[0]][0]["model_us_at_TBs"]
+            out[name] = {"mesh": [s.nx, s.ny], "nimg": s.nimg, "cg_impl": s.plan_value("cg_impl"), "cg_items": s.plan_value("cg_items"),
+                         "iterations_per_run": iters, "per_iter_us": {f"fold{k}": v for k, v in per.items()},
+                         "per_iter_us_best": {f"fold{k}": v for k, v in best.items()},
+                         "spread_us": {f"fold{k}": max(v) - min(v) for k, v in per.items()},
+                         "over_fold0": {f"fold{k}": best[k] / best[keys[0]] for k in keys},
+                         "model_us_at_TBs": model,
+                         "best_over_model_6.3": {f"fold{k}": best[k] / model["6.3"] for k in keys}}
+    return out
+
+
+def fold_profile(stats_out):
+    """Keys 0 / 1 / 2 kernel by kernel at 1024^2 and 4096^2: one child process under rocprofv3 --kernel-trace --stats per size."""
+    import csv
+    import glob
+    out = {}
+    lines = []
+    for name in ("synth_1024", "synth_4096"):
+        with tempfile.TemporaryDirectory() as d:
+            run = os.path.join(d, "run.json")
+            p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(d, "prof"), "-o", "run",
+                                "--", sys.executable, os.path.abspath(__file__), "--cases", "fold_iter", "--runs", "1", "--only-fold", name,
+                                "--out", run], capture_output=True, text=True, timeout=900)
+            if p.returncode != 0 or not os.path.exists(run):
+                out[name] = {"error": (p.stderr or p.stdout)[-1500:]}
+                continue
+            files = glob.glob(os.path.join(d, "prof", "**", "*kernel_stats*.csv"), recursive=True)
+            if not files:
+                out[name] = {"error": "no kernel stats written"}
+                continue
+            out[name] = {"runs_per_key": 2, "iterations_per_run": json.load(open(run))["fold_iter"][name]["iterations_per_run"],
+                         "kernels": {}}
+            text = open(files[0]).read().splitlines()
+            lines += [("\"Workload\"," + text[0])] if not lines else []
+            lines += [f"\"{name}\"," + t for t in text[1:]]
+            for k in csv.DictReader(text):
+                out[name]["kernels"][k["Name"].split("(")[0]] = {"calls": int(k["Calls"]), "total_ms": float(k["TotalDurationNs"]) / 1e6,
+                                                                 "average_us": float(k["AverageNs"]) / 1e3, "percent": float(k["Percentage"])}
+    if stats_out and lines:
+        open(stats_out, "w").write("\n".join(lines) + "\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="config1,config2,bench4096,stack16x1024,shipped00042")
@@ -508,7 +612,8 @@ def main():
     ap.add_argument("--only-onchip", action="store_true")
     ap.add_argument("--only-stream", action="store_true")
     ap.add_argument("--only-planes-4096", action="store_true")
-    ap.add_argument("--stats-out", default=None, help="planes_profile: where the kernel-stats table is kept")
+    ap.add_argument("--only-fold", default=None, help="fold_iter: these workloads only (comma-separated)")
+    ap.add_argument("--stats-out", default=None, help="planes_profile / fold_profile: where the kernel-stats table is kept")
     ap.add_argument("--per-iter-us", type=float, default=11.1, help="k_cg_image per iteration (onchip_profile), for the CU-busy share")
     a = ap.parse_args()
     jac = not a.no_jacobi
@@ -545,6 +650,10 @@ def main():
             out[case] = planes_to_rtol(a.rtol, a.max_iter)
         elif case == "planes_profile":
             out[case] = planes_profile(a.stats_out)
+        elif case == "fold_iter":
+            out[case] = fold_iter(a.runs, a.only_fold.split(",") if a.only_fold else None)
+        elif case == "fold_profile":
+            out[case] = fold_profile(a.stats_out)
         elif case == "stream_profile":
             out[case] = stream_profile(a.rtol, a.images)
         elif case == "stream_driver":
