@@ -5,6 +5,7 @@
 // reference's algorithm: it reaches the same discrete fixed point (same A, b, wall-flux Deff) as the weighted Jacobi loop of
 // deff_solve, in far fewer iterations.  Nothing of the Jacobi path is touched: its tables (lut, c0 plane), plans and knobs
 // stay as they are (the "fma" knob does not apply here: CG's arithmetic is written-order FP64 only).
+// The launches of one iteration, in every form and under every fold key, are CgIteration::enqueue's, for both solves.
 #include "ctx.hpp"
 #include "kernels_cg.hpp"
 #include "kernels_cg_planes.hpp"
@@ -100,6 +101,55 @@ static int cgp_buffers(deff_ctx *c)
     return DEFF_OK;
 }
 
+// One CG iteration on the context's stream: four launches, or two with the reductions folded in (fold 1, 2: tuning "cg_fold",
+// kernels_cg_fold.hpp), on the row table or on the coefficient planes.  What does not change from one iteration to the next
+// is set once per call; p_in / p_out swap.  Returns the number of launches.
+struct CgIteration {
+    deff_ctx *c;
+    bool planes;
+    int fold;
+    dim3 grid, fin;
+    CgGeom g;
+    double *x, *part, *part_rz, *part_rr;
+    unsigned *tick_a, *tick_b;
+    double tol2;
+    long long max_iter;
+
+    int enqueue(const double *p_in, double *p_out) const
+    {
+        const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, c->b};
+        CgScal *sc = (CgScal *)c->cg_scal;
+        if (fold) {
+            if (planes) {
+                hipLaunchKernelGGL(k_cgpf_dir, grid, dim3(256), 0, c->stream, P, c->cg_inv, c->cg_r, p_in, p_out, c->cg_q, sc, g,
+                                   part, tick_a);
+                hipLaunchKernelGGL(k_cgpf_update, grid, dim3(256), 0, c->stream, c->cg_inv, p_out, c->cg_q, x, c->cg_r, sc, g,
+                                   part_rz, part_rr, tol2, max_iter, tick_b);
+            } else {
+                hipLaunchKernelGGL(fold == 2 ? k_cgf_dir2 : k_cgf_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows,
+                                   c->code, c->cg_r, p_in, p_out, sc, g, part, tick_a);
+                hipLaunchKernelGGL(k_cgf_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x,
+                                   c->cg_r, sc, g, part_rz, part_rr, tol2, max_iter, tick_b);
+            }
+            return 2;
+        }
+        if (planes)
+            hipLaunchKernelGGL(k_cgp_dir, grid, dim3(256), 0, c->stream, P, c->cg_inv, c->cg_r, p_in, p_out, c->cg_q, sc, g, part);
+        else
+            hipLaunchKernelGGL(k_cg_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->cg_r, p_in, p_out, sc,
+                               g, part);
+        hipLaunchKernelGGL(k_cg_alpha, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc);
+        if (planes)
+            hipLaunchKernelGGL(k_cgp_update, grid, dim3(256), 0, c->stream, c->cg_inv, p_out, c->cg_q, x, c->cg_r, sc, g, part_rz,
+                               part_rr);
+        else
+            hipLaunchKernelGGL(k_cg_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x, c->cg_r, sc,
+                               g, part_rz, part_rr);
+        hipLaunchKernelGGL(k_cg_beta, fin, dim3(CG_FIN), 0, c->stream, part_rz, part_rr, g.per_img, sc, tol2, max_iter);
+        return 4;
+    }
+};
+
 extern "C" int deff_solve_cg(deff_ctx *c, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out,
                              double *MFL, double *MFR)
 try {
@@ -179,7 +229,8 @@ try {
     double *x = c->x[c->cur];
     double *part = c->cg_part, *part_rz = c->cg_part + items, *part_rr = c->cg_part + 2 * items;
     CgScal *sc = (CgScal *)c->cg_scal;
-    unsigned *tick_a = c->cg_tick, *tick_b = c->cg_tick + cgf_ticks(g.per_img, (size_t)c->nimg);
+    const CgIteration iteration{c, planes, fold, grid, fin, g, x, part, part_rz, part_rr, c->cg_tick,
+                                c->cg_tick + cgf_ticks(g.per_img, (size_t)c->nimg), tol2, (long long)max_iter};
     std::vector<CgScal> hs(c->nimg);
     auto true_residual = [&](int mode, int allow) -> int {
         if (planes) hipLaunchKernelGGL(k_cgp_resid, grid, dim3(256), 0, c->stream, P, c->cg_inv, x, c->cg_r, g, part);
@@ -218,38 +269,7 @@ try {
             HIP_TRY(hipGetLastError());
             continue;
         }
-        for (int64_t i = 0; i < check_every; ++i, ++k) {
-            double *p_in = c->cg_p[k & 1], *p_out = c->cg_p[(k + 1) & 1];
-            if (fold) {
-                if (planes) {
-                    hipLaunchKernelGGL(k_cgpf_dir, grid, dim3(256), 0, c->stream, P, c->cg_inv, c->cg_r, p_in, p_out, c->cg_q, sc,
-                                       g, part, tick_a);
-                    hipLaunchKernelGGL(k_cgpf_update, grid, dim3(256), 0, c->stream, c->cg_inv, p_out, c->cg_q, x, c->cg_r, sc, g,
-                                       part_rz, part_rr, tol2, (long long)max_iter, tick_b);
-                } else {
-                    hipLaunchKernelGGL(fold == 2 ? k_cgf_dir2 : k_cgf_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows,
-                                       c->code, c->cg_r, p_in, p_out, sc, g, part, tick_a);
-                    hipLaunchKernelGGL(k_cgf_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x,
-                                       c->cg_r, sc, g, part_rz, part_rr, tol2, (long long)max_iter, tick_b);
-                }
-                continue;
-            }
-            if (planes)
-                hipLaunchKernelGGL(k_cgp_dir, grid, dim3(256), 0, c->stream, P, c->cg_inv, c->cg_r, p_in, p_out, c->cg_q, sc, g,
-                                   part);
-            else
-                hipLaunchKernelGGL(k_cg_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->cg_r, p_in,
-                                   p_out, sc, g, part);
-            hipLaunchKernelGGL(k_cg_alpha, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc);
-            if (planes)
-                hipLaunchKernelGGL(k_cgp_update, grid, dim3(256), 0, c->stream, c->cg_inv, p_out, c->cg_q, x, c->cg_r, sc, g,
-                                   part_rz, part_rr);
-            else
-                hipLaunchKernelGGL(k_cg_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x,
-                                   c->cg_r, sc, g, part_rz, part_rr);
-            hipLaunchKernelGGL(k_cg_beta, fin, dim3(CG_FIN), 0, c->stream, part_rz, part_rr, g.per_img, sc, tol2,
-                               (long long)max_iter);
-        }
+        for (int64_t i = 0; i < check_every; ++i, ++k) iteration.enqueue(c->cg_p[k & 1], c->cg_p[(k + 1) & 1]);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(c->cg_ev1, c->stream));
@@ -430,7 +450,9 @@ try {
 
     const double tol2 = rtol * rtol;
     const dim3 grid((unsigned)((items + 3) / 4)), fin((unsigned)B);
-    double *part = c->cg_part, *part_rz = c->cg_part + items, *part_rr = c->cg_part + 2 * items;
+    double *part = c->cg_part;
+    const CgIteration iteration{c, false, fold, grid, fin, g, x, part, part + items, part + 2 * items, c->cg_tick,
+                                c->cg_tick + cgf_ticks(g.per_img, (size_t)B), tol2, (long long)max_iter};
     struct Slot { bool live = false; int64_t id = -1, valid_from = 0; };
     std::vector<Slot> S(B);
     bool more = true;
@@ -481,25 +503,8 @@ try {
                                (long long)max_iter);
             launches += 1;
         } else {
-            for (int64_t q = 0; q < check_every; ++q, ++k_it) {
-                double *p_in = c->cg_p[k_it & 1], *p_out = c->cg_p[(k_it + 1) & 1];
-                if (fold) {
-                    hipLaunchKernelGGL(fold == 2 ? k_cgf_dir2 : k_cgf_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows,
-                                       c->code, c->cg_r, p_in, p_out, sc, g, part, c->cg_tick);
-                    hipLaunchKernelGGL(k_cgf_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x,
-                                       c->cg_r, sc, g, part_rz, part_rr, tol2, (long long)max_iter,
-                                       c->cg_tick + cgf_ticks(g.per_img, (size_t)B));
-                    continue;
-                }
-                hipLaunchKernelGGL(k_cg_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->cg_r, p_in, p_out,
-                                   sc, g, part);
-                hipLaunchKernelGGL(k_cg_alpha, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc);
-                hipLaunchKernelGGL(k_cg_update, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, p_out, x,
-                                   c->cg_r, sc, g, part_rz, part_rr);
-                hipLaunchKernelGGL(k_cg_beta, fin, dim3(CG_FIN), 0, c->stream, part_rz, part_rr, g.per_img, sc, tol2,
-                                   (long long)max_iter);
-            }
-            launches += (fold ? 2 : 4) * check_every;
+            for (int64_t q = 0; q < check_every; ++q, ++k_it)
+                launches += iteration.enqueue(c->cg_p[k_it & 1], c->cg_p[(k_it + 1) & 1]);
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(bf.h_snap[i & 1], sc, sizeof(CgScal) * B, hipMemcpyDeviceToHost, c->stream));

@@ -10,7 +10,7 @@
 // The tail.  Every image has two sets of counters (cg_tick: one for the direction launch, one for the update launch), zeroed
 // by the host at the start of every call.  A wave that has stored its item's partial(s) adds 1 to a counter of its image; the
 // wave whose add completes the image is the image's last and marks the image in LDS.  Behind a workgroup barrier the whole
-// workgroup runs the body of k_cg_alpha / k_cg_beta for every marked image (up to four: one per wave) and puts the counter
+// workgroup runs k_cg_alpha's / k_cg_beta's sum and step for every marked image (up to four: one per wave) and puts the counter
 // back to 0.  The counting has two levels: adds to one address are served one after the other, about 10 ns each, so one
 // counter per image costs 4 096 items 40 us (measured: DESIGN.md).  An image's items are counted in shards of CGF_SHARD
 // consecutive items, every counter on 256 bytes of its own; the wave that completes a shard resets it and adds 1 to the
@@ -26,8 +26,10 @@
 // anywhere: an agent-scope release in the streaming workgroups would write back the L2 lines their own p', x, r stores have
 // just dirtied.
 //
-// Bits: the work items (cg_item), the expressions (cg_apply, cgp_apply), the wave sum, the partial slots and the order of the
-// final sum (cgf_image_sum = cg_image_sum for a given image) are those of the four-launch form, and so is every result.
+// Bits: a folded kernel calls the row walk of the four-launch kernel it folds (cg_dir_rows, cg_update_rows of kernels_cg.hpp;
+// cgp_dir_rows, cgp_update_rows of kernels_cg_planes.hpp) on the same work items (cg_item) and partial slots, and its tail
+// the same sum and scalar step (cg_image_sum, cg_alpha_step, cg_beta_step): every result is the four-launch form's.
+// k_cgf_dir2 alone has a row walk of its own -- another load discipline around the same cg_apply, in the same order.
 // The per-image scalars are written by a tail while other images' items still read theirs: `sc` is neither const nor
 // __restrict__ here.  An image's items have all read beta / restart / alpha before they tick, so its tail may overwrite them.
 #pragma once
@@ -55,16 +57,41 @@ __device__ __forceinline__ void cgf_store(double *p, double v)           // writ
                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The end of every wave of a folded launch.  `ticks`: the wave has stored the partials of item `idx` (wave-uniform).  Returns
-// behind the workgroup barrier; mark[w] is then the image wave w was the last of, or -1.
-__device__ __forceinline__ void cgf_arrive(bool ticks, int lane, int wave, int img, unsigned idx, unsigned per_img,
-                                           unsigned *tick, int *mark)
+// A wave of a folded launch: its item, and whether it has work (`run`: the item exists and its image is not frozen).  ws / mark:
+// the tail's LDS, CGF_LDS doubles.
+struct CgfWave {
+    int lane, wave;
+    CgItem it;
+    bool run;
+    double *ws;
+    int *mark;
+};
+
+// The start of every wave of a folded launch (a table-form kernel loads its table first).  No wave returns here.
+__device__ __forceinline__ CgfWave cgf_begin(const CgGeom &g, const CgScal *sc, double *lds)
 {
-    if (lane == 63) {
+    CgfWave w;
+    w.ws = lds;
+    w.mark = reinterpret_cast<int *>(lds + 4);
+    w.lane = threadIdx.x & 63;
+    w.wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    w.it.img = 0;
+    w.it.idx = 0;
+    w.run = cg_item(g, w.wave, w.lane, w.it);
+    if (w.run) w.run = sc[w.it.img].done == 0;                    // frozen image: no writes, no tick
+    return w;
+}
+
+// The end of every wave of a folded launch: a wave that ran has stored the partials of its item.  Returns behind the
+// workgroup barrier; mark[v] is then the image wave v was the last of, or -1.
+__device__ __forceinline__ void cgf_arrive(const CgfWave &w, unsigned per_img, unsigned *tick)
+{
+    if (w.lane == 63) {
         int m = -1;
-        if (ticks) {
+        if (w.run) {
+            const int img = w.it.img;
             unsigned *ti = cgf_tick_of(tick, per_img, img);
-            const unsigned sh = (idx - (unsigned)img * per_img) / CGF_SHARD;
+            const unsigned sh = (w.it.idx - (unsigned)img * per_img) / CGF_SHARD;
             const unsigned full = min(CGF_SHARD, per_img - sh * CGF_SHARD);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the partials have left
             unsigned *ts = ti + (size_t)(1 + sh) * CGF_PAD;
@@ -78,61 +105,36 @@ __device__ __forceinline__ void cgf_arrive(bool ticks, int lane, int wave, int i
                 }
             }
         }
-        mark[wave] = m;
+        w.mark[w.wave] = m;
     }
     __syncthreads();
 }
 
-// cg_image_sum of image `img`: thread t adds t, t + 256, ... in index order, the wave tree, then the four wave sums in wave order
-__device__ __forceinline__ double cgf_image_sum(const double *part, int img, unsigned per_img, double *ws)
+// k_cg_alpha's step for every image this workgroup was the last of (done == 0: a frozen image does not tick)
+__device__ __forceinline__ void cgf_tail_alpha(const double *part, unsigned per_img, CgScal *sc, unsigned *tick, const CgfWave &w)
 {
-    const double *pp = part + (size_t)img * per_img;
-    double acc = 0.0;
-    for (unsigned i = threadIdx.x; i < per_img; i += CG_FIN) acc += pp[i];
-    const double s = wave_sum_to_lane63(acc);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-
-// k_cg_alpha's body for every image this workgroup was the last of (done == 0: a frozen image does not tick)
-__device__ __forceinline__ void cgf_tail_alpha(const double *part, unsigned per_img, CgScal *sc, unsigned *tick, double *ws,
-                                               const int *mark)
-{
-    for (int w = 0; w < 4; ++w) {
-        const int img = mark[w];
+    for (int k = 0; k < 4; ++k) {
+        const int img = w.mark[k];
         if (img < 0) continue;
-        const double pap = cgf_image_sum(part, img, per_img, ws);
+        const double pap = cg_image_sum(part + (size_t)img * per_img, per_img, 1, 0, w.ws);
         if (threadIdx.x == 0) {
-            CgScal &s = sc[img];
-            if (pap > 0.0 && pap <= 1.7976931348623157e308) s.alpha = s.rho / pap;
-            else { s.alpha = 0.0; s.done = 3; }
-            s.restart = 0;
+            cg_alpha_step(sc[img], pap);
             __hip_atomic_store(cgf_tick_of(tick, per_img, img), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
 
-// k_cg_beta's body likewise
+// k_cg_beta's step likewise
 __device__ __forceinline__ void cgf_tail_beta(const double *part_rz, const double *part_rr, unsigned per_img, CgScal *sc,
-                                              double tol2, long long max_iter, unsigned *tick, double *ws, const int *mark)
+                                              double tol2, long long max_iter, unsigned *tick, const CgfWave &w)
 {
-    for (int w = 0; w < 4; ++w) {
-        const int img = mark[w];
+    for (int k = 0; k < 4; ++k) {
+        const int img = w.mark[k];
         if (img < 0) continue;
-        const double rz = cgf_image_sum(part_rz, img, per_img, ws);
-        const double rr = cgf_image_sum(part_rr, img, per_img, ws);
+        const double rz = cg_image_sum(part_rz + (size_t)img * per_img, per_img, 1, 0, w.ws);
+        const double rr = cg_image_sum(part_rr + (size_t)img * per_img, per_img, 1, 0, w.ws);
         if (threadIdx.x == 0) {
-            CgScal &s = sc[img];
-            s.iters += 1;
-            s.rr = rr;
-            if (rr <= tol2 * s.bb) s.done = 1;
-            else if (s.iters >= max_iter) s.done = 2;
-            else {
-                s.beta = rz / s.rho;
-                s.rho = rz;
-            }
+            cg_beta_step(sc[img], rz, rr, tol2, max_iter);
             __hip_atomic_store(cgf_tick_of(tick, per_img, img), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
@@ -140,64 +142,22 @@ __device__ __forceinline__ void cgf_tail_beta(const double *part_rz, const doubl
 
 // ---- table form --------------------------------------------------------------------------------------------------------
 
-// Launch A: k_cg_dir's item, then the tail.
+// Launch A: k_cg_dir's item (cg_dir_rows), then the tail.
 __global__ __launch_bounds__(256) void k_cgf_dir(const double *__restrict__ tab_g, int nrows, const uint16_t *__restrict__ code,
                                                  const double *__restrict__ r, const double *__restrict__ p_in,
                                                  double *__restrict__ p_out, CgScal *sc, CgGeom g, double *partial, unsigned *tick)
 {
     __shared__ double tab[CG_DOUBLES + CGF_LDS];
-    double *ws = tab + CG_DOUBLES;
-    int *mark = reinterpret_cast<int *>(ws + 4);
     cg_load_tab(tab, tab_g, nrows);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CgItem it;
-    it.img = 0;
-    it.idx = 0;
-    bool run = cg_item(g, wave, lane, it);
-    if (run) run = sc[it.img].done == 0;                          // frozen image: no writes, no tick
-    if (run) {
-        const bool restart = sc[it.img].restart != 0;
-        const double beta = sc[it.img].beta;
-        const bool v = it.col < g.nx;
-        const int jh = cg_halo_col(g, it, lane);
-        auto pn1 = [&](size_t q) -> double {
-            const double z = r[q] * cg_v<CG_INV>(tab, code[q]);
-            return restart ? z : z + beta * p_in[q];
-        };
-        auto pn2 = [&](int l) -> double2 {                       // p' of the lane's two cells of row l (0 outside)
-            double2 o = make_double2(0.0, 0.0);
-            if (v && l >= 0 && l < g.ny) {
-                const size_t q = it.base + (size_t)l * g.nx + it.col;
-                const unsigned cw = *reinterpret_cast<const unsigned *>(code + q);
-                const double2 rr = *reinterpret_cast<const double2 *>(r + q);
-                const double2 z = make_double2(rr.x * cg_v<CG_INV>(tab, cw & 0xFFFFu), rr.y * cg_v<CG_INV>(tab, cw >> 16));
-                if (restart) o = z;
-                else {
-                    const double2 pp = *reinterpret_cast<const double2 *>(p_in + q);
-                    o = make_double2(z.x + beta * pp.x, z.y + beta * pp.y);
-                }
-            }
-            return o;
-        };
-        double2 up = pn2(it.l0 - 1), cur = pn2(it.l0);
-        double acc = 0.0;
-#pragma unroll 1
-        for (int l = it.l0; l < it.l1; ++l) {
-            const double2 dn = pn2(l + 1);
-            const size_t q = it.base + (size_t)l * g.nx + it.col;
-            const double h = jh >= 0 ? pn1(it.base + (size_t)l * g.nx + jh) : 0.0;
-            const unsigned cw = v ? *reinterpret_cast<const unsigned *>(code + q) : 0u;
-            const double2 ap = cg_apply(tab, cw & 0xFFFFu, cw >> 16, cur, up, dn, h);
-            acc += cur.x * ap.x + cur.y * ap.y;
-            if (v) *reinterpret_cast<double2 *>(p_out + q) = cur;
-            up = cur;
-            cur = dn;
-        }
-        const double s = wave_sum_to_lane63(acc);
-        if (lane == 63) cgf_store(partial + it.idx, s);
+    const CgfWave w = cgf_begin(g, sc, tab + CG_DOUBLES);
+    if (w.run) {
+        const CgItem &it = w.it;
+        const double s = cg_dir_rows(tab, code, r, p_in, p_out, cg_win(g, it), g.nx, it.col, it.l0, it.l1,
+                                     cg_halo_col(g.nx, it.col, w.lane), sc[it.img].restart != 0, sc[it.img].beta, false, false);
+        if (w.lane == 63) cgf_store(partial + it.idx, s);
     }
-    cgf_arrive(run, lane, wave, it.img, it.idx, g.per_img, tick, mark);
-    cgf_tail_alpha(partial, g.per_img, sc, tick, ws, mark);
+    cgf_arrive(w, g.per_img, tick);
+    cgf_tail_alpha(partial, g.per_img, sc, tick, w);
 }
 
 // what p' of a lane's two cells / of its halo cell is made of
@@ -221,16 +181,11 @@ __global__ __launch_bounds__(256) void k_cgf_dir2(const double *__restrict__ tab
                                                   double *__restrict__ p_out, CgScal *sc, CgGeom g, double *partial, unsigned *tick)
 {
     __shared__ double tab[CG_DOUBLES + CGF_LDS];
-    double *ws = tab + CG_DOUBLES;
-    int *mark = reinterpret_cast<int *>(ws + 4);
     cg_load_tab(tab, tab_g, nrows);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CgItem it;
-    it.img = 0;
-    it.idx = 0;
-    bool run = cg_item(g, wave, lane, it);
-    if (run) run = sc[it.img].done == 0;
-    if (run) {
+    const CgfWave w = cgf_begin(g, sc, tab + CG_DOUBLES);
+    if (w.run) {
+        const CgItem &it = w.it;
+        const int lane = w.lane;
         const bool restart = sc[it.img].restart != 0;
         // (what is the same in every lane is kept in scalar registers: the vector registers go to the rows in flight)
         const double bv = sc[it.img].beta;
@@ -238,7 +193,7 @@ __global__ __launch_bounds__(256) void k_cgf_dir2(const double *__restrict__ tab
                                              __builtin_amdgcn_readfirstlane(__double2loint(bv)));
         const int l0 = __builtin_amdgcn_readfirstlane(it.l0), l1 = __builtin_amdgcn_readfirstlane(it.l1);
         const bool v = it.col < g.nx;
-        const int jh = cg_halo_col(g, it, lane);
+        const int jh = cg_halo_col(g.nx, it.col, lane);
         const unsigned cb = v ? (unsigned)it.col * 8u : 0u, hb = (unsigned)max(jh, 0) * 8u;
         auto row_of = [&](const void *a, int l, int cell) {
             return cgp_uniform(reinterpret_cast<const double *>(
@@ -314,232 +269,65 @@ __global__ __launch_bounds__(256) void k_cgf_dir2(const double *__restrict__ tab
         const double s = wave_sum_to_lane63(acc);
         if (lane == 63) cgf_store(partial + it.idx, s);
     }
-    cgf_arrive(run, lane, wave, it.img, it.idx, g.per_img, tick, mark);
-    cgf_tail_alpha(partial, g.per_img, sc, tick, ws, mark);
+    cgf_arrive(w, g.per_img, tick);
+    cgf_tail_alpha(partial, g.per_img, sc, tick, w);
 }
 
-// Launch B: k_cg_update's item, then the tail.
+// Launch B: k_cg_update's item (cg_update_rows), then the tail.
 __global__ __launch_bounds__(256) void k_cgf_update(const double *__restrict__ tab_g, int nrows, const uint16_t *__restrict__ code,
                                                     const double *__restrict__ p, double *__restrict__ x, double *__restrict__ r,
                                                     CgScal *sc, CgGeom g, double *partial_rz, double *partial_rr, double tol2,
                                                     long long max_iter, unsigned *tick)
 {
     __shared__ double tab[CG_DOUBLES + CGF_LDS];
-    double *ws = tab + CG_DOUBLES;
-    int *mark = reinterpret_cast<int *>(ws + 4);
     cg_load_tab(tab, tab_g, nrows);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CgItem it;
-    it.img = 0;
-    it.idx = 0;
-    bool run = cg_item(g, wave, lane, it);
-    if (run) run = sc[it.img].done == 0;
-    if (run) {
-        const double alpha = sc[it.img].alpha;
-        const bool v = it.col < g.nx;
-        const int jh = cg_halo_col(g, it, lane);
-        auto p2 = [&](int l) -> double2 {
-            return (v && l >= 0 && l < g.ny) ? *reinterpret_cast<const double2 *>(p + it.base + (size_t)l * g.nx + it.col)
-                                             : make_double2(0.0, 0.0);
-        };
-        double2 up = p2(it.l0 - 1), cur = p2(it.l0);
-        double rz = 0.0, rr = 0.0;
-#pragma unroll 1
-        for (int l = it.l0; l < it.l1; ++l) {
-            const double2 dn = p2(l + 1);
-            const size_t q = it.base + (size_t)l * g.nx + it.col;
-            const double h = jh >= 0 ? p[it.base + (size_t)l * g.nx + jh] : 0.0;
-            const unsigned cw = v ? *reinterpret_cast<const unsigned *>(code + q) : 0u;
-            const unsigned o0 = cw & 0xFFFFu, o1 = cw >> 16;
-            const double2 ap = cg_apply(tab, o0, o1, cur, up, dn, h);
-            if (v) {
-                double2 xx = *reinterpret_cast<const double2 *>(x + q), rv = *reinterpret_cast<const double2 *>(r + q);
-                xx.x = xx.x + alpha * cur.x;
-                xx.y = xx.y + alpha * cur.y;
-                rv.x = rv.x - alpha * ap.x;
-                rv.y = rv.y - alpha * ap.y;
-                *reinterpret_cast<double2 *>(x + q) = xx;
-                *reinterpret_cast<double2 *>(r + q) = rv;
-                rz += rv.x * (rv.x * cg_v<CG_INV>(tab, o0)) + rv.y * (rv.y * cg_v<CG_INV>(tab, o1));
-                rr += rv.x * rv.x + rv.y * rv.y;
-            }
-            up = cur;
-            cur = dn;
-        }
-        const double s1 = wave_sum_to_lane63(rz);
-        const double s2 = wave_sum_to_lane63(rr);
-        if (lane == 63) { cgf_store(partial_rz + it.idx, s1); cgf_store(partial_rr + it.idx, s2); }
+    const CgfWave w = cgf_begin(g, sc, tab + CG_DOUBLES);
+    if (w.run) {
+        const CgItem &it = w.it;
+        double s1, s2;
+        cg_update_rows(tab, code, p, x, r, cg_win(g, it), g.nx, it.col, it.l0, it.l1,
+                       cg_halo_col(g.nx, it.col, w.lane), sc[it.img].alpha, s1, s2);
+        if (w.lane == 63) { cgf_store(partial_rz + it.idx, s1); cgf_store(partial_rr + it.idx, s2); }
     }
-    cgf_arrive(run, lane, wave, it.img, it.idx, g.per_img, tick, mark);
-    cgf_tail_beta(partial_rz, partial_rr, g.per_img, sc, tol2, max_iter, tick, ws, mark);
+    cgf_arrive(w, g.per_img, tick);
+    cgf_tail_beta(partial_rz, partial_rr, g.per_img, sc, tol2, max_iter, tick, w);
 }
 
 // ---- plane form --------------------------------------------------------------------------------------------------------
 
-// Launch A: k_cgp_dir's item (its rolling window of loads included), then the tail.
+// Launch A: k_cgp_dir's item (cgp_dir_rows, its rolling window of loads included), then the tail.
 __global__ __launch_bounds__(256) void k_cgpf_dir(CgpPlanes A, const double *__restrict__ inv, const double *__restrict__ r,
                                                   const double *__restrict__ p_in, double *__restrict__ p_out,
                                                   double *__restrict__ q_out, CgScal *sc, CgGeom g, double *partial, unsigned *tick)
 {
-    __shared__ double ws[CGF_LDS];
-    int *mark = reinterpret_cast<int *>(ws + 4);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CgItem it;
-    it.img = 0;
-    it.idx = 0;
-    bool run = cg_item(g, wave, lane, it);
-    if (run) run = sc[it.img].done == 0;
-    if (run) {
-        const bool restart = sc[it.img].restart != 0;
-        const double beta = sc[it.img].beta;
-        const bool v = it.col < g.nx;
-        const int jh = cg_halo_col(g, it, lane);
-        const unsigned cb = v ? (unsigned)it.col * 8u : 0u, hb = (unsigned)max(jh, 0) * 8u;
-        auto row_of = [&](const double *a, int l) { return cgp_uniform(a + it.base + (size_t)min(max(l, 0), g.ny - 1) * g.nx); };
-        auto inside = [&](int l) { return v && l >= 0 && l < g.ny; };
-        auto raw2 = [&](int l) -> CgpRaw2 {
-            CgpRaw2 o;
-            o.r = cgp_gld2(row_of(r, l), cb);
-            o.inv = cgp_gld2(row_of(inv, l), cb);
-            o.p = cgp_gld2(row_of(p_in, l), cb);
-            return o;
-        };
-        auto pn2 = [&](const CgpRaw2 &o, int l) -> double2 {
-            const double2 z = make_double2(o.r.x * o.inv.x, o.r.y * o.inv.y);
-            const double2 t = restart ? z : make_double2(z.x + beta * o.p.x, z.y + beta * o.p.y);
-            return inside(l) ? t : make_double2(0.0, 0.0);
-        };
-        auto raw1 = [&](int l) -> CgpRaw1 {
-            CgpRaw1 o;
-            o.r = cgp_gld1(row_of(r, l), hb);
-            o.inv = cgp_gld1(row_of(inv, l), hb);
-            o.p = cgp_gld1(row_of(p_in, l), hb);
-            return o;
-        };
-        auto pn1 = [&](const CgpRaw1 &o) -> double {
-            const double z = o.r * o.inv;
-            const double t = restart ? z : z + beta * o.p;
-            return jh >= 0 ? t : 0.0;
-        };
-        auto mrow = [&](int l) -> CgpRow {
-            CgpRow o;
-            o.a0 = cgp_gldc2(row_of(A.a0, l), cb);
-            o.aW = cgp_gldc2(row_of(A.aW, l), cb);
-            o.aE = cgp_gldc2(row_of(A.aE, l), cb);
-            o.aS = cgp_gldc2(row_of(A.aS, l), cb);
-            o.aN = cgp_gldc2(row_of(A.aN, l), cb);
-            return o;
-        };
-        const CgpRaw2 r0 = raw2(it.l0 - 1), r1 = raw2(it.l0);
-        CgpRow ma = mrow(it.l0), mb = ma;
-        CgpRaw2 rd = raw2(it.l0 + 1);
-        CgpRaw1 hd = raw1(it.l0);
-        double2 up = pn2(r0, it.l0 - 1), cur = pn2(r1, it.l0);
-        unsigned act = cgp_act(r1.inv);
-        double acc = 0.0;
-        auto step = [&](auto more_c, int l, const CgpRow &m, CgpRow &mn) {
-            constexpr bool MORE = decltype(more_c)::value;
-            if constexpr (MORE) mn = mrow(l + 1);
-            const double2 dn = pn2(rd, l + 1);
-            const double h = pn1(hd);
-            const unsigned act_dn = cgp_act(rd.inv);
-            if constexpr (MORE) {
-                __builtin_amdgcn_sched_barrier(0);
-                rd = raw2(l + 2);
-                hd = raw1(l + 1);
-            }
-            double2 ap = cgp_apply(m, act, cur, up, dn, h);
-            if (!v) ap = make_double2(0.0, 0.0);
-            acc += cur.x * ap.x + cur.y * ap.y;
-            if (v) {
-                cgp_gst2(row_of(p_out, l), cb, cur);
-                cgp_gst2(row_of(q_out, l), cb, ap);
-            }
-            up = cur;
-            cur = dn;
-            act = act_dn;
-        };
-        const std::true_type more;
-        const std::false_type last;
-        int l = it.l0;
-#pragma unroll 1
-        for (; l + 2 < it.l1; l += 2) {
-            step(more, l, ma, mb);
-            step(more, l + 1, mb, ma);
-        }
-        if (l + 1 < it.l1) {
-            step(more, l, ma, mb);
-            step(last, l + 1, mb, ma);
-        } else step(last, l, ma, mb);
-        const double s = wave_sum_to_lane63(acc);
-        if (lane == 63) cgf_store(partial + it.idx, s);
+    __shared__ double lds[CGF_LDS];
+    const CgfWave w = cgf_begin(g, sc, lds);
+    if (w.run) {
+        const CgItem &it = w.it;
+        const double s = cgp_dir_rows(A, inv, r, p_in, p_out, q_out, cg_win(g, it), g.nx, it.col, it.l0, it.l1,
+                                      cg_halo_col(g.nx, it.col, w.lane), sc[it.img].restart != 0, sc[it.img].beta);
+        if (w.lane == 63) cgf_store(partial + it.idx, s);
     }
-    cgf_arrive(run, lane, wave, it.img, it.idx, g.per_img, tick, mark);
-    cgf_tail_alpha(partial, g.per_img, sc, tick, ws, mark);
+    cgf_arrive(w, g.per_img, tick);
+    cgf_tail_alpha(partial, g.per_img, sc, tick, w);
 }
 
-// Launch B: k_cgp_update's item, then the tail.
+// Launch B: k_cgp_update's item (cgp_update_rows), then the tail.
 __global__ __launch_bounds__(256) void k_cgpf_update(const double *__restrict__ inv, const double *__restrict__ p,
                                                      const double *__restrict__ qv, double *x, double *r, CgScal *sc, CgGeom g,
                                                      double *partial_rz, double *partial_rr, double tol2, long long max_iter,
                                                      unsigned *tick)
 {
-    __shared__ double ws[CGF_LDS];
-    int *mark = reinterpret_cast<int *>(ws + 4);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CgItem it;
-    it.img = 0;
-    it.idx = 0;
-    bool run = cg_item(g, wave, lane, it);
-    if (run) run = sc[it.img].done == 0;
-    if (run) {
-        const double alpha = sc[it.img].alpha;
-        const bool v = it.col < g.nx;
-        const unsigned cb = v ? (unsigned)it.col * 8u : 0u;
-        auto row_of = [&](const double *a, int l) { return cgp_uniform(a + it.base + (size_t)l * g.nx); };
-        auto load = [&](int l) -> CgpUpd {
-            CgpUpd o;
-            o.p = cgp_gld2(row_of(p, l), cb);
-            o.q = cgp_gld2(row_of(qv, l), cb);
-            o.x = cgp_gld2(row_of(x, l), cb);
-            o.r = cgp_gld2(row_of(r, l), cb);
-            o.inv = cgp_gld2(row_of(inv, l), cb);
-            return o;
-        };
-        double rz = 0.0, rr = 0.0;
-        auto step = [&](int l, const CgpUpd &d) {
-            if (v) {
-                double2 xx = d.x, rv = d.r;
-                xx.x = xx.x + alpha * d.p.x;
-                xx.y = xx.y + alpha * d.p.y;
-                rv.x = rv.x - alpha * d.q.x;
-                rv.y = rv.y - alpha * d.q.y;
-                cgp_gst2(row_of(x, l), cb, xx);
-                cgp_gst2(row_of(r, l), cb, rv);
-                rz += rv.x * (rv.x * d.inv.x) + rv.y * (rv.y * d.inv.y);
-                rr += rv.x * rv.x + rv.y * rv.y;
-            }
-        };
-        CgpUpd da = load(it.l0), db = da;
-        int l = it.l0;
-#pragma unroll 1
-        for (; l + 2 < it.l1; l += 2) {
-            db = load(l + 1);
-            step(l, da);
-            da = load(l + 2);
-            step(l + 1, db);
-        }
-        if (l + 1 < it.l1) {
-            db = load(l + 1);
-            step(l, da);
-            step(l + 1, db);
-        } else step(l, da);
-        const double s1 = wave_sum_to_lane63(rz);
-        const double s2 = wave_sum_to_lane63(rr);
-        if (lane == 63) { cgf_store(partial_rz + it.idx, s1); cgf_store(partial_rr + it.idx, s2); }
+    __shared__ double lds[CGF_LDS];
+    const CgfWave w = cgf_begin(g, sc, lds);
+    if (w.run) {
+        const CgItem &it = w.it;
+        double s1, s2;
+        cgp_update_rows(inv, p, qv, x, r, cg_win(g, it), g.nx, it.col, it.l0, it.l1, sc[it.img].alpha, s1, s2);
+        if (w.lane == 63) { cgf_store(partial_rz + it.idx, s1); cgf_store(partial_rr + it.idx, s2); }
     }
-    cgf_arrive(run, lane, wave, it.img, it.idx, g.per_img, tick, mark);
-    cgf_tail_beta(partial_rz, partial_rr, g.per_img, sc, tol2, max_iter, tick, ws, mark);
+    cgf_arrive(w, g.per_img, tick);
+    cgf_tail_beta(partial_rz, partial_rr, g.per_img, sc, tol2, max_iter, tick, w);
 }
 
 }  // namespace deff

@@ -19,6 +19,7 @@
 // The coefficient planes are read once per iteration and loaded non-temporally: the caches are left to r, p and inv, which
 // neighbouring items and the next launch read again.  There is no table in LDS: registers alone bound the occupancy.
 // k_cgp_dir and k_cgp_update issue the loads of row l + 1 before the arithmetic of row l needs row l's.
+// Their row walks are cgp_dir_rows and cgp_update_rows below, which the folded k_cgpf_dir / k_cgpf_update call too.
 #pragma once
 #include <type_traits>
 #include "kernels_cg.hpp"
@@ -154,23 +155,20 @@ struct CgpRaw1 {
     double r, inv, p;
 };
 
-// Launch A.  p_out = r inv + beta p_in and q = A p_out on every cell of the item, partial[idx] = p_out . q.
+// ---- the row walks of the iteration: one body per step, shared by k_cgp_* and the folded k_cgpf_* (kernels_cg_fold.hpp).
+// As in kernels_cg.hpp: rows [l0, l1) of the item, two cells per lane from column `col`, the window `w`, the image's scalars
+// as values; the wave's sums are returned, valid in lane 63, and the caller stores them.
+
+// p_out = r inv + beta p_in and q = A p_out on every cell of the item; returns p_out . q.
 // Rolling window: in front of row l's arithmetic the loads of row l + 1 are issued -- its matrix rows, its halo cell and what
-// p' of row l + 2 is made of --, so a row's arithmetic never waits for what its own turn asked for.  90 VGPRs: five waves per
-// SIMD, the table form's occupancy (how the loads are written below is what keeps it there).
-__global__ __launch_bounds__(256) void k_cgp_dir(CgpPlanes A, const double *__restrict__ inv, const double *__restrict__ r,
-                                                 const double *__restrict__ p_in, double *__restrict__ p_out,
-                                                 double *__restrict__ q_out, const CgScal *__restrict__ sc, CgGeom g,
-                                                 double *__restrict__ partial)
+// p' of row l + 2 is made of --, so a row's arithmetic never waits for what its own turn asked for.  90 VGPRs in k_cgp_dir:
+// five waves per SIMD, the table form's occupancy (how the loads are written below is what keeps it there).
+__device__ __forceinline__ double cgp_dir_rows(const CgpPlanes &A, const double *__restrict__ inv, const double *__restrict__ r,
+                                               const double *__restrict__ p_in, double *__restrict__ p_out,
+                                               double *__restrict__ q_out, const CgWin &w, int nx, int col, int l0, int l1, int jh,
+                                               bool restart, double beta)
 {
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CgItem it;
-    if (!cg_item(g, wave, lane, it)) return;
-    if (sc[it.img].done) return;                                 // frozen image: no writes
-    const bool restart = sc[it.img].restart != 0;
-    const double beta = sc[it.img].beta;
-    const bool v = it.col < g.nx;
-    const int jh = cg_halo_col(g, it, lane);
+    const bool v = col < nx;
     // Loads without branches: a load that a branch may skip makes the count of loads in flight unknown where the next wait is
     // placed, and the wait becomes one for all of them.  So every lane loads from a clamped address (a lane beyond the row's
     // end reads the row's first cells, a row outside the image the nearest one inside) and what may not count is zeroed
@@ -178,9 +176,9 @@ __global__ __launch_bounds__(256) void k_cgp_dir(CgpPlanes A, const double *__re
     // Addresses: the row's first cell (uniform in the wave: a scalar base, kept apart from the lane's part by readfirstlane)
     // + the lane's byte offset in the row (32 bits, one register for every array); a 64-bit address per array and lane would
     // cost the fifth wave per SIMD.
-    const unsigned cb = v ? (unsigned)it.col * 8u : 0u, hb = (unsigned)max(jh, 0) * 8u;
-    auto row_of = [&](const double *a, int l) { return cgp_uniform(a + it.base + (size_t)min(max(l, 0), g.ny - 1) * g.nx); };
-    auto inside = [&](int l) { return v && l >= 0 && l < g.ny; };
+    const unsigned cb = v ? (unsigned)col * 8u : 0u, hb = (unsigned)max(jh, 0) * 8u;
+    auto row_of = [&](const double *a, int l) { return cgp_uniform(a + w.base + (size_t)min(max(l, w.lo), w.hi - 1) * nx); };
+    auto inside = [&](int l) { return v && l >= w.lo && l < w.hi; };
     auto raw2 = [&](int l) -> CgpRaw2 {
         CgpRaw2 o;
         o.r = cgp_gld2(row_of(r, l), cb);
@@ -214,11 +212,11 @@ __global__ __launch_bounds__(256) void k_cgp_dir(CgpPlanes A, const double *__re
         o.aN = cgp_gldc2(row_of(A.aN, l), cb);
         return o;
     };
-    const CgpRaw2 r0 = raw2(it.l0 - 1), r1 = raw2(it.l0);
-    CgpRow ma = mrow(it.l0), mb = ma;
-    CgpRaw2 rd = raw2(it.l0 + 1);                               // row l + 1
-    CgpRaw1 hd = raw1(it.l0);
-    double2 up = pn2(r0, it.l0 - 1), cur = pn2(r1, it.l0);
+    const CgpRaw2 r0 = raw2(l0 - 1), r1 = raw2(l0);
+    CgpRow ma = mrow(l0), mb = ma;
+    CgpRaw2 rd = raw2(l0 + 1);                                  // row l + 1
+    CgpRaw1 hd = raw1(l0);
+    double2 up = pn2(r0, l0 - 1), cur = pn2(r1, l0);
     unsigned act = cgp_act(r1.inv);
     double acc = 0.0;
     // Row l: its matrix is in `m`, the next row's goes into `mn` -- the two sets take turns, because a copy from one register
@@ -250,38 +248,33 @@ __global__ __launch_bounds__(256) void k_cgp_dir(CgpPlanes A, const double *__re
     };
     const std::true_type more;
     const std::false_type last;
-    int l = it.l0;
+    int l = l0;
 #pragma unroll 1
-    for (; l + 2 < it.l1; l += 2) {
+    for (; l + 2 < l1; l += 2) {
         step(more, l, ma, mb);
         step(more, l + 1, mb, ma);
     }
-    if (l + 1 < it.l1) {
+    if (l + 1 < l1) {
         step(more, l, ma, mb);
         step(last, l + 1, mb, ma);
     } else step(last, l, ma, mb);
-    const double s = wave_sum_to_lane63(acc);
-    if (lane == 63) partial[it.idx] = s;
+    return wave_sum_to_lane63(acc);
 }
 
 struct CgpUpd {
     double2 p, q, x, r, inv;
 };
 
-// Launch B.  x += alpha p, r -= alpha q; partial_rz[idx] = r.(r inv), partial_rr[idx] = r.r of the updated r.
-__global__ __launch_bounds__(256) void k_cgp_update(const double *__restrict__ inv, const double *__restrict__ p,
-                                                    const double *__restrict__ qv, double *x, double *r, const CgScal *__restrict__ sc, CgGeom g,
-                                                    double *__restrict__ partial_rz, double *__restrict__ partial_rr)
+// x += alpha p, r -= alpha q on the item's cells; s_rz = r.(r inv), s_rr = r.r of the updated r.  (x and r are read and
+// written through the same pointers: no __restrict__.)
+__device__ __forceinline__ void cgp_update_rows(const double *__restrict__ inv, const double *__restrict__ p,
+                                                const double *__restrict__ qv, double *x, double *r, const CgWin &w, int nx,
+                                                int col, int l0, int l1, double alpha, double &s_rz, double &s_rr)
 {
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    CgItem it;
-    if (!cg_item(g, wave, lane, it)) return;
-    if (sc[it.img].done) return;
-    const double alpha = sc[it.img].alpha;
-    const bool v = it.col < g.nx;
-    // as in k_cgp_dir: loads without branches from a scalar row base, two register sets that take turns
-    const unsigned cb = v ? (unsigned)it.col * 8u : 0u;
-    auto row_of = [&](const double *a, int l) { return cgp_uniform(a + it.base + (size_t)l * g.nx); };
+    const bool v = col < nx;
+    // as in cgp_dir_rows: loads without branches from a scalar row base, two register sets that take turns
+    const unsigned cb = v ? (unsigned)col * 8u : 0u;
+    auto row_of = [&](const double *a, int l) { return cgp_uniform(a + w.base + (size_t)l * nx); };
     auto load = [&](int l) -> CgpUpd {
         CgpUpd o;
         o.p = cgp_gld2(row_of(p, l), cb);
@@ -305,22 +298,50 @@ __global__ __launch_bounds__(256) void k_cgp_update(const double *__restrict__ i
             rr += rv.x * rv.x + rv.y * rv.y;
         }
     };
-    CgpUpd da = load(it.l0), db = da;
-    int l = it.l0;
+    CgpUpd da = load(l0), db = da;
+    int l = l0;
 #pragma unroll 1
-    for (; l + 2 < it.l1; l += 2) {
+    for (; l + 2 < l1; l += 2) {
         db = load(l + 1);
         step(l, da);
         da = load(l + 2);
         step(l + 1, db);
     }
-    if (l + 1 < it.l1) {
+    if (l + 1 < l1) {
         db = load(l + 1);
         step(l, da);
         step(l + 1, db);
     } else step(l, da);
-    const double s1 = wave_sum_to_lane63(rz);
-    const double s2 = wave_sum_to_lane63(rr);
+    s_rz = wave_sum_to_lane63(rz);
+    s_rr = wave_sum_to_lane63(rr);
+}
+
+// Launch A.  p_out = r inv + beta p_in and q = A p_out on every cell of the item, partial[idx] = p_out . q.
+__global__ __launch_bounds__(256) void k_cgp_dir(CgpPlanes A, const double *__restrict__ inv, const double *__restrict__ r,
+                                                 const double *__restrict__ p_in, double *__restrict__ p_out,
+                                                 double *__restrict__ q_out, const CgScal *__restrict__ sc, CgGeom g,
+                                                 double *__restrict__ partial)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    CgItem it;
+    if (!cg_item(g, wave, lane, it)) return;
+    if (sc[it.img].done) return;                                 // frozen image: no writes
+    const double s = cgp_dir_rows(A, inv, r, p_in, p_out, q_out, cg_win(g, it), g.nx, it.col, it.l0, it.l1,
+                                  cg_halo_col(g.nx, it.col, lane), sc[it.img].restart != 0, sc[it.img].beta);
+    if (lane == 63) partial[it.idx] = s;
+}
+
+// Launch B.  x += alpha p, r -= alpha q; partial_rz[idx] = r.(r inv), partial_rr[idx] = r.r of the updated r.
+__global__ __launch_bounds__(256) void k_cgp_update(const double *__restrict__ inv, const double *__restrict__ p,
+                                                    const double *__restrict__ qv, double *x, double *r, const CgScal *__restrict__ sc, CgGeom g,
+                                                    double *__restrict__ partial_rz, double *__restrict__ partial_rr)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    CgItem it;
+    if (!cg_item(g, wave, lane, it)) return;
+    if (sc[it.img].done) return;
+    double s1, s2;
+    cgp_update_rows(inv, p, qv, x, r, cg_win(g, it), g.nx, it.col, it.l0, it.l1, sc[it.img].alpha, s1, s2);
     if (lane == 63) { partial_rz[it.idx] = s1; partial_rr[it.idx] = s2; }
 }
 
@@ -332,7 +353,7 @@ __global__ __launch_bounds__(256) void k_cgp_resid(CgpPlanes A, const double *__
     CgItem it;
     if (!cg_item(g, wave, lane, it)) return;
     const bool v = it.col < g.nx;
-    const int jh = cg_halo_col(g, it, lane);
+    const int jh = cg_halo_col(g.nx, it.col, lane);
     auto x1 = [&](size_t q) -> double { return inv[q] != 0.0 ? x[q] : 0.0; };
     auto x2 = [&](int l, double2 &iv) -> double2 {
         double2 o = make_double2(0.0, 0.0);
@@ -370,11 +391,7 @@ __global__ __launch_bounds__(256) void k_cgp_resid(CgpPlanes A, const double *__
         icur = idn;
     }
     const double s1 = wave_sum_to_lane63(rr), s2 = wave_sum_to_lane63(rz), s3 = wave_sum_to_lane63(bb);
-    if (lane == 63) {
-        partial[3 * (size_t)it.idx] = s1;
-        partial[3 * (size_t)it.idx + 1] = s2;
-        partial[3 * (size_t)it.idx + 2] = s3;
-    }
+    if (lane == 63) cg_store3(partial, it.idx, s1, s2, s3);
 }
 
 }  // namespace deff

@@ -9,9 +9,9 @@
 // or enter in it.
 //   k_cgs_enter       pixels (staged by one H2D copy) -> the slot's pixels, 16-bit codes, wall diffusivities, linear guess:
 //                     the arithmetic of k_phase_codes, k_wall_D_2phase and k_init_linear (kernels_setup.hpp)
-//   k_cgs_admissible  k_cg_admissible's rule on the listed slots
-//   k_cgs_resid       k_cg_resid of the listed slots: the same work items (cg_item), wave sums and partials per image
-//   k_cgs_check       k_cg_check of the listed slots; the restart allowance of mode 1 is the slot's own count of rounds
+//   k_cgs_admissible  k_cg_admissible's rule (cg_cell_bad) on the listed slots
+//   k_cgs_resid       k_cg_resid of the listed slots: the same work items (cg_item) and row walk (cg_resid_rows), partials per image
+//   k_cgs_check       k_cg_check of the listed slots (cg_check_step); the restart allowance of mode 1 is the slot's own count of rounds
 //   k_cgs_flux        the wall fluxes of the listed slots and their sums {Q1, Q2} (k_wall_flux, k_flux_sum)
 // Partial sums are stored by LIST POSITION (cg_item / cg_image_sum index them by the launch's image number), images by slot.
 //
@@ -23,7 +23,7 @@
 
 namespace deff {
 
-// r = b - A x of the listed slots; g.nimg = the number of listed slots.  Body: k_cg_resid's.
+// r = b - A x of the listed slots; g.nimg = the number of listed slots.  cg_resid_rows on the slot's window.
 __global__ __launch_bounds__(256) void k_cgs_resid(const double *__restrict__ tab_g, int nrows, const uint16_t *__restrict__ code,
                                                    double *__restrict__ x, double *__restrict__ r, CgGeom g,
                                                    const int *__restrict__ list, double *__restrict__ partial)
@@ -33,49 +33,10 @@ __global__ __launch_bounds__(256) void k_cgs_resid(const double *__restrict__ ta
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     CgItem it;
     if (!cg_item(g, wave, lane, it)) return;
-    it.base = (size_t)list[it.img] * g.ny * g.nx;                // the cells of the listed slot; it.idx stays the list's
-    const bool v = it.col < g.nx;
-    const int jh = cg_halo_col(g, it, lane);
-    auto x1 = [&](size_t q) -> double { return cg_v<CG_INV>(tab, code[q]) != 0.0 ? x[q] : 0.0; };
-    auto x2 = [&](int l) -> double2 {
-        double2 o = make_double2(0.0, 0.0);
-        if (v && l >= 0 && l < g.ny) {
-            const size_t q = it.base + (size_t)l * g.nx + it.col;
-            const unsigned cw = *reinterpret_cast<const unsigned *>(code + q);
-            const double2 xx = *reinterpret_cast<const double2 *>(x + q);
-            o.x = cg_v<CG_INV>(tab, cw & 0xFFFFu) != 0.0 ? xx.x : 0.0;
-            o.y = cg_v<CG_INV>(tab, cw >> 16) != 0.0 ? xx.y : 0.0;
-        }
-        return o;
-    };
-    double2 up = x2(it.l0 - 1), cur = x2(it.l0);
-    double rr = 0.0, rz = 0.0, bb = 0.0;
-#pragma unroll 1
-    for (int l = it.l0; l < it.l1; ++l) {
-        const double2 dn = x2(l + 1);
-        const size_t q = it.base + (size_t)l * g.nx + it.col;
-        const double h = jh >= 0 ? x1(it.base + (size_t)l * g.nx + jh) : 0.0;
-        const unsigned cw = v ? *reinterpret_cast<const unsigned *>(code + q) : 0u;
-        const unsigned o0 = cw & 0xFFFFu, o1 = cw >> 16;
-        const double2 ax = cg_apply(tab, o0, o1, cur, up, dn, h);
-        if (v) {
-            const double b0 = cg_v<CG_B>(tab, o0), b1 = cg_v<CG_B>(tab, o1);
-            const double2 rv = make_double2(b0 - ax.x, b1 - ax.y);
-            *reinterpret_cast<double2 *>(r + q) = rv;
-            *reinterpret_cast<double2 *>(x + q) = cur;
-            rr += rv.x * rv.x + rv.y * rv.y;
-            rz += rv.x * (rv.x * cg_v<CG_INV>(tab, o0)) + rv.y * (rv.y * cg_v<CG_INV>(tab, o1));
-            bb += b0 * b0 + b1 * b1;
-        }
-        up = cur;
-        cur = dn;
-    }
-    const double s1 = wave_sum_to_lane63(rr), s2 = wave_sum_to_lane63(rz), s3 = wave_sum_to_lane63(bb);
-    if (lane == 63) {
-        partial[3 * (size_t)it.idx] = s1;
-        partial[3 * (size_t)it.idx + 1] = s2;
-        partial[3 * (size_t)it.idx + 2] = s3;
-    }
+    const CgWin w{(size_t)list[it.img] * g.ny * g.nx, 0, g.ny};  // the cells of the listed slot; it.idx stays the list's
+    double s1, s2, s3;
+    cg_resid_rows(tab, code, x, r, w, g.nx, it.col, it.l0, it.l1, cg_halo_col(g.nx, it.col, lane), s1, s2, s3);
+    if (lane == 63) cg_store3(partial, it.idx, s1, s2, s3);
 }
 
 // after k_cgs_resid, one workgroup per listed slot.  mode 0: the slot's image starts (its rounds count from 0);  mode 1: the
@@ -87,30 +48,14 @@ __global__ __launch_bounds__(CG_FIN) void k_cgs_check(const double *__restrict__
 {
     __shared__ double ws[4];
     const int slot = list[blockIdx.x];
-    CgScal &s = sc[slot];
-    const double rr = cg_image_sum(part, per_img, 3, 0, ws);
-    const double rz = cg_image_sum(part, per_img, 3, 1, ws);
-    const double bb = cg_image_sum(part, per_img, 3, 2, ws);
+    const double *pp = part + (size_t)blockIdx.x * per_img * 3;
+    const double rr = cg_image_sum(pp, per_img, 3, 0, ws);
+    const double rz = cg_image_sum(pp, per_img, 3, 1, ws);
+    const double bb = cg_image_sum(pp, per_img, 3, 2, ws);
     if (threadIdx.x != 0) return;
-    s.rr = rr;
-    s.rel = bb > 0.0 ? __builtin_sqrt(rr) / __builtin_sqrt(bb) : (rr == 0.0 ? 0.0 : __builtin_inf());
-    const bool ok = rr <= tol2 * bb;
-    if (mode == 0) {
-        s.bb = bb;
-        s.iters = 0;
-        s.rho = rz;
-        s.alpha = 0.0;
-        s.beta = 0.0;
-        s.restart = 1;
-        s.done = ok ? 1 : (max_iter <= 0 ? 2 : 0);
-        rounds[slot] = 0;
-    } else if (!ok && rounds[slot] < max_rounds && s.iters < max_iter) {
-        s.rho = rz;
-        s.beta = 0.0;
-        s.restart = 1;
-        s.done = 0;
-        rounds[slot] += 1;
-    }
+    const bool again = cg_check_step(sc[slot], rr, rz, bb, tol2, max_iter, mode, rounds[slot] < max_rounds);
+    if (mode == 0) rounds[slot] = 0;
+    else if (again) rounds[slot] += 1;
 }
 
 // Entry of the listed slots: image `blockIdx.y` of the staging buffer becomes the image of slot list[blockIdx.y].
@@ -159,27 +104,10 @@ __global__ __launch_bounds__(256) void k_cgs_admissible(const double *__restrict
     const size_t n = (size_t)nx * ny;
     const uint16_t *cd = code + (size_t)list[blockIdx.y] * n;
     bool bad = false;
-    auto same = [](double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); };
     for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (size_t)gridDim.x * 256) {
-        const unsigned me = cd[p];
-        if (cg_v<CG_INV>(tab, me) == 0.0) continue;
+        if (cg_v<CG_INV>(tab, cd[p]) == 0.0) continue;
         const int li = (int)(p / nx), j = (int)(p - (size_t)li * nx);
-        if (j > 0) {
-            const unsigned o = cd[p - 1];
-            if (cg_v<CG_INV>(tab, o) != 0.0) bad |= !same(cg_v<CG_W>(tab, me), cg_v<CG_E>(tab, o));
-        } else bad |= cg_v<CG_W>(tab, me) != 0.0;
-        if (j + 1 < nx) {
-            const unsigned o = cd[p + 1];
-            if (cg_v<CG_INV>(tab, o) != 0.0) bad |= !same(cg_v<CG_E>(tab, me), cg_v<CG_W>(tab, o));
-        } else bad |= cg_v<CG_E>(tab, me) != 0.0;
-        if (li > 0) {
-            const unsigned o = cd[p - nx];
-            if (cg_v<CG_INV>(tab, o) != 0.0) bad |= !same(cg_v<CG_N>(tab, me), cg_v<CG_S>(tab, o));
-        } else bad |= cg_v<CG_N>(tab, me) != 0.0;
-        if (li + 1 < ny) {
-            const unsigned o = cd[p + nx];
-            if (cg_v<CG_INV>(tab, o) != 0.0) bad |= !same(cg_v<CG_S>(tab, me), cg_v<CG_N>(tab, o));
-        } else bad |= cg_v<CG_S>(tab, me) != 0.0;
+        bad |= cg_cell_bad(tab, cd, p, j, nx, li > 0 ? CG_NEIGHBOUR : CG_WALL, li + 1 < ny ? CG_NEIGHBOUR : CG_WALL);
     }
     if (bad) atomicOr(flag, 1u);
 }
