@@ -12,6 +12,7 @@
 #include <algorithm>
 #include "driver/jpeg_gray.hpp"
 #include "flood_fill.hpp"
+#include "row_index3.hpp"
 
 // ------------------------------------------------------------- errors -----
 
@@ -122,7 +123,8 @@ try {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *bufs[] = {c->pix, c->a0, c->c0, c->aW, c->aE, c->aS, c->aN, c->b, c->code, c->lut,
-                    c->Dl, c->Dr, c->mf, c->x[0], c->x[1], c->scratch, c->active};
+                    c->Dl, c->Dr, c->mf, c->x[0], c->x[1], c->scratch, c->active,
+                    c->fill_open, c->fill_reach, c->fill_status, c->fill_changed};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (c->mf_host) (void)hipHostFree(c->mf_host);
     if (c->q) (void)hipFree(c->q);
@@ -299,6 +301,11 @@ try {
                                      "has no dictionary) or 2 (always on the coefficient planes)");
         c->cg_planes = value;
     }
+    else if (!strcmp(key, "fill_impl")) {
+        if (value > 2) return fail(DEFF_EINVAL, "fill_impl takes 0 (by size), 1 (one workgroup per image) or 2 (row tiles)");
+        c->fill_impl = value;
+    }
+    else if (!strcmp(key, "fill_tile_rows")) c->fill_tile_rows = value;
     else if (!strcmp(key, "cg_fold")) {
         if (value > 2)
             return fail(DEFF_EINVAL, "cg_fold takes 0 (four launches per CG iteration), 1 (two: the per-image sums are taken by the "
@@ -343,6 +350,12 @@ try {
     else if (!strcmp(key, "cgs_waits")) *value = c->cgs_waits;
     else if (!strcmp(key, "res_kt")) *value = c->res_plan_kt;
     else if (!strcmp(key, "res_items")) *value = c->res_plan_items;
+    else if (!strcmp(key, "fill_impl")) *value = c->fill_plan_impl;
+    else if (!strcmp(key, "fill_launches")) *value = c->fill_plan_launches;
+    else if (!strcmp(key, "fill_rounds")) *value = c->fill_plan_rounds;
+    else if (!strcmp(key, "fill_runs")) *value = c->fill_runs;
+    else if (!strcmp(key, "fill_fallbacks")) *value = c->fill_fallbacks;
+    else if (!strcmp(key, "native3_rows")) *value = c->native3 ? NATIVE3_ROWS : 0;
     else return fail(DEFF_EINVAL, "unknown plan key '%s'", key);
     return DEFF_OK;
 }
@@ -360,6 +373,7 @@ int image_shape(deff_ctx *c, int W, int H, int ampX, int ampY)
     if (c->pix && (c->W != W || c->H != H)) { HIP_TRY(hipFree(c->pix)); c->pix = nullptr; }
     TRY(dev_alloc(&c->pix, (size_t)W * H * c->nimg));
     c->W = W; c->H = H; c->ampX = ampX; c->ampY = ampY;
+    c->fill_valid = false; c->codes3_valid = false;   // new pixels follow: the fill and its codes are the old image's
     return DEFF_OK;
 }
 
@@ -411,6 +425,7 @@ DEFF_API_CATCH
 // same routine the device assembly uses, so it holds the very same doubles.  Row 0 = zeros.
 void build_lut_rows(deff_ctx *c, double Ds, double Df, double CL, double CR)
 {
+    c->native3 = false; c->codes3_valid = false;       // the 2-phase system takes over the table and the codes
     c->lut_nrows = LUT_NATIVE_ROWS;
     c->lut_rows.assign((size_t)c->lut_nrows * 6, 0.0);
     for (int ycls = 0; ycls < 3; ++ycls)
@@ -490,6 +505,7 @@ int explicit_from_image(deff_ctx *c)
 {
     if (c->have_explicit) return DEFF_OK;
     if (!c->have_matfree) return fail(DEFF_ESTATE, "no system assembled");
+    if (c->native3) return native3_explicit(c);
     TRY(ensure_explicit(c));
     TRY(ensure_scratch(c, sizeof(double) * c->n));
     double *D = (double *)c->scratch;
@@ -537,7 +553,7 @@ try {
     HIP_TRY(hipStreamSynchronize(c->stream));        // Grid may be freed by the caller
     c->have_explicit = true; c->c0_omega = NAN; c->have_walls = true;
     c->phase_mode = 3; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = Dg;
-    c->have_matfree = false; c->dict_tried = false; c->wrap_links = false;
+    c->have_matfree = false; c->dict_tried = false; c->wrap_links = false; c->native3 = false;
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -602,7 +618,7 @@ try {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_explicit = true; c->c0_omega = NAN; c->have_walls = true;
     c->phase_mode = 0;
-    c->have_matfree = false; c->dict_tried = false; c->wrap_links = false;
+    c->have_matfree = false; c->dict_tried = false; c->wrap_links = false; c->native3 = false;
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -656,7 +672,7 @@ try {
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_explicit = true; c->c0_omega = NAN;
-    c->have_matfree = false; c->dict_tried = false;
+    c->have_matfree = false; c->dict_tried = false; c->native3 = false;
     c->wrap_links = wrap;
     return DEFF_OK;
 }

@@ -56,6 +56,7 @@ static int try_dict(deff_ctx *c)
     const int nrows = (int)ents.size();
     hipLaunchKernelGGL(k_dict_gather, dim3((nrows + 255) / 256), dim3(256), 0, c->stream, planes, d_cells, nrows, d_rows);
     TRY(dev_alloc(&c->code, c->n));
+    c->codes3_valid = false;
     hipLaunchKernelGGL(k_dict_encode, dim3(grid_for(c->n, 4096)), dim3(256), 0, c->stream, planes, c->n, c->nx, c->nxt, t,
                        d_slot2code, c->code);
     HIP_TRY(hipGetLastError());

@@ -3,6 +3,7 @@
 // (JacobiCheck, check_step, deff_of_fluxes), which every Jacobi solve loop uses.
 //   api_core.hip   library, context lifecycle, image, assembly (native / from D / imported), field
 //   api_dict.hip   the row dictionary harvested from an explicit system
+//   api_fill.hip   the flood fill on the device and the native 3-phase assembly on it (codes + a-priori row table)
 //   api_sweep.hip  everything that plans or launches a sweep: the planner, the dealt tiles, the resident-launch
 //                  protocol, the launchers, deff_sweeps; the streaming and single-sweep kernels
 //   tiles_8wave.hip, tiles_tall.hip, tiles_12wave.hip
@@ -267,6 +268,23 @@ struct deff_ctx {
     // ev0 / ev1 belong to the solve loops alone, which read them at every check and may call the residual in between
     // (a deff_set_progress or deff_image_done_fn callback)
     hipEvent_t resid_ev0 = nullptr, resid_ev1 = nullptr;
+
+    // Native 3-phase system (kernels_fill.hpp, api_fill.hip): the flood fill of the pore space as bitmaps -- one `open` and
+    // one `reach` word per 64 columns of a row, fill_nw words per row --, its status words and the tiled form's `changed` words.
+    // fill_valid: reach is the fill of the current pixels (image_shape clears it: every new image goes through there);
+    // codes3_valid: code[] holds the native 3-phase codes of that fill (cleared by whoever else writes code[]);
+    // native3: the current system is the native 3-phase one (its explicit planes are built on demand, explicit_from_image)
+    uint64_t *fill_open = nullptr, *fill_reach = nullptr;
+    int *fill_status = nullptr;
+    unsigned *fill_changed = nullptr;
+    int fill_nw = 0;
+    bool fill_valid = false, codes3_valid = false, native3 = false;
+    std::vector<int> fill_path;                  // PathFlag per image
+    unsigned rows3_used[16] = {};                // bit k: some cell of the current image has table row k (k_phase_codes3)
+    int fill_impl = 0, fill_tile_rows = 0;       // tuning: form (0 = by size, 1 = one workgroup per image, 2 = tiles), rows per tile
+    // deff_get_plan: form and launches of the last fill, fills computed and images handed to the host fill since creation
+    int fill_plan_impl = 0, fill_plan_launches = 0, fill_runs = 0, fill_fallbacks = 0;
+    int fill_plan_rounds = 0;                    // most rounds a workgroup of the last fill took ("fill_rounds")
 };
 
 static inline int use_device(const deff_ctx *c)
@@ -434,6 +452,8 @@ void build_lut_rows(deff_ctx *c, double Ds, double Df, double CL, double CR);
 int upload_lut(deff_ctx *c, double omega);
 int consolidate(deff_ctx *c);
 int explicit_from_image(deff_ctx *c);
+// api_fill.hip
+int native3_explicit(deff_ctx *c);                       // explicit planes of the native 3-phase system
 // api_dict.hip
 int ensure_dictionary(deff_ctx *c);                      // harvest the row dictionary of an explicit system, if allowed
 // api_sweep.hip

@@ -125,6 +125,7 @@ static int g_cg_batch = 0;         // --cg-batch B: 2-phase batch mode solves ru
 static bool g_cg_slabs = false;    // --cg-slabs: --solver cg on row slabs (deff_slab_group_solve_cg)
 static int g_cg_stream = 0;        // --cg-stream B: ... keeps B slots full instead (deff_solve_cg_stream)
 static int g_cg_fold = 0;          // --cg-fold N: the tuning key "cg_fold" of every context that runs CG
+static bool g_fill_device = false; // --fill device: 3 phases through deff_assemble_3phase_native (flood fill and row codes on the GPU)
 
 struct Session {                   // one solver context, re-created only when the mesh / batch size changes
     deff_ctx *ctx = nullptr;
@@ -189,9 +190,11 @@ struct OneGpu {
     bool residual(double *r) { CK(deff_residual(S.ctx, r, nullptr)); return true; }
     bool assemble3(const Options &o, double DCG, const unsigned int *grid)
     {
-        CK(deff_assemble_3phase(S.ctx, o.DCsolid, o.DCfluid, DCG, grid, o.CLeft, o.CRight));
+        if (g_fill_device) CK(deff_assemble_3phase_native(S.ctx, o.DCsolid, o.DCfluid, DCG, o.CLeft, o.CRight));
+        else CK(deff_assemble_3phase(S.ctx, o.DCsolid, o.DCfluid, DCG, grid, o.CLeft, o.CRight));
         return true;
     }
+    bool device_path(int *path) { CK(deff_get_grid(S.ctx, nullptr, path)); return true; }   // --fill device: after an assembly
     bool solve_with(const Options &o, double tol, int64_t max_iter, bool show, double *scale, deff_result *r)
     {
         if (g_solver_cg) { CK(solve_cg(S.ctx, max_iter, r)); return true; }
@@ -247,6 +250,7 @@ struct Slabs {
         CK(deff_slab_group_assemble_3phase(g, o.DCsolid, o.DCfluid, DCG, grid, o.CLeft, o.CRight));
         return true;
     }
+    bool device_path(int *) { return false; }                        // (--fill device is refused for row slabs)
     bool solve_with(const Options &, double tol, int64_t max_iter, bool, double *, deff_result *r)
     {
         if (g_solver_cg) { CK(solve_cg(max_iter, r)); return true; }
@@ -315,8 +319,13 @@ static bool solve_3phase(Target &&T, const Image &im, const Options &o, Row *row
 {
     const int nx = im.W * o.MeshIncreaseX, ny = im.H * o.MeshIncreaseY;
     row->nElements = nx * ny;
-    std::vector<unsigned int> grid = grid_of(im, o, 200);
-    CK(deff_flood_fill(grid.data(), nx, ny, &row->path));
+    // --fill device: the pixels are uploaded once (T.open), every stage is a native assembly -- the fill is computed by the
+    // first one, the later ones rebuild the row table only -- and PathFlag comes back from the device
+    std::vector<unsigned int> grid;
+    if (!g_fill_device) {
+        grid = grid_of(im, o, 200);
+        CK(deff_flood_fill(grid.data(), nx, ny, &row->path));
+    }
     if (!T.open(im, o, nx, ny)) return false;
     const double DCF = o.DCfluid, DCG = o.DCgas, DCS = o.DCsolid;
     int stage_no = 1;
@@ -342,6 +351,7 @@ static bool solve_3phase(Target &&T, const Image &im, const Options &o, Row *row
         row->SVF = s; row->LVF = l;
     }
     if (!T.assemble3(o, DCG, grid.data())) return false;
+    if (g_fill_device && !T.device_path(&row->path)) return false;
     deff_result r;
     double scale = DCF;
     if (!T.solve_with(o, o.ConvergeCriteria, o.MAX_ITER, true, &scale, &r)) return false;
@@ -369,14 +379,16 @@ static bool solve_3phase_group(Session &S, const std::vector<Image> &ims, const 
     if (!S.prepare(nx, ny, B)) return false;
     const size_t npix = (size_t)ims[0].W * ims[0].H, ncell = (size_t)nx * ny;
     std::vector<uint8_t> stack(npix * B);
-    std::vector<unsigned int> grid(ncell * B);
+    std::vector<unsigned int> grid(g_fill_device ? 0 : ncell * B);
     const double DCF = o.DCfluid, DCG = o.DCgas, DCS = o.DCsolid;
     for (int k = 0; k < B; ++k) {
         std::memcpy(&stack[npix * k], ims[k].pix.data(), npix);
         rows[k].nElements = nx * ny;
-        std::vector<unsigned int> g = grid_of(ims[k], o, 200);
-        CK(deff_flood_fill(g.data(), nx, ny, &rows[k].path));
-        std::memcpy(&grid[ncell * k], g.data(), sizeof(unsigned int) * ncell);
+        if (!g_fill_device) {
+            std::vector<unsigned int> g = grid_of(ims[k], o, 200);
+            CK(deff_flood_fill(g.data(), nx, ny, &rows[k].path));
+            std::memcpy(&grid[ncell * k], g.data(), sizeof(unsigned int) * ncell);
+        }
         const double total = (double)ncell;                          // calcFracts3D, cuh:411-448
         double s = 0, l = 0;
         for (int i = 0; i < ny; ++i)
@@ -391,12 +403,22 @@ static bool solve_3phase_group(Session &S, const std::vector<Image> &ims, const 
     CK(deff_set_image(S.ctx, stack.data(), ims[0].W, ims[0].H, o.MeshIncreaseX, o.MeshIncreaseY));
     CK(deff_init_linear(S.ctx, o.CLeft, o.CRight));
     std::vector<deff_result> res(B);
+    // --fill device: the stack's fill is computed on the GPU by the first native assembly, every later stage rebuilds the table
+    auto assemble = [&](double g) {
+        return g_fill_device ? deff_assemble_3phase_native(S.ctx, DCS, DCF, g, o.CLeft, o.CRight)
+                             : deff_assemble_3phase(S.ctx, DCS, DCF, g, grid.data(), o.CLeft, o.CRight);
+    };
     for (double g = 10; g < DCG; g *= 10) {                          // JacobiGPUPreCond stages, cuh:2184-2326
-        CK(deff_assemble_3phase(S.ctx, DCS, DCF, g, grid.data(), o.CLeft, o.CRight));
+        CK(assemble(g));
         CK(deff_solve_batch(S.ctx, 2.0 / 3.0, o.ConvergeCriteria * 10, g_precond_maxiter, 10000, res.data(), nullptr, nullptr));
         for (int k = 0; k < B; ++k) rows[k].stages.push_back((long)res[k].iters);
     }
-    CK(deff_assemble_3phase(S.ctx, DCS, DCF, DCG, grid.data(), o.CLeft, o.CRight));
+    CK(assemble(DCG));
+    if (g_fill_device) {
+        std::vector<int> path(B);
+        CK(deff_get_grid(S.ctx, nullptr, path.data()));
+        for (int k = 0; k < B; ++k) rows[k].path = path[k];
+    }
     CK(deff_solve_batch(S.ctx, 2.0 / 3.0, o.ConvergeCriteria, o.MAX_ITER, 10000, res.data(), nullptr, nullptr));
     for (int k = 0; k < B; ++k) {
         rows[k].stages.push_back((long)res[k].iters);
@@ -782,8 +804,16 @@ int main(int argc, char **argv)
             cg_fold_given = true;
         }
         else if (s == "--cg-slabs") g_cg_slabs = true;
+        else if (s == "--fill" && a + 1 < argc) {
+            const std::string v = argv[++a];
+            if (v != "host" && v != "device") { std::fprintf(stderr, "deff2d: --fill host|device\n"); return 2; }
+            g_fill_device = v == "device";
+        }
         else if (s == "-h" || s == "--help") {
-            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B] [--cg-stream B] [--cg-slabs] [--cg-fold N]\n"
+            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B] [--cg-stream B] [--cg-slabs] [--cg-fold N] [--fill host|device]\n"
+                        "--fill device (3 phases, one GPU per image): the flood fill of the pore space and the row codes are computed on the\n"
+                        "GPU from the pixels (deff_assemble_3phase_native) and every continuation stage rebuilds a table of 452 rows only;\n"
+                        "host (default) = flood fill on the host and an explicit assembly per stage.  The same results bit for bit.\n"
                         "--cg-slabs (with --solver cg, RunBatch 0 and --devices a,b,...): conjugate gradients over the row slabs; the dot\n"
                         "products are summed slab by slab, so the result agrees with the one-GPU solve to rounding, not bit for bit.\n"
                         "--cg-batch B (with --solver cg, RunBatch 1, 2 phases): runs of up to B consecutive, equally sized images are solved\n"
@@ -826,6 +856,16 @@ int main(int argc, char **argv)
     if (!deff::read_input_file(input.c_str(), &o, &err)) { std::fprintf(stderr, "deff2d: %s\n", err.c_str()); return 1; }
     if (o.verbose == 1) deff::print_options(o);
 
+    if (g_fill_device && o.nPhase == 2) {
+        std::fprintf(stderr, "deff2d: --fill device applies to 3 phases: the 2-phase system is assembled on the device already and its "
+                             "PathFlag is not part of the solve\n");
+        return 2;
+    }
+    if (g_fill_device && (g_cg_slabs || (!o.BatchFlag && devices.size() >= 2))) {
+        std::fprintf(stderr, "deff2d: --fill device does not run over row slabs (--devices with RunBatch 0, --cg-slabs): the fill is a "
+                             "property of the whole image, a slab holds a window of it\n");
+        return 2;
+    }
     if (g_cg_slabs && (o.BatchFlag || devices.size() < 2)) {
         std::fprintf(stderr, "deff2d: --cg-slabs needs a row-slab run: RunBatch 0 and --devices with two or more entries\n");
         return 2;

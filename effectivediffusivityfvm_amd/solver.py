@@ -142,6 +142,18 @@ class Solver:
             g = grid.ctypes.data_as(C.c_void_p)
         check(self._L.deff_assemble_3phase(self._ctx, Ds, Df, Dg, g, CL, CR))
 
+    def assemble_3phase_native(self, Ds, Df, Dg, CL, CR):
+        """The 3-phase system with the flood-filled Grid, assembled on the device from the pixels: flood fill on bitmaps, row
+        codes, an a-priori table of 452 rows.  A further call on the same image (a continuation stage) rebuilds the table only."""
+        check(self._L.deff_assemble_3phase_native(self._ctx, Ds, Df, Dg, CL, CR))
+
+    def grid(self):
+        """The device fill of the current image: (grid[nimg*ny, nx] uint32 in FloodFill's encoding, path[nimg] bool)."""
+        g = np.empty((self.rows, self.nx), dtype=np.uint32)
+        path = np.zeros(self.nimg, dtype=np.int32)
+        check(self._L.deff_get_grid(self._ctx, g.ctypes.data_as(C.c_void_p), path.ctypes.data_as(C.c_void_p)))
+        return g, path.astype(bool)
+
     def assemble_from_D(self, D, CL, CR, grid=None):
         D = np.ascontiguousarray(D, dtype=np.float64)
         g = None

@@ -92,6 +92,10 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  *   values above 2 are DEFF_EINVAL; see there),
  * "cg_fold" (deff_solve_cg / deff_solve_cg_stream: 1 = two launches per iteration instead of four, 2 = as 1 with loads a row
  *   ahead; values above 2 are DEFF_EINVAL; see deff_solve_cg),
+ * "fill_impl" (deff_assemble_3phase_native: form of the flood fill on the device, 0 = by size, 1 = one workgroup per image,
+ *   2 = row tiles over several launches; values above 2 are DEFF_EINVAL, 1 on an image whose bitmaps do not fit one
+ *   workgroup is DEFF_EINVAL at the assembly) and "fill_tile_rows" (rows per tile of form 2, 0 = the planner's choice; clipped
+ *   to the image and to what fits a workgroup) -- both exist so that the tiled form and its seams can be tested at small shapes,
  * "res_kt" (deff_residual / deff_residual_slot: tiles of 8 rows one wave streams through, a "run"; 0 = the planner's choice,
  *   about 4 096 work items per launch; clipped to the image's tile rows; deff_get_plan "res_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
@@ -115,7 +119,11 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * last deff_residual / deff_residual_slot / deff_residual_D that launched (0 before one; a refused call leaves them alone):
  * "res_kt" (tiles of 8 rows per run as used: after the planner, the tuning key and the clip to the image's tile rows;
  * 0 after deff_residual_D, which has no runs) and "res_items" (partial sums added per image by the final reduction:
- * strips of 128 columns x ceil(tile rows / res_kt), or for deff_residual_D rows x segments of 256 columns) */
+ * strips of 128 columns x ceil(tile rows / res_kt), or for deff_residual_D rows x segments of 256 columns).  Of the flood fill
+ * on the device (deff_assemble_3phase_native): "fill_impl" (form of the last fill: 1 = one workgroup per image, 2 = row tiles),
+ * "fill_launches" (kernel launches of the last fill), "fill_rounds" (most rounds one workgroup of it took), "fill_runs" (fills
+ * computed since the context was created: a continuation stage on the same image computes none), "fill_fallbacks" (images
+ * handed to the host fill since then) and "native3_rows" (452 while the system is the native 3-phase one, else 0) */
 int deff_get_plan(deff_ctx *ctx, const char *key, int *value);
 
 /* ---- image -> phases: replaces the mask->D loops cuh:1988-2000 (2-phase),
@@ -145,6 +153,22 @@ int deff_assemble_3phase(deff_ctx *ctx, double Ds, double Df, double Dg, const u
 /* FloodFill cuh:557-713 on the host, linear time: Grid[n] (1 = solid) gets 2 where the pore
  * space is not connected to the left wall; *path_flag = PathFlag.  Needs no context. */
 int deff_flood_fill(unsigned int *Grid, int nx, int ny, int *path_flag);
+/* native 3-phase path: the 3-phase system with the flood-filled Grid (what deff_flood_fill on `pixel > 200` followed by
+ * deff_assemble_3phase gives, the same doubles) without leaving the device.  The connectivity of the pore space is computed
+ * from the context's pixels by a flood fill on bitmaps (per image of a stack: 4-connected, periodic between the image's
+ * first and last row, seeded from column 0, the reference's right-column quirk cuh:601 included); every cell gets a 16-bit
+ * row code and the row table is enumerated a priori (452 rows: identity for Grid 1 / 2, else the cell's phase and its
+ * existing neighbours' pixel classes per position class).  The fill is computed when the context has none for its current
+ * image (deff_set_image / deff_synth_image invalidate it); a further call on the same image -- a continuation stage with
+ * another Dg -- rebuilds the table and the wall diffusivities only.  Explicit planes are built on demand (deff_get_system,
+ * DEFF_KERNEL_EXPLICIT / _SCALAR, "cg_planes").  Everything downstream runs as on a harvested 3-phase dictionary and gives
+ * the same bits.  An image the device fill cannot finish within its launch budget is filled on the host (deff_get_plan
+ * "fill_fallbacks"), which is not an error.  Row-slab contexts: DEFF_EINVAL; no image: DEFF_ESTATE; a refusal leaves the
+ * field and the previous system as they were.  Tuning keys "fill_impl", "fill_tile_rows". */
+int deff_assemble_3phase_native(deff_ctx *ctx, double Ds, double Df, double Dg, double CL, double CR);
+/* the device fill of the current image in FloodFill's encoding (0 reached, 1 solid, 2 not reached) and the PathFlag of
+ * every image (the flags are on the host already: with Grid NULL nothing is copied); DEFF_ESTATE before a fill exists */
+int deff_get_grid(deff_ctx *ctx, unsigned int *Grid /* nimg*ny*nx, may be NULL */, int *path_flag /* [nimg], may be NULL */);
 /* host-assembled system as the reference passes it to JacobiGPU (cuh:1163):
  * A[n*5] AoS, b[n], D[n] (only its first and last column are read, cuh:1256-1257) */
 int deff_set_system(deff_ctx *ctx, const double *A, const double *b, const double *D,
