@@ -122,7 +122,7 @@ try {
     if (!c) return DEFF_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void *bufs[] = {c->pix, c->a0, c->c0, c->aW, c->aE, c->aS, c->aN, c->b, c->code, c->lut,
+    void *bufs[] = {c->pix, c->a0, c->c0, c->aW, c->aE, c->aS, c->aN, c->b, c->code, c->lut, c->lut_pre,
                     c->Dl, c->Dr, c->mf, c->x[0], c->x[1], c->scratch, c->active,
                     c->fill_open, c->fill_reach, c->fill_status, c->fill_changed};
     for (void *p : bufs) if (p) (void)hipFree(p);
@@ -280,6 +280,11 @@ try {
     else if (!strcmp(key, "dict")) c->dict_enabled = value ? 1 : 0;
     else if (!strcmp(key, "tb_xmajor")) c->tb_xmajor = value ? 1 : 0;
     else if (!strcmp(key, "fma")) c->fma = value ? 1 : 0;
+    else if (!strcmp(key, "prescaled")) {
+        if (c->slab) return fail(DEFF_EINVAL, "prescaled: not for row-slab contexts (the slab passes have no pre-scaled form)");
+        if (value > 1) return fail(DEFF_EINVAL, "prescaled takes 0 (the reference's arithmetic, or its contracted form with fma = 1) or 1 (pre-scaled five-FMA sweeps)");
+        c->prescaled = value;
+    }
     else if (!strcmp(key, "tb_wall_halo")) c->tb_wall_halo = value > 2 ? 2 : value;
     else if (!strcmp(key, "tb_wg")) c->tb_wg = (value + 7) / 8 * 8;
     else if (!strcmp(key, "tb_ranked")) { c->tb_ranked = value ? 1 : 0; c->tb_rank_lost = 0; }
@@ -332,6 +337,7 @@ try {
     else if (!strcmp(key, "tb_sym")) *value = c->links_sym;
     else if (!strcmp(key, "tb_NW")) *value = c->plan_NW;
     else if (!strcmp(key, "tb_fallbacks")) *value = c->res_fallbacks;
+    else if (!strcmp(key, "prescaled")) *value = c->plan_prescaled;
     else if (!strcmp(key, "tb_ranked")) *value = c->plan_ranked;
     else if (!strcmp(key, "tb_chain")) *value = c->plan_chain;
     else if (!strcmp(key, "tb_chunk_min")) *value = c->plan_ranked ? c->tb_dealt_min : 0;   // dealt tiles: rows of the shortest / tallest chunk
@@ -464,6 +470,30 @@ int upload_lut(deff_ctx *c, double omega)
     // diffuse made a singular row) the guarded kernels keep its skip semantics.
     c->lut_guard = guard;
     c->lut_omega = omega;
+    c->lut_pre_omega = NAN;                     // another dictionary or another omega: the pre-scaled table is the old one's
+    return DEFF_OK;
+}
+
+// The pre-scaled table for the same omega (kernels_sweep.hpp, pre_cell): aK' = c0 * aK, b' = c0 * b with c0 = omega / A0, the
+// double upload_lut put into plane 0 -- one rounded product each (this file is built with contraction off).  Row 0 stays zeros.
+int upload_lut_pre(deff_ctx *c, double omega)
+{
+    if (c->lut_pre_omega == omega) return DEFF_OK;
+    std::vector<double> t(LUT_DOUBLES, 0.0);
+    bool allb = false;
+    for (int k = 1; k < c->lut_nrows; ++k) {
+        const double *row = &c->lut_rows[(size_t)k * 6];
+        const double c0 = omega / row[0];
+        for (int pl = 1; pl < LUT_PLANES; ++pl) t[(size_t)pl * LUT_PLANE_STRIDE + k] = c0 * row[pl];
+        // a strip without a wall column passes +0.0 for b' instead of looking it up: only if that is what the table holds
+        const double bp = t[(size_t)5 * LUT_PLANE_STRIDE + k];
+        if (row[5] == 0.0 && (bp != 0.0 || std::signbit(bp))) allb = true;
+    }
+    TRY(dev_alloc(&c->lut_pre, (size_t)LUT_DOUBLES));
+    HIP_TRY(hipMemcpyAsync(c->lut_pre, t.data(), sizeof(double) * LUT_DOUBLES, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // `t` goes out of scope
+    c->lut_pre_allb = allb;
+    c->lut_pre_omega = omega;
     return DEFF_OK;
 }
 

@@ -21,6 +21,9 @@ static constexpr auto STREAMING = streaming_passes<1, 2, 4, 6, 8>();
 // ... and its chained form, [2 fma + guard]: dealt tiles exist for T = 8 only (plan_streaming)
 static constexpr auto STREAMING_CHAIN = by_flags([](auto f, auto g) { return k_sweep_matfree_tb_chain<8, decltype(f)::value, decltype(g)::value>; });
 static_assert(TB_CHAIN_NB == TB_CHAIN_MAXN && TB_CHAIN_COLS == TB_COLS && sizeof(TbChainTile) == sizeof(int4), "tb_chain.hpp and kernels_tb.hpp disagree");
+// ... and its pre-scaled form (tuning "prescaled"), [tb_index(T)]: one launch per pass, never chained
+static constexpr std::array STREAMING_PRE = {k_sweep_matfree_tb_pre<1>, k_sweep_matfree_tb_pre<2>, k_sweep_matfree_tb_pre<4>,
+                                             k_sweep_matfree_tb_pre<6>, k_sweep_matfree_tb_pre<8>};
 static int tb_index(int T) { return T == 1 ? 0 : T == 2 ? 1 : T == 4 ? 2 : T == 6 ? 3 : 4; }
 
 // The first workgroup tile (tile_kernels.hpp) that pred accepts: 8-wave, tall, 12-wave tiles, each list in its order.
@@ -216,7 +219,8 @@ int default_tb_impl(const deff_ctx *c)
 int default_tb_T(const deff_ctx *c)
 {
     // workgroup tiles: 8 sweeps per pass amortise the launch gap and the first-load latency (1024^2: T = 8 556, T = 4 457)
-    if ((c->tb_impl ? c->tb_impl : default_tb_impl(c)) == 2) return 8;
+    // (the pre-scaled arithmetic streams at every size: its T is the streaming form's, as with tb_impl = 1)
+    if (!c->prescaled && (c->tb_impl ? c->tb_impl : default_tb_impl(c)) == 2) return 8;
     // streaming: below 4 Mi cells the launch is latency-bound and T = 4 wins; above, T = 8 everywhere (with the
     // prefetch really in flight, kernels_tb.hpp, stacks no longer prefer T = 6: 1 024 x 128^2 1 222 vs
     // 1 125 G cells*iter/s, 64 x 1024^2 1 258 vs 1 156, 16 x 1024^2 1 106 vs 1 064)
@@ -732,7 +736,8 @@ static int plan_streaming(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int own
     pl->guard = c->lut_guard;                          // the reference's non-zero link test matters only when a phase cannot diffuse
     int resident = c->tb_wg;
     if (!resident) {
-        TRY(resident_blocks(c, STREAMING[tb_index(T)][2 * pl->fma + pl->guard], 256, &resident));
+        if (pl->pre) TRY(resident_blocks(c, STREAMING_PRE[tb_index(T)], 256, &resident));
+        else TRY(resident_blocks(c, STREAMING[tb_index(T)][2 * pl->fma + pl->guard], 256, &resident));
         if (resident < 1) TRY(cu_count(c, &resident));                // at least one workgroup per CU
     }
     pl->dealt = nullptr;
@@ -742,7 +747,8 @@ static int plan_streaming(deff_ctx *c, SweepPlan *pl, int T, int own_lo, int own
         TRY(deal_ranked_tiles(c, pl, T, own_lo, own_h, resident, &dealt));
         // chained passes: on the conditions of the resident tiles (a whole context, 32-bit offsets, the caller has not asked
         // for one launch per pass, no earlier fallback) when the neighbour lists fit and where it was measured to win
-        if (dealt) pl->chained = pl->nbrs && c->tb_chain && resident_allowed(c, pl) && chain_pays(c);
+        // (the pre-scaled form is not chained: one launch per pass)
+        if (dealt) pl->chained = !pl->pre && pl->nbrs && c->tb_chain && resident_allowed(c, pl) && chain_pays(c);
         if (pl->chained) {
             // every wave of the grid must be on the chip for the whole launch: by the chained kernel's own occupancy
             int at_once = 0;
@@ -869,8 +875,10 @@ static int plan_blocked_pass(deff_ctx *c, SweepPlan *pl)
     pl->own_h = own_h;
     plan_strips(c, T, pl);
     int tall_R = 0;
-    TRY(choose_tall_R(c, pl, T, own_h, &tall_R));
+    if (!pl->pre) TRY(choose_tall_R(c, pl, T, own_h, &tall_R));
     int want_impl = c->tb_impl ? c->tb_impl : default_tb_impl(c);
+    // the pre-scaled arithmetic exists on the streaming form alone: taken at every size, as tb_impl = 1 would
+    if (pl->pre) want_impl = 1;
     // a context just above the 4 Mi cells where the streaming form takes over still runs faster on tall tiles when they fit
     if (!c->tb_impl && want_impl == 1 && tall_R) want_impl = 2;
     // workgroup tiles exist for T = 4 and 8 (the 12-wave link-symmetric form also for T = 6, on request); slabs' T = 1 remainder
@@ -894,11 +902,27 @@ int plan_sweeps(deff_ctx *c, double omega, SweepPlan *pl)
     if (c->kernel == DEFF_KERNEL_AUTO || c->kernel == DEFF_KERNEL_MATFREE || c->kernel == DEFF_KERNEL_MATFREE_TB)
         TRY(ensure_dictionary(c));
     TRY(resolve_kernel(c, &pl->kernel));
-    pl->fma = c->fma != 0;
+    // The pre-scaled arithmetic (tuning "prescaled"): matrix-free sweeps only, refused here -- before the field, the system or
+    // the recorded plan are touched -- for everything else.  `fma` is ignored by the sweeps while it is set.
+    pl->pre = c->prescaled != 0;
+    if (pl->pre) {
+        if (c->slab) return fail(DEFF_EINVAL, "prescaled: not for row-slab contexts");
+        if (c->kernel == DEFF_KERNEL_EXPLICIT || c->kernel == DEFF_KERNEL_SCALAR)
+            return fail(DEFF_EINVAL, "prescaled: the explicit and scalar kernels have no pre-scaled form (deff_set_kernel: auto, matfree or matfree_tb)");
+        if (pl->kernel != DEFF_KERNEL_MATFREE && pl->kernel != DEFF_KERNEL_MATFREE_TB)
+            return fail(DEFF_EINVAL, "prescaled: the system has no row dictionary (the pre-scaled sweeps are matrix-free)");
+    }
+    pl->fma = c->fma != 0 && !pl->pre;
     pl->omega = omega;
     pl->omw = 1.0 - omega;                              // cuh:89 evaluates (1.0 - w) in double
     if (pl->kernel == DEFF_KERNEL_MATFREE || pl->kernel == DEFF_KERNEL_MATFREE_TB) {
         TRY(upload_lut(c, omega));
+        if (pl->pre) {
+            if (c->lut_guard)
+                return fail(DEFF_EINVAL, "prescaled: the row dictionary has a singular row (a phase that cannot diffuse): "
+                                         "omega / A0 is not finite there and the table cannot be pre-scaled");
+            TRY(upload_lut_pre(c, omega));
+        }
         if (pl->kernel == DEFF_KERNEL_MATFREE_TB) TRY(plan_blocked_pass(c, pl));
         // single sweeps (the first sweep and the n mod T remainder): 4 rows per tile and up to 8 192 workgroups (measured at
         // 4096^2: 52.0 us = 5.8 TB/s against 59-61 us for 8 rows x 2 048 persistent workgroups; 16384^2: 960-990 us = 4.9-5.0
@@ -918,6 +942,7 @@ int plan_sweeps(deff_ctx *c, double omega, SweepPlan *pl)
         if (pl->kernel == DEFF_KERNEL_EXPLICIT)
             tile_grid(c, 512, pick_R(c->rows_explicit, 1), pl);
     }
+    c->plan_prescaled = pl->pre ? 1 : 0;                // deff_get_plan "prescaled": the arithmetic of the sweeps this plan runs
     return DEFF_OK;
 }
 
@@ -952,6 +977,7 @@ template <int... R> static constexpr auto matfree_sweeps()
 }
 static constexpr auto EXPLICIT_SWEEPS = explicit_sweeps<1, 2, 4, 8>();
 static constexpr auto MATFREE_SWEEPS = matfree_sweeps<1, 2, 4, 8>();
+static constexpr std::array MATFREE_SWEEPS_PRE = {k_sweep_matfree_pre<1>, k_sweep_matfree_pre<2>, k_sweep_matfree_pre<4>, k_sweep_matfree_pre<8>};
 static int rows_index(int rows) { return rows == 1 ? 0 : rows == 2 ? 1 : rows == 4 ? 2 : 3; }
 
 // Enqueue one sweep x[cur] -> x[cur^1] and flip (the reference copies instead, cuh:1281).
@@ -973,6 +999,11 @@ void enqueue_sweep(deff_ctx *c, const SweepPlan &pl)
                            c->nx, c->ny, c->rows, pl.cpi, mask, pl.gx, pl.gy, flip, pl.omw);
         break;
     default:
+        if (pl.pre) {
+            hipLaunchKernelGGL(MATFREE_SWEEPS_PRE[rows_index(pl.rows)], dim3(pl.blocks), dim3(256), 0, c->stream, c->lut_pre, c->code, xin,
+                               xout, c->nx, c->ny, c->rows, pl.cpi, mask, pl.gx, pl.gy, flip, c->lut_nrows, pl.omw);
+            break;
+        }
         hipLaunchKernelGGL(MATFREE_SWEEPS[rows_index(pl.rows)][pl.fma], dim3(pl.blocks), dim3(256), 0, c->stream, c->lut, c->code, xin,
                            xout, c->nx, c->ny, c->rows, pl.cpi, mask, pl.gx, pl.gy, flip, c->lut_nrows, pl.omw);
         break;
@@ -1019,6 +1050,16 @@ int launch_tb_pass(deff_ctx *c, const SweepPlan &pl)
                            c->mesh_ny, c->ny, c->dom_lo, pl.own_lo, pl.own_h, pl.tcpi, pl.LY, mask, pl.ntx, pl.tgy, c->tb_xmajor, allb,
                            c->lut_nrows, pl.shift, pl.omw, c->tb_stamps);
         HIP_TRY(hipPeekAtLastError());
+        return DEFF_OK;
+    }
+    if (pl.pre) {
+        // the same tiles over the pre-scaled table; b' is looked up everywhere unless it is +0.0 wherever b is zero
+        const int allb_pre = (allb || c->lut_pre_allb) ? 1 : 0;
+        hipLaunchKernelGGL(STREAMING_PRE[tb_index(pl.T)], dim3(pl.tblocks), dim3(256), 0, c->stream, c->lut_pre, c->code, xin, xout,
+                           c->nx, c->mesh_ny, c->ny, c->dom_lo, pl.own_lo, pl.own_h, pl.tcpi, mask, pl.LY, pl.ntx, pl.tgx, pl.tgy, flip,
+                           c->tb_xmajor, allb_pre, c->lut_nrows, pl.shift, pl.omw, c->tb_stamps, pl.dealt);
+        HIP_TRY(hipPeekAtLastError());
+        if (pl.dealt) c->tb_dealt_waves += (int64_t)pl.tblocks * 4;
         return DEFF_OK;
     }
     hipLaunchKernelGGL(STREAMING[tb_index(pl.T)][2 * pl.fma + pl.guard], dim3(pl.tblocks), dim3(256), 0, c->stream, c->lut, c->code,

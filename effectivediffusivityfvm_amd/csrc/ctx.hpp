@@ -110,6 +110,14 @@ struct deff_ctx {
     // temporally blocked kernel treat a wall column's outer neighbour as absent -- such a system stays explicit.
     bool wrap_links = false;
     double lut_omega = NAN;
+    // Pre-scaled sweep arithmetic (kernels_sweep.hpp, pre_cell; tuning key "prescaled", opt-in): a second device table in the
+    // dictionary's layout with aK' = (w/A0) aK in planes 1...4 and b' = (w/A0) b in plane 5 (plane 0 unused), built from lut_rows
+    // by upload_lut_pre for one omega; upload_lut invalidates it whenever it rebuilds the dictionary's table.
+    // lut_pre_allb: some row with b = 0 has a b' that is not +0.0 -- every strip then looks b' up.
+    int prescaled = 0, plan_prescaled = 0;
+    double *lut_pre = nullptr;
+    double lut_pre_omega = NAN;
+    bool lut_pre_allb = false;
     double Ds = 0, Df = 0;          // phase diffusivities of the native 2-phase system
     // what deff_residual() needs to know about a system assembled from the image: 2 / 3 pixel classes (0 = the system came
     // from a caller's D plane or matrix) and their diffusivities {fluid, solid, gas}
@@ -384,6 +392,7 @@ struct SweepPlan {
     int rows = 0, cpi = 0, gx = 0, gy = 0, blocks = 0;   // single-sweep kernels (cpi: row tiles per image)
     // temporally blocked kernel
     bool fma = false;
+    bool pre = false;                                     // the pre-scaled arithmetic (tuning "prescaled"): matrix-free family only
     int T = 0, LY = 0, tcpi = 0, ntx = 0, tgx = 0, tgy = 0, tblocks = 0;
     int shift = 0;                                        // column shift of the strips (0: no halo outside the walls)
     int T_override = 0;                                   // slab mode plans a T = 1 pass for remainders
@@ -450,6 +459,7 @@ int resolve_kernel(const deff_ctx *c, int *k);
 int image_shape(deff_ctx *c, int W, int H, int ampX, int ampY);
 void build_lut_rows(deff_ctx *c, double Ds, double Df, double CL, double CR);
 int upload_lut(deff_ctx *c, double omega);
+int upload_lut_pre(deff_ctx *c, double omega);           // after upload_lut(c, omega), on a table without a singular row
 int consolidate(deff_ctx *c);
 int explicit_from_image(deff_ctx *c);
 // api_fill.hip

@@ -9,7 +9,7 @@
 // --field-bin dumps the FP64 concentration field.
 //
 //   deff2d [input.txt] [--device N | --devices 0,1,..] [--json results.json] [--field-bin prefix] [--batch-size B]
-//          [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K]
+//          [--progress file] [--arith reference|contracted|prescaled] [--precond-maxiter N] [--prefetch-threads K]
 //          [--solver jacobi|cg] [--cg-rtol R] [--cg-slabs]
 // --solver cg: every solve of a one-GPU image runs preconditioned conjugate gradients to ||b - A x|| <= R ||b||
 // (deff_solve_cg, R = --cg-rtol, default 1e-10) instead of the reference's Jacobi loop; the 3-phase continuation
@@ -19,6 +19,10 @@
 // bit); batch mode then solves one image at a time per worker instead of in stacked slots.
 // --arith contracted: products fused into adds the way a compiler contracts the reference's expressions
 // (kernels_sweep.hpp); default is the reference's written operation order.
+// --arith prescaled: the pre-scaled five-FMA sweeps (deff_set_tuning(ctx, "prescaled", 1)): every sweep of every mode runs on
+// a table scaled by omega / A0 once -- NOT the reference's operation order, results agree with it to ~1e-13 (field, Deff), not
+// bit for bit; the iteration counts are the same.  One GPU per image only: with --devices a,b on one image (row slabs) it is
+// refused.  Systems with a phase that cannot diffuse and no ImpSolid rows (2 phases, Ds = 0) are refused by the library.
 //
 // --devices with RunBatch 0: the one image (2 or 3 phases) is split into row slabs over the listed GPUs.
 // --devices: batch mode over several GPUs from one process -- one host thread and one solver context
@@ -114,6 +118,7 @@ static std::vector<unsigned int> grid_of(const Image &im, const Options &o, int 
 }
 
 static int g_contracted = 0;       // --arith contracted: deff_set_tuning(ctx, "fma", 1) on every context
+static int g_prescaled = 0;        // --arith prescaled: deff_set_tuning(ctx, "prescaled", 1) on every context
 // MAX_ITER of the 3-phase continuation stages: the reference's literal 1e6 (cuh:1503).  --precond-maxiter N replaces it so
 // that a capped run of a large image fits a CPU oracle run (tests/golden/make_img00042_golden.py); not an input.txt key.
 static int64_t g_precond_maxiter = 1000000;
@@ -138,6 +143,7 @@ struct Session {                   // one solver context, re-created only when t
         ctx = nullptr;
         CK(deff_create_batch(device, nx_, ny_, nimg_, &ctx));
         CK(deff_set_tuning(ctx, "fma", g_contracted));
+        CK(deff_set_tuning(ctx, "prescaled", g_prescaled));
         if (g_solver_cg) CK(deff_set_tuning(ctx, "cg_fold", g_cg_fold));
         nx = nx_; ny = ny_; nimg = nimg_;
         return true;
@@ -756,9 +762,10 @@ int main(int argc, char **argv)
         else if (s == "--progress" && a + 1 < argc) progress_path = argv[++a];
         else if (s == "--arith" && a + 1 < argc) {
             const std::string v = argv[++a];
-            if (v == "contracted" || v == "fma") g_contracted = 1;
-            else if (v == "reference" || v == "plain") g_contracted = 0;
-            else { std::fprintf(stderr, "deff2d: --arith takes 'reference' or 'contracted'\n"); return 2; }
+            if (v == "contracted" || v == "fma") { g_contracted = 1; g_prescaled = 0; }
+            else if (v == "reference" || v == "plain") { g_contracted = 0; g_prescaled = 0; }
+            else if (v == "prescaled") { g_contracted = 0; g_prescaled = 1; }
+            else { std::fprintf(stderr, "deff2d: --arith takes 'reference', 'contracted' or 'prescaled'\n"); return 2; }
         }
         else if (s == "--prefetch-threads" && a + 1 < argc) g_prefetch_threads = std::atoi(argv[++a]);
         else if (s == "--precond-maxiter" && a + 1 < argc) {
@@ -810,7 +817,9 @@ int main(int argc, char **argv)
             g_fill_device = v == "device";
         }
         else if (s == "-h" || s == "--help") {
-            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B] [--cg-stream B] [--cg-slabs] [--cg-fold N] [--fill host|device]\n"
+            std::printf("usage: deff2d [input.txt] [--device N] [--json results.json] [--field-bin prefix] [--batch-size B] [--devices 0,1,...] [--progress file] [--arith reference|contracted|prescaled] [--precond-maxiter N] [--prefetch-threads K] [--solver jacobi|cg] [--cg-rtol R] [--cg-batch B] [--cg-stream B] [--cg-slabs] [--cg-fold N] [--fill host|device]\n"
+                        "--arith prescaled: pre-scaled five-FMA Jacobi sweeps (deff_set_tuning \"prescaled\"): same iteration counts, results within\n"
+                        "~1e-13 of the reference's arithmetic, not bit-identical; one GPU per image (refused over row slabs).\n"
                         "--fill device (3 phases, one GPU per image): the flood fill of the pore space and the row codes are computed on the\n"
                         "GPU from the pixels (deff_assemble_3phase_native) and every continuation stage rebuilds a table of 452 rows only;\n"
                         "host (default) = flood fill on the host and an explicit assembly per stage.  The same results bit for bit.\n"
@@ -864,6 +873,11 @@ int main(int argc, char **argv)
     if (g_fill_device && (g_cg_slabs || (!o.BatchFlag && devices.size() >= 2))) {
         std::fprintf(stderr, "deff2d: --fill device does not run over row slabs (--devices with RunBatch 0, --cg-slabs): the fill is a "
                              "property of the whole image, a slab holds a window of it\n");
+        return 2;
+    }
+    if (g_prescaled && !o.BatchFlag && devices.size() >= 2) {
+        std::fprintf(stderr, "deff2d: --arith prescaled does not run over row slabs (--devices with RunBatch 0): the slab passes have no "
+                             "pre-scaled form; use one device, or --arith reference|contracted\n");
         return 2;
     }
     if (g_cg_slabs && (o.BatchFlag || devices.size() < 2)) {
@@ -953,6 +967,7 @@ int main(int argc, char **argv)
             }
             if (deff_create_batch(dev, nx, ny, slots, &st.ctx) != DEFF_OK ||
                 deff_set_tuning(st.ctx, "fma", g_contracted) != DEFF_OK ||
+                deff_set_tuning(st.ctx, "prescaled", g_prescaled) != DEFF_OK ||
                 (cg && deff_set_tuning(st.ctx, "cg_onchip", 1) != DEFF_OK) ||
                 (cg && deff_set_tuning(st.ctx, "cg_fold", g_cg_fold) != DEFF_OK)) {
                 std::fprintf(stderr, "deff2d: %s\n", deff_last_error());

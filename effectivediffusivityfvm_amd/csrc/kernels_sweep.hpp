@@ -59,6 +59,22 @@ __device__ __forceinline__ double jacobi_cell(double c0, double aW, double aE, d
     else return omw * xc + c0 * (b - sigma);
 }
 
+// The pre-scaled arithmetic (opt-in: deff_set_tuning(ctx, "prescaled", 1)): the table holds aK' = (w/A0) * aK and b' = (w/A0) * b,
+// rounded once per table row on the host (upload_lut_pre, api_core.hip), and a cell is five dependent FMAs
+//   acc = fma(1-w, xC, b'); acc = fma(-aW', xW, acc); ... E, S ...; xNew = fma(-aN', xN, acc)
+// with every term evaluated (no non-zero test) and neighbours outside the mesh read as +0.0.  NOT the reference's written
+// order: results agree with it to ~1e-13, not bit for bit.  5 instead of 11 FP64 instructions and
+// 5 instead of 6 lookups per cell.  Only for tables without a singular row (no guard).
+__device__ __forceinline__ double pre_cell(double aW, double aE, double aS, double aN, double b, double xc, double xw, double xe,
+                                           double xs, double xn, double omw)
+{
+    double acc = __builtin_fma(omw, xc, b);
+    acc = __builtin_fma(-aW, xw, acc);
+    acc = __builtin_fma(-aE, xe, acc);
+    acc = __builtin_fma(-aS, xs, acc);
+    return __builtin_fma(-aN, xn, acc);
+}
+
 // Workgroup -> tile map.  Workgroups are dealt round-robin over the 8 XCDs, so
 // blocks id and id+8 share an L2.  Give every XCD a contiguous run of tiles in
 // column-major order (tiles above/below each other, which share halo rows of
@@ -192,12 +208,17 @@ __global__ __launch_bounds__(256) void k_sweep_explicit(CoefConst c, const doubl
 
 // One cell from the row dictionary (lut_layout.hpp); `off` is the cell's code = byte offset of
 // its row inside a plane.
-template <bool FMA>
+// PRE = `lut` is the pre-scaled table (plane 0 unused) and the cell is pre_cell().
+template <bool FMA, bool PRE = false>
 __device__ __forceinline__ double jacobi_cell_lut(const double *lut, unsigned off, double xc, double xw,
                                                   double xe, double xs, double xn, double omw)
 {
     const char *base = reinterpret_cast<const char *>(lut) + off;
     constexpr int PS = LUT_PLANE_STRIDE * 8;
+    if constexpr (PRE)
+        return pre_cell(*reinterpret_cast<const double *>(base + PS), *reinterpret_cast<const double *>(base + 2 * PS),
+                        *reinterpret_cast<const double *>(base + 3 * PS), *reinterpret_cast<const double *>(base + 4 * PS),
+                        *reinterpret_cast<const double *>(base + 5 * PS), xc, xw, xe, xs, xn, omw);
     return jacobi_cell<FMA>(*reinterpret_cast<const double *>(base), *reinterpret_cast<const double *>(base + PS),
                             *reinterpret_cast<const double *>(base + 2 * PS), *reinterpret_cast<const double *>(base + 3 * PS),
                             *reinterpret_cast<const double *>(base + 4 * PS), *reinterpret_cast<const double *>(base + 5 * PS),
@@ -226,22 +247,16 @@ __device__ __forceinline__ void tile_coords(unsigned t, int gy, int &bx, int &by
     by = (int)(t % (unsigned)gy);
 }
 
-// VEC = 2 (the form in use: array rows are always even, an odd mesh width is padded); VEC = 1 is the
-// one-cell-per-thread form, no longer instantiated.  Tile = 256*VEC columns x R
-// rows.  Position classes are folded into the codes at assembly, the kernel only looks rows up.  Persistent: the grid is a few workgroups per CU, each loads the tables
-// into LDS once and then walks its share of the tiles.
-template <int VEC, int R, bool FMA>
-__global__ __launch_bounds__(256) void k_sweep_matfree(const double *__restrict__ lut_g,
-                                                       const uint16_t *__restrict__ code,
-                                                       const double *__restrict__ x,
-                                                       double *__restrict__ xnew, int nx, int ny,
-                                                       int rows, int cpi,
-                                                       const uint8_t *__restrict__ active, int gx,
-                                                       int gy, int flip, int nrows, double omw)
+// The row walk over a workgroup's share of the tiles, shared by the kernels below (`lut` = the table in LDS, loaded).
+// PRE = the pre-scaled arithmetic on the pre-scaled table (pre_cell): neighbours outside the image -- beyond a wall column,
+// above the first or below the last row of this image of a stack -- then read as +0.0 instead of the linearly addressed
+// cell (whose link is zero: the default arithmetic cannot tell, a chain of FMAs can by the sign of a zero).
+template <int VEC, int R, bool FMA, bool PRE = false>
+__device__ __forceinline__ void matfree_rows(const double *lut, const uint16_t *__restrict__ code, const double *__restrict__ x,
+                                             double *__restrict__ xnew, int nx, int ny, int rows, int cpi,
+                                             const uint8_t *__restrict__ active, int gx, int gy, int flip, double omw)
 {
-    __shared__ double lut[LUT_DOUBLES];
-    load_lut(lut, lut_g, nrows);
-
+    static_assert(!PRE || VEC == 2, "the pre-scaled form exists for two cells per thread");
     const size_t n = (size_t)nx * rows;
     const unsigned total = (unsigned)gx * (unsigned)gy;
     const unsigned per = (total + 7u) / 8u;              // tiles per XCD
@@ -266,20 +281,20 @@ __global__ __launch_bounds__(256) void k_sweep_matfree(const double *__restrict_
             double2 xr[R + 2];
             double xw[R], xe[R];
             unsigned cc[R];
-            xr[0] = (p0 >= (size_t)nx) ? ld2(x + p0 - nx) : zero;
-#pragma unroll
+            xr[0] = (PRE ? r0 > row_lo : p0 >= (size_t)nx) ? ld2(x + p0 - nx) : zero;
+    #pragma unroll
             for (int q = 0; q <= R; ++q) {
                 const size_t p = p0 + (size_t)q * nx;
-                xr[q + 1] = (p < n) ? ld2(x + p) : zero;
+                xr[q + 1] = (p < n && (!PRE || r0 + q < rlim)) ? ld2(x + p) : zero;
             }
-#pragma unroll
+    #pragma unroll
             for (int q = 0; q < R; ++q) {
                 const size_t p = p0 + (size_t)q * nx;
-                xw[q] = (p >= 1 && p < n) ? x[p - 1] : 0.0;
-                xe[q] = (p + 2 < n) ? x[p + 2] : 0.0;
+                xw[q] = (p >= 1 && p < n && (!PRE || col > 0)) ? x[p - 1] : 0.0;
+                xe[q] = (p + 2 < n && (!PRE || col + 2 < nx)) ? x[p + 2] : 0.0;
                 cc[q] = (p < n) ? *reinterpret_cast<const uint32_t *>(code + p) : 0u;   // two 16-bit codes
             }
-#pragma unroll
+    #pragma unroll
             for (int q = 0; q < R; ++q) {
                 const int r = r0 + q;
                 if (r >= rlim) break;
@@ -287,27 +302,27 @@ __global__ __launch_bounds__(256) void k_sweep_matfree(const double *__restrict_
                 const unsigned i0 = cc[q] & 0xFFFFu, i1 = cc[q] >> 16;
                 const double2 xm = xr[q], xc = xr[q + 1], xp = xr[q + 2];
                 double2 o;
-                o.x = jacobi_cell_lut<FMA>(lut, i0, xc.x, xw[q], xc.y, xp.x, xm.x, omw);
-                o.y = jacobi_cell_lut<FMA>(lut, i1, xc.y, xc.x, xe[q], xp.y, xm.y, omw);
+                o.x = jacobi_cell_lut<FMA, PRE>(lut, i0, xc.x, xw[q], xc.y, xp.x, xm.x, omw);
+                o.y = jacobi_cell_lut<FMA, PRE>(lut, i1, xc.y, xc.x, xe[q], xp.y, xm.y, omw);
                 st2(xnew + p, o);
             }
         } else {
             double xr[R + 2], xw[R], xe[R];
             unsigned cc[R];
             xr[0] = (p0 >= (size_t)nx) ? x[p0 - nx] : 0.0;
-#pragma unroll
+    #pragma unroll
             for (int q = 0; q <= R; ++q) {
                 const size_t p = p0 + (size_t)q * nx;
                 xr[q + 1] = (p < n) ? x[p] : 0.0;
             }
-#pragma unroll
+    #pragma unroll
             for (int q = 0; q < R; ++q) {
                 const size_t p = p0 + (size_t)q * nx;
                 xw[q] = (p >= 1 && p < n) ? x[p - 1] : 0.0;
                 xe[q] = (p + 1 < n) ? x[p + 1] : 0.0;
                 cc[q] = (p < n) ? code[p] : 0u;
             }
-#pragma unroll
+    #pragma unroll
             for (int q = 0; q < R; ++q) {
                 const int r = r0 + q;
                 if (r >= rlim) break;
@@ -317,6 +332,39 @@ __global__ __launch_bounds__(256) void k_sweep_matfree(const double *__restrict_
             }
         }
     }
+}
+
+// VEC = 2 (the form in use: array rows are always even, an odd mesh width is padded); VEC = 1 is the
+// one-cell-per-thread form, no longer instantiated.  Tile = 256*VEC columns x R
+// rows.  Position classes are folded into the codes at assembly, the kernel only looks rows up.  Persistent: the grid is a few workgroups per CU, each loads the tables
+// into LDS once and then walks its share of the tiles.
+template <int VEC, int R, bool FMA>
+__global__ __launch_bounds__(256) void k_sweep_matfree(const double *__restrict__ lut_g,
+                                                       const uint16_t *__restrict__ code,
+                                                       const double *__restrict__ x,
+                                                       double *__restrict__ xnew, int nx, int ny,
+                                                       int rows, int cpi,
+                                                       const uint8_t *__restrict__ active, int gx,
+                                                       int gy, int flip, int nrows, double omw)
+{
+    __shared__ double lut[LUT_DOUBLES];
+    load_lut(lut, lut_g, nrows);
+    matfree_rows<VEC, R, FMA>(lut, code, x, xnew, nx, ny, rows, cpi, active, gx, gy, flip, omw);
+}
+
+// ... and its pre-scaled form: lut_g is the pre-scaled table (same layout, same codes).
+template <int R>
+__global__ __launch_bounds__(256) void k_sweep_matfree_pre(const double *__restrict__ lut_g,
+                                                           const uint16_t *__restrict__ code,
+                                                           const double *__restrict__ x,
+                                                           double *__restrict__ xnew, int nx, int ny,
+                                                           int rows, int cpi,
+                                                           const uint8_t *__restrict__ active, int gx,
+                                                           int gy, int flip, int nrows, double omw)
+{
+    __shared__ double lut[LUT_DOUBLES];
+    load_lut(lut, lut_g, nrows);
+    matfree_rows<2, R, true, true>(lut, code, x, xnew, nx, ny, rows, cpi, active, gx, gy, flip, omw);
 }
 
 }  // namespace deff

@@ -109,21 +109,50 @@ constexpr int TB_STAGE_FENCE = 0x4;                             // sched_barrier
 struct TbCoef {
     double c0[2], aW[2], aE[2], aS[2], aN[2], b[2];
 };
-template <bool WALL>
+// PRE = the pre-scaled table (kernels_sweep.hpp, pre_cell): plane 0 is not read, b' comes first because the chain starts with it
+template <bool WALL, bool PRE = false>
 __device__ __forceinline__ void tb_lookup(const double *lut, unsigned o0, unsigned o1, TbCoef &k)
 {
     constexpr int PS = LUT_PLANE_STRIDE * 8;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const char *base = reinterpret_cast<const char *>(lut) + (h ? o1 : o0);
+        if constexpr (PRE) {
+            if constexpr (WALL) k.b[h] = *reinterpret_cast<const double *>(base + 5 * PS);
+            else k.b[h] = 0.0;
+        }
         k.aW[h] = *reinterpret_cast<const double *>(base + PS);
         k.aE[h] = *reinterpret_cast<const double *>(base + 2 * PS);
         k.aS[h] = *reinterpret_cast<const double *>(base + 3 * PS);
         k.aN[h] = *reinterpret_cast<const double *>(base + 4 * PS);
-        k.c0[h] = *reinterpret_cast<const double *>(base);
-        if constexpr (WALL) k.b[h] = *reinterpret_cast<const double *>(base + 5 * PS);
-        else k.b[h] = 0.0;
+        if constexpr (!PRE) {
+            k.c0[h] = *reinterpret_cast<const double *>(base);
+            if constexpr (WALL) k.b[h] = *reinterpret_cast<const double *>(base + 5 * PS);
+            else k.b[h] = 0.0;
+        }
     }
+}
+// The pre-scaled arithmetic of a lane's two cells, stage-wise like tb_apply below: five stages of two independent FMAs, so
+// that each FMA has the other cell's between itself and its consumer.  A strip without a wall column passes b' = +0.0 (the
+// table's value there: the host looks every row up otherwise, upload_lut_pre), still through an FMA -- fma(omw, x, +0.0)
+// is not the bare product when that is -0.0.
+template <bool PINNED = false>
+__device__ __forceinline__ double2 tb_apply_pre(const TbCoef &k, double2 vC, double xw0, double xe1, double2 vS, double2 vN, double omw)
+{
+    auto stage = []() __attribute__((always_inline)) {
+        if constexpr (PINNED) __builtin_amdgcn_sched_barrier(TB_STAGE_FENCE);
+    };
+    double s0 = __builtin_fma(omw, vC.x, k.b[0]), s1 = __builtin_fma(omw, vC.y, k.b[1]);
+    stage();
+    s0 = __builtin_fma(-k.aW[0], xw0, s0); s1 = __builtin_fma(-k.aW[1], vC.x, s1);
+    stage();
+    s0 = __builtin_fma(-k.aE[0], vC.y, s0); s1 = __builtin_fma(-k.aE[1], xe1, s1);
+    stage();
+    s0 = __builtin_fma(-k.aS[0], vS.x, s0); s1 = __builtin_fma(-k.aS[1], vS.y, s1);
+    stage();
+    double2 o;
+    o.x = __builtin_fma(-k.aN[0], vN.x, s0); o.y = __builtin_fma(-k.aN[1], vN.y, s1);
+    return o;
 }
 // PINNED = the stages stay in the order written (a fence between them that only scalar instructions may cross): see tb_strip
 template <bool FMA, bool PINNED = false>
@@ -210,12 +239,15 @@ template <class P> __device__ __forceinline__ __amdgpu_buffer_rsrc_t tb_rsrc(P *
 // RAMP = full-halo tiles cross their first steps as straight-line code (below).  Off in the loop over the tiles of a workgroup
 // that was dealt none (k_sweep_matfree_tb without a table): what the previous tile left in flight would reach this tile's
 // steady-state loop along the edge described below.
-template <int T, bool GUARD, bool WALL, bool FMA, int XAUX = 0, bool RAMP = true>
+// PRE = the pre-scaled arithmetic (kernels_sweep.hpp, pre_cell) on the pre-scaled table: same rows, same codes, same pipeline;
+// a level is 10 lookups and five stages of two FMAs.  Unguarded tables only.
+template <int T, bool GUARD, bool WALL, bool FMA, int XAUX = 0, bool RAMP = true, bool PRE = false>
 __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__restrict__ code,
                                          const double *__restrict__ x, double *__restrict__ xnew, int nx,
                                          int ny, int row_lo, int own_hi, int tx, int ntx, int shift, int ry0, int LY,
                                          int lane, double omw, TbMarks *marks = nullptr)
 {
+    static_assert(!(PRE && GUARD), "the pre-scaled form has no guarded variant");
     // column halo rounded up to even so that odd T keeps the 16-B alignment of a lane's pair
     constexpr int HW = (T + 1) & ~1;
     constexpr int WOUT = TB_COLS - 2 * HW;
@@ -294,9 +326,10 @@ __device__ __forceinline__ void tb_strip(const double *lut, const uint16_t *__re
             // That it did not do so before was an accident of a register pressure ABOVE the budget, which made it
             // give the schedule up and keep the source order; the fences say it.
             TbCoef k;
-            tb_lookup<WALL>(lut, o0, o1, k);
+            tb_lookup<WALL, PRE>(lut, o0, o1, k);
             __builtin_amdgcn_sched_barrier(TB_STAGE_FENCE);
-            o = tb_apply<FMA, true>(k, vC, xw0, xe1, vS, vN, omw);
+            if constexpr (PRE) o = tb_apply_pre<true>(k, vC, xw0, xe1, vS, vN, omw);
+            else o = tb_apply<FMA, true>(k, vC, xw0, xe1, vS, vN, omw);
         }
         if (t < T) w[t][sS] = o;
         else store(rt, o);
@@ -470,23 +503,15 @@ template <int T> __device__ __forceinline__ bool tb_wall_strip(int tx, int ntx, 
 #ifndef TB_ROWS_AUX
 #define TB_ROWS_AUX 0
 #endif
-template <int T, bool FMA, bool GUARD>
-__global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(const double *__restrict__ lut_g,
-                                                          const uint16_t *__restrict__ code,
-                                                          const double *__restrict__ x,
-                                                          double *__restrict__ xnew, int nx, int ny,
-                                                          int img_stride, int dom_lo, int own_lo,
-                                                          int own_h, int cpi,
-                                                          const uint8_t *__restrict__ active,
-                                                          int LY, int ntx, int nbt, int gy, int flip,
-                                                          int xmajor, int allb, int nrows, int shift,
-                                                          double omw, unsigned long long *__restrict__ stamps,
-                                                          const int4 *__restrict__ dealt)
+// (the body of the kernel, shared with its pre-scaled form k_sweep_matfree_tb_pre below: `lut` is the table in LDS, loaded)
+template <int T, bool FMA, bool GUARD, bool PRE = false>
+__device__ __forceinline__ void tb_tiles(const double *lut, const uint16_t *__restrict__ code, const double *__restrict__ x,
+                                         double *__restrict__ xnew, int nx, int ny, int img_stride, int dom_lo, int own_lo,
+                                         int own_h, int cpi, const uint8_t *__restrict__ active, int LY, int ntx, int nbt, int gy,
+                                         int flip, int xmajor, int allb, int shift, double omw,
+                                         unsigned long long *__restrict__ stamps, const int4 *__restrict__ dealt)
 {
     static_assert(T >= 1 && T <= 8, "unsupported T");
-    __shared__ double lut[LUT_DOUBLES];
-    load_lut(lut, lut_g, nrows);
-
     const int lane = threadIdx.x & 63;
     // readfirstlane makes the wave index (and everything derived from it: strip, chunk, row
     // classes, loop bounds) provably wave-uniform, i.e. SGPR/SALU work; left as a VGPR it
@@ -517,9 +542,9 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(cons
         if (active && !active[img]) return;
         const int row_lo = dom_lo + img * img_stride, own_hi = own_lo + img * img_stride + own_h;
         if (allb || tb_wall_strip<T>(tx, ntx, shift, nx))
-            tb_strip<T, GUARD, true, FMA, TB_ROWS_AUX>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
+            tb_strip<T, GUARD, true, FMA, TB_ROWS_AUX, true, PRE>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
         else
-            tb_strip<T, GUARD, false, FMA, TB_ROWS_AUX>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
+            tb_strip<T, GUARD, false, FMA, TB_ROWS_AUX, true, PRE>(lut, code, x, xnew, nx, ny, row_lo, own_hi, tx, ntx, shift, d.y, d.z, lane, omw);
         if (stamps && lane == 0) {
             const unsigned long long where = (unsigned long long)(__builtin_amdgcn_s_getreg(0xF804) & 0xFFFFu) |
                                              ((unsigned long long)(__builtin_amdgcn_s_getreg(0xF814) & 0xFu) << 16);
@@ -546,9 +571,9 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(cons
         // b is read only where it can be non-zero: strips holding a wall column, or everywhere for a
         // harvested dictionary whose right-hand side is not confined to the walls
         if (allb || tb_wall_strip<T>(tx, ntx, shift, nx))
-            tb_strip<T, GUARD, true, FMA, 0, false>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
+            tb_strip<T, GUARD, true, FMA, 0, false, PRE>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
         else
-            tb_strip<T, GUARD, false, FMA, 0, false>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
+            tb_strip<T, GUARD, false, FMA, 0, false, PRE>(lut, code, x, xnew, nx, ny, row_lo, own0 + own_h, tx, ntx, shift, ry0, LY, lane, omw);
         if (stamps && lane == 0) {
             // end stamp: low 32 bits = duration in 10-ns ticks, bits 32...47 = HW_ID (wave slot, SIMD, CU, SE), 48...51 = XCC
             const unsigned long long where = (unsigned long long)(__builtin_amdgcn_s_getreg(0xF804) & 0xFFFFu) |
@@ -557,6 +582,46 @@ __global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(cons
             stamps[2 * (size_t)wt + 1] = ((wall_clock64() - t_begin) & 0xFFFFFFFFull) | (where << 32);
         }
     }
+}
+
+template <int T, bool FMA, bool GUARD>
+__global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb(const double *__restrict__ lut_g,
+                                                          const uint16_t *__restrict__ code,
+                                                          const double *__restrict__ x,
+                                                          double *__restrict__ xnew, int nx, int ny,
+                                                          int img_stride, int dom_lo, int own_lo,
+                                                          int own_h, int cpi,
+                                                          const uint8_t *__restrict__ active,
+                                                          int LY, int ntx, int nbt, int gy, int flip,
+                                                          int xmajor, int allb, int nrows, int shift,
+                                                          double omw, unsigned long long *__restrict__ stamps,
+                                                          const int4 *__restrict__ dealt)
+{
+    __shared__ double lut[LUT_DOUBLES];
+    load_lut(lut, lut_g, nrows);
+    tb_tiles<T, FMA, GUARD>(lut, code, x, xnew, nx, ny, img_stride, dom_lo, own_lo, own_h, cpi, active, LY, ntx, nbt, gy, flip, xmajor,
+                            allb, shift, omw, stamps, dealt);
+}
+
+// The pre-scaled form (kernels_sweep.hpp, pre_cell): the same tiles, dealt or not, over the pre-scaled table lut_g; `allb`
+// here also covers a table whose b' is not +0.0 on every row away from the walls.  Same arguments as k_sweep_matfree_tb.
+template <int T>
+__global__ __launch_bounds__(256, (T >= 6 ? 3 : 1)) void k_sweep_matfree_tb_pre(const double *__restrict__ lut_g,
+                                                          const uint16_t *__restrict__ code,
+                                                          const double *__restrict__ x,
+                                                          double *__restrict__ xnew, int nx, int ny,
+                                                          int img_stride, int dom_lo, int own_lo,
+                                                          int own_h, int cpi,
+                                                          const uint8_t *__restrict__ active,
+                                                          int LY, int ntx, int nbt, int gy, int flip,
+                                                          int xmajor, int allb, int nrows, int shift,
+                                                          double omw, unsigned long long *__restrict__ stamps,
+                                                          const int4 *__restrict__ dealt)
+{
+    __shared__ double lut[LUT_DOUBLES];
+    load_lut(lut, lut_g, nrows);
+    tb_tiles<T, true, false, true>(lut, code, x, xnew, nx, ny, img_stride, dom_lo, own_lo, own_h, cpi, active, LY, ntx, nbt, gy, flip,
+                                   xmajor, allb, shift, omw, stamps, dealt);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

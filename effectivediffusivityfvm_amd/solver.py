@@ -98,9 +98,10 @@ class Solver:
     def plan(self):
         """What the temporally blocked kernel's last launch plan chose (zeros before any sweep), and "cg_impl": the form of
         the last solve_cg (1 streaming kernels, 2 one image per compute unit: set_tuning("cg_onchip", 1), 3 on the coefficient
-        planes: set_tuning("cg_planes", 1 or 2); 0 before one)."""
+        planes: set_tuning("cg_planes", 1 or 2); 0 before one).  "prescaled": 1 when the last sweeps ran the pre-scaled five-FMA
+        arithmetic (set_tuning("prescaled", 1): opt-in, not bit-identical to the reference's written order)."""
         out = {}
-        for key in ("tb_T", "tb_LY", "tb_strips", "tb_chunks_per_image", "tb_blocks", "tb_impl", "tb_R", "tb_NW", "tb_resident", "tb_sym", "tb_ranked", "tb_aged", "cg_impl"):
+        for key in ("tb_T", "tb_LY", "tb_strips", "tb_chunks_per_image", "tb_blocks", "tb_impl", "tb_R", "tb_NW", "tb_resident", "tb_sym", "tb_ranked", "tb_aged", "cg_impl", "prescaled"):
             v = C.c_int()
             check(self._L.deff_get_plan(self._ctx, key.encode(), C.byref(v)))
             out[key] = v.value

@@ -106,7 +106,23 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  *   "fma" = 1: contracted arithmetic -- the reference's expressions (cuh:74-89, cuh:1957) with each
  *   product fused into the following add, as nvcc's default -fmad=true / gcc -ffp-contract=fast compile
  *   them; bit-identical to the oracle's fma build, not to the default (written-order) arithmetic.
- *   Set it before deff_init_linear(); it applies to every sweep kernel. */
+ *   Set it before deff_init_linear(); it applies to every sweep kernel.
+ *   "prescaled" = 1 (0 restores the default; values above 1 are DEFF_EINVAL): pre-scaled sweep arithmetic, opt-in.  The row
+ *   dictionary is scaled once per table row on the host, aK' = (w/A0) aK and b' = (w/A0) b (one rounded product each), and a
+ *   cell of a sweep is five dependent FMAs,
+ *       acc = fma(1 - w, xC, b'); acc = fma(-aW', xW, acc); ... E, S ...; xNew = fma(-aN', xN, acc),
+ *   every term evaluated, neighbours outside the mesh read as +0.0: 5 FP64 instructions and 5 lookups per cell instead of
+ *   11 and 6.  NOT the reference's written operation order: results agree with the default to ~1e-13 (field rel-L2, Deff),
+ *   with the same iteration counts on the recorded configurations, and are never bit-identical to it.  Applies to
+ *   deff_sweeps, deff_solve, deff_solve_batch and deff_solve_stream on plain and stacked contexts; flux, residual and CG
+ *   are untouched; "fma" is ignored by the sweeps while it is set (and still governs deff_init_linear).  Matrix-free
+ *   kernels only: blocked passes take the streaming form at every size, one launch per pass (never chained or resident;
+ *   "tb_T", "tb_LY", "tb_ranked", "tb_xmajor", "wg_matfree" keep working).  The workgroup-tile, resident, chained, explicit
+ *   and scalar forms have no pre-scaled variant: below ~4 Mi cells the default arithmetic on resident tiles may well stay
+ *   faster.  Refused with DEFF_EINVAL at the call that would sweep (field, system and plan stay as they were): a system
+ *   without a row dictionary, a context set to DEFF_KERNEL_EXPLICIT / _SCALAR, a dictionary with a singular row (a phase
+ *   with D = 0 and no ImpSolid rows: w/A0 is not finite).  Row-slab contexts refuse the key itself.
+ *   deff_get_plan "prescaled" reports what the last planned sweeps ran. */
 int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
 /* what the last launch plan of the temporally blocked kernel chose: "tb_T", "tb_LY" (rows per chunk),
  * "tb_strips", "tb_chunks_per_image", "tb_blocks" (workgroups launched), "tb_impl", "tb_R", "tb_resident" (1: the
