@@ -1,0 +1,67 @@
+"""Deff as a differentiable torch op: the forward pass is a conjugate-gradient solve on the coefficient planes of the D map,
+the backward pass the library's one-pass gradient (deff_sensitivity_D) -- no second solve, the problem is self-adjoint.
+
+torch is imported inside the functions only: importing the package does not import it.  D makes a host round trip (plumbing;
+the solve and the gradient run in the library's HIP kernels)."""
+import numpy as np
+
+from .solver import Solver
+
+_FN = None
+
+
+def _function():
+    """The torch.autograd.Function, created at first use."""
+    global _FN
+    if _FN is not None:
+        return _FN
+    import torch
+
+    class _EffectiveDiffusivity(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, D, CL, CR, rtol, max_iter, solver):
+            Dh = np.ascontiguousarray(D.detach().cpu().numpy(), dtype=np.float64)
+            stack = Dh.ndim == 3
+            nimg = Dh.shape[0] if stack else 1
+            ny, nx = Dh.shape[-2:]
+            s = solver if solver is not None else Solver(nx, ny, nimg=nimg)
+            try:
+                if (s.nx, s.ny, s.nimg) != (nx, ny, nimg):
+                    raise ValueError(f"solver is {s.nimg} x ({s.ny}, {s.nx}), D is {tuple(Dh.shape)}")
+                s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
+                s.init_linear(CL, CR)
+                s.set_tuning("cg_planes", 1)
+                rs = s.solve_cg(rtol=rtol, max_iter=max_iter)
+                rs = rs if isinstance(rs, list) else [rs]
+                bad = [k for k, r in enumerate(rs) if not r.converged]
+                if bad:
+                    raise RuntimeError(f"effective_diffusivity: CG did not converge to rtol {rtol} for image(s) {bad} "
+                                       f"(rel_residual {[rs[k].rel_residual for k in bad]}, max_iter {max_iter})")
+                g, _ = s.sensitivity(Dh.reshape(nimg * ny, nx), CL, CR)
+            finally:
+                if solver is None:
+                    s.close()
+            deff = np.array([r.deff_raw for r in rs], dtype=np.float64)
+            ctx.save_for_backward(torch.from_numpy(np.ascontiguousarray(g).reshape(Dh.shape)).to(D.device))
+            out = torch.from_numpy(deff).to(D.device)
+            return out if stack else out[0]
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            (g,) = ctx.saved_tensors
+            return grad_out[..., None, None] * g, None, None, None, None, None
+
+    _FN = _EffectiveDiffusivity
+    return _FN
+
+
+def effective_diffusivity(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, solver=None):
+    """deff_raw of the diffusivity map D -- a float64 tensor (ny, nx), or (nimg, ny, nx) for a stack, on any device -- as a
+    tensor on D's device, shape () or (nimg,), differentiable with respect to D.  Forward: deff_assemble_from_D, the linear
+    guess, conjugate gradients on the coefficient planes to rtol (raises RuntimeError if they do not converge), then the
+    gradient map of the converged field; backward: grad_out[..., None, None] * g.  `solver`: a Solver of the same shape to
+    reuse (its system, field and the tuning key "cg_planes" are overwritten); otherwise one is created and closed."""
+    import torch
+    if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() not in (2, 3):
+        raise TypeError("D must be a float64 tensor of shape (ny, nx) or (nimg, ny, nx)")
+    return _function().apply(D, float(CL), float(CR), float(rtol), int(max_iter), solver)

@@ -143,6 +143,10 @@ try {
     for (hipEvent_t e : c->cgs_ev) if (e) (void)hipEventDestroy(e);
     if (c->resid_ev0) (void)hipEventDestroy(c->resid_ev0);
     if (c->resid_ev1) (void)hipEventDestroy(c->resid_ev1);
+    if (c->sens_g) (void)hipFree(c->sens_g);
+    if (c->sens_part) (void)hipFree(c->sens_part);
+    if (c->sens_ev0) (void)hipEventDestroy(c->sens_ev0);
+    if (c->sens_ev1) (void)hipEventDestroy(c->sens_ev1);
     if (c->q_host) (void)hipHostFree(c->q_host);
     if (c->chain_counted) resident_chain_ctx_destroyed(c->device);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -270,6 +274,7 @@ try {
     else if (!strcmp(key, "tb_debug_stall")) c->tb_debug_stall = value;
     else if (!strcmp(key, "tb_debug_stall_skip")) c->tb_debug_stall_skip = value;
     else if (!strcmp(key, "res_kt")) c->res_kt = value;
+    else if (!strcmp(key, "sens_kt")) c->sens_kt = value;
     else if (!strcmp(key, "tb_sym")) c->tb_sym = value;
     else if (!strcmp(key, "tb_launch")) {            // 0: resident passes where possible; 1: one launch per pass
         if (value > 1) return fail(DEFF_EINVAL, "tb_launch takes 0 (resident passes where the tiles fit the chip) or 1 (one launch per pass)");
@@ -356,6 +361,8 @@ try {
     else if (!strcmp(key, "cgs_waits")) *value = c->cgs_waits;
     else if (!strcmp(key, "res_kt")) *value = c->res_plan_kt;
     else if (!strcmp(key, "res_items")) *value = c->res_plan_items;
+    else if (!strcmp(key, "sens_kt")) *value = c->sens_plan_kt;
+    else if (!strcmp(key, "sens_items")) *value = c->sens_plan_items;
     else if (!strcmp(key, "fill_impl")) *value = c->fill_plan_impl;
     else if (!strcmp(key, "fill_launches")) *value = c->fill_plan_launches;
     else if (!strcmp(key, "fill_rounds")) *value = c->fill_plan_rounds;
@@ -583,6 +590,7 @@ try {
     HIP_TRY(hipStreamSynchronize(c->stream));        // Grid may be freed by the caller
     c->have_explicit = true; c->c0_omega = NAN; c->have_walls = true;
     c->phase_mode = 3; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = Dg;
+    c->grid_given = Grid != nullptr;
     c->have_matfree = false; c->dict_tried = false; c->wrap_links = false; c->native3 = false;
     return DEFF_OK;
 }

@@ -11,6 +11,7 @@
 //   api_solve.hip  wall fluxes and the Jacobi solve loops (one image, batch, streaming batch); no sweep kernel
 //   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg) and through refilled slots (deff_solve_cg_stream);
 //                  every CG kernel, the slab forms included: their launches for one slab (cg_slab.hpp)
+//   api_sens.hip   the Deff gradient dDeff/dD per cell and its Euler sum (deff_sensitivity, deff_sensitivity_D)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
 //                  RCCL or a caller-supplied transport with one process per GPU); conjugate gradients over the slabs
@@ -276,6 +277,16 @@ struct deff_ctx {
     // ev0 / ev1 belong to the solve loops alone, which read them at every check and may call the residual in between
     // (a deff_set_progress or deff_image_done_fn callback)
     hipEvent_t resid_ev0 = nullptr, resid_ev1 = nullptr;
+
+    // deff_sensitivity / deff_sensitivity_D (api_sens.hip): the last map (pitch nx, kept until the next call: deff_device_sensitivity),
+    // the work items' Euler sums + one sum per image, and the calls' own event pair, all allocated by the first call.
+    // sens_kt: tuning, tiles of 8 rows a wave streams through (0 = planner); sens_plan_*: deff_get_plan "sens_kt" / "sens_items"
+    double *sens_g = nullptr, *sens_part = nullptr;
+    size_t sens_part_cap = 0;
+    bool sens_have = false;
+    hipEvent_t sens_ev0 = nullptr, sens_ev1 = nullptr;
+    int sens_kt = 0, sens_plan_kt = 0, sens_plan_items = 0;
+    bool grid_given = false;        // the last deff_assemble_3phase was given a Grid (deff_sensitivity refuses such a system)
 
     // Native 3-phase system (kernels_fill.hpp, api_fill.hip): the flood fill of the pore space as bitmaps -- one `open` and
     // one `reach` word per 64 columns of a row, fill_nw words per row --, its status words and the tiled form's `changed` words.

@@ -375,6 +375,34 @@ class Solver:
         out = r[0] if self.nimg == 1 else np.array(r[:])
         return (out, ms.value) if timing else out
 
+    def sensitivity(self, D=None, CL=None, CR=None, timing=False):
+        """The Deff gradient of the current field (deff_sensitivity / deff_sensitivity_D): (g, euler) with g[p] = d deff_raw /
+        d D[p] as (ny, nx), or (nimg, ny, nx) for a stack, and euler = sum of D * g per image (a float, or an array), which
+        equals deff_raw for a converged field.  D = None: the diffusivities of the system assembled from the image
+        (assemble_2phase, or assemble_3phase without a grid) with its CL, CR; otherwise the plane (rows, nx) with the wall
+        values.  timing=True appends the device time in ms."""
+        g = np.empty((self.rows, self.nx), dtype=np.float64)
+        e = (C.c_double * self.nimg)()
+        ms = C.c_float()
+        msp = C.byref(ms) if timing else None
+        if D is None:
+            check(self._L.deff_sensitivity(self._ctx, g.ctypes.data_as(C.c_void_p), e, msp))
+        else:
+            D = np.ascontiguousarray(D, dtype=np.float64)
+            assert D.size == self.nx * self.rows
+            check(self._L.deff_sensitivity_D(self._ctx, D.ctypes.data_as(C.c_void_p), float(CL), float(CR),
+                                             g.ctypes.data_as(C.c_void_p), e, msp))
+        g = g if self.nimg == 1 else g.reshape(self.nimg, self.ny, self.nx)
+        euler = e[0] if self.nimg == 1 else np.array(e[:])
+        return (g, euler, ms.value) if timing else (g, euler)
+
+    def device_sensitivity_ptr(self):
+        """(device pointer, row pitch in bytes) of the last sensitivity map; valid until the next one, an assembly or close()."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_device_sensitivity(self._ctx, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
     def set_progress(self, fn):
         """fn(iter, deff_raw, change) after every convergence check, or None."""
         if fn is None:

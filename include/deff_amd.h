@@ -98,6 +98,7 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  *   to the image and to what fits a workgroup) -- both exist so that the tiled form and its seams can be tested at small shapes,
  * "res_kt" (deff_residual / deff_residual_slot: tiles of 8 rows one wave streams through, a "run"; 0 = the planner's choice,
  *   about 4 096 work items per launch; clipped to the image's tile rows; deff_get_plan "res_kt"),
+ * "sens_kt" (deff_sensitivity / deff_sensitivity_D: the same for the gradient pass; deff_get_plan "sens_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
  *   run every pass between two checks in ONE launch, neighbouring tiles synchronised by flags: 1 = one launch per
  *   pass instead; a resident launch that cannot make progress -- another process holds part of the GPU -- gives up
@@ -135,7 +136,8 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * last deff_residual / deff_residual_slot / deff_residual_D that launched (0 before one; a refused call leaves them alone):
  * "res_kt" (tiles of 8 rows per run as used: after the planner, the tuning key and the clip to the image's tile rows;
  * 0 after deff_residual_D, which has no runs) and "res_items" (partial sums added per image by the final reduction:
- * strips of 128 columns x ceil(tile rows / res_kt), or for deff_residual_D rows x segments of 256 columns).  Of the flood fill
+ * strips of 128 columns x ceil(tile rows / res_kt), or for deff_residual_D rows x segments of 256 columns).  Of the last
+ * deff_sensitivity / deff_sensitivity_D that launched: "sens_kt" and "sens_items", with the same meaning.  Of the flood fill
  * on the device (deff_assemble_3phase_native): "fill_impl" (form of the last fill: 1 = one workgroup per image, 2 = row tiles),
  * "fill_launches" (kernel launches of the last fill), "fill_rounds" (most rounds one workgroup of it took), "fill_runs" (fills
  * computed since the context was created: a continuation stage on the same image computes none), "fill_fallbacks" (images
@@ -336,6 +338,32 @@ int deff_residual(deff_ctx *ctx, double *r /* [nimg] */, float *ms);
 /* ... of ONE image of a stack, wherever its newest field lives: callable from the deff_image_done_fn callback of a stream */
 int deff_residual_slot(deff_ctx *ctx, int slot, double *r);
 int deff_residual_D(deff_ctx *ctx, const double *D, double CL, double CR, double *r /* [nimg] */, float *ms);
+/* The Deff gradient of the current field, meaningful for a CONVERGED one (deff_solve_cg): g[p] = d deff_raw / d D[p] for every
+ * cell, in one pass over the field and the diffusivities -- the problem is self-adjoint, no second solve.  With dx, dy of
+ * deff_mesh, wx = dy / dx for W / E faces, wy = dx / dy for N / S faces (the assembly's weights), each face of cell p adds
+ *   interior, to q:  s = Dp + Dq;  t = (s == 0) ? 0 : Dq / s;  e = xp - xq;  c = (2.0 * (t * t)) * (w * (e * e))
+ *   left / right wall:  e = xp - CL (CR);  c = (dy / (dx / 2.0)) * (e * e);      no face (first / last row):  c = +0.0
+ *   g[p] = (((cW + cE) + cN) + cS) / ((CR - CL) * (CR - CL)),  and g[p] = 0 where D[p] == 0.
+ * These doubles, in this order (tests/sensitivity_model.py states them in numpy).  euler[k] = sum over image k of D[p] * g[p],
+ * which equals deff_raw for the exact solution (Deff is homogeneous of degree 1 in D): a wave-level reduction in a fixed order
+ * (csrc/kernels_sens.hpp), the same bits on every call.  g (nimg*ny*nx, true width) and euler ([nimg]) may each be NULL;
+ * *ms (may be NULL) = device time of the pass, on an event pair of its own.
+ *   deff_sensitivity_D: D[nimg*ny*nx] on the host, as deff_assemble_from_D takes it, with the wall values.
+ *   deff_sensitivity: D from the context's image system -- deff_assemble_2phase, or deff_assemble_3phase with Grid == NULL --,
+ *     filled on the device from the stored phase diffusivities; CL, CR are the system's.  A system assembled with a Grid
+ *     (ImpSolid rows, deff_assemble_3phase_native) is DEFF_EINVAL; deff_set_system, deff_assemble_from_D or no system: DEFF_ESTATE.
+ * Plain and stack contexts; row slabs and CR == CL are DEFF_EINVAL.  Pending work is settled first and every image's newest
+ * field is read; nothing else changes (field, system, plans, tuning, the solvers' timing), and a refused call leaves the
+ * previous map alone.  Negative or non-finite D: unspecified values, never a fault.
+ * Tuning "sens_kt": tiles of 8 rows one wave streams through (0 = the planner's choice, clipped to the image);
+ * deff_get_plan "sens_kt" / "sens_items": what the last call used, and the partial sums added per image
+ * (strips of 128 columns x ceil(tile rows / sens_kt)).
+ * deff_device_sensitivity: the device buffer of the last map (row pitch as deff_device_field), valid until the next
+ * sensitivity call, assembly or deff_destroy; DEFF_ESTATE before one exists. */
+int deff_sensitivity_D(deff_ctx *ctx, const double *D, double CL, double CR,
+                       double *g /* nimg*ny*nx, may be NULL */, double *euler /* [nimg], may be NULL */, float *ms);
+int deff_sensitivity(deff_ctx *ctx, double *g, double *euler, float *ms);
+int deff_device_sensitivity(deff_ctx *ctx, void **d_g, size_t *row_pitch_bytes);
 /* sweep-kernel launches issued by the last deff_sweeps()/deff_solve() and the sweeps one
  * temporally blocked launch performs (1 for the single-sweep kernels).  A chained launch of the streaming kernel
  * (deff_get_plan "tb_chain" = 1: several passes of *sweeps_per_pass sweeps in one launch) counts its PASSES, so that
