@@ -21,12 +21,12 @@
 
 // CG table from the host dictionary: planes A0, 1/A0, aW, aE, aS, aN, b; decoupled rows (four zero links, b == 0) stay all
 // zeros.  An active row must have a finite positive A0 with a normal 1/A0 and finite links and b.
-static int cg_table(const deff_ctx *c, std::vector<double> &t)
+static int cg_table(const std::vector<double> &rows, int nrows, std::vector<double> &t)
 {
     t.assign(CG_DOUBLES, 0.0);
     constexpr int S = LUT_PLANE_STRIDE;
-    for (int k = 1; k < c->lut_nrows; ++k) {
-        const double *row = &c->lut_rows[(size_t)k * 6];
+    for (int k = 1; k < nrows; ++k) {
+        const double *row = &rows[(size_t)k * 6];
         const double a0 = row[0], aW = row[1], aE = row[2], aS = row[3], aN = row[4], b = row[5];
         if (aW == 0.0 && aE == 0.0 && aS == 0.0 && aN == 0.0 && b == 0.0) continue;   // decoupled: x = 0
         const double inv = 1.0 / a0;
@@ -45,6 +45,8 @@ static int cg_table(const deff_ctx *c, std::vector<double> &t)
     }
     return DEFF_OK;
 }
+
+static int cg_table(const deff_ctx *c, std::vector<double> &t) { return cg_table(c->lut_rows, c->lut_nrows, t); }
 
 // rows per work item of an image of `ntx` strips and ny rows: ~8 192 items per image, 2..16 rows each
 static int cg_rows_per_item(int ntx, int ny) { return (int)std::max(2L, std::min(16L, (long)ntx * ny / 8192)); }
@@ -373,20 +375,15 @@ try {
                                  "deff_slab_group_solve_cg or deff_slab_rank_solve_cg)");
     TRY(use_device(c));
     TRY(resident_check(c));                                          // an unchecked resident interval is settled under the OLD system
-    // the table first: a refusal leaves the context's dictionary as it was
+    // the table first, as a candidate of its own: a refusal (an inadmissible row, an image that does not match the mesh) leaves
+    // every field of the context as it was -- its dictionary, a native 3-phase system, a caller's wall-column links
     std::vector<double> tab;
     {
-        std::vector<double> rows0 = c->lut_rows;
-        const int nrows0 = c->lut_nrows;
-        const bool allb0 = c->lut_allb;
-        const double omega0 = c->lut_omega;
-        build_lut_rows(c, Ds, Df, CL, CR);
-        int rc = cg_table(c, tab);
-        if (rc == DEFF_OK) rc = image_shape(c, W, H, ampX, ampY);
-        if (rc != DEFF_OK) {
-            c->lut_rows.swap(rows0); c->lut_nrows = nrows0; c->lut_allb = allb0; c->lut_omega = omega0;
-            return rc;
-        }
+        std::vector<double> rows;
+        native2_rows(c, Ds, Df, CL, CR, rows);
+        TRY(cg_table(rows, LUT_NATIVE_ROWS, tab));
+        TRY(image_shape(c, W, H, ampX, ampY));
+        commit_lut_rows(c, rows);
     }
     TRY(ensure_walls(c));
     TRY(dev_alloc(&c->code, c->n));
@@ -396,7 +393,6 @@ try {
     c->CL = CL; c->CR = CR; c->Ds = Ds; c->Df = Df;
     c->phase_mode = 2; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = 0.0;
     c->have_image = true; c->have_walls = true; c->have_matfree = true; c->have_explicit = false;
-    c->wrap_links = false;
     c->links_sym = 0;
     c->dict_tried = false; c->have_field = true;
     c->q_valid = false;

@@ -436,21 +436,35 @@ DEFF_API_CATCH
 // Row dictionary of the native 2-phase system, enumerated a priori: for every position class and
 // every own/W/E/S/N phase pattern the matrix row fvm_row() produces -- built on the host with the
 // same routine the device assembly uses, so it holds the very same doubles.  Row 0 = zeros.
-void build_lut_rows(deff_ctx *c, double Ds, double Df, double CL, double CR)
+void native2_rows(const deff_ctx *c, double Ds, double Df, double CL, double CR, std::vector<double> &rows)
 {
-    c->native3 = false; c->codes3_valid = false;       // the 2-phase system takes over the table and the codes
-    c->lut_nrows = LUT_NATIVE_ROWS;
-    c->lut_rows.assign((size_t)c->lut_nrows * 6, 0.0);
+    rows.assign((size_t)LUT_NATIVE_ROWS * 6, 0.0);
     for (int ycls = 0; ycls < 3; ++ycls)
         for (int xcls = 0; xcls < 3; ++xcls)
             for (int code = 0; code < 32; ++code) {
                 auto D = [&](int bit) { return ((code >> bit) & 1) ? Ds : Df; };
                 const FvmRow r = fvm_row(D(0), D(1), D(2), D(3), D(4), xcls, ycls, c->dx, c->dy, CL, CR);
-                double *row = &c->lut_rows[(size_t)(1 + (ycls * 3 + xcls) * 32 + code) * 6];
+                double *row = &rows[(size_t)(1 + (ycls * 3 + xcls) * 32 + code) * 6];
                 row[0] = r.a0; row[1] = r.aW; row[2] = r.aE; row[3] = r.aS; row[4] = r.aN; row[5] = r.b;
             }
+}
+
+// The context takes a table of native2_rows() as its dictionary: whatever belonged to the system before it goes.
+void commit_lut_rows(deff_ctx *c, std::vector<double> &rows)
+{
+    c->native3 = false; c->codes3_valid = false;       // the 2-phase system takes over the table and the codes
+    c->wrap_links = false;                             // ... and a caller's system with wall-column links is gone with its planes
+    c->lut_nrows = LUT_NATIVE_ROWS;
+    c->lut_rows.swap(rows);
     c->lut_allb = false;
     c->lut_omega = NAN;
+}
+
+void build_lut_rows(deff_ctx *c, double Ds, double Df, double CL, double CR)
+{
+    std::vector<double> rows;
+    native2_rows(c, Ds, Df, CL, CR, rows);
+    commit_lut_rows(c, rows);
 }
 
 // Device tables for a given omega: plane 0 holds c0 = omega / A0 (the reference divides w by

@@ -200,13 +200,25 @@ try {
     if (check_every < 1) return fail(DEFF_EINVAL, "check_every must be >= 1");
     if (c->slab) return fail(DEFF_EINVAL, "not for slab contexts");
     TRY(use_device(c));
+    std::vector<double> rows;
+    native2_rows(c, Ds, Df, CL, CR, rows);
+    if (c->prescaled) {
+        // what plan_sweeps would refuse below, with the images taken and the old system gone: said here, where a refusal still
+        // leaves field, system and plan as they were (deff_amd.h, "prescaled")
+        if (c->kernel == DEFF_KERNEL_EXPLICIT || c->kernel == DEFF_KERNEL_SCALAR)
+            return fail(DEFF_EINVAL, "prescaled: the explicit and scalar kernels have no pre-scaled form (deff_set_kernel: auto, matfree or matfree_tb)");
+        for (int k = 1; k < LUT_NATIVE_ROWS; ++k)
+            if (!std::isfinite(omega / rows[(size_t)k * 6]))
+                return fail(DEFF_EINVAL, "prescaled: the row dictionary has a singular row (a phase that cannot diffuse): "
+                                         "omega / A0 is not finite there and the table cannot be pre-scaled");
+    }
     TRY(image_shape(c, W, H, ampX, ampY));
     TRY(ensure_walls(c));
     TRY(dev_alloc(&c->code, c->n));
     const int B = c->nimg;
     c->CL = CL; c->CR = CR; c->Ds = Ds; c->Df = Df;
     c->phase_mode = 2; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = 0.0;
-    build_lut_rows(c, Ds, Df, CL, CR);
+    commit_lut_rows(c, rows);
     c->have_image = true; c->have_walls = true; c->have_matfree = true; c->have_explicit = false;
     c->links_sym = 0;
     c->dict_tried = false; c->have_field = true;

@@ -468,7 +468,9 @@ static inline double deff_of_fluxes(const double *L, const double *R, int ny, do
 void reset_batch_state(deff_ctx *c);
 int resolve_kernel(const deff_ctx *c, int *k);
 int image_shape(deff_ctx *c, int W, int H, int ampX, int ampY);
-void build_lut_rows(deff_ctx *c, double Ds, double Df, double CL, double CR);
+void native2_rows(const deff_ctx *c, double Ds, double Df, double CL, double CR, std::vector<double> &rows);   // changes nothing
+void commit_lut_rows(deff_ctx *c, std::vector<double> &rows);
+void build_lut_rows(deff_ctx *c, double Ds, double Df, double CL, double CR);                                // both of them
 int upload_lut(deff_ctx *c, double omega);
 int upload_lut_pre(deff_ctx *c, double omega);           // after upload_lut(c, omega), on a table without a singular row
 int consolidate(deff_ctx *c);

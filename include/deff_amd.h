@@ -311,7 +311,8 @@ int deff_get_slot_field(deff_ctx *ctx, int slot, double *x /* nx*ny */);
  *   DEFF_EINVAL before `next` is ever called: NULL callbacks, rtol negative or not finite, max_iter < 0, check_every < 1, a
  * row-slab context, an image that does not match the mesh, a table that is not admissible (an active row without a finite
  * A0 > 0, e.g. Df < 0 or not finite; the rule is deff_solve_cg's, so Df = 0 or Ds = 0 is admitted: that phase's rows are
- * decoupled and its cells get x = 0).  A `next` that returns < 0: DEFF_EINVAL.  The symmetry of an entering slot's system is checked on the
+ * decoupled and its cells get x = 0).  Such a refusal changes nothing: image, fill, system (a native 3-phase one included),
+ * field and plans are what they were.  A `next` that returns < 0: DEFF_EINVAL.  The symmetry of an entering slot's system is checked on the
  * device and reported (DEFF_EINVAL) with the next look at the slots.
  *   After DEFF_OK the context is an ordinary stack context, as after deff_solve_stream: slot k holds the last image that ran in
  * it, its system and its final field; slots that never received an image hold the zero place holder described above. */

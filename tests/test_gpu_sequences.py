@@ -46,17 +46,24 @@ class Model:
         self.pix = draw_images(self.rng, self.nx, self.ny, self.B)
         self.kind = None
 
-    def assemble(self, kind, Ds, Df, Dg, CL, CR, D=None):
+    def assemble(self, kind, Ds, Df, Dg, CL, CR, D=None, base=None):
+        """kind "3n" / "3g": three pixel classes with the flood-filled Grid (ImpSolid rows); "S" / "Sw": a caller's system, the
+        oracle's of the plane `base` names, "Sw" with the wall-column links of wrap_system()."""
         ob = self.ob
         self.CL, self.CR, self.kind = CL, CR, kind
-        if kind == "2p":
+        plane = base if kind in ("S", "Sw") else kind
+        if plane == "2p":
             self.D = [ob.fill_D_2phase(p, Df, Ds) for p in self.pix]
-        elif kind == "3p":
+        elif plane in ("3p", "3n", "3g"):
             self.D = [ob.fill_D_3phase(p, Df, Ds, Dg) for p in self.pix]
         else:
             self.D = D if D is not None else draw_D_planes(self.rng, self.nx, self.ny, self.B, Ds, Df, Dg)
-        sys_ = [ob.discretize(D, CL, CR) for D in self.D]
+        self.grid = [ob.floodfill((p > 200).astype(np.uint32))[0] for p in self.pix] if kind in ("3n", "3g") else None
+        sys_ = [ob.discretize(D, CL, CR, grid=self.grid[k] if self.grid else None) for k, D in enumerate(self.D)]
         self.A, self.b = [s[0] for s in sys_], [s[1] for s in sys_]
+        if kind == "Sw":
+            for A in self.A:
+                A.reshape(self.ny, self.nx, 5)[1:, 0, 1] = -0.125
 
     def stacked(self, arrs):
         return np.concatenate(arrs, axis=0)
@@ -95,10 +102,36 @@ ASSEMBLE_D = [(1e-3, 1.0, 10.0), (1e-2, 1.0, 50.0), (0.1, 2.0, 7.0)]
 ASSEMBLE_C = [(0.0, 1.0), (0.25, 0.75)]
 
 
+# The options below draw what the ABI gained after those (each has a flow test of its own; here it meets a context that other
+# calls have changed).  The draw then follows a few more facts of the model's state -- whether the device fill is the current
+# image's, the kernel and "prescaled" settings (a pre-scaled stream on the explicit kernel is refused and changes nothing),
+# the last two ops -- and still nothing the GPU returns:
+#
+#   native3   assembly kinds "3n" (deff_assemble_3phase_native) and "3g" (deff_assemble_3phase with the oracle's flood-filled
+#             Grid), the ops "stage" (the native assembly again on the same image: a continuation stage) and "grid"
+#             (deff_get_grid, while the device fill is the current image's), the keys "fill_impl" / "fill_tile_rows", and the
+#             kernel draw on "3n" as on "2p" (explicit / scalar force the planes that are built on demand)
+#   system    kinds "S" (deff_set_system with the oracle's system of a drawn 2p / 3p / D plane) and "Sw" (even widths: the same
+#             with wall-column links into the neighbouring row, an explicit-only system), the op "getsys" (deff_get_system)
+#   cgkeys    the keys "cg_planes" and "cg_fold"
+#   cgstream  deff_solve_cg_stream of B ... 3B+1 images on a stack (B >= 2); about one in four is asked with Df = -1 and refused
+#   sens      deff_sensitivity / deff_sensitivity_D of the current field
+#   prescaled the key "prescaled" (never with fma or stamps: the pre-scaled sweeps ignore the one and have no stamped form)
+
+# (key, values) pairs the tune draw gains per option; "cg keys" sets both CG keys in one draw, "prescaled" mostly toggles
+TUNE_EXTRA = dict(native3=[("fill_impl", [0, 1, 2])] * 3 + [("fill_tile_rows", [0, 8, 16])] * 4,
+                  cgkeys=[("cg keys", None)] * 12,
+                  prescaled=[("prescaled", None)] * 10,
+                  sens=[("tb_impl", [2])] * 8 + [("tb_launch", [0])] * 2)     # (towards resident tiles: a gradient inside a pending interval)
+CG_PLANES_DRAW, CG_FOLD_DRAW = [0, 0, 1, 2], [0, 1, 1, 2, 2]
+
+
 def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30, onchip=False, stream=False, ptr=False,
-                  slot=False, stamps=False, fma=False):
+                  slot=False, stamps=False, fma=False, native3=False, system=False, cgkeys=False, cgstream=False, sens=False,
+                  prescaled=False):
     """Generator of (op, arguments...) tuples; the first is ("open", nx, ny, B, fma) and the second the first image."""
     assert not (fma and with_cg)                             # CG's arithmetic has no contracted form to compare with
+    assert not (prescaled and (fma or stamps))
     rng = np.random.default_rng(seed)
     nx, ny = shapes[rng.integers(len(shapes))]
     B = int(rng.choice(list(stacks)))
@@ -106,6 +139,15 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
     yield ("open", nx, ny, B, use_fma)
     yield ("image", draw_images(rng, nx, ny, B))
     kind, have_x = None, False
+    fill = False                                             # the context holds a device fill of the current image
+    kset, pre = "auto", 0                                    # deff_set_kernel's and "prescaled"'s current values
+    prev = prev2 = None                                      # the two ops before
+    refused_on_3n = False                                    # the last call was a refused CG stream on a native 3-phase system
+    after_stream = False                                     # a stream filled the slots and no assembly has followed
+    pre_swept = False                                        # the current system has been swept under "prescaled" 1
+    sw = "Sw" if nx % 2 == 0 else "S"                        # (an odd width cannot represent a wall-column link: refused)
+    kinds = ["2p", "2p", "3p", "D"] + (["3n", "3n", "3g"] if native3 else []) + (["S", sw, sw] if system else [])
+    extra = [kv for name, on in (("native3", native3), ("cgkeys", cgkeys), ("prescaled", prescaled), ("sens", sens)) if on for kv in TUNE_EXTRA[name]]
     for step in range(steps):
         ops = ["image", "assemble", "tune"]
         if kind is not None:
@@ -122,20 +164,90 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
                     ops += ["slot"]
                 if stamps:
                     ops += ["stamps"]
+                if sens:
+                    # (sweeps, the gradient, then a solve in a row -- the gradient inside a resident interval that no check has
+                    # settled yet -- would be a rare order at even weights)
+                    ops += ["sens", "sens"] + (["sens"] * 12 if prev == "sweeps" else []) + (["solve"] * 16 if (prev2, prev) == ("sweeps", "sens") else [])
+            if system:
+                ops += ["getsys"]
         if stream and B >= 2:
             ops += ["stream"]
+        # The weights of the later options.  Even weights would leave the call orders they are there for (the list in
+        # test_sequences_host.py) to a seed in a hundred: an order of three particular calls among twenty kinds.  So what has
+        # just happened raises the weight of what makes such an order: keys change often; a native fill is followed by another
+        # kind and by the native assembly again; wall-column links by a 2-phase assembly; a refused CG stream on a native
+        # system by a read of its planes; pre-scaled sweeps by the key and by sweeps again.
+        if extra:
+            ops += ["tune", "tune"]
+        if native3 or system:
+            ops += ["assemble"] * (3 if fill or kind == "Sw" or after_stream else 1)
+        if native3:
+            ops += (["stage"] * 3 if kind == "3n" else []) + (["grid"] * 2 if fill else [])
+            if system and kind == "3n":
+                ops += ["getsys"] * 3                        # (the planes of a native system are built on demand)
+        if system and kind == "Sw" and have_x and (with_cg or onchip):
+            ops += ["cg"] * 9                                # (refused: an explicit-only system)
+        if cgstream and B >= 2:
+            ops += ["cgstream"] * (6 if kind == "3n" else 1)
+            if refused_on_3n and kind == "3n":
+                ops += ["getsys"] * 8
+        if prescaled and have_x and kind is not None:
+            ops += ["sweeps"] * (8 if pre_swept and not pre else 3) + (["prescaled"] * 5 if prev == "sweeps" and pre else [])
         op = ops[rng.integers(len(ops))]
+        prev2, prev = prev, op
+        refused_on_3n = False
         if op == "image":
             yield ("image", draw_images(rng, nx, ny, B))
-            kind = None
+            kind, fill, after_stream, pre_swept = None, False, False, False
         elif op == "assemble":
-            kind = ["2p", "2p", "3p", "D"][rng.integers(4)]
+            more = (["3n"] * 4 if (fill and kind != "3n") or (native3 and after_stream) else []) + (["2p"] * 4 if kind == "Sw" else [])
+            if fill and kind == "3n":
+                more = [k for k in kinds if k != "3n"]       # (another kind on the filled image, then "3n" again)
+            kind = (kinds + more)[rng.integers(len(kinds) + len(more))]
             Ds, Df, Dg = ASSEMBLE_D[rng.integers(3)]
             CL, CR = ASSEMBLE_C[rng.integers(2)]
-            yield ("assemble", kind, Ds, Df, Dg, CL, CR, draw_D_planes(rng, nx, ny, B, Ds, Df, Dg) if kind == "D" else None)
+            if kind in ("S", "Sw"):                          # the plane whose system the caller hands over
+                base = ["2p", "3p", "D"][rng.integers(3)]
+                yield ("assemble", kind, Ds, Df, Dg, CL, CR, draw_D_planes(rng, nx, ny, B, Ds, Df, Dg) if base == "D" else None, base)
+            else:
+                yield ("assemble", kind, Ds, Df, Dg, CL, CR, draw_D_planes(rng, nx, ny, B, Ds, Df, Dg) if kind == "D" else None)
+            fill = fill or kind == "3n"
+            after_stream = pre_swept = False
+            if kind in ("D", "S", "Sw"):
+                kset = "auto"                                # (run_sequence sets the kernel back for a caller's planes)
+        elif op == "stage":
+            Ds, Df, Dg = ASSEMBLE_D[rng.integers(3)]
+            CL, CR = ASSEMBLE_C[rng.integers(2)]
+            yield ("stage", Ds, Df, Dg, CL, CR)
+        elif op == "cgstream":
+            count = int(rng.integers(B, 3 * B + 2))
+            imgs = draw_images(rng, nx, ny, count)
+            Ds, Df, _ = ASSEMBLE_D[rng.integers(3)]
+            CL, CR = ASSEMBLE_C[rng.integers(2)]
+            rtol = float(rng.choice([1e-6, 1e-10]))
+            max_iter = int(rng.choice([3, 100000, 100000]))
+            ce = int(rng.choice([1, 64]))
+            refused = bool(rng.random() < (0.5 if kind == "3n" else 0.2))       # (about one in four over a group)
+            yield ("cgstream", imgs, Ds, -1.0 if refused else Df, CL, CR, rtol, max_iter, ce)
+            if not refused:
+                kind, have_x, fill, after_stream = "2p", True, False, True
+            refused_on_3n = refused and kind == "3n"
+        elif op == "prescaled":
+            pre = 1 - pre
+            yield ("tune", "prescaled", pre)
         elif op == "tune":
-            what = rng.integers(9 if onchip else 5)         # (the key is drawn as often as the four blocked-pass keys together)
-            if what == 0:
+            what = rng.integers((9 if onchip else 5) + len(extra))      # (cg_onchip is drawn as often as the four blocked-pass keys together)
+            if what >= (9 if onchip else 5):
+                key, values = extra[what - (9 if onchip else 5)]
+                if key == "cg keys":
+                    yield ("tune", "cg_planes", int(rng.choice(CG_PLANES_DRAW)))
+                    yield ("tune", "cg_fold", int(rng.choice(CG_FOLD_DRAW)))
+                elif key == "prescaled":
+                    pre = 1 - pre if rng.random() < 0.8 else pre
+                    yield ("tune", "prescaled", pre)
+                else:
+                    yield ("tune", key, int(rng.choice(values)))
+            elif what == 0:
                 yield ("tune", "tb_T", int(rng.choice([0, 2, 4, 8])))
             elif what == 1:
                 yield ("tune", "tb_impl", int(rng.choice([0, 1, 2])))
@@ -144,7 +256,8 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             elif what == 3:
                 yield ("tune", "flux_reduce", int(rng.choice([0, 1])))
             elif what == 4:
-                yield ("kernel", ["auto", "matfree_tb", "explicit", "matfree"][rng.integers(4)] if kind == "2p" else "auto")
+                kset = ["auto", "matfree_tb", "explicit", "matfree"][rng.integers(4)] if kind in ("2p", "3n") else "auto"
+                yield ("kernel", kset)
             else:
                 yield ("tune", "cg_onchip", int(rng.choice([0, 1, 1])))
         elif op == "init":
@@ -157,6 +270,7 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             k = int(rng.choice([1, 3, 8, 17, 40, 64]))
             omega, kern = [(2.0 / 3.0, 0), (1.0, 1)][rng.integers(2)]
             yield ("sweeps", k, omega, kern)
+            pre_swept = pre_swept or bool(pre)
         elif op == "solve":
             tol = float(rng.choice(SOLVE_TOL))
             max_iter = int(rng.choice(SOLVE_MAX_ITER))
@@ -179,7 +293,8 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             tol = float(rng.choice(SOLVE_TOL))
             max_iter = int(rng.choice(SOLVE_MAX_ITER))
             yield ("stream", imgs, Ds, Df, CL, CR, tol, max_iter, int(rng.choice(SOLVE_CE)))
-            kind, have_x = "2p", True
+            if not (pre and kset == "explicit"):             # (refused before anything changes: no pre-scaled explicit sweeps)
+                kind, have_x, fill, after_stream = "2p", True, False, True
         elif op == "slot":
             yield ("slot", int(rng.integers(B)))
         elif op == "stamps":
@@ -281,8 +396,41 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
     flavour = "fma" if use_fma else None
     m = Model(ob, nx, ny, B, None)
     log = []
-    onchip_key = 0
+    onchip_key = planes_key = fold_key = pre_key = 0
+    kernel_set = "auto"
+    m.fill_fresh, m.fill_count = False, 0                    # the device fill: of the current image? / how many were computed
+    sens_model = pre_model = None
+    if options.get("sens"):
+        import sensitivity_model as sens_model
+    if options.get("prescaled"):
+        import prescaled_model as pre_model
+
+    def distinct_rows():
+        return len(np.unique(np.column_stack([np.concatenate(m.A), np.concatenate(m.b)]), axis=0))
+
     with pkg.Solver(nx, ny, nimg=B) as s:
+        def prescaled_refused(call, own_system=False):
+            """While "prescaled" is 1 a call that would sweep is refused for a system or a kernel setting without a pre-scaled
+            form (deff_amd.h) -- decided from the model alone -- and changes nothing."""
+            if not pre_key:
+                return False
+            refuse = kernel_set in ("explicit", "scalar") or (not own_system and (m.kind == "Sw" or distinct_rows() > 511))
+            try:
+                call()
+            except pkg.DeffError as e:
+                assert refuse and e.code == -1 and "prescaled" in str(e), (seed, log, e)
+                log[-1] += " refused"
+                if m.x is not None:
+                    fields_equal()
+                return True
+            assert not refuse, (seed, log, "a pre-scaled call that should have been refused")
+            assert s.plan_value("prescaled") == 1, (seed, log)
+            return False
+
+        def native_counters():
+            assert (s.plan_value("fill_runs"), s.plan_value("fill_fallbacks"), s.plan_value("native3_rows")) == (m.fill_count, 0, 452), \
+                (seed, log, s.plan_value("fill_runs"), m.fill_count, s.plan_value("fill_fallbacks"), s.plan_value("native3_rows"))
+
         def fields_equal():
             got = s.get_field()
             for k in range(B):
@@ -315,29 +463,69 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
         s.set_image(np.stack(m.pix))
         for op, *args in draw:
             if op == "image":
-                m.pix, m.kind = args[0], None
+                m.pix, m.kind, m.fill_fresh = args[0], None, False
                 s.set_image(np.stack(m.pix))
                 log.append("image")
             elif op == "assemble":
-                kind, Ds, Df, Dg, CL, CR, D = args
-                m.assemble(kind, Ds, Df, Dg, CL, CR, D)
+                kind, Ds, Df, Dg, CL, CR, D, *base = args
+                m.assemble(kind, Ds, Df, Dg, CL, CR, D, *base)
                 m.phases = (Ds, Df, Dg)
+                log.append(f"assemble {kind} {Ds} {Df} {CL}")
                 if kind == "2p":
                     s.assemble_2phase(Ds, Df, CL, CR)
                 elif kind == "3p":
                     s.assemble_3phase(Ds, Df, Dg, CL, CR)
+                elif kind == "3g":
+                    s.assemble_3phase(Ds, Df, Dg, CL, CR, grid=m.stacked(m.grid))
+                elif kind == "3n":
+                    m.fill_count += 0 if m.fill_fresh else 1
+                    m.fill_fresh = True
+                    s.assemble_3phase_native(Ds, Df, Dg, CL, CR)
+                    native_counters()
+                elif kind in ("S", "Sw"):
+                    s.set_kernel("auto")                     # as for a caller's D plane
+                    kernel_set = "auto"
+                    s.set_system(m.stacked(m.A), m.stacked(m.b), m.stacked(m.D), CL, CR)
+                    log[-1] += " of " + base[0]
                 else:
                     s.set_kernel("auto")                     # a caller's D plane: explicit planes, dictionary if it has few rows
+                    kernel_set = "auto"
                     s.assemble_from_D(m.stacked(m.D), CL, CR)
-                log.append(f"assemble {kind} {Ds} {Df} {CL}")
+                if kind != "3n" and options.get("native3"):
+                    assert s.plan_value("native3_rows") == 0, (seed, log)
+            elif op == "stage":
+                Ds, Df, Dg, CL, CR = args
+                assert m.kind == "3n" and m.fill_fresh
+                log.append(f"stage {Ds} {Df} {Dg} {CL}")
+                m.assemble("3n", Ds, Df, Dg, CL, CR)
+                m.phases = (Ds, Df, Dg)
+                s.assemble_3phase_native(Ds, Df, Dg, CL, CR)
+                native_counters()
+            elif op == "grid":
+                log.append("grid")
+                g, path = s.grid()
+                for k in range(B):
+                    want, flag = ob.floodfill((m.pix[k] > 200).astype(np.uint32))
+                    assert np.array_equal(g[k * ny:(k + 1) * ny], want) and bool(path[k]) == flag, (seed, log, k)
+            elif op == "getsys":
+                log.append("getsys")
+                A, b = s.get_system()
+                assert np.array_equal(A, m.stacked(m.A)) and np.array_equal(b, m.stacked(m.b)), (seed, log)
             elif op == "tune":
                 key, v = args
                 s.set_tuning(key, v)
                 if key == "cg_onchip":
                     onchip_key = v
+                elif key == "cg_planes":
+                    planes_key = v
+                elif key == "cg_fold":
+                    fold_key = v
+                elif key == "prescaled":
+                    pre_key = v
                 log.append(f"{key} {v}")
             elif op == "kernel":
                 s.set_kernel(args[0]); log.append(f"kernel {args[0]}")
+                kernel_set = args[0]
             elif op == "init":
                 s.init_linear(m.CL, m.CR)
                 m.x = [ob.linear_guess(nx, ny, m.CL, m.CR, flavour=flavour) for _ in range(B)]
@@ -348,18 +536,36 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 log.append("set_field")
             elif op == "sweeps":
                 k, omega, kern = args
-                s.sweeps(k, omega)
-                m.x = [ob.sweeps(m.A[i], m.b[i], m.x[i], k, kernel=kern, omega=omega, flavour=flavour) for i in range(B)]
                 log.append(f"sweeps {k} {omega:.3f}")
+                if pre_key:
+                    if prescaled_refused(lambda: s.sweeps(k, omega)):
+                        continue
+                    m.x = [pre_model.sweeps(m.A[i], m.b[i], m.x[i], k, omega=omega) for i in range(B)]
+                else:
+                    s.sweeps(k, omega)
+                    m.x = [ob.sweeps(m.A[i], m.b[i], m.x[i], k, kernel=kern, omega=omega, flavour=flavour) for i in range(B)]
+                if m.kind == "Sw":
+                    assert s.kernel_in_use() in ("explicit", "scalar"), (seed, log, s.kernel_in_use())
                 fields_equal()
             elif op == "solve":
                 tol, max_iter, ce, reader = args
-                res = s.solve(tol, max_iter, check_every=ce)
-                res = [res] if B == 1 else res
                 log.append(f"solve {tol} {max_iter} {ce}")
+                got_res = []
+                if pre_key:
+                    if prescaled_refused(lambda: got_res.append(s.solve(tol, max_iter, check_every=ce))):
+                        continue
+                    res = got_res[0]
+                else:
+                    res = s.solve(tol, max_iter, check_every=ce)
+                res = [res] if B == 1 else res
+                if m.kind == "Sw":
+                    assert s.kernel_in_use() in ("explicit", "scalar"), (seed, log, s.kernel_in_use())
                 for i in range(B):
-                    it, deff, conv, x, MFL, MFR = ob.jacobi(m.A[i], m.b[i], m.x[i], m.D[i], m.CL, m.CR, tol, max_iter, check_every=ce,
-                                                            flavour=flavour)
+                    if pre_key:
+                        it, deff, conv, x, MFL, MFR = pre_model.jacobi(m.A[i], m.b[i], m.x[i], m.D[i], m.CL, m.CR, tol, max_iter, check_every=ce)
+                    else:
+                        it, deff, conv, x, MFL, MFR = ob.jacobi(m.A[i], m.b[i], m.x[i], m.D[i], m.CL, m.CR, tol, max_iter, check_every=ce,
+                                                                flavour=flavour)
                     assert (res[i].iters, res[i].deff_raw, res[i].conv) == (it, deff, conv), (seed, log, i)
                     m.x[i] = x
                 if reader == "ptr":
@@ -378,44 +584,74 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 try:
                     res = s.solve_cg(rtol=rtol, max_iter=max_iter, check_every=ce)
                 except pkg.DeffError as e:
-                    # the one refusal these sequences can meet: three pixel classes or a D plane drawn cell by cell can give more
+                    # the refusals these sequences can meet: three pixel classes or a D plane drawn cell by cell can give more
                     # distinct rows than a dictionary holds (LUT_MAX_ROWS = 512 with the zero row, lut_layout.hpp), and CG runs on
-                    # the dictionary form only; nothing is changed then
-                    rows = np.unique(np.column_stack([np.concatenate(m.A), np.concatenate(m.b)]), axis=0)
-                    assert e.code == -1 and "no row dictionary" in str(e) and len(rows) > 511, (seed, log, e, len(rows))
+                    # the dictionary form unless "cg_planes" lets it read the planes; a caller's system with wall-column links
+                    # is explicit-only whatever the key says; nothing is changed then
+                    if m.kind == "Sw":
+                        assert e.code == -1 and "explicit-only" in str(e), (seed, log, e)
+                    else:
+                        rows = distinct_rows()
+                        assert e.code == -1 and "no row dictionary" in str(e) and rows > 511 and planes_key == 0, (seed, log, e, rows)
                     log[-1] += " refused"
                     fields_equal()
                     continue
+                assert m.kind != "Sw", (seed, log, "CG ran on an explicit-only system")
+                has_dict = True
+                if options.get("cgkeys"):
+                    has_dict = distinct_rows() <= 511
+                    assert has_dict or planes_key, (seed, log, "CG ran without a dictionary and without cg_planes")
+                want_impl = 3 if planes_key == 2 or not has_dict else expected_cg_impl(nx, ny, onchip_key)
                 if options.get("onchip"):
-                    assert s.plan_value("cg_impl") == expected_cg_impl(nx, ny, onchip_key), (seed, log, onchip_key)
-                    log[-1] += " impl %d" % expected_cg_impl(nx, ny, onchip_key)
+                    assert s.plan_value("cg_impl") == want_impl, (seed, log, onchip_key, planes_key)
+                    log[-1] += " impl %d" % want_impl
+                if options.get("cgkeys"):
+                    # the fold that ran: the key on the streaming forms (on the planes 2 means 1, deff_amd.h), 0 on chip
+                    want_fold = {1: fold_key, 2: 0, 3: min(fold_key, 1)}[want_impl]
+                    assert s.plan_value("cg_fold") == want_fold, (seed, log, fold_key, want_impl, s.plan_value("cg_fold"))
+                    log[-1] += " fold %d" % want_fold
                 res = [res] if B == 1 else res
                 got = s.get_field()
                 if options.get("onchip"):
                     # nothing of the context's history is in the result: a fresh context with the same system, the same field
                     # and the same form gives the same bits -- under the OTHER check interval, which the results do not depend
                     # on (deff_amd.h); the forms share cg_p[0], the per-image scalars and the restart flag between calls
+                    # With "cgkeys" the fresh context also runs four launches per iteration (cg_fold 0) and, where the system
+                    # has a dictionary, on the table (cg_planes 0): the same bits in both cases (deff_amd.h; the plane form has
+                    # the work items and summation order of the STREAMING table form, so that is the form it is compared with).
+                    fresh_onchip = 0 if want_impl == 3 else onchip_key
+                    fresh_impl = 3 if not has_dict else expected_cg_impl(nx, ny, fresh_onchip)
                     with pkg.Solver(nx, ny, nimg=B) as f:
-                        f.set_tuning("cg_onchip", onchip_key)
+                        f.set_tuning("cg_onchip", fresh_onchip)
+                        f.set_tuning("cg_planes", 0 if has_dict else planes_key)
                         f.set_image(np.stack(m.pix))
                         if m.kind == "2p":
                             f.assemble_2phase(m.phases[0], m.phases[1], m.CL, m.CR)
                         elif m.kind == "3p":
                             f.assemble_3phase(*m.phases, m.CL, m.CR)
+                        elif m.kind == "3g":
+                            f.assemble_3phase(*m.phases, m.CL, m.CR, grid=m.stacked(m.grid))
+                        elif m.kind == "3n":
+                            f.assemble_3phase_native(*m.phases, m.CL, m.CR)
+                        elif m.kind == "S":
+                            f.set_system(m.stacked(m.A), m.stacked(m.b), m.stacked(m.D), m.CL, m.CR)
                         else:
                             f.assemble_from_D(m.stacked(m.D), m.CL, m.CR)
                         f.set_field(before)
                         res_f = f.solve_cg(rtol=rtol, max_iter=max_iter, check_every=1 if ce == 64 else 64)
                         res_f = [res_f] if B == 1 else res_f
-                        assert f.plan_value("cg_impl") == s.plan_value("cg_impl")
+                        assert (f.plan_value("cg_impl"), f.plan_value("cg_fold")) == (fresh_impl, 0), (seed, log)
                         assert [(r.iters, r.rel_residual, r.deff_raw) for r in res_f] == [(r.iters, r.rel_residual, r.deff_raw) for r in res], (seed, log)
                         assert np.array_equal(f.get_field(), got), (seed, log, "CG on a fresh context")
+                        assert all(np.array_equal(u.MFL, v.MFL) and np.array_equal(u.MFR, v.MFR) for u, v in zip(res_f, res)), (seed, log)
                 for i in range(B):
                     x = got[i * ny:(i + 1) * ny].copy()
                     rn = residual_np(m.A[i], m.b[i], x, nx, ny)
                     assert res[i].iters <= max_iter and res[i].converged == (res[i].rel_residual <= rtol), (seed, log, i)
                     if res[i].converged:                     # the additive term: test_gpu_cg.py::assert_honest
                         assert rn <= rtol * (1 + 1e-6) + 1e-13, (seed, log, i, rn)
+                    elif rn == np.inf:                       # b = 0 (no pore reaches the right wall of a Grid system, CL = 0) and A x != 0
+                        assert res[i].rel_residual == np.inf, (seed, log, i, res[i].rel_residual)
                     elif rn >= 1e-6:                         # two float64 evaluations of a residual far above their rounding
                         assert abs(res[i].rel_residual - rn) <= 1e-9 * rn, (seed, log, i, res[i].rel_residual, rn)
                     want, L, R = ob.flux_deff(x, m.D[i], m.CL, m.CR)
@@ -432,7 +668,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 fields_equal()
                 log.append("get")
             elif op == "residual":
-                got = s.residual() if m.kind in ("2p", "3p") else s.residual(m.stacked(m.D), m.CL, m.CR)
+                got = s.residual() if m.kind in ("2p", "3p", "3n", "3g") else s.residual(m.stacked(m.D), m.CL, m.CR)
                 got = [got] if B == 1 else list(got)
                 log.append("residual")
                 for i in range(B):
@@ -446,14 +682,28 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 # 2-phase system, that image's final field (deff_amd.h)
                 imgs, Ds, Df, CL, CR, tol, max_iter, ce = args
                 log.append(f"stream {len(imgs)} {Ds} {Df} {CL} {tol} {max_iter} {ce}")
-                res = s.solve_stream(imgs, Ds, Df, CL, CR, tol, max_iter, check_every=ce, want_fields=True)
+                if pre_key:
+                    # (a stream brings its own 2-phase dictionary: only the kernel setting can stand in the way)
+                    got_res = []
+                    if prescaled_refused(lambda: got_res.append(s.solve_stream(imgs, Ds, Df, CL, CR, tol, max_iter, check_every=ce,
+                                                                               want_fields=True)), own_system=True):
+                        if options.get("native3"):
+                            assert s.plan_value("native3_rows") == (452 if m.kind == "3n" else 0), (seed, log)
+                        continue
+                    res = got_res[0]
+                else:
+                    res = s.solve_stream(imgs, Ds, Df, CL, CR, tol, max_iter, check_every=ce, want_fields=True)
+                m.fill_fresh = False
                 assert len(res) == len(imgs)
                 want = []
                 for i, pix in enumerate(imgs):
                     D = ob.fill_D_2phase(pix, Df, Ds)
                     A, b = ob.discretize(D, CL, CR)
-                    it, deff, conv, x, _, _ = ob.jacobi(A, b, ob.linear_guess(nx, ny, CL, CR, flavour=flavour), D, CL, CR, tol, max_iter,
-                                                        check_every=ce, flavour=flavour)
+                    if pre_key:
+                        it, deff, conv, x, _, _ = pre_model.jacobi(A, b, ob.linear_guess(nx, ny, CL, CR), D, CL, CR, tol, max_iter, check_every=ce)
+                    else:
+                        it, deff, conv, x, _, _ = ob.jacobi(A, b, ob.linear_guess(nx, ny, CL, CR, flavour=flavour), D, CL, CR, tol, max_iter,
+                                                            check_every=ce, flavour=flavour)
                     assert (res[i].iters, res[i].deff_raw, res[i].conv) == (it, deff, conv), (seed, log, i)
                     assert np.array_equal(res[i].field, x), (seed, log, "stream image %d" % i)
                     want.append((D, A, b, x))
@@ -462,6 +712,77 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 last = {k: i for i, k in enumerate(slot_of)}                     # the last image of every slot
                 assert sorted(last) == list(range(B))
                 log[-1] += " early %s" % [k for k in range(B) if retired[last[k]] < end]
+                m.pix = [imgs[last[k]] for k in range(B)]
+                m.D, m.A, m.b = ([want[last[k]][j] for k in range(B)] for j in range(3))
+                m.x = [want[last[k]][3] for k in range(B)]
+                m.CL, m.CR, m.kind, m.phases = CL, CR, "2p", (Ds, Df, None)
+                fields_equal()
+            elif op == "sens":
+                # the Deff gradient of the current field: it uses the upload scratch and events of its own and changes nothing
+                # else -- the closing fields_equal() and every later op show that
+                log.append("sens")
+                if m.kind in ("3n", "3g"):                   # a Grid system's Deff is no function of the phase diffusivities alone
+                    with pytest.raises(pkg.DeffError) as e:
+                        s.sensitivity()
+                    assert e.value.code == -1 and "Grid" in str(e.value), (seed, log, e.value)
+                g, euler = s.sensitivity() if m.kind in ("2p", "3p") else s.sensitivity(m.stacked(m.D), m.CL, m.CR)
+                g, euler = g.reshape(B, ny, nx), np.atleast_1d(euler)
+                p, pitch = s.device_sensitivity_ptr()
+                assert pitch == 8 * (nx + (nx & 1)), (seed, log, pitch)
+                dev = device_rows(p, B * ny, pitch)
+                for k in range(B):
+                    want, want_euler = sens_model.sensitivity(m.x[k], m.D[k], m.CL, m.CR)
+                    assert np.array_equal(g[k], want), (seed, log, "sensitivity of image %d" % k)
+                    assert abs(float(np.longdouble(euler[k]) - want_euler)) <= 1e-13 * abs(float(want_euler)), (seed, log, k, euler[k], want_euler)
+                    assert np.array_equal(dev[k * ny:(k + 1) * ny, :nx], want), (seed, log, "device map of image %d" % k)
+                if nx & 1:
+                    assert np.array_equal(dev[:, nx], np.zeros(B * ny)), (seed, log, "pad column of the map")
+            elif op == "cgstream":
+                # deff_solve_cg_stream: every image is solved from the linear guess "exactly as a one-image deff_solve_cg call
+                # would" (deff_amd.h) -- compared with that call on a fresh one-image context under the same cg_onchip key --
+                # and afterwards slot k is an ordinary image of the stack: the last image reported there, the call's 2-phase
+                # system, that image's field.  A refused call (Df = -1: no admissible table) changes nothing at all.
+                imgs, Ds, Df, CL, CR, rtol, max_iter, ce = args
+                log.append(f"cgstream {len(imgs)} {Ds} {Df} {CL} {rtol} {max_iter} {ce}")
+                if Df < 0:
+                    with pytest.raises(pkg.DeffError) as e:
+                        s.solve_cg_stream(imgs, Ds, Df, CL, CR, rtol=rtol, max_iter=max_iter, check_every=ce, want_fields=True)
+                    assert e.value.code == -1 and "admissible" in str(e.value), (seed, log, e.value)
+                    log[-1] += " refused"
+                    if options.get("native3"):
+                        assert s.plan_value("native3_rows") == (452 if m.kind == "3n" else 0), (seed, log)
+                        if m.fill_fresh:
+                            assert s.plan_value("fill_runs") == m.fill_count, (seed, log)
+                    if m.x is not None:
+                        fields_equal()
+                    continue
+                res = s.solve_cg_stream(imgs, Ds, Df, CL, CR, rtol=rtol, max_iter=max_iter, check_every=ce, want_fields=True)
+                m.fill_fresh = False
+                assert len(res) == len(imgs)
+                assert [r.slot for r in res[:B]] == list(range(B)) and all(0 <= r.slot < B for r in res), (seed, log, [r.slot for r in res])
+                want = []
+                with pkg.Solver(nx, ny) as f:
+                    f.set_tuning("cg_onchip", onchip_key)
+                    for i, pix in enumerate(imgs):
+                        D = ob.fill_D_2phase(pix, Df, Ds)
+                        A, b = ob.discretize(D, CL, CR)
+                        x = res[i].field
+                        rn = residual_np(A, b, x, nx, ny)
+                        assert res[i].iters <= max_iter and res[i].converged == (res[i].rel_residual <= rtol), (seed, log, i)
+                        if res[i].converged:
+                            assert rn <= rtol * (1 + 1e-6) + 1e-13, (seed, log, i, rn)
+                        elif rn >= 1e-6:
+                            assert abs(res[i].rel_residual - rn) <= 1e-9 * rn, (seed, log, i, res[i].rel_residual, rn)
+                        assert res[i].deff_raw == ob.flux_deff(x, D, CL, CR)[0], (seed, log, i)
+                        f.set_image(pix)
+                        f.assemble_2phase(Ds, Df, CL, CR)
+                        f.init_linear(CL, CR)
+                        one = f.solve_cg(rtol=rtol, max_iter=max_iter, check_every=ce)
+                        assert (one.iters, one.rel_residual, one.deff_raw) == (res[i].iters, res[i].rel_residual, res[i].deff_raw), (seed, log, i)
+                        assert np.array_equal(f.get_field(), x), (seed, log, "cgstream image %d against a one-image solve_cg" % i)
+                        want.append((D, A, b, x))
+                last = {r.slot: i for i, r in enumerate(res)}                    # the last image of every slot
+                assert sorted(last) == list(range(B))
                 m.pix = [imgs[last[k]] for k in range(B)]
                 m.D, m.A, m.b = ([want[last[k]][j] for k in range(B)] for j in range(3))
                 m.x = [want[last[k]][3] for k in range(B)]
@@ -522,10 +843,37 @@ ABI_SHAPES = [(64, 48), (130, 70), (97, 41), (256, 130), (40, 300), (129, 200)]
 ONCHIP_SEEDS = dict(first=3000, count=48, with_cg=True, shapes=ONCHIP_SHAPES, steps=40, onchip=True)
 STREAM_SEEDS = dict(first=4000, count=48, shapes=ABI_SHAPES, stacks=(2, 3, 4), stream=True, ptr=True, slot=True, stamps=True)
 FMA_SEEDS = dict(first=6000, count=24, shapes=ABI_SHAPES, stacks=(1, 2, 3), stream=True, ptr=True, slot=True, stamps=True, fma=True)
+# ... and what came after those: the native 3-phase assembly and its fill, a caller's system, the Deff gradient; the CG keys and
+# the CG stream; the pre-scaled sweeps.  Their shapes add the even width (64, 24) of the directed tests above: a wall-column
+# link can be represented there.  On every shape one workgroup holds an image's fill bitmaps ("fill_impl" 1 is never refused:
+# test_sequences_host.py checks the rule of api_fill.hip).
+NATIVE_SHAPES = ABI_SHAPES + [(64, 24)]
+CGKEY_SHAPES = ONCHIP_SHAPES + [(64, 24)]
+NATIVE_SEEDS = dict(first=7000, count=40, shapes=NATIVE_SHAPES, stacks=(1, 2, 3), steps=40, native3=True, system=True, sens=True,
+                    ptr=True, slot=True, stream=True)
+CGKEY_SEEDS = dict(first=8000, count=40, with_cg=True, shapes=CGKEY_SHAPES, stacks=(1, 2, 2, 3), steps=40, onchip=True, cgkeys=True,
+                   cgstream=True, native3=True, system=True)
+PRESCALED_SEEDS = dict(first=9000, count=40, shapes=NATIVE_SHAPES, stacks=(1, 2, 3), steps=40, prescaled=True, native3=True,
+                       system=True, stream=True)
 
 
 def seed_options(group):
     return {k: v for k, v in group.items() if k not in ("first", "count")}
+
+
+@pytest.mark.parametrize("seed", range(NATIVE_SEEDS["count"]))
+def test_random_call_sequences_with_native_3phase_systems_and_sensitivities(pkg, oracle, seed):
+    run_sequence(pkg, oracle, NATIVE_SEEDS["first"] + seed, **seed_options(NATIVE_SEEDS))
+
+
+@pytest.mark.parametrize("seed", range(CGKEY_SEEDS["count"]))
+def test_random_call_sequences_with_cg_keys_and_cg_streams(pkg, oracle, seed):
+    run_sequence(pkg, oracle, CGKEY_SEEDS["first"] + seed, **seed_options(CGKEY_SEEDS))
+
+
+@pytest.mark.parametrize("seed", range(PRESCALED_SEEDS["count"]))
+def test_random_call_sequences_with_prescaled_sweeps(pkg, oracle, seed):
+    run_sequence(pkg, oracle, PRESCALED_SEEDS["first"] + seed, **seed_options(PRESCALED_SEEDS))
 
 
 @pytest.mark.parametrize("seed", range(ONCHIP_SEEDS["count"]))
@@ -564,6 +912,153 @@ def test_cg_ignores_the_fma_key(pkg, oracle):
                 got.append((r.iters, r.rel_residual, r.deff_raw, r.MFL.copy(), r.MFR.copy(), s.get_field()))
         a, b = got
         assert a[:3] == b[:3] and all(np.array_equal(u, v) for u, v in zip(a[3:], b[3:])), (onchip_key, a[:3], b[:3])
+
+
+def wrap_system(ob, pix, Ds, Df, CL, CR):
+    """The oracle's 2-phase system of `pix` with a W link in column 0 of every row but the first (it reads the previous row's
+    last cell: test_gpu_parity.py::test_wall_column_links_keep_linear_addressing) -> (A, b, D)."""
+    ny, nx = pix.shape
+    D = ob.fill_D_2phase(pix, Df, Ds)
+    A, b = ob.discretize(D, CL, CR)
+    A = A.copy().reshape(ny, nx, 5)
+    A[1:, 0, 1] = -0.125
+    return A.reshape(-1, 5), b, D
+
+
+@pytest.mark.parametrize("assembly", ["assemble_2phase", "solve_stream"])
+def test_a_native_assembly_forgets_the_wrap_links_of_a_callers_system(pkg, oracle, assembly):
+    """deff_set_system marks a system whose A links a wall column to the neighbouring row as explicit-only, and deff_solve_cg
+    refuses such a system.  The mark belongs to that system: after set_image + assemble_2phase (or a deff_solve_stream) the
+    context holds the native 2-phase system, and CG on it gives the bits of a context that never saw the caller's A."""
+    nx, ny = 64, 24
+    B = 1 if assembly == "assemble_2phase" else 2
+    rng = np.random.default_rng(64024)
+    pix = [np.where(rng.random((ny, nx)) < 0.5, 0, 255).astype(np.uint8) for _ in range(B)]
+    x0 = [rng.random((ny, nx)) for _ in range(B)]
+    wrapped = [wrap_system(oracle, p, 1e-2, 1.0, 0.0, 1.0) for p in pix]
+
+    def native(s):
+        if assembly == "assemble_2phase":
+            s.set_image(np.stack(pix))
+            s.assemble_2phase(1e-2, 1.0, 0.0, 1.0)
+        else:
+            res = s.solve_stream(pix, 1e-2, 1.0, 0.0, 1.0, 1e-2, 7, check_every=7)
+            assert [r.slot for r in res] == [0, 1]
+        s.init_linear(0.0, 1.0)
+        r = s.solve_cg(rtol=1e-10)
+        r = r if isinstance(r, list) else [r]
+        assert all(q.converged for q in r)
+        return [(q.iters, q.rel_residual, q.deff_raw) for q in r], s.get_field()
+
+    with pkg.Solver(nx, ny, nimg=B) as s:
+        s.set_system(np.concatenate([w[0] for w in wrapped]), np.concatenate([w[1] for w in wrapped]),
+                     np.concatenate([w[2] for w in wrapped]), 0.0, 1.0)
+        s.set_field(np.concatenate(x0))
+        s.sweeps(3)
+        assert s.kernel_in_use() in ("explicit", "scalar")
+        got = s.get_field()
+        for k in range(B):
+            assert np.array_equal(got[k * ny:(k + 1) * ny], oracle.sweeps(wrapped[k][0], wrapped[k][1], x0[k], 3)), k
+        with pytest.raises(pkg.DeffError) as e:              # the caller's system itself stays refused
+            s.solve_cg(rtol=1e-10)
+        assert e.value.code == -1 and "explicit-only" in str(e.value)
+        after = native(s)
+    with pkg.Solver(nx, ny, nimg=B) as f:
+        fresh = native(f)
+    assert after[0] == fresh[0], (after[0], fresh[0])
+    assert np.array_equal(after[1], fresh[1])
+
+
+def test_a_refused_cg_stream_leaves_a_native_3phase_system_alone(pkg, oracle):
+    """deff_solve_cg_stream validates its table and its image shape before it changes anything: after a refusal (an
+    inadmissible Df, images that do not match the mesh) the context still holds the native 3-phase system -- its 452 rows,
+    the planes built on demand from the fill, the refusal of deff_sensitivity for a Grid system -- and its field."""
+    import ctypes as C
+    from effectivediffusivityfvm_amd import _capi
+    nx, ny, B = 64, 24, 2
+    rng = np.random.default_rng(3452)
+    pix = []
+    for k in range(B):
+        f = rng.random((ny, nx))
+        p = np.where(f < 0.3, 255, np.where(f < 0.55, 20, 150)).astype(np.uint8)      # solid > 200, gas < 50, fluid
+        p[8:13, 30 + k:35 + k] = 255                         # a ring of solid around one fluid cell: a pocket the fill takes out
+        p[10, 32 + k] = 150
+        pix.append(p)
+    grids = [oracle.floodfill((p > 200).astype(np.uint32))[0] for p in pix]
+    assert all(g[10, 32 + k] == 2 for k, g in enumerate(grids)) and all(len(np.unique(p)) == 3 for p in pix)
+    Ds, Df, Dg, CL, CR = 1e-3, 1.0, 10.0, 0.0, 1.0
+    sys_ = [oracle.discretize(oracle.fill_D_3phase(p, Df, Ds, Dg), CL, CR, grid=g) for p, g in zip(pix, grids)]
+    with pkg.Solver(nx, ny, nimg=B) as s:
+        s.set_image(np.stack(pix))
+        s.assemble_3phase_native(Ds, Df, Dg, CL, CR)
+        s.init_linear(CL, CR)
+        A0, b0 = s.get_system()
+        x0 = s.get_field()
+        assert np.array_equal(A0, np.concatenate([q[0] for q in sys_])) and np.array_equal(b0, np.concatenate([q[1] for q in sys_]))
+        assert s.plan_value("native3_rows") == 452
+
+        def unchanged(what):
+            assert s.plan_value("native3_rows") == 452, what
+            A1, b1 = s.get_system()
+            assert np.array_equal(A1, A0) and np.array_equal(b1, b0), what
+            with pytest.raises(pkg.DeffError) as e:
+                s.sensitivity()
+            assert e.value.code == -1 and "Grid" in str(e.value), (what, str(e.value))
+            assert np.array_equal(s.get_field(), x0), what
+
+        with pytest.raises(pkg.DeffError) as e:
+            s.solve_cg_stream(pix, Ds, -1.0, CL, CR, rtol=1e-6, max_iter=10)
+        assert e.value.code == -1 and "admissible" in str(e.value), str(e.value)
+        unchanged("an inadmissible Df")
+        called = []
+        nxt = _capi.NEXT_IMAGE_FN(lambda *a: called.append("next") or 0)
+        dn = _capi.CG_IMAGE_DONE_FN(lambda *a: called.append("done"))
+        rc = _capi.load().deff_solve_cg_stream(s._ctx, nx + 1, ny, 1, 1, Ds, Df, CL, CR, 1e-6, 10, 64, nxt, dn, None)
+        assert rc == -1 and not called, (rc, called)
+        unchanged("images of the wrong shape")
+        s.set_kernel("explicit")
+        s.sweeps(5)
+        assert s.kernel_in_use() == "explicit"
+        got = s.get_field()
+        for k in range(B):
+            want = oracle.sweeps(sys_[k][0], sys_[k][1], oracle.linear_guess(nx, ny, CL, CR), 5)
+            assert np.array_equal(got[k * ny:(k + 1) * ny], want), k
+
+
+def test_a_prescaled_stream_refused_for_the_explicit_kernel_changes_nothing(pkg, oracle):
+    """"prescaled" is refused "at the call that would sweep (field, system and plan stay as they were)" (deff_amd.h).  For
+    deff_solve_stream on a context set to the explicit kernel that call is the stream itself: it must say so before it asks
+    for an image, zeroes the slots or replaces the system (found while the refusal was modelled for PRESCALED_SEEDS, whose
+    draw knows this refusal; few of its seeds reach it, so it is held here by construction)."""
+    nx, ny, B = 64, 24, 2
+    rng = np.random.default_rng(9)
+    pix = [np.where(rng.random((ny, nx)) < 0.5, 0, 255).astype(np.uint8) for _ in range(B)]
+    sys_ = [oracle.discretize(oracle.fill_D_2phase(p, 1.0, 1e-2), 0.25, 0.75) for p in pix]
+    pulled = []
+
+    def images():
+        for p in pix:
+            pulled.append(1)
+            yield 255 - p
+
+    with pkg.Solver(nx, ny, nimg=B, kernel="explicit") as s:
+        s.set_image(np.stack(pix))
+        s.assemble_2phase(1e-2, 1.0, 0.25, 0.75)
+        s.init_linear(0.25, 0.75)
+        s.sweeps(3)
+        x0 = s.get_field()
+        s.set_tuning("prescaled", 1)
+        with pytest.raises(pkg.DeffError) as e:
+            s.solve_stream(images(), 1e-3, 1.0, 0.0, 1.0, 1e-2, 7, check_every=7)
+        assert e.value.code == -1 and "prescaled" in str(e.value) and not pulled, (str(e.value), pulled)
+        assert np.array_equal(s.get_field(), x0)
+        A, b = s.get_system()
+        assert np.array_equal(A, np.concatenate([q[0] for q in sys_])) and np.array_equal(b, np.concatenate([q[1] for q in sys_]))
+        s.set_tuning("prescaled", 0)
+        s.sweeps(2)
+        got = s.get_field()
+        for k in range(B):
+            assert np.array_equal(got[k * ny:(k + 1) * ny], oracle.sweeps(sys_[k][0], sys_[k][1], x0[k * ny:(k + 1) * ny], 2)), k
 
 
 @pytest.mark.parametrize("launch,T", [(0, 4), (0, 8), (1, 4), (1, 8)])     # workgroup tiles exist for passes of 4 and 8

@@ -6,7 +6,12 @@ drew (tests/golden/sequence_draws_seeds_1000_2000.json: their op logs and a SHA-
 call order.  The file was recorded from run_sequence() as it was before the draw was separated from it -- that function run
 on a GPU with the Solver wrapped so that every array passed to set_image, assemble_from_D and set_field was hashed on its
 way in, and its own log taken without the "refused" marks), and the seed ranges of the options reach the call orders they were added
-for -- an option nobody draws, or a stream nobody reads after, would leave the GPU tests green and empty."""
+for -- an option nobody draws, or a stream nobody reads after, would leave the GPU tests green and empty.
+
+The seeds of those option groups are pinned in turn (tests/golden/sequence_draws_option_seeds.json, written with draw_log()
+below before the draw gained its later options), and the later groups -- the native 3-phase assembly, a caller's system, the
+Deff gradient, the CG keys and the CG stream, the pre-scaled sweeps -- have a census of their own: every op, kind and key value
+they add, and the call orders they are there for."""
 import hashlib
 import json
 import os
@@ -40,9 +45,9 @@ def draw_log(seed, **options):
             h.update(np.stack(a[0]).tobytes())
             log.append("image")
         elif op == "assemble":
-            if a[0] == "D":
+            if a[6] is not None:                             # a D plane, or the plane behind a caller's system
                 h.update(np.concatenate(a[6], axis=0).tobytes())
-            log.append(f"assemble {a[0]} {a[1]} {a[2]} {a[4]}")
+            log.append(f"assemble {a[0]} {a[1]} {a[2]} {a[4]}" + (f" of {a[7]}" if len(a) > 7 else ""))
         elif op == "tune":
             log.append(f"{a[0]} {a[1]}")
         elif op == "kernel":
@@ -54,6 +59,11 @@ def draw_log(seed, **options):
             log.append(f"sweeps {a[0]} {a[1]:.3f}")
         elif op in ("solve", "cg"):
             log.append(f"{op} {a[0]} {a[1]} {a[2]}")
+        elif op == "stage":
+            log.append(f"stage {a[0]} {a[1]} {a[2]} {a[3]}")
+        elif op == "cgstream":
+            h.update(np.stack(a[0]).tobytes())
+            log.append(f"cgstream {len(a[0])} {a[1]} {a[2]} {a[3]} {a[5]} {a[6]} {a[7]}")
         else:
             log.append(op)
     return log, h.hexdigest()
@@ -65,6 +75,19 @@ def test_the_old_seeds_draw_what_they_always_drew():
     assert len(recorded) == 64
     for seed in list(range(1000, 1040)) + list(range(2000, 2024)):
         log, digest = draw_log(seed, with_cg=seed >= 2000)
+        assert "|".join(log) == recorded[str(seed)]["log"], seed
+        assert digest == recorded[str(seed)]["data"], seed
+
+
+def test_the_option_seeds_draw_what_they_drew_before_the_later_options():
+    """The seeds of the on-chip, stream and fma groups, recorded (with draw_log above) before the draw gained native3, system,
+    cgkeys, cgstream, sens and prescaled: with those off the generator is consumed as it was."""
+    with open(os.path.join(GOLDEN, "sequence_draws_option_seeds.json")) as f:
+        recorded = json.load(f)
+    seeds = [(seed, options) for group in ("onchip", "stream", "fma") for seed, options in seeds_of(group)]
+    assert len(recorded) == len(seeds) == 120
+    for seed, options in seeds:
+        log, digest = draw_log(seed, **options)
         assert "|".join(log) == recorded[str(seed)]["log"], seed
         assert digest == recorded[str(seed)]["data"], seed
 
@@ -159,3 +182,178 @@ def test_the_option_seeds_reach_what_they_were_added_for(oracle):
     shapes = [(nx + (nx & 1)) * ny <= seq.ONCHIP_LIMIT for nx, ny in seq.ONCHIP_SHAPES]
     assert not all(shapes) and sum(shapes) > len(shapes) / 2 and (128, 128) in seq.ONCHIP_SHAPES
     assert any(nx & 1 and (nx + 1) * ny <= seq.ONCHIP_LIMIT for nx, ny in seq.ONCHIP_SHAPES)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The later option groups: what their seeds draw, and the call orders they were added for.  All of it follows from the draw
+# and from facts of the model's state (kind of system, keys set, whether the device fill is the current image's); the one
+# thing that needs the oracle is the number of distinct rows of a system (whether it has a dictionary: the CG form).
+
+NEW_GROUPS = {"native": seq.NATIVE_SEEDS, "cgkey": seq.CGKEY_SEEDS, "prescaled": seq.PRESCALED_SEEDS}
+
+
+def distinct_rows(oracle, pix, kind, Ds, Df, Dg, CL, CR, D, base):
+    m = seq.Model(oracle, pix[0].shape[1], pix[0].shape[0], len(pix), None)
+    m.pix = pix
+    m.assemble(kind, Ds, Df, Dg, CL, CR, D, base)
+    return len(np.unique(np.column_stack([np.concatenate(m.A), np.concatenate(m.b)]), axis=0))
+
+
+def new_census(oracle):
+    """Per seed of the later groups: `kinds` = the ops, assembly kinds ("assemble 3n") and key values ("cg_fold 2") drawn, and
+    `orders` = which of the call orders below it reaches."""
+    out = {}
+    for group, g in NEW_GROUPS.items():
+        for i in range(g["count"]):
+            seed, options = g["first"] + i, seq.seed_options(g)
+            draw = seq.draw_sequence(seed, **options)
+            _, nx, ny, B, _ = next(draw)
+            pix = next(draw)[1]
+            kinds, orders = set(), set()
+            kind, asm, nrows = None, None, None              # the system: its kind, the arguments it was assembled with, its rows
+            keys = dict(cg_onchip=0, cg_planes=0, cg_fold=0, prescaled=0, tb_impl=0, tb_launch=0)
+            kset = "auto"
+            planes_built = False                             # of a "3n" system: its planes exist already
+            n3_chain = 0                                     # 1: "3n" on this image; 2: ... then another kind
+            after_stream = False                             # a stream put images into the slots, no deff_set_image since
+            sw_chain = 0                                     # 1: "Sw"; 2: ... then assemble "2p" or a stream
+            b_pending = False                                # a refused cgstream on a "3n" system, no assembly since
+            pre_chain, pre_omegas = {}, set()                # per omega: 1 = sweeps under prescaled 1, 2 = then prescaled 0
+            hist = []
+
+            def rows():
+                nonlocal nrows
+                if nrows is None:
+                    nrows = distinct_rows(oracle, pix, *asm)
+                return nrows
+
+            def took_stream():
+                nonlocal kind, asm, nrows, after_stream, n3_chain, b_pending, sw_chain, pre_chain
+                kind, nrows, asm = "2p", 1, None
+                after_stream, n3_chain, b_pending, pre_chain = True, 0, False, {}
+                sw_chain = 2 if sw_chain >= 1 else 0
+
+            for op, *a in draw:
+                explicit_sweep = op in ("sweeps", "solve") and kset == "explicit" and not keys["prescaled"]
+                if op == "tune":
+                    kinds.add(f"{a[0]} {a[1]}")
+                    if a[0] in keys:
+                        keys[a[0]] = a[1]
+                    if a[0] == "prescaled" and a[1] == 0:
+                        pre_chain = {w: 2 for w in pre_chain}
+                elif op == "assemble":
+                    kinds.add("assemble " + a[0])
+                else:
+                    kinds.add(op)
+                if op == "kernel":
+                    kset = a[0]
+                elif op == "image":
+                    pix, kind = a[0], None
+                    n3_chain, after_stream, b_pending, pre_chain = 0, False, False, {}
+                elif op in ("assemble", "stage"):
+                    if op == "stage":
+                        a = ["3n"] + a + [None]
+                    if a[0] == "3n":
+                        if n3_chain == 2:
+                            orders.add(2)
+                        if after_stream:
+                            orders.add(3)
+                        n3_chain, after_stream = 1, False
+                    elif n3_chain:
+                        n3_chain = 2
+                    sw_chain = 1 if a[0] == "Sw" else 2 if a[0] == "2p" and sw_chain >= 1 else 0
+                    if a[0] in ("D", "S", "Sw"):
+                        kset = "auto"
+                    kind, asm, nrows = a[0], (a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7] if len(a) > 7 else None), None
+                    planes_built, b_pending, pre_chain = False, False, {}
+                elif op == "stream":
+                    if not (keys["prescaled"] and kset == "explicit"):
+                        took_stream()
+                elif op == "cgstream":
+                    if a[2] < 0:
+                        kinds.add("cgstream refused")
+                        b_pending = b_pending or kind == "3n"
+                    else:
+                        took_stream()
+                elif op == "cg" and kind != "Sw":
+                    has_dict = kind in ("2p", "3n") or rows() <= 511
+                    if has_dict or keys["cg_planes"]:
+                        impl = 3 if keys["cg_planes"] == 2 or not has_dict else seq.expected_cg_impl(nx, ny, keys["cg_onchip"])
+                        kinds.add(f"cg impl {impl}")
+                        if impl in (1, 3) and keys["cg_fold"]:
+                            kinds.add(f"cg impl {impl} fold {keys['cg_fold']}")
+                        if kind == "3n" and impl == 3 and not planes_built:
+                            orders.add(1)
+                            planes_built = True
+                        if sw_chain == 2:
+                            orders.add(4)
+                elif op == "cg":
+                    kinds.add("cg on Sw")
+                if kind == "3n" and (op == "getsys" or explicit_sweep):
+                    if not planes_built:
+                        orders.add(1)
+                    planes_built = True
+                    if b_pending:
+                        orders.add(5)
+                if op == "solve" and hist[-2:] == ["sweeps", "sens"] and keys["tb_impl"] == 2 and keys["tb_launch"] == 0 \
+                        and kset in ("auto", "matfree_tb") and kind != "Sw" and keys_at_sweeps == (2, 0):
+                    orders.add(6)
+                if op == "sweeps":
+                    keys_at_sweeps = (keys["tb_impl"], keys["tb_launch"])
+                    refused = keys["prescaled"] and (kset == "explicit" or kind == "Sw" or (kind not in ("2p", "3n") and rows() > 511))
+                    if keys["prescaled"] and not refused:
+                        kinds.add("prescaled sweeps")
+                        pre_chain[a[1]] = 1
+                    elif keys["prescaled"]:
+                        kinds.add("prescaled refused")
+                    elif pre_chain.get(a[1]) == 2 and kset != "explicit":
+                        orders.add(7)
+                        pre_omegas.add(a[1])
+                if op in ("init", "set_field"):
+                    pass                                     # (a new field does not touch the tables the orders are about)
+                hist.append(op)
+            out[seed] = dict(group=group, kinds=kinds, orders=orders, pre_omegas=pre_omegas, shape=(nx, ny), B=B)
+    return out
+
+
+NEW_KINDS = {
+    "native": ["assemble 3n", "assemble 3g", "stage", "grid", "fill_impl 0", "fill_impl 1", "fill_impl 2", "fill_tile_rows 0",
+               "fill_tile_rows 8", "fill_tile_rows 16", "assemble S", "assemble Sw", "getsys", "sens"],
+    "cgkey": ["cg_planes 0", "cg_planes 1", "cg_planes 2", "cg_fold 0", "cg_fold 1", "cg_fold 2", "cgstream", "cgstream refused",
+              "assemble 3n", "assemble S", "assemble Sw", "getsys", "cg on Sw"],
+    "prescaled": ["prescaled 0", "prescaled 1", "prescaled sweeps", "prescaled refused", "assemble 3n", "assemble S", "stream"],
+}
+NEW_ORDERS = {"native": [1, 2, 3, 6], "cgkey": [1, 2, 3, 4, 5], "prescaled": [7]}
+
+
+def test_the_later_option_seeds_reach_what_they_were_added_for(oracle):
+    """Every new op, kind and key value is drawn by at least 8 seeds of its group, and at least 4 seeds of a group reach each of
+    1  "3n", then what needs its planes built on demand: an explicit sweep, deff_get_system, CG under cg_planes 2
+    2  "3n" -> an assembly of another kind -> "3n" on the same image (the fill is reused)
+    3  a stream or a CG stream, then "3n" (a fresh fill of the slots' images)
+    4  "Sw" -> assemble "2p" or a stream -> cg (a caller's wall-column links must not outlive its system)
+    5  a refused CG stream on a "3n" system, then deff_get_system or an explicit sweep (the refusal must change nothing)
+    6  sweeps, the gradient, a solve in a row under tb_impl 2 / tb_launch 0 (a resident interval no check has settled)
+    7  prescaled 1 -> sweeps -> prescaled 0 -> sweeps on one system (the pre-scaled table next to the dictionary's)
+    8  CG in each of its three forms, and folded (cg_fold 1 and 2) on the table and on the planes."""
+    c = new_census(oracle)
+    for group in NEW_GROUPS:
+        mine = [v for v in c.values() if v["group"] == group]
+        drawn = {k: sum(1 for v in mine if k in v["kinds"]) for k in NEW_KINDS[group]}
+        reached = {k: sum(1 for v in mine if k in v["orders"]) for k in NEW_ORDERS[group]}
+        print(f"{group}: seeds that draw {drawn}; seeds that reach the orders {reached}")
+        assert all(n >= 8 for n in drawn.values()), (group, drawn)
+        assert all(n >= 4 for n in reached.values()), (group, reached)
+    cg = [v for v in c.values() if v["group"] == "cgkey"]
+    forms = {k: sum(1 for v in cg if k in v["kinds"]) for k in ["cg impl 1", "cg impl 2", "cg impl 3", "cg impl 1 fold 1", "cg impl 1 fold 2",
+                                                                 "cg impl 3 fold 1", "cg impl 3 fold 2"]}
+    print(f"cgkey: seeds that run {forms}")
+    assert all(n >= 4 for n in forms.values()), forms
+    omegas = set().union(*(v["pre_omegas"] for v in c.values() if v["group"] == "prescaled"))
+    assert len(omegas) == 2, omegas
+    # the even width on which a wall-column link can be represented, and stacks for the streams
+    assert all(any(v["shape"][0] % 2 == 0 for v in c.values() if v["group"] == g) for g in NEW_GROUPS)
+    # "fill_impl" 1 is never refused: one workgroup holds the fill bitmaps of every shape (api_fill.hip: fill_fits_one_workgroup,
+    # ny rows of ceil(nx / 64) words within FILL_LARGE_WORDS = 8192); and nothing is larger than 256 x 130 cells
+    for nx, ny in set(seq.NATIVE_SHAPES + seq.CGKEY_SHAPES):
+        assert ny * ((nx + 63) // 64) <= 8192 and nx * ny <= 256 * 130, (nx, ny)
