@@ -20,7 +20,7 @@ SYMBOLS = [
     "deff_version", "deff_last_error", "deff_error_string", "deff_device_count",
     "deff_create", "deff_create_batch", "deff_batch_size", "deff_recommended_batch", "deff_destroy", "deff_mesh", "deff_set_kernel", "deff_get_kernel",
     "deff_set_tuning", "deff_get_plan", "deff_set_image", "deff_synth_image", "deff_get_image",
-    "deff_load_jpeg_gray", "deff_free", "deff_assemble_2phase", "deff_assemble_3phase", "deff_assemble_3phase_native", "deff_get_grid", "deff_flood_fill", "deff_assemble_from_D", "deff_set_system", "deff_get_system",
+    "deff_load_jpeg_gray", "deff_free", "deff_assemble_2phase", "deff_assemble_3phase", "deff_assemble_3phase_native", "deff_get_grid", "deff_flood_fill", "deff_assemble_from_D", "deff_set_system", "deff_get_system", "deff_get_dictionary",
     "deff_init_linear", "deff_set_field", "deff_get_field", "deff_solve", "deff_solve_batch", "deff_solve_cg", "deff_sweeps",
     "deff_slab_group_create", "deff_slab_group_destroy", "deff_slab_group_layout", "deff_slab_group_set_tuning", "deff_slab_group_get_plan",
     "deff_slab_group_set_image", "deff_slab_group_synth_image", "deff_slab_group_assemble_2phase",
@@ -105,6 +105,8 @@ def load():
     L.deff_assemble_from_D.argtypes = [ctx, _dp, C.c_void_p, C.c_double, C.c_double]
     L.deff_set_system.argtypes = [ctx, _dp, _dp, C.c_void_p, C.c_double, C.c_double]
     L.deff_get_system.argtypes = [ctx, _dp, _dp]
+    if hasattr(L, "deff_get_dictionary"):                # DEFF_AMD_LIB may name a build from before it (A/B runs against a parent)
+        L.deff_get_dictionary.argtypes = [ctx, C.c_void_p, C.c_void_p]
     L.deff_init_linear.argtypes = [ctx, C.c_double, C.c_double]
     L.deff_set_field.argtypes = [ctx, _dp]
     L.deff_get_field.argtypes = [ctx, _dp]

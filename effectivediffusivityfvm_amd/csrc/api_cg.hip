@@ -394,7 +394,7 @@ try {
     c->phase_mode = 2; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = 0.0;
     c->have_image = true; c->have_walls = true; c->have_matfree = true; c->have_explicit = false;
     c->links_sym = 0;
-    c->dict_tried = false; c->have_field = true;
+    dict_reset(c); c->have_field = true;
     c->q_valid = false;
     reset_batch_state(c);                                            // every slot's field lives in x[cur], now and afterwards
     double *x = c->x[c->cur];

@@ -369,6 +369,9 @@ try {
     else if (!strcmp(key, "fill_runs")) *value = c->fill_runs;
     else if (!strcmp(key, "fill_fallbacks")) *value = c->fill_fallbacks;
     else if (!strcmp(key, "native3_rows")) *value = c->native3 ? NATIVE3_ROWS : 0;
+    else if (!strcmp(key, "dict_outcome")) *value = c->dict_outcome;
+    else if (!strcmp(key, "dict_rows")) *value = c->dict_rows;
+    else if (!strcmp(key, "lut_rows")) *value = c->have_matfree ? c->lut_nrows : 0;
     else return fail(DEFF_EINVAL, "unknown plan key '%s'", key);
     return DEFF_OK;
 }
@@ -533,7 +536,7 @@ try {
 
     // matrix-free form: 1 byte per cell + lookup tables
     TRY(dev_alloc(&c->code, c->n));
-    c->dict_tried = false;
+    dict_reset(c);
     hipLaunchKernelGGL(k_phase_codes, dim3(grid_for(c->n)), dim3(256), 0, c->stream, c->pix, c->W, c->ampX,
                        c->ampY, c->nx, c->nxt, c->ny, c->rows, c->dom_lo, c->mesh_ny, c->code);
     HIP_TRY(hipGetLastError());
@@ -605,7 +608,7 @@ try {
     c->have_explicit = true; c->c0_omega = NAN; c->have_walls = true;
     c->phase_mode = 3; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = Dg;
     c->grid_given = Grid != nullptr;
-    c->have_matfree = false; c->dict_tried = false; c->wrap_links = false; c->native3 = false;
+    c->have_matfree = false; dict_reset(c); c->wrap_links = false; c->native3 = false;
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -670,7 +673,7 @@ try {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_explicit = true; c->c0_omega = NAN; c->have_walls = true;
     c->phase_mode = 0;
-    c->have_matfree = false; c->dict_tried = false; c->wrap_links = false; c->native3 = false;
+    c->have_matfree = false; dict_reset(c); c->wrap_links = false; c->native3 = false;
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -724,7 +727,7 @@ try {
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_explicit = true; c->c0_omega = NAN;
-    c->have_matfree = false; c->dict_tried = false; c->native3 = false;
+    c->have_matfree = false; dict_reset(c); c->native3 = false;
     c->wrap_links = wrap;
     return DEFF_OK;
 }

@@ -10,6 +10,7 @@
 static int try_dict(deff_ctx *c)
 {
     c->dict_tried = true;
+    c->dict_outcome = 0; c->dict_rows = 0;
     if (!c->have_explicit) return DEFF_OK;
     const size_t S = DICT_SLOTS;
     const size_t bytes = S * (8 + 4 + 8) + 16 + S * 2 + (size_t)LUT_MAX_ROWS * (8 + 48);
@@ -35,36 +36,48 @@ static int try_dict(deff_ctx *c)
     HIP_TRY(hipMemcpyAsync(cnt.data(), t.count, S * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(flags, t.flags, 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (flags[0]) return DEFF_OK;                                 // table overflow: far too many rows
-    struct Ent { unsigned int count; unsigned long long cell; unsigned slot; };
+    if (flags[0]) { c->dict_outcome = 3; return DEFF_OK; }        // table overflow: far too many rows
+    struct Ent { unsigned int count; unsigned slot; unsigned long long bits[6]; };
     std::vector<Ent> ents;
+    std::vector<unsigned long long> cells;
     for (unsigned sl = 0; sl < S; ++sl)
-        if (key[sl]) ents.push_back({cnt[sl], rp[sl] - 1, sl});
-    if (ents.empty() || (int)ents.size() + 1 > LUT_MAX_ROWS) return DEFF_OK;
-    // most populous rows first: the 32 commonest rows then share one conflict-free LDS bank row
+        if (key[sl]) {
+            if ((int)ents.size() + 2 > LUT_MAX_ROWS) { c->dict_outcome = 2; return DEFF_OK; }   // no seat left beside the zero row
+            ents.push_back(Ent{cnt[sl], sl, {0, 0, 0, 0, 0, 0}});
+            cells.push_back(rp[sl] - 1);
+        }
+    if (ents.empty()) return DEFF_OK;
+    // one representative row per slot, in slot order: the code order below is decided by the rows themselves, so which
+    // cell of a slot arrived first (it differs from run to run) never shows in a code
+    const int nrows = (int)ents.size();
+    HIP_TRY(hipMemcpyAsync(d_cells, cells.data(), cells.size() * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_dict_gather, dim3((nrows + 255) / 256), dim3(256), 0, c->stream, planes, d_cells, nrows, d_rows);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> slot_rows((size_t)nrows * 6);
+    HIP_TRY(hipMemcpyAsync(slot_rows.data(), d_rows, slot_rows.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < nrows; ++k) memcpy(ents[k].bits, &slot_rows[(size_t)k * 6], 48);
+    // most populous rows first: the 32 commonest rows then share one conflict-free LDS bank row.  Ties: the six doubles' bit
+    // patterns as unsigned integers, in plane order -- the numbering is a function of the system alone
     std::sort(ents.begin(), ents.end(), [](const Ent &a, const Ent &b) {
-        return a.count != b.count ? a.count > b.count : a.cell < b.cell;
+        if (a.count != b.count) return a.count > b.count;
+        return std::lexicographical_compare(a.bits, a.bits + 6, b.bits, b.bits + 6);
     });
     std::vector<uint16_t> slot2code(S, 0xFFFFu);
-    std::vector<unsigned long long> cells(ents.size());
-    for (size_t k = 0; k < ents.size(); ++k) {
+    std::vector<double> rows((size_t)nrows * 6);
+    for (int k = 0; k < nrows; ++k) {
         slot2code[ents[k].slot] = (uint16_t)((k + 1) * 8);
-        cells[k] = ents[k].cell;
+        memcpy(&rows[(size_t)k * 6], ents[k].bits, 48);
     }
     HIP_TRY(hipMemcpyAsync(d_slot2code, slot2code.data(), S * 2, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_cells, cells.data(), cells.size() * 8, hipMemcpyHostToDevice, c->stream));
-    const int nrows = (int)ents.size();
-    hipLaunchKernelGGL(k_dict_gather, dim3((nrows + 255) / 256), dim3(256), 0, c->stream, planes, d_cells, nrows, d_rows);
     TRY(dev_alloc(&c->code, c->n));
     c->codes3_valid = false;
     hipLaunchKernelGGL(k_dict_encode, dim3(grid_for(c->n, 4096)), dim3(256), 0, c->stream, planes, c->n, c->nx, c->nxt, t,
                        d_slot2code, c->code);
     HIP_TRY(hipGetLastError());
-    std::vector<double> rows((size_t)nrows * 6);
-    HIP_TRY(hipMemcpyAsync(rows.data(), d_rows, rows.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(flags, t.flags, 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (flags[1]) return DEFF_OK;                                 // hash collision (astronomically unlikely): stay explicit
+    if (flags[1]) { c->dict_outcome = 4; return DEFF_OK; }        // hash collision (astronomically unlikely): stay explicit
     c->lut_nrows = nrows + 1;
     c->lut_rows.assign((size_t)c->lut_nrows * 6, 0.0);
     memcpy(&c->lut_rows[6], rows.data(), rows.size() * 8);
@@ -72,6 +85,7 @@ static int try_dict(deff_ctx *c)
     c->lut_omega = NAN;
     c->have_matfree = true;
     c->links_sym = 0;
+    c->dict_outcome = 1; c->dict_rows = nrows;
     return DEFF_OK;
 }
 
@@ -82,3 +96,19 @@ int ensure_dictionary(deff_ctx *c)
     if (!c->have_matfree && c->have_explicit && !c->dict_tried && c->dict_enabled && !c->wrap_links) TRY(try_dict(c));
     return DEFF_OK;
 }
+
+// The matrix-free form as the kernels see it: the table's rows (row 0 = the zero row) and every cell's code, pad column included.
+extern "C" int deff_get_dictionary(deff_ctx *c, double *rows, uint16_t *codes)
+try {
+    if (!c) return fail(DEFF_EINVAL, "ctx is NULL");
+    if (!c->have_matfree) return fail(DEFF_ESTATE, "no matrix-free form: the system has no row dictionary");
+    if (!rows && !codes) return fail(DEFF_EINVAL, "NULL argument");
+    if (rows) memcpy(rows, c->lut_rows.data(), sizeof(double) * 6 * (size_t)c->lut_nrows);
+    if (codes) {
+        TRY(use_device(c));
+        HIP_TRY(hipMemcpyAsync(codes, c->code, sizeof(uint16_t) * c->n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return DEFF_OK;
+}
+DEFF_API_CATCH

@@ -199,7 +199,7 @@ try {
     c->lut_omega = NAN;
     c->have_matfree = true;
     c->links_sym = 0;
-    c->dict_tried = false;
+    dict_reset(c);
     c->wrap_links = false;
     c->phase_mode = 3; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = Dg;
     c->have_explicit = false;                        // built on demand (native3_explicit)

@@ -221,7 +221,7 @@ try {
     commit_lut_rows(c, rows);
     c->have_image = true; c->have_walls = true; c->have_matfree = true; c->have_explicit = false;
     c->links_sym = 0;
-    c->dict_tried = false; c->have_field = true;
+    dict_reset(c); c->have_field = true;
     HIP_TRY(hipMemsetAsync(c->code, 0, sizeof(uint16_t) * c->n, c->stream));      // empty slots: zero rows
     HIP_TRY(hipMemsetAsync(c->x[0], 0, sizeof(double) * c->n, c->stream));
     HIP_TRY(hipMemsetAsync(c->x[1], 0, sizeof(double) * c->n, c->stream));

@@ -105,6 +105,10 @@ struct deff_ctx {
     bool have_matfree = false;
     bool dict_tried = false;        // a dictionary was already looked for in the current explicit system
     int dict_enabled = 1;
+    // deff_get_plan "dict_outcome" / "dict_rows": how the harvest of the current explicit system ended -- 0 none tried, 1 harvested,
+    // 2 more distinct rows than the table seats, 3 the hash table overflowed, 4 the verification pass found a mismatch -- and
+    // the rows it found (the zero row not counted; 0 unless the outcome is 1).  Reset together with dict_tried (dict_reset).
+    int dict_outcome = 0, dict_rows = 0;
     // an imported system (deff_set_system) with a non-zero W link in the first column or E link in the last:
     // the reference's kernel addresses neighbours linearly (x[p-1], x[p+1], cuh:80-83), so such a link reads the
     // neighbouring ROW's end cell.  Only the explicit / scalar kernels keep that addressing; the dictionary and the
@@ -376,6 +380,9 @@ static inline int rows_d2h(deff_ctx *c, T *dst, const T *src, size_t rows)
 }
 
 static inline CoefSoA soa_of(deff_ctx *c) { return CoefSoA{c->a0, c->aW, c->aE, c->aS, c->aN, c->b}; }
+
+// a new system: no dictionary was looked for in it yet
+static inline void dict_reset(deff_ctx *c) { c->dict_tried = false; c->dict_outcome = 0; c->dict_rows = 0; }
 
 // No C++ exception may unwind through the C ABI: every `extern "C" int` entry point is a
 // function-try-block ending in DEFF_API_CATCH, which turns std::bad_alloc (host vectors sized by the

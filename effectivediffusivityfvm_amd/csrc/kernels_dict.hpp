@@ -49,11 +49,21 @@ __device__ __forceinline__ unsigned long long row_hash(const CoefSoA &c, size_t 
     return h ? h : 1ull;
 }
 
-// returns the slot of key h, inserting it when absent; DICT_SLOTS when the table is full
+// has some cell found the table full?  (flags[0]: stored and loaded at device scope, so that the other XCDs see it while the
+// kernel runs; a cell that misses it only probes as it always did)
+__device__ __forceinline__ bool dict_overflowed(DictTable t)
+{
+    return __hip_atomic_load(&t.flags[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+}
+
+// returns the slot of key h, inserting it when absent; DICT_SLOTS when the table is full -- or, while inserting, as soon as
+// another cell has found it full: the harvest is refused then whatever this cell would find, and a probe sequence through a
+// full table is 16 384 slots long (looked at every 64 probes: the sequences of a system that can be harvested are shorter)
 __device__ __forceinline__ unsigned dict_slot(DictTable t, unsigned long long h, bool insert)
 {
     unsigned s = (unsigned)(h >> 20) & (DICT_SLOTS - 1);
     for (unsigned probe = 0; probe < DICT_SLOTS; ++probe, s = (s + 1) & (DICT_SLOTS - 1)) {
+        if (insert && (probe & 63) == 63 && dict_overflowed(t)) return DICT_SLOTS;
         unsigned long long k = t.key[s];
         if (k == h) return s;
         if (k == 0) {
@@ -68,8 +78,9 @@ __device__ __forceinline__ unsigned dict_slot(DictTable t, unsigned long long h,
 static __global__ void k_dict_insert(CoefSoA c, size_t n, DictTable t)
 {
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
+        if (dict_overflowed(t)) return;                               // the result is discarded: no cell after that probes at all
         const unsigned s = dict_slot(t, row_hash(c, p), true);
-        if (s == DICT_SLOTS) { t.flags[0] = 1; continue; }
+        if (s == DICT_SLOTS) { __hip_atomic_store(&t.flags[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
         atomicAdd(&t.count[s], 1u);
         if (t.rep[s] == 0) atomicCAS(&t.rep[s], 0ull, (unsigned long long)p + 1);
     }

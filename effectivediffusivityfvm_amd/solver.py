@@ -179,6 +179,21 @@ class Solver:
         check(self._L.deff_get_system(self._ctx, A, b))
         return A, b
 
+    def dictionary(self):
+        """(rows, codes) of the matrix-free form (deff_get_dictionary): rows (R, 6) = a0, aW, aE, aS, aN, b with row 0 the
+        zero row, codes (nimg*ny, pitch) uint16 = 8 x each cell's row index, pitch = nx rounded up to even (the pad column of
+        an odd width included).  Harvested and a-priori tables alike; DeffError (DEFF_ESTATE) without a matrix-free form.
+        A harvested table is ordered by population, ties by the rows' bit patterns: plan_value("dict_outcome") says how the
+        harvest ended (0 none tried, 1 harvested, 2 too many rows, 3 hash table overflow, 4 mismatch), "dict_rows" how many
+        rows it found."""
+        nrows = self.plan_value("lut_rows")
+        if nrows == 0:
+            check(self._L.deff_get_dictionary(self._ctx, None, None))   # raises: the library's own refusal
+        rows = np.empty((nrows, 6), dtype=np.float64)
+        codes = np.empty((self.rows, self.nx + (self.nx & 1)), dtype=np.uint16)
+        check(self._L.deff_get_dictionary(self._ctx, rows.ctypes.data_as(C.c_void_p), codes.ctypes.data_as(C.c_void_p)))
+        return rows, codes
+
     # -- field ------------------------------------------------------------
     def init_linear(self, CL, CR):
         check(self._L.deff_init_linear(self._ctx, CL, CR))

@@ -141,7 +141,12 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * on the device (deff_assemble_3phase_native): "fill_impl" (form of the last fill: 1 = one workgroup per image, 2 = row tiles),
  * "fill_launches" (kernel launches of the last fill), "fill_rounds" (most rounds one workgroup of it took), "fill_runs" (fills
  * computed since the context was created: a continuation stage on the same image computes none), "fill_fallbacks" (images
- * handed to the host fill since then) and "native3_rows" (452 while the system is the native 3-phase one, else 0) */
+ * handed to the host fill since then) and "native3_rows" (452 while the system is the native 3-phase one, else 0).  Of the
+ * row dictionary: "dict_outcome" (how the harvest of the current explicit system ended: 0 = none tried since the system was
+ * set, 1 = harvested, 2 = more distinct rows than the table seats -- 511 beside the zero row, the identity row of an odd
+ * width's pad column being one of them --, 3 = the hash table of 16 384 slots overflowed, 4 = the verification pass found a
+ * mismatch), "dict_rows" (rows harvested, the zero row not counted; 0 unless the outcome is 1) and "lut_rows" (rows of the
+ * current matrix-free table, harvested or a-priori, the zero row counted; 0 without one) */
 int deff_get_plan(deff_ctx *ctx, const char *key, int *value);
 
 /* ---- image -> phases: replaces the mask->D loops cuh:1988-2000 (2-phase),
@@ -193,6 +198,13 @@ int deff_set_system(deff_ctx *ctx, const double *A, const double *b, const doubl
                     double CL, double CR);
 /* assembled coefficients back in the reference's AoS layout (parity tests, drop-in) */
 int deff_get_system(deff_ctx *ctx, double *A, double *b);
+/* the matrix-free form as the matrix-free kernels see it, harvested and a-priori tables alike: rows[R * 6] = a0, aW, aE, aS,
+ * aN, b of the table's R rows (R = deff_get_plan "lut_rows"; row 0 is the zero row), codes[nimg*ny * pitch] = every cell's
+ * code (8 x its row index) with pitch = nx rounded up to even -- the pad column of an odd mesh width included.  Either
+ * pointer may be NULL.  Read-only.  DEFF_ESTATE when the system has no matrix-free form.
+ * A harvested table is ordered by population, most cells first; rows of equal population by the bit patterns of their six
+ * doubles, compared as unsigned 64-bit integers in the order above.  The codes are therefore a function of the system. */
+int deff_get_dictionary(deff_ctx *ctx, double *rows, uint16_t *codes);
 
 /* ---- field ------------------------------------------------------------- */
 int deff_init_linear(deff_ctx *ctx, double CL, double CR);          /* cuh:1955-1959 */
