@@ -29,7 +29,9 @@ SYMBOLS = [
     "deff_rccl_unique_id", "deff_slab_rank_create", "deff_slab_rank_create_custom", "deff_slab_rank_destroy", "deff_slab_rank_layout",
     "deff_slab_rank_window", "deff_slab_rank_context", "deff_slab_rank_set_tuning", "deff_slab_rank_set_image_window",
     "deff_slab_rank_synth_image", "deff_slab_rank_assemble_3phase", "deff_slab_group_assemble_3phase", "deff_slab_rank_get_field", "deff_slab_rank_sweeps", "deff_slab_rank_solve",
-    "deff_solve_stream", "deff_solve_cg_stream", "deff_get_slot_field", "deff_debug_tb_stamps", "deff_flux", "deff_residual", "deff_residual_slot", "deff_residual_D", "deff_sensitivity_D", "deff_sensitivity", "deff_device_sensitivity", "deff_set_progress", "deff_last_launches", "deff_device_field", "deff_synchronize",
+    "deff_solve_stream", "deff_solve_cg_stream", "deff_get_slot_field", "deff_debug_tb_stamps", "deff_flux", "deff_residual", "deff_residual_slot", "deff_residual_D", "deff_sensitivity_D", "deff_sensitivity", "deff_device_sensitivity",
+    "deff_solve_adjoint", "deff_set_adjoint", "deff_get_adjoint", "deff_device_adjoint", "deff_field_vjp_D", "deff_device_field_vjp",
+    "deff_set_progress", "deff_last_launches", "deff_device_field", "deff_synchronize",
 ]
 
 
@@ -123,6 +125,13 @@ def load():
     L.deff_sensitivity_D.argtypes = [ctx, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
     L.deff_sensitivity.argtypes = [ctx, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
     L.deff_device_sensitivity.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    if hasattr(L, "deff_solve_adjoint"):                 # DEFF_AMD_LIB may name a build from before the field adjoint
+        L.deff_solve_adjoint.argtypes = [ctx, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.POINTER(CGResultC)]
+        L.deff_set_adjoint.argtypes = [ctx, C.c_void_p]
+        L.deff_get_adjoint.argtypes = [ctx, C.c_void_p]
+        L.deff_device_adjoint.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.deff_field_vjp_D.argtypes = [ctx, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.deff_device_field_vjp.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.deff_set_progress.argtypes = [ctx, PROGRESS_FN, C.c_void_p]
     L.deff_last_launches.argtypes = [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     ip = C.POINTER(C.c_int)

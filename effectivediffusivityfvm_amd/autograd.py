@@ -1,5 +1,7 @@
 """Deff as a differentiable torch op: the forward pass is a conjugate-gradient solve on the coefficient planes of the D map,
 the backward pass the library's one-pass gradient (deff_sensitivity_D) -- no second solve, the problem is self-adjoint.
+The concentration field as one: the same forward solve; the backward pass is one adjoint solve with the incoming gradient as
+right-hand side (deff_solve_adjoint) and one pass over (x, lambda, D) (deff_field_vjp_D), for any loss on the field.
 
 torch is imported inside the functions only: importing the package does not import it.  D makes a host round trip (plumbing;
 the solve and the gradient run in the library's HIP kernels)."""
@@ -65,3 +67,81 @@ def effective_diffusivity(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, sol
     if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() not in (2, 3):
         raise TypeError("D must be a float64 tensor of shape (ny, nx) or (nimg, ny, nx)")
     return _function().apply(D, float(CL), float(CR), float(rtol), int(max_iter), solver)
+
+
+_FIELD_FN = None
+
+
+def _converged(who, rs, rtol, max_iter):
+    rs = rs if isinstance(rs, list) else [rs]
+    bad = [k for k, r in enumerate(rs) if not r.converged]
+    if bad:
+        raise RuntimeError(f"{who}: CG did not converge to rtol {rtol} for image(s) {bad} "
+                           f"(rel_residual {[rs[k].rel_residual for k in bad]}, max_iter {max_iter})")
+
+
+def _field_function():
+    """The torch.autograd.Function of concentration_field, created at first use."""
+    global _FIELD_FN
+    if _FIELD_FN is not None:
+        return _FIELD_FN
+    import torch
+
+    class _ConcentrationField(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, D, CL, CR, rtol, max_iter, solver):
+            Dh = np.ascontiguousarray(D.detach().cpu().numpy(), dtype=np.float64)
+            nimg = Dh.shape[0] if Dh.ndim == 3 else 1
+            ny, nx = Dh.shape[-2:]
+            s = solver if solver is not None else Solver(nx, ny, nimg=nimg)
+            try:
+                if (s.nx, s.ny, s.nimg) != (nx, ny, nimg):
+                    raise ValueError(f"solver is {s.nimg} x ({s.ny}, {s.nx}), D is {tuple(Dh.shape)}")
+                s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
+                s.init_linear(CL, CR)
+                s.set_tuning("cg_planes", 1)
+                _converged("concentration_field", s.solve_cg(rtol=rtol, max_iter=max_iter, fluxes=False), rtol, max_iter)
+                x = s.get_field().reshape(Dh.shape)
+            finally:
+                if solver is None:
+                    s.close()
+            ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver)
+            return torch.from_numpy(x.copy()).to(D.device)
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            Dh, x, CL, CR, rtol, max_iter, solver = ctx.deff_args
+            nimg = Dh.shape[0] if Dh.ndim == 3 else 1
+            ny, nx = Dh.shape[-2:]
+            w = np.ascontiguousarray(grad_out.detach().cpu().numpy(), dtype=np.float64)
+            s = solver if solver is not None else Solver(nx, ny, nimg=nimg)
+            try:
+                # whatever happened to the solver since the forward pass: its system and field are set again
+                s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
+                s.set_field(x.reshape(nimg * ny, nx))
+                _converged("concentration_field (adjoint)",
+                           s.solve_adjoint(w.reshape(nimg * ny, nx), rtol=rtol, max_iter=max_iter), rtol, max_iter)
+                g, _ = s.field_vjp(Dh.reshape(nimg * ny, nx), CL, CR)
+            finally:
+                if solver is None:
+                    s.close()
+            g = torch.from_numpy(np.ascontiguousarray(g).reshape(Dh.shape)).to(grad_out.device)
+            return g, None, None, None, None, None
+
+    _FIELD_FN = _ConcentrationField
+    return _FIELD_FN
+
+
+def concentration_field(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, solver=None):
+    """The concentration field x of the diffusivity map D -- a float64 tensor (ny, nx), or (nimg, ny, nx) for a stack, on any
+    device -- as a tensor of D's shape on D's device, differentiable with respect to D for ANY loss on x.  Forward, as
+    effective_diffusivity: deff_assemble_from_D, the linear guess, conjugate gradients on the coefficient planes to rtol
+    (RuntimeError if they do not converge).  Backward, with the incoming gradient w = dL/dx: the system is assembled from D
+    again and the saved x set as its field -- on `solver` when one was passed, otherwise on a Solver created and closed for the
+    backward pass --, then one adjoint solve A lambda = w to rtol (deff_solve_adjoint; RuntimeError if it does not converge)
+    and one pass over (x, lambda, D) (deff_field_vjp_D) give dL/dD.  D and w make a host round trip.  `solver`: a Solver of the
+    same shape to reuse (its system, field, adjoint field and the tuning key "cg_planes" are overwritten, in both passes)."""
+    import torch
+    if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() not in (2, 3):
+        raise TypeError("D must be a float64 tensor of shape (ny, nx) or (nimg, ny, nx)")
+    return _field_function().apply(D, float(CL), float(CR), float(rtol), int(max_iter), solver)

@@ -6,6 +6,8 @@
 // deff_solve, in far fewer iterations.  Nothing of the Jacobi path is touched: its tables (lut, c0 plane), plans and knobs
 // stay as they are (the "fma" knob does not apply here: CG's arithmetic is written-order FP64 only).
 // The launches of one iteration, in every form and under every fold key, are CgIteration::enqueue's, for both solves.
+// deff_solve_adjoint (A lambda = w for the gradient of a loss on the field, api_vjp.hip) runs deff_solve_cg's host loop,
+// cg_host_loop, on the coefficient planes with its own solution and right-hand side buffers.
 #include "ctx.hpp"
 #include "kernels_cg.hpp"
 #include "kernels_cg_planes.hpp"
@@ -116,10 +118,11 @@ struct CgIteration {
     unsigned *tick_a, *tick_b;
     double tol2;
     long long max_iter;
+    const double *rhs = nullptr;    // plane form: the right-hand side plane (the iteration's kernels read the matrix planes only)
 
     int enqueue(const double *p_in, double *p_out) const
     {
-        const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, c->b};
+        const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, rhs};
         CgScal *sc = (CgScal *)c->cg_scal;
         if (fold) {
             if (planes) {
@@ -151,6 +154,70 @@ struct CgIteration {
         return 4;
     }
 };
+
+// The host loop of a CG solve, for deff_solve_cg (x = the field, rhs = the b plane) and deff_solve_adjoint (x = lambda,
+// rhs = w'): the start's true residual, check_every iterations between two looks at the images' flags, the true-residual
+// rounds at the end.  The caller has prepared the table or cg_inv, zeroed cg_flags and cg_tick and set the "cg_*" plan keys;
+// `planes` reads the matrix from the coefficient planes and the right-hand side from `rhs` (the table form has b in its
+// table and ignores it).  hs[img] = the images' final scalars, *ms = the loop's time on cg_ev0 / cg_ev1.
+static int cg_host_loop(deff_ctx *c, double *x, const double *rhs, bool planes, bool onchip, int fold, const CgGeom &g,
+                        double rtol, int64_t max_iter, int64_t check_every, std::vector<CgScal> &hs, float *ms)
+{
+    const size_t items = (size_t)g.per_img * c->nimg;
+    const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, rhs};
+    unsigned flag1 = 0;
+    const double tol2 = rtol * rtol;
+    const dim3 grid((unsigned)((items + 3) / 4)), fin((unsigned)c->nimg);
+    double *part = c->cg_part, *part_rz = c->cg_part + items, *part_rr = c->cg_part + 2 * items;
+    CgScal *sc = (CgScal *)c->cg_scal;
+    const CgIteration iteration{c, planes, fold, grid, fin, g, x, part, part_rz, part_rr, c->cg_tick,
+                                c->cg_tick + cgf_ticks(g.per_img, (size_t)c->nimg), tol2, (long long)max_iter, rhs};
+    hs.resize(c->nimg);
+    auto true_residual = [&](int mode, int allow) -> int {
+        if (planes) hipLaunchKernelGGL(k_cgp_resid, grid, dim3(256), 0, c->stream, P, c->cg_inv, x, c->cg_r, g, part);
+        else hipLaunchKernelGGL(k_cg_resid, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, x, c->cg_r, g, part);
+        hipLaunchKernelGGL(k_cg_check, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc, tol2, (long long)max_iter, mode,
+                           allow, c->cg_flags + 1);
+        HIP_TRY(hipGetLastError());
+        return DEFF_OK;
+    };
+    HIP_TRY(hipEventRecord(c->cg_ev0, c->stream));
+    TRY(true_residual(0, 0));
+    int64_t k = 0;                                                   // iterations enqueued (parity of the p buffers)
+    int rounds = 0;
+    for (;;) {
+        HIP_TRY(hipMemcpyAsync(hs.data(), sc, sizeof(CgScal) * c->nimg, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        bool all_done = true;
+        for (const CgScal &s : hs) all_done &= s.done != 0;
+        if (all_done) {
+            // the recurrence's residual drifts from b - A x: recompute it; an image whose true residual misses rtol goes on
+            HIP_TRY(hipMemsetAsync(c->cg_flags + 1, 0, sizeof(unsigned), c->stream));
+            TRY(true_residual(1, rounds < CG_MAX_RESTARTS));
+            HIP_TRY(hipMemcpyAsync(&flag1, c->cg_flags + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(hs.data(), sc, sizeof(CgScal) * c->nimg, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (flag1 == 0) break;
+            ++rounds;
+            c->cg_plan_restarts = rounds;
+        }
+        if (onchip) {
+            // up to check_every iterations of every running image, p in cg_p[0] throughout (the streaming loop below starts
+            // every call at cg_p[0] with the restart flag set, so the two forms never read each other's p)
+            hipLaunchKernelGGL(k_cg_image, dim3((unsigned)std::min(c->nimg, c->cg_cus)), dim3(CGI_THREADS), 0, c->stream,
+                               c->cg_tab, c->lut_nrows, c->code, x, c->cg_r, c->cg_p[0], sc, c->nx, c->ny, c->nimg,
+                               (long long)check_every, tol2, (long long)max_iter);
+            HIP_TRY(hipGetLastError());
+            continue;
+        }
+        for (int64_t i = 0; i < check_every; ++i, ++k) iteration.enqueue(c->cg_p[k & 1], c->cg_p[(k + 1) & 1]);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(c->cg_ev1, c->stream));
+    HIP_TRY(hipEventSynchronize(c->cg_ev1));
+    HIP_TRY(hipEventElapsedTime(ms, c->cg_ev0, c->cg_ev1));
+    return DEFF_OK;
+}
 
 extern "C" int deff_solve_cg(deff_ctx *c, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out,
                              double *MFL, double *MFR)
@@ -226,58 +293,9 @@ try {
         return fail(DEFF_EINVAL, "deff_solve_cg: the system is not symmetric (a link between two active cells differs from "
                                  "its partner, or an active row links out of its image)");
 
-    const double tol2 = rtol * rtol;
-    const dim3 grid((unsigned)((items + 3) / 4)), fin((unsigned)c->nimg);
-    double *x = c->x[c->cur];
-    double *part = c->cg_part, *part_rz = c->cg_part + items, *part_rr = c->cg_part + 2 * items;
-    CgScal *sc = (CgScal *)c->cg_scal;
-    const CgIteration iteration{c, planes, fold, grid, fin, g, x, part, part_rz, part_rr, c->cg_tick,
-                                c->cg_tick + cgf_ticks(g.per_img, (size_t)c->nimg), tol2, (long long)max_iter};
-    std::vector<CgScal> hs(c->nimg);
-    auto true_residual = [&](int mode, int allow) -> int {
-        if (planes) hipLaunchKernelGGL(k_cgp_resid, grid, dim3(256), 0, c->stream, P, c->cg_inv, x, c->cg_r, g, part);
-        else hipLaunchKernelGGL(k_cg_resid, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, x, c->cg_r, g, part);
-        hipLaunchKernelGGL(k_cg_check, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc, tol2, (long long)max_iter, mode,
-                           allow, c->cg_flags + 1);
-        HIP_TRY(hipGetLastError());
-        return DEFF_OK;
-    };
-    HIP_TRY(hipEventRecord(c->cg_ev0, c->stream));
-    TRY(true_residual(0, 0));
-    int64_t k = 0;                                                   // iterations enqueued (parity of the p buffers)
-    int rounds = 0;
-    for (;;) {
-        HIP_TRY(hipMemcpyAsync(hs.data(), sc, sizeof(CgScal) * c->nimg, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        bool all_done = true;
-        for (const CgScal &s : hs) all_done &= s.done != 0;
-        if (all_done) {
-            // the recurrence's residual drifts from b - A x: recompute it; an image whose true residual misses rtol goes on
-            HIP_TRY(hipMemsetAsync(c->cg_flags + 1, 0, sizeof(unsigned), c->stream));
-            TRY(true_residual(1, rounds < CG_MAX_RESTARTS));
-            HIP_TRY(hipMemcpyAsync(&flags[1], c->cg_flags + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(hs.data(), sc, sizeof(CgScal) * c->nimg, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (flags[1] == 0) break;
-            ++rounds;
-            c->cg_plan_restarts = rounds;
-        }
-        if (onchip) {
-            // up to check_every iterations of every running image, p in cg_p[0] throughout (the streaming loop below starts
-            // every call at cg_p[0] with the restart flag set, so the two forms never read each other's p)
-            hipLaunchKernelGGL(k_cg_image, dim3((unsigned)std::min(c->nimg, c->cg_cus)), dim3(CGI_THREADS), 0, c->stream,
-                               c->cg_tab, c->lut_nrows, c->code, x, c->cg_r, c->cg_p[0], sc, c->nx, c->ny, c->nimg,
-                               (long long)check_every, tol2, (long long)max_iter);
-            HIP_TRY(hipGetLastError());
-            continue;
-        }
-        for (int64_t i = 0; i < check_every; ++i, ++k) iteration.enqueue(c->cg_p[k & 1], c->cg_p[(k + 1) & 1]);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(c->cg_ev1, c->stream));
-    HIP_TRY(hipEventSynchronize(c->cg_ev1));
+    std::vector<CgScal> hs;
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->cg_ev0, c->cg_ev1));
+    TRY(cg_host_loop(c, c->x[c->cur], c->b, planes, onchip, fold, g, rtol, max_iter, check_every, hs, &ms));
 
     // Deff and wall fluxes of the final field: the same evaluation as deff_flux
     std::vector<double> deff(c->nimg);
@@ -286,6 +304,81 @@ try {
         out[i].iters = hs[i].iters;
         out[i].rel_residual = hs[i].rel;
         out[i].deff_raw = deff[i];
+        out[i].loop_ms = ms;
+        out[i].converged = hs[i].rel <= rtol;
+    }
+    return DEFF_OK;
+}
+DEFF_API_CATCH
+
+// ---- deff_solve_adjoint -------------------------------------------------------------------------------------------------
+//
+// A lambda = w on the current matrix (symmetric: the adjoint system of A x = b is the same A), for the gradient of a loss on
+// the field (api_vjp.hip).  The plane form of deff_solve_cg with two pointers changed: the solution is adj_lam instead of the
+// field, the right-hand side adj_w (w, zeroed where the FORWARD system's row is decoupled: cg_inv == 0) instead of the b
+// plane.  cg_inv and the admissibility verdict are k_cgp_prepare's on the forward planes, b included.  Nothing the forward
+// solve or the Jacobi path reads is written.
+extern "C" int deff_solve_adjoint(deff_ctx *c, const double *w, double rtol, int64_t max_iter, int64_t check_every,
+                                  deff_cg_result *out)
+try {
+    if (!c || !w || !out) return fail(DEFF_EINVAL, "NULL argument");
+    if (!(rtol >= 0.0) || !std::isfinite(rtol)) return fail(DEFF_EINVAL, "deff_solve_adjoint: rtol must be finite and >= 0");
+    if (max_iter < 0) return fail(DEFF_EINVAL, "deff_solve_adjoint: negative max_iter");
+    if (check_every < 1) return fail(DEFF_EINVAL, "check_every must be >= 1");
+    if (c->slab)
+        return fail(DEFF_EINVAL, "deff_solve_adjoint: not for row-slab contexts (the rows of the image live on several devices)");
+    if (c->wrap_links)
+        return fail(DEFF_EINVAL, "deff_solve_adjoint: the system links a wall column to the neighbouring row (explicit-only system)");
+    if (!c->have_explicit && !c->have_matfree) return fail(DEFF_ESTATE, "no system assembled");
+    TRY(use_device(c));
+    TRY(resident_check(c));                                          // the scratch and the stream are about to be used
+    TRY(explicit_from_image(c));                                     // a native system's planes; nothing to do for any other
+    const CgGeom g = cg_geometry(c);
+    const size_t items = (size_t)g.per_img * c->nimg;
+    TRY(cg_buffers(c, items));
+    TRY(cgp_buffers(c));
+    TRY(dev_alloc(&c->adj_lam, c->n));
+    TRY(dev_alloc(&c->adj_w, c->n));
+    const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, c->b};
+
+    unsigned flags[2] = {0, 0};
+    HIP_TRY(hipMemsetAsync(c->cg_flags, 0, sizeof(unsigned) * 2, c->stream));
+    HIP_TRY(hipMemsetAsync(c->cg_tick, 0, sizeof(unsigned) * 2 * cgf_ticks(g.per_img, (size_t)c->nimg), c->stream));
+    hipLaunchKernelGGL(k_cgp_prepare, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, P, c->nx, c->rows, c->ny, c->cg_inv,
+                       c->cg_flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(flags, c->cg_flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flags[0] & CGP_FLAG_ROW)
+        return fail(DEFF_EINVAL, "deff_solve_adjoint: a matrix row is not admissible: an active row needs a finite A0 > 0 and "
+                                 "finite links");
+    if (flags[0])
+        return fail(DEFF_EINVAL, "deff_solve_adjoint: the system is not symmetric (a link between two active cells differs from "
+                                 "its partner, or an active row links out of its image)");
+
+    // from here on lambda is the new call's
+    c->adj_valid = false;
+    c->cg_plan_kr = g.kr;
+    c->cg_plan_ntx = g.ntx;
+    c->cg_plan_items = (int)g.per_img;
+    c->cg_plan_restarts = 0;
+    c->cg_plan_impl = 3;
+    const int fold = c->cg_fold == 2 ? 1 : c->cg_fold;
+    c->cg_plan_fold = fold;
+    if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(c->adj_w, 0, sizeof(double) * c->n, c->stream));
+    TRY(rows_h2d(c, c->adj_w, w, (size_t)c->rows));
+    hipLaunchKernelGGL(k_cgp_mask_rhs, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, c->cg_inv, c->n, c->adj_w);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(c->adj_lam, 0, sizeof(double) * c->n, c->stream));     // the guess, always
+
+    std::vector<CgScal> hs;
+    float ms = 0;
+    TRY(cg_host_loop(c, c->adj_lam, c->adj_w, true, false, fold, g, rtol, max_iter, check_every, hs, &ms));
+    c->adj_valid = true;
+    for (int i = 0; i < c->nimg; ++i) {
+        out[i].iters = hs[i].iters;
+        out[i].rel_residual = hs[i].rel;
+        out[i].deff_raw = 0.0;                                       // lambda has no flux
         out[i].loop_ms = ms;
         out[i].converged = hs[i].rel <= rtol;
     }
@@ -395,6 +488,7 @@ try {
     c->have_image = true; c->have_walls = true; c->have_matfree = true; c->have_explicit = false;
     c->links_sym = 0;
     dict_reset(c); c->have_field = true;
+    adjoint_reset(c);
     c->q_valid = false;
     reset_batch_state(c);                                            // every slot's field lives in x[cur], now and afterwards
     double *x = c->x[c->cur];

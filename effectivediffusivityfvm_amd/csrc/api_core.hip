@@ -147,6 +147,10 @@ try {
     if (c->sens_part) (void)hipFree(c->sens_part);
     if (c->sens_ev0) (void)hipEventDestroy(c->sens_ev0);
     if (c->sens_ev1) (void)hipEventDestroy(c->sens_ev1);
+    void *adj_bufs[] = {c->adj_lam, c->adj_w, c->vjp_g, c->vjp_part};
+    for (void *p : adj_bufs) if (p) (void)hipFree(p);
+    if (c->vjp_ev0) (void)hipEventDestroy(c->vjp_ev0);
+    if (c->vjp_ev1) (void)hipEventDestroy(c->vjp_ev1);
     if (c->q_host) (void)hipHostFree(c->q_host);
     if (c->chain_counted) resident_chain_ctx_destroyed(c->device);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -275,6 +279,7 @@ try {
     else if (!strcmp(key, "tb_debug_stall_skip")) c->tb_debug_stall_skip = value;
     else if (!strcmp(key, "res_kt")) c->res_kt = value;
     else if (!strcmp(key, "sens_kt")) c->sens_kt = value;
+    else if (!strcmp(key, "vjp_kt")) c->vjp_kt = value;
     else if (!strcmp(key, "tb_sym")) c->tb_sym = value;
     else if (!strcmp(key, "tb_launch")) {            // 0: resident passes where possible; 1: one launch per pass
         if (value > 1) return fail(DEFF_EINVAL, "tb_launch takes 0 (resident passes where the tiles fit the chip) or 1 (one launch per pass)");
@@ -363,6 +368,8 @@ try {
     else if (!strcmp(key, "res_items")) *value = c->res_plan_items;
     else if (!strcmp(key, "sens_kt")) *value = c->sens_plan_kt;
     else if (!strcmp(key, "sens_items")) *value = c->sens_plan_items;
+    else if (!strcmp(key, "vjp_kt")) *value = c->vjp_plan_kt;
+    else if (!strcmp(key, "vjp_items")) *value = c->vjp_plan_items;
     else if (!strcmp(key, "fill_impl")) *value = c->fill_plan_impl;
     else if (!strcmp(key, "fill_launches")) *value = c->fill_plan_launches;
     else if (!strcmp(key, "fill_rounds")) *value = c->fill_plan_rounds;
@@ -403,6 +410,7 @@ try {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_image = true;
     c->have_matfree = false;
+    adjoint_reset(c);
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -419,6 +427,7 @@ try {
     HIP_TRY(hipGetLastError());
     c->have_image = true;
     c->have_matfree = false;
+    adjoint_reset(c);
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -548,6 +557,7 @@ try {
     c->Ds = Ds; c->Df = Df;
     c->phase_mode = 2; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = 0.0;
     c->have_explicit = false;
+    adjoint_reset(c);
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -609,6 +619,7 @@ try {
     c->phase_mode = 3; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = Dg;
     c->grid_given = Grid != nullptr;
     c->have_matfree = false; dict_reset(c); c->wrap_links = false; c->native3 = false;
+    adjoint_reset(c);
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -674,6 +685,7 @@ try {
     c->have_explicit = true; c->c0_omega = NAN; c->have_walls = true;
     c->phase_mode = 0;
     c->have_matfree = false; dict_reset(c); c->wrap_links = false; c->native3 = false;
+    adjoint_reset(c);
     return DEFF_OK;
 }
 DEFF_API_CATCH
@@ -729,6 +741,7 @@ try {
     c->have_explicit = true; c->c0_omega = NAN;
     c->have_matfree = false; dict_reset(c); c->native3 = false;
     c->wrap_links = wrap;
+    adjoint_reset(c);
     return DEFF_OK;
 }
 DEFF_API_CATCH

@@ -204,6 +204,7 @@ try {
     c->phase_mode = 3; c->phase_D[0] = Df; c->phase_D[1] = Ds; c->phase_D[2] = Dg;
     c->have_explicit = false;                        // built on demand (native3_explicit)
     c->native3 = true;
+    adjoint_reset(c);
     return DEFF_OK;
 }
 DEFF_API_CATCH

@@ -222,6 +222,7 @@ try {
     c->have_image = true; c->have_walls = true; c->have_matfree = true; c->have_explicit = false;
     c->links_sym = 0;
     dict_reset(c); c->have_field = true;
+    adjoint_reset(c);
     HIP_TRY(hipMemsetAsync(c->code, 0, sizeof(uint16_t) * c->n, c->stream));      // empty slots: zero rows
     HIP_TRY(hipMemsetAsync(c->x[0], 0, sizeof(double) * c->n, c->stream));
     HIP_TRY(hipMemsetAsync(c->x[1], 0, sizeof(double) * c->n, c->stream));

@@ -12,6 +12,8 @@
 //   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg) and through refilled slots (deff_solve_cg_stream);
 //                  every CG kernel, the slab forms included: their launches for one slab (cg_slab.hpp)
 //   api_sens.hip   the Deff gradient dDeff/dD per cell and its Euler sum (deff_sensitivity, deff_sensitivity_D)
+//   api_vjp.hip    the field adjoint: lambda's buffer (deff_set_adjoint, deff_get_adjoint, deff_device_adjoint) and the pass
+//                  (x, lambda, D) -> dL/dD (deff_field_vjp_D); deff_solve_adjoint itself is in api_cg.hip, beside the loop it runs
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
 //                  RCCL or a caller-supplied transport with one process per GPU); conjugate gradients over the slabs
@@ -292,6 +294,20 @@ struct deff_ctx {
     int sens_kt = 0, sens_plan_kt = 0, sens_plan_items = 0;
     bool grid_given = false;        // the last deff_assemble_3phase was given a Grid (deff_sensitivity refuses such a system)
 
+    // The field adjoint (api_vjp.hip; the solve itself is api_cg.hip's loop).  adj_lam: lambda of A lambda = w (pitch nx, pad
+    // column 0), adj_w: the right-hand side w' = w with the forward system's decoupled cells zeroed; both allocated by the
+    // first deff_solve_adjoint / deff_set_adjoint.  adj_valid: lambda belongs to the current system and image (adjoint_reset
+    // below: every call that replaces either clears it).
+    // deff_field_vjp_D: the last map dL/dD (pitch nx, kept until the next call: deff_device_field_vjp), the work items' Euler sums
+    // + one sum per image, the call's own event pair; vjp_kt: tuning "vjp_kt"; vjp_plan_*: deff_get_plan "vjp_kt" / "vjp_items"
+    double *adj_lam = nullptr, *adj_w = nullptr;
+    bool adj_valid = false;
+    double *vjp_g = nullptr, *vjp_part = nullptr;
+    size_t vjp_part_cap = 0;
+    bool vjp_have = false;
+    hipEvent_t vjp_ev0 = nullptr, vjp_ev1 = nullptr;
+    int vjp_kt = 0, vjp_plan_kt = 0, vjp_plan_items = 0;
+
     // Native 3-phase system (kernels_fill.hpp, api_fill.hip): the flood fill of the pore space as bitmaps -- one `open` and
     // one `reach` word per 64 columns of a row, fill_nw words per row --, its status words and the tiled form's `changed` words.
     // fill_valid: reach is the fill of the current pixels (image_shape clears it: every new image goes through there);
@@ -383,6 +399,9 @@ static inline CoefSoA soa_of(deff_ctx *c) { return CoefSoA{c->a0, c->aW, c->aE, 
 
 // a new system: no dictionary was looked for in it yet
 static inline void dict_reset(deff_ctx *c) { c->dict_tried = false; c->dict_outcome = 0; c->dict_rows = 0; }
+
+// a new system or image: the adjoint field was the old one's (deff_get_adjoint, deff_device_adjoint, deff_field_vjp_D: DEFF_ESTATE)
+static inline void adjoint_reset(deff_ctx *c) { c->adj_valid = false; }
 
 // No C++ exception may unwind through the C ABI: every `extern "C" int` entry point is a
 // function-try-block ending in DEFF_API_CATCH, which turns std::bad_alloc (host vectors sized by the

@@ -147,6 +147,14 @@ __global__ __launch_bounds__(256) void k_cgp_prepare(CgpPlanes A, int nx, int ro
     if (bad) atomicOr(flag, bad);
 }
 
+// A right-hand side that is not the system's own b (deff_solve_adjoint): w[p] = 0 on the cells k_cgp_prepare found decoupled
+// (inv == 0; a select, so a NaN there goes too), so that r = w - A x is 0 there as it is for b.  In place.
+__global__ __launch_bounds__(256) void k_cgp_mask_rhs(const double *__restrict__ inv, size_t n, double *__restrict__ w)
+{
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (size_t)gridDim.x * 256)
+        if (inv[p] == 0.0) w[p] = 0.0;
+}
+
 // what p' of a lane's two cells is made of (zeros outside the image)
 struct CgpRaw2 {
     double2 r, inv, p;

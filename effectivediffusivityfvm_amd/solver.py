@@ -418,6 +418,67 @@ class Solver:
         check(self._L.deff_device_sensitivity(self._ctx, C.byref(p), C.byref(pitch)))
         return p.value, pitch.value
 
+    # -- field adjoint: dL/dD for a loss on the field ----------------------
+    def solve_adjoint(self, w, rtol=1e-10, max_iter=1_000_000, check_every=64):
+        """A lambda = w on the current matrix with homogeneous walls (deff_solve_adjoint), w = dL/dx as (rows, nx): the
+        iteration of solve_cg on the coefficient planes from lambda = 0, into a buffer of the context's own -- the field, the
+        system and its dictionary stay as they are.  Cells the forward system decouples ignore w and get lambda = 0.
+        One image: a CGResult (deff_raw 0.0, MFL / MFR None); a stack: a list, one per image."""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        assert w.size == self.nx * self.rows
+        res = (CGResultC * self.nimg)()
+        check(self._L.deff_solve_adjoint(self._ctx, w.ctypes.data_as(C.c_void_p), float(rtol), int(max_iter),
+                                         int(check_every), res))
+        outs = []
+        for k in range(self.nimg):
+            out = CGResult()
+            out.iters, out.rel_residual, out.deff_raw = res[k].iters, res[k].rel_residual, res[k].deff_raw
+            out.converged, out.loop_ms = bool(res[k].converged), res[k].loop_ms
+            out.MFL = out.MFR = None
+            outs.append(out)
+        return outs[0] if self.nimg == 1 else outs
+
+    def set_adjoint(self, lam):
+        """A caller's own lambda as the adjoint field (deff_set_adjoint)."""
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        assert lam.size == self.nx * self.rows
+        check(self._L.deff_set_adjoint(self._ctx, lam.ctypes.data_as(C.c_void_p)))
+
+    def get_adjoint(self):
+        """The adjoint field as (rows, nx); DeffError (DEFF_ESTATE) while none is valid for the current system."""
+        lam = np.empty((self.rows, self.nx), dtype=np.float64)
+        check(self._L.deff_get_adjoint(self._ctx, lam.ctypes.data_as(C.c_void_p)))
+        return lam
+
+    def device_adjoint_ptr(self):
+        """(device pointer, row pitch in bytes) of the adjoint field; the pitch is device_field_ptr's."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_device_adjoint(self._ctx, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+    def field_vjp(self, D, CL, CR, timing=False):
+        """dL/dD from the current field, the current adjoint field and the diffusivity plane D (rows, nx), in one pass
+        (deff_field_vjp_D): (g, euler) with g as (ny, nx), or (nimg, ny, nx) for a stack, and euler = sum of D * g per image
+        (a float, or an array), which is 0 for a converged field.  timing=True appends the device time in ms."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        assert D.size == self.nx * self.rows
+        g = np.empty((self.rows, self.nx), dtype=np.float64)
+        e = (C.c_double * self.nimg)()
+        ms = C.c_float()
+        check(self._L.deff_field_vjp_D(self._ctx, D.ctypes.data_as(C.c_void_p), float(CL), float(CR),
+                                       g.ctypes.data_as(C.c_void_p), e, C.byref(ms) if timing else None))
+        g = g if self.nimg == 1 else g.reshape(self.nimg, self.ny, self.nx)
+        euler = e[0] if self.nimg == 1 else np.array(e[:])
+        return (g, euler, ms.value) if timing else (g, euler)
+
+    def device_field_vjp_ptr(self):
+        """(device pointer, row pitch in bytes) of the last field_vjp map; valid until the next one or close()."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_device_field_vjp(self._ctx, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
     def set_progress(self, fn):
         """fn(iter, deff_raw, change) after every convergence check, or None."""
         if fn is None:

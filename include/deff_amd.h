@@ -99,6 +99,7 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  * "res_kt" (deff_residual / deff_residual_slot: tiles of 8 rows one wave streams through, a "run"; 0 = the planner's choice,
  *   about 4 096 work items per launch; clipped to the image's tile rows; deff_get_plan "res_kt"),
  * "sens_kt" (deff_sensitivity / deff_sensitivity_D: the same for the gradient pass; deff_get_plan "sens_kt"),
+ * "vjp_kt" (deff_field_vjp_D: the same for the field adjoint's pass; deff_get_plan "vjp_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
  *   run every pass between two checks in ONE launch, neighbouring tiles synchronised by flags: 1 = one launch per
  *   pass instead; a resident launch that cannot make progress -- another process holds part of the GPU -- gives up
@@ -137,7 +138,8 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * "res_kt" (tiles of 8 rows per run as used: after the planner, the tuning key and the clip to the image's tile rows;
  * 0 after deff_residual_D, which has no runs) and "res_items" (partial sums added per image by the final reduction:
  * strips of 128 columns x ceil(tile rows / res_kt), or for deff_residual_D rows x segments of 256 columns).  Of the last
- * deff_sensitivity / deff_sensitivity_D that launched: "sens_kt" and "sens_items", with the same meaning.  Of the flood fill
+ * deff_sensitivity / deff_sensitivity_D that launched: "sens_kt" and "sens_items", with the same meaning; of the last
+ * deff_field_vjp_D that launched: "vjp_kt" and "vjp_items", likewise.  Of the flood fill
  * on the device (deff_assemble_3phase_native): "fill_impl" (form of the last fill: 1 = one workgroup per image, 2 = row tiles),
  * "fill_launches" (kernel launches of the last fill), "fill_rounds" (most rounds one workgroup of it took), "fill_runs" (fills
  * computed since the context was created: a continuation stage on the same image computes none), "fill_fallbacks" (images
@@ -377,6 +379,64 @@ int deff_sensitivity_D(deff_ctx *ctx, const double *D, double CL, double CR,
                        double *g /* nimg*ny*nx, may be NULL */, double *euler /* [nimg], may be NULL */, float *ms);
 int deff_sensitivity(deff_ctx *ctx, double *g, double *euler, float *ms);
 int deff_device_sensitivity(deff_ctx *ctx, void **d_g, size_t *row_pitch_bytes);
+/* ---- field adjoint: dL/dD for ANY loss L(x) on the concentration field, one adjoint solve and one pass (nothing like it in
+ * the reference).  The system is A(D) x = b(D) with A symmetric, so for w = dL/dx the adjoint system is the same matrix:
+ * A lambda = w with homogeneous walls, and dL/dD[p] = -lambda^T (dA/dD[p] x - db/dD[p]), a face-wise pass over (x, lambda, D).
+ *
+ * deff_solve_adjoint: A lambda = w on the context's CURRENT matrix; lambda goes into a buffer of the context's own.
+ *   Reads: the system (its coefficient planes; a native 2- / 3-phase system's are built from its image first, as under the
+ *   tuning key "cg_planes" 2) and w[nimg*ny*nx] on the host, true width.  Needs neither a field nor wall diffusivities.
+ *   The iteration is deff_solve_cg's on the coefficient planes, whatever "cg_planes" and "cg_onchip" are set to ("cg_fold"
+ *   applies as it does to that form): the same work items, recurrence and summation order, the same stop on the device
+ *   (||r|| <= rtol ||w'||), the same true-residual rounds and restart limit, results independent of check_every.  The guess
+ *   is always lambda = 0.  Which cells are decoupled is decided by the FORWARD system (four zero links and forward b == 0):
+ *   there w is ignored (w' = 0) and lambda = 0; everywhere else w' = w.  An image with ||w'|| = 0 returns at once: iters 0,
+ *   rel_residual 0, converged 1, lambda = 0.  out[k].rel_residual = ||w' - A lambda|| / ||w'|| recomputed from lambda,
+ *   out[k].deff_raw is 0.0 (lambda has no flux), loop_ms as in deff_solve_cg.  Non-finite w: unspecified values, never a fault.
+ *   Writes: lambda, w', the CG work vectors, the upload scratch and the "cg_*" plan keys ("cg_impl" 3).  Left as they are: the
+ *   field and which buffer holds it, b and every other coefficient plane, the row dictionary, the Jacobi plans and tuning,
+ *   the sensitivity map and the events the solve loops time themselves with.
+ *   Refusals, each changing nothing: NULL ctx / w / out, rtol negative or not finite, max_iter < 0, check_every < 1, a row-slab
+ *   context, an explicit-only system (a wall link into the neighbouring row), a system that is not admissible or not symmetric
+ *   (deff_solve_cg's verdict on the forward planes): DEFF_EINVAL; no system: DEFF_ESTATE.
+ * The adjoint field's lifetime: deff_solve_adjoint and deff_set_adjoint make it valid; every call that replaces the system or
+ *   the image (the deff_assemble_* calls, deff_set_system, deff_set_image, deff_synth_image, deff_solve_stream,
+ *   deff_solve_cg_stream) invalidates it.  While it is invalid deff_get_adjoint, deff_device_adjoint and deff_field_vjp_D
+ *   return DEFF_ESTATE.
+ * deff_set_adjoint: lam[nimg*ny*nx] (host, true width) becomes the adjoint field -- a caller's own lambda.  deff_get_adjoint:
+ *   the adjoint field back.  deff_device_adjoint: its device buffer, row pitch as deff_device_field (the pad column of an odd
+ *   width holds 0); valid until the context is destroyed, its contents until the next deff_solve_adjoint / deff_set_adjoint.
+ *   NULL arguments and row-slab contexts: DEFF_EINVAL.
+ *
+ * deff_field_vjp_D: g[p] = dL/dD[p] from the current field x, the current lambda and D, in one pass.  With dx, dy of deff_mesh,
+ * wx = dy / dx, wy = dx / dy, ww = dy / (dx / 2.0), x and l (lambda) of cell p and of its neighbour q:
+ *   interior face of p towards q (weight w = wx for W / E, wy for N / S):
+ *       s = Dp + Dq;  t = (s == 0) ? 0 : Dq / s;  e = xp - xq;  f = lp - lq;  c = (2.0 * (t * t)) * (w * (e * f))
+ *   left / right wall:  e = xp - CL (CR);  f = lp;  c = ww * (e * f)          no face (first / last row of an image):  c = +0.0
+ *   g[p] = -(((cW + cE) + cN) + cS),   and g[p] = 0 where D[p] == 0.
+ * These doubles, in this order (tests/field_vjp_model.py states them in numpy; the library is built without contraction).
+ * euler[k] = sum over image k of D[p] * g[p]: A and b are homogeneous of degree 1 in D, so x is of degree 0 and the sum is
+ * -lambda^T (A x - b) = 0 for a converged x, whatever lambda is -- a check that needs no reference.  It is a wave-level
+ * reduction in a fixed order (csrc/kernels_vjp.hpp), the same bits on every call.  g (nimg*ny*nx, true width) and euler
+ * ([nimg]) may each be NULL; *ms (may be NULL) = device time of the pass, on an event pair of its own.
+ *   D[nimg*ny*nx] on the host, as deff_sensitivity_D takes it.  CR == CL is allowed (nothing is divided by it).
+ *   Plain and stack contexts; row slabs: DEFF_EINVAL; NULL ctx or D: DEFF_EINVAL; no field, or no valid lambda: DEFF_ESTATE.
+ *   Pending work is settled first and every image's newest field is read.  The call writes only its own map, its partial sums
+ *   and the upload scratch; a refused call leaves the previous map alone.  Negative or non-finite D: unspecified values,
+ *   never a fault.
+ * Tuning "vjp_kt": tiles of 8 rows one wave streams through (0 = the planner's choice -- the gradient pass's planner --, values
+ * above the image's tile rows are clipped); deff_get_plan "vjp_kt" / "vjp_items": what the last call used, and the partial sums
+ * added per image (strips of 128 columns x ceil(tile rows / vjp_kt)).
+ * deff_device_field_vjp: the device buffer of the last map (row pitch as deff_device_field), valid until the next
+ * deff_field_vjp_D or deff_destroy; DEFF_ESTATE before one exists. */
+int deff_solve_adjoint(deff_ctx *ctx, const double *w /* nimg*ny*nx, host, true width */, double rtol, int64_t max_iter,
+                       int64_t check_every, deff_cg_result *out /* [nimg] */);
+int deff_set_adjoint(deff_ctx *ctx, const double *lam);
+int deff_get_adjoint(deff_ctx *ctx, double *lam);
+int deff_device_adjoint(deff_ctx *ctx, void **d_lam, size_t *row_pitch_bytes);
+int deff_field_vjp_D(deff_ctx *ctx, const double *D, double CL, double CR,
+                     double *g /* nimg*ny*nx, may be NULL */, double *euler /* [nimg], may be NULL */, float *ms);
+int deff_device_field_vjp(deff_ctx *ctx, void **d_g, size_t *row_pitch_bytes);
 /* sweep-kernel launches issued by the last deff_sweeps()/deff_solve() and the sweeps one
  * temporally blocked launch performs (1 for the single-sweep kernels).  A chained launch of the streaming kernel
  * (deff_get_plan "tb_chain" = 1: several passes of *sweeps_per_pass sweeps in one launch) counts its PASSES, so that
