@@ -137,6 +137,176 @@ def test_adjoint_solve_equals_twin_forward_solve(pkg, nimg, nx, ny):
         print(f"adjoint twin {nimg} x {nx}x{ny}: {[r.iters for r in rb]} iterations, rel {[r.rel_residual for r in rb]}")
 
 
+def _twin_solve(pkg, nx, ny, A, wp, D, CL, CR, **kw):
+    """A fresh one-image context that solves A lambda = w' as a forward system on the planes from a zero field, unfolded ->
+    ((iters, rel_residual, converged), field)."""
+    with pkg.Solver(nx, ny) as b:
+        b.set_system(A, np.ascontiguousarray(wp).ravel(), D, CL, CR)
+        b.set_tuning("cg_planes", 2)
+        b.set_field(np.zeros((ny, nx)))
+        r = b.solve_cg(**kw)
+        assert b.plan_value("cg_impl") == 3 and b.plan_value("cg_fold") == 0
+        return (r.iters, r.rel_residual, r.converged), b.get_field()
+
+
+def test_adjoint_solve_on_a_stack_with_images_that_have_nothing_to_solve(pkg):
+    """"An image with ||w'|| = 0 returns at once" while the others iterate: on a stack of 3, image 1 has w = 0 and image 2 has
+    w != 0 only where the forward system decouples the cell (so w' = 0 although w is not).  Both report iters 0, residual 0,
+    converged, lambda = 0; image 0 is solved as if it were alone -- its twin's bits -- under cg_fold 0 and 1."""
+    nimg, nx, ny = 3, 33, 20
+    CL, CR = 2.0, -1.0
+    rng = np.random.default_rng(33203)
+    _, D = make_case(nx, ny, nimg, CL, CR, 5)
+    D2 = D.reshape(nimg * ny, nx)
+    with pkg.Solver(nx, ny, nimg=nimg) as a:
+        a.assemble_from_D(D2, CL, CR)
+        Am, bm = a.get_system()
+        dec = decoupled_of(Am, bm).reshape(nimg, ny, nx)
+        assert dec[2].any() and not dec[2].all()
+        w = np.zeros((nimg, ny, nx))
+        w[0] = rng.standard_normal((ny, nx))
+        w[2][dec[2]] = rng.standard_normal(int(dec[2].sum())) + 3.0
+        assert w[2].any()
+        n = nx * ny
+        want, twin = _twin_solve(pkg, nx, ny, Am[:n], np.where(dec[0], 0.0, w[0]), D[0], CL, CR, rtol=1e-11)
+        assert want[2] and want[0] > 10, want
+        for fold in (0, 1):
+            a.set_adjoint(np.ones((nimg * ny, nx)))          # (whatever lambda was before, a finished image holds 0)
+            a.set_tuning("cg_fold", fold)
+            r = a.solve_adjoint(w.reshape(nimg * ny, nx), rtol=1e-11)
+            lam = a.get_adjoint().reshape(nimg, ny, nx)
+            assert a.plan_value("cg_fold") == fold
+            for k in (1, 2):
+                assert (r[k].iters, r[k].rel_residual, r[k].converged, r[k].deff_raw) == (0, 0.0, True, 0.0), (fold, k, r[k].iters)
+                assert not lam[k].any(), (fold, k)
+            assert (r[0].iters, r[0].rel_residual, r[0].converged) == want, (fold, r[0].iters, r[0].rel_residual, want)
+            bad = np.argwhere(lam[0] != twin)
+            assert bad.size == 0, (fold, len(bad), bad[:5].tolist())
+
+
+@pytest.mark.parametrize("max_iter", [0, 3])
+@pytest.mark.parametrize("nimg,nx,ny", [(1, 130, 71), (3, 33, 20)])
+def test_a_partial_lambda_is_the_twins_and_valid(pkg, nimg, nx, ny, max_iter):
+    """max_iter 0 and 3: lambda is what that many iterations leave -- the twin's bits, iterations and residual, image by image
+    --, it is not converged, and it is valid all the same: deff_get_adjoint returns it and deff_field_vjp_D takes it (the
+    model's map of the field and that lambda)."""
+    CL, CR = 0.0, 1.0
+    rng = np.random.default_rng(nx + max_iter)
+    x, D = make_case(nx, ny, nimg, CL, CR, nx)
+    D2 = D.reshape(nimg * ny, nx)
+    w = rng.standard_normal((nimg, ny, nx))
+    n = nx * ny
+    with pkg.Solver(nx, ny, nimg=nimg) as a:
+        a.assemble_from_D(D2, CL, CR)
+        a.set_field(x.reshape(nimg * ny, nx))
+        Am, bm = a.get_system()
+        dec = decoupled_of(Am, bm).reshape(nimg, ny, nx)
+        r = a.solve_adjoint(w.reshape(nimg * ny, nx), rtol=1e-11, max_iter=max_iter)
+        r = r if isinstance(r, list) else [r]
+        lam = a.get_adjoint().reshape(nimg, ny, nx)
+        g, _ = a.field_vjp(D2, CL, CR)
+        g = g.reshape(nimg, ny, nx)
+        assert np.array_equal(a.get_adjoint().reshape(nimg, ny, nx), lam)
+        for k in range(nimg):
+            want, twin = _twin_solve(pkg, nx, ny, Am[k * n:(k + 1) * n], np.where(dec[k], 0.0, w[k]), D[k], CL, CR, rtol=1e-11,
+                                     max_iter=max_iter)
+            assert (r[k].iters, r[k].rel_residual, r[k].converged) == want, (k, r[k].iters, r[k].rel_residual, want)
+            assert r[k].iters == max_iter and not r[k].converged and r[k].rel_residual > 1e-11, (k, r[k].iters, r[k].rel_residual)
+            assert np.array_equal(lam[k], twin), k
+            assert lam[k].any() == (max_iter > 0)
+            assert np.array_equal(g[k], model(x[k], lam[k], D[k], CL, CR)[0]), k
+
+
+@pytest.mark.parametrize("nx,ny", [(130, 71), (33, 20)])
+def test_an_active_row_without_links_counts(pkg, oracle, nx, ny):
+    """The forward system decides which cells are decoupled: four zero links AND b == 0.  A cell of a caller's system with four
+    zero links, A0 > 0 and b != 0 (its neighbours' links to it 0 as well: the matrix stays symmetric) is active, so its w
+    counts: lambda there solves its own row, A0 lambda = w, and the whole lambda meets the honest-residual bar of
+    test_gpu_cg.py::assert_honest.  Bar of the one row: its residual is one entry of r, so |w - A0 lambda| <= ||r|| <= that bar
+    times ||w'||."""
+    from test_cg_host import residual_np
+    CL, CR = 0.0, 1.0
+    rtol = 1e-11
+    rng = np.random.default_rng(nx)
+    D = np.exp(rng.standard_normal((ny, nx)))
+    A, b = oracle.discretize(D, CL, CR)
+    A = A.copy().reshape(ny, nx, 5)                          # P, W, E, S (row + 1), N (row - 1)
+    b = b.copy().reshape(ny, nx)
+    i, j = ny // 2, 128 if nx > 129 else nx // 2             # (column 128: its W neighbour lies across a 128-column seam)
+    A[i, j] = (2.5, 0.0, 0.0, 0.0, 0.0)
+    b[i, j] = 0.75
+    A[i, j - 1, 2] = A[i, j + 1, 1] = A[i - 1, j, 3] = A[i + 1, j, 4] = 0.0
+    A, b = A.reshape(-1, 5), b.ravel()
+    dec = decoupled_of(A, b).reshape(ny, nx)
+    assert not dec.any()
+    w = rng.standard_normal((ny, nx))
+    with pkg.Solver(nx, ny) as s:
+        s.set_system(A, b, D, CL, CR)
+        r = s.solve_adjoint(w, rtol=rtol)
+        lam = s.get_adjoint()
+    bar = rtol * (1 + 1e-6) + 1e-13
+    rn = residual_np(A, w.ravel(), lam, nx, ny)
+    own = abs(w[i, j] - 2.5 * lam[i, j]) / float(np.sqrt(np.sum(w * w)))
+    print(f"active row without links {nx}x{ny}: {r.iters} iterations, rel {r.rel_residual:.3e}, host {rn:.3e}, own row {own:.3e}")
+    assert r.converged and r.iters > 10
+    assert rn <= bar, rn
+    assert lam[i, j] != 0.0 and own <= bar, (lam[i, j], w[i, j] / 2.5, own)
+
+
+def test_lifetime_across_streams(pkg, oracle):
+    """deff_amd.h lists both streams among the calls that invalidate lambda, and a refused call changes nothing: on a stack of
+    2, an accepted deff_solve_stream and an accepted deff_solve_cg_stream leave deff_get_adjoint, deff_device_adjoint and
+    deff_field_vjp_D refused (DEFF_ESTATE); a deff_solve_cg_stream refused for Df = -1 and a deff_solve_stream refused under
+    "prescaled" 1 on the explicit kernel leave lambda's bits, and its validity, as they were."""
+    nimg, nx, ny = 2, 33, 20
+    CL, CR = 0.0, 1.0
+    rng = np.random.default_rng(2033)
+    pix = [np.where(rng.random((ny, nx)) < 0.5, 0, 255).astype(np.uint8) for _ in range(nimg)]
+    w = rng.standard_normal((nimg * ny, nx))
+    lam0 = rng.standard_normal((nimg * ny, nx))
+    Dp = np.exp(rng.standard_normal((nimg * ny, nx)))
+
+    def invalid(s):
+        _refused(pkg, s.get_adjoint, -5)
+        _refused(pkg, s.device_adjoint_ptr, -5)
+        _refused(pkg, lambda: s.field_vjp(Dp, CL, CR), -5, "adjoint")
+
+    with pkg.Solver(nx, ny, nimg=nimg) as s:
+        s.set_image(np.stack(pix))
+        s.assemble_2phase(1e-2, 1.0, CL, CR)
+        s.init_linear(CL, CR)
+        s.set_adjoint(lam0)
+        assert np.array_equal(s.get_adjoint(), lam0)
+        res = s.solve_stream(pix + pix[:1], 1e-2, 1.0, CL, CR, 1e-2, 7, check_every=7)
+        assert len(res) == 3
+        invalid(s)
+        r = s.solve_adjoint(w, rtol=1e-9)                    # on the system the stream left in the slots
+        assert all(q.converged for q in r)
+        res = s.solve_cg_stream(pix + pix[:1], 1e-2, 1.0, CL, CR, rtol=1e-6, max_iter=100000)
+        assert len(res) == 3
+        invalid(s)
+        r = s.solve_adjoint(w, rtol=1e-9)
+        assert all(q.converged and q.iters > 0 for q in r)
+        lam = s.get_adjoint()
+        x = s.get_field()
+        g0, e0 = s.field_vjp(Dp, CL, CR)
+        with pytest.raises(pkg.DeffError) as e:
+            s.solve_cg_stream(pix, 1e-2, -1.0, CL, CR, rtol=1e-6, max_iter=10)
+        assert e.value.code == -1 and "admissible" in str(e.value), str(e.value)
+        assert np.array_equal(s.get_adjoint(), lam) and np.array_equal(s.get_field(), x)
+        s.set_kernel("explicit")
+        s.set_tuning("prescaled", 1)
+        with pytest.raises(pkg.DeffError) as e:
+            s.solve_stream(pix, 1e-2, 1.0, CL, CR, 1e-2, 7, check_every=7)
+        assert e.value.code == -1 and "prescaled" in str(e.value), str(e.value)
+        assert np.array_equal(s.get_adjoint(), lam) and np.array_equal(s.get_field(), x)
+        p, pitch = s.device_adjoint_ptr()
+        dev = device_rows(p, nimg * ny, pitch)
+        assert pitch == 8 * (nx + 1) and np.array_equal(dev[:, :nx], lam) and np.all(dev[:, nx] == 0.0)
+        g1, e1 = s.field_vjp(Dp, CL, CR)
+        assert np.array_equal(g1, g0) and np.array_equal(e1, e0)
+
+
 # ---- against the direct solves, and end to end ---------------------------------------------------------------------------
 
 @functools.lru_cache(maxsize=None)

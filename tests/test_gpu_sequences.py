@@ -117,6 +117,11 @@ ASSEMBLE_C = [(0.0, 1.0), (0.25, 0.75)]
 #   cgstream  deff_solve_cg_stream of B ... 3B+1 images on a stack (B >= 2); about one in four is asked with Df = -1 and refused
 #   sens      deff_sensitivity / deff_sensitivity_D of the current field
 #   prescaled the key "prescaled" (never with fma or stamps: the pre-scaled sweeps ignore the one and have no stamped form)
+#   adjoint   the field adjoint: "adj" (deff_solve_adjoint: refused on "Sw"; small max_iter leaves a partial lambda, which is
+#             valid all the same; on a stack about one call in four has w = 0 on one image), "setadj" (deff_set_adjoint),
+#             "getadj" (deff_get_adjoint + deff_device_adjoint) and "vjp" (deff_field_vjp_D on the model's planes or on a drawn
+#             plane with zero cells, walls drawn anew, + deff_device_field_vjp; also the first reader of some solves).  The draw
+#             follows one more fact: whether lambda is valid -- deff_amd.h's lifetime rule applied to the ops drawn so far
 
 # (key, values) pairs the tune draw gains per option; "cg keys" sets both CG keys in one draw, "prescaled" mostly toggles
 TUNE_EXTRA = dict(native3=[("fill_impl", [0, 1, 2])] * 3 + [("fill_tile_rows", [0, 8, 16])] * 4,
@@ -128,7 +133,7 @@ CG_PLANES_DRAW, CG_FOLD_DRAW = [0, 0, 1, 2], [0, 1, 1, 2, 2]
 
 def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30, onchip=False, stream=False, ptr=False,
                   slot=False, stamps=False, fma=False, native3=False, system=False, cgkeys=False, cgstream=False, sens=False,
-                  prescaled=False):
+                  prescaled=False, adjoint=False):
     """Generator of (op, arguments...) tuples; the first is ("open", nx, ny, B, fma) and the second the first image."""
     assert not (fma and with_cg)                             # CG's arithmetic has no contracted form to compare with
     assert not (prescaled and (fma or stamps))
@@ -145,6 +150,10 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
     refused_on_3n = False                                    # the last call was a refused CG stream on a native 3-phase system
     after_stream = False                                     # a stream filled the slots and no assembly has followed
     pre_swept = False                                        # the current system has been swept under "prescaled" 1
+    lam_valid = lam_lost = False                             # the adjoint field: valid / was valid and an invalidator has just run
+    adj_since = False                                        # an adjoint solve has run on the current system
+    refused_last = False                                     # the op before was refused (as far as the draw can know)
+    tb_keys = {"tb_impl": 0, "tb_launch": 0}                 # (followed under `adjoint` only: towards resident tiles)
     sw = "Sw" if nx % 2 == 0 else "S"                        # (an odd width cannot represent a wall-column link: refused)
     kinds = ["2p", "2p", "3p", "D"] + (["3n", "3n", "3g"] if native3 else []) + (["S", sw, sw] if system else [])
     extra = [kv for name, on in (("native3", native3), ("cgkeys", cgkeys), ("prescaled", prescaled), ("sens", sens)) if on for kv in TUNE_EXTRA[name]]
@@ -193,9 +202,55 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
                 ops += ["getsys"] * 8
         if prescaled and have_x and kind is not None:
             ops += ["sweeps"] * (8 if pre_swept and not pre else 3) + (["prescaled"] * 5 if prev == "sweeps" and pre else [])
+        if adjoint:
+            tb2 = (tb_keys["tb_impl"], tb_keys["tb_launch"]) == (2, 0) and kset in ("auto", "matfree_tb") and kind != "Sw"
+            # The adjoint's ops and the weights of the orders they are drawn for (A1 ... A8 in test_sequences_host.py).  The reads
+            # are offered at a low weight whatever the state (refused while lambda is invalid or no field exists) and at a high
+            # one right after an invalidator took a valid lambda away, or after a refused call left one in place.
+            ops += ["getadj", "vjp"] + (["getadj"] * 10 + ["vjp"] * 10 if lam_lost else [])
+            if kind is not None:
+                ops += ["adj", "adj", "setadj", "tune", "tune", "tune"]
+                if kind in ("2p", "3n"):                     # (the first call that needs a native system's planes, then a read of them)
+                    ops += ["getsys"] * 6 if adj_since else ["adj"] * 8
+                if kind == "Sw":                             # (refused: an explicit-only system; with a caller's lambda in place)
+                    ops += ["adj"] * 30 if lam_valid else ["setadj"] * 20 + ["adj"] * 10
+                if prev == "setadj":
+                    ops += ["adj"] * 14
+                if prev == "adj":                            # (then CG, in whichever form "cgform" has just chosen)
+                    ops += ["setadj"] * 20 + (["cg"] * 10 + ["cgform"] * 40 if have_x else [])
+                if (prev2, prev) == ("adj", "cgform") and have_x:
+                    ops += ["cg"] * 100
+                if prev == "cg":
+                    ops += ["adj"] * 10
+                if (prev2, prev) == ("cg", "adj") and have_x:
+                    ops += ["cg"] * 40
+                if tb2 and have_x and prev != "sweeps":
+                    ops += ["sweeps"] * 8
+                if prev == "sweeps":
+                    ops += (["adj"] * 10 + (["vjp"] * 10 if lam_valid else [])) * (3 if tb2 else 1)
+                if prev2 == "sweeps" and prev in ("adj", "vjp") and have_x:
+                    ops += ["solve"] * (60 if tb2 else 10)   # (inside a resident interval that no check has settled)
+                if lam_valid:
+                    ops += ["getadj"] * 2 + (["vjp"] * 2 if have_x else [])
+                    if refused_last or (prev == "cg" and prev2 in ("adj", "cgform")):
+                        ops += ["getadj"] * 60
+                    if (prev2, prev) == ("adj", "setadj") and have_x:
+                        ops += ["vjp"] * 60
+                    if have_x and prev == "vjp" and sens:
+                        ops += ["sens"] * 14
+                    if have_x and prev == "sens":
+                        ops += ["vjp"] * 16
+                    if have_x and prev == "solve" and B >= 2:
+                        ops += ["solve"] * 2                 # (a stack's solve whose first reader may be the pass)
+                    # the invalidators that even weights would leave rare while a lambda is there to lose
+                    ops += (["stream"] * 2 if stream and B >= 2 else []) + (["cgstream"] * 5 if cgstream and B >= 2 else [])
+                    ops += ["stage"] * 24 if native3 and kind == "3n" else []
         op = ops[rng.integers(len(ops))]
         prev2, prev = prev, op
         refused_on_3n = False
+        refused_last = False
+        if op in ("image", "assemble", "stage"):             # (a new image or system: lambda was the old one's)
+            lam_lost, lam_valid, adj_since = lam_lost or lam_valid, False, False
         if op == "image":
             yield ("image", draw_images(rng, nx, ny, B))
             kind, fill, after_stream, pre_swept = None, False, False, False
@@ -203,6 +258,8 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             more = (["3n"] * 4 if (fill and kind != "3n") or (native3 and after_stream) else []) + (["2p"] * 4 if kind == "Sw" else [])
             if fill and kind == "3n":
                 more = [k for k in kinds if k != "3n"]       # (another kind on the filled image, then "3n" again)
+            if adjoint and system and sw == "Sw" and kind != "Sw":
+                more = more + ["Sw"] * 3                     # (the system the adjoint solve refuses)
             kind = (kinds + more)[rng.integers(len(kinds) + len(more))]
             Ds, Df, Dg = ASSEMBLE_D[rng.integers(3)]
             CL, CR = ASSEMBLE_C[rng.integers(2)]
@@ -227,11 +284,13 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             rtol = float(rng.choice([1e-6, 1e-10]))
             max_iter = int(rng.choice([3, 100000, 100000]))
             ce = int(rng.choice([1, 64]))
-            refused = bool(rng.random() < (0.5 if kind == "3n" else 0.2))       # (about one in four over a group)
+            refused = bool(rng.random() < (0.5 if kind == "3n" or (adjoint and lam_valid) else 0.2))       # (about one in four over a group)
             yield ("cgstream", imgs, Ds, -1.0 if refused else Df, CL, CR, rtol, max_iter, ce)
             if not refused:
                 kind, have_x, fill, after_stream = "2p", True, False, True
+                lam_lost, lam_valid, adj_since = lam_lost or lam_valid, False, False
             refused_on_3n = refused and kind == "3n"
+            refused_last = refused
         elif op == "prescaled":
             pre = 1 - pre
             yield ("tune", "prescaled", pre)
@@ -246,13 +305,18 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
                     pre = 1 - pre if rng.random() < 0.8 else pre
                     yield ("tune", "prescaled", pre)
                 else:
-                    yield ("tune", key, int(rng.choice(values)))
+                    v = int(rng.choice(values))
+                    if key in tb_keys:
+                        tb_keys[key] = v
+                    yield ("tune", key, v)
             elif what == 0:
                 yield ("tune", "tb_T", int(rng.choice([0, 2, 4, 8])))
             elif what == 1:
-                yield ("tune", "tb_impl", int(rng.choice([0, 1, 2])))
+                tb_keys["tb_impl"] = int(rng.choice([0, 1, 2]))
+                yield ("tune", "tb_impl", tb_keys["tb_impl"])
             elif what == 2:
-                yield ("tune", "tb_launch", int(rng.choice([0, 1])))
+                tb_keys["tb_launch"] = int(rng.choice([0, 1]))
+                yield ("tune", "tb_launch", tb_keys["tb_launch"])
             elif what == 3:
                 yield ("tune", "flux_reduce", int(rng.choice([0, 1])))
             elif what == 4:
@@ -280,11 +344,53 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             # other two take its place in some solves: deff_device_field (consolidates itself) and deff_get_slot_field of
             # every slot (reads each slot where it froze and leaves the stack as it is for the next call)
             readers = ["get"] + (["ptr"] if ptr else []) + (["slot"] if slot else [])
+            if adjoint and lam_valid:                        # ... and deff_field_vjp_D, which consolidates itself
+                readers += ["vjp"] * 8
             yield ("solve", tol, max_iter, ce, readers[rng.integers(len(readers))] if len(readers) > 1 else "get")
         elif op == "cg":
             rtol = float(rng.choice([1e-6, 1e-10]))
             max_iter = int(rng.choice([0, 3, 100000]))
             yield ("cg", rtol, max_iter, int(rng.choice([1, 64])))
+            refused_last = kind == "Sw"
+        elif op == "adj":
+            rtol = float(rng.choice([1e-6, 1e-10]))
+            max_iter = int(rng.choice([0, 3, 100000, 100000]))
+            ce = int(rng.choice([1, 64]))
+            w = [rng.standard_normal((ny, nx)) for _ in range(B)]
+            if B >= 2 and rng.random() < 0.25:               # one image of the stack has nothing to solve
+                w[int(rng.integers(B))][:] = 0.0
+            yield ("adj", w, rtol, max_iter, ce)
+            if kind == "Sw":
+                refused_last = True                          # (an explicit-only system; lambda stays what it was)
+            else:
+                lam_valid, lam_lost, adj_since = True, False, True
+        elif op == "cgform":                                 # the keys of one of CG's three forms, set together
+            # (on chip where the system surely has a dictionary; elsewhere the form that never needs one is likelier)
+            form = int(rng.choice([0, 1, 1, 1, 2] if kind in ("2p", "3n") else [0, 1, 2, 2]))
+            yield ("tune", "cg_onchip", 1 if form == 1 else 0)
+            yield ("tune", "cg_planes", 2 if form == 2 else 0)
+            yield ("tune", "cg_fold", int(rng.choice(CG_FOLD_DRAW)))
+        elif op == "setadj":
+            yield ("setadj", [rng.standard_normal((ny, nx)) for _ in range(B)])
+            lam_valid, lam_lost = True, False
+        elif op == "getadj":
+            yield ("getadj",)
+            lam_lost = False
+        elif op == "vjp":
+            # the model's planes, or a plane of the caller's with zero cells; the walls are drawn independently of the system's
+            own = kind is None or bool(rng.random() < 1.0 / 3.0)
+            CL, CR = ASSEMBLE_C[rng.integers(2)]
+            D = None
+            if own:
+                Ds, Df, Dg = ASSEMBLE_D[rng.integers(3)]
+                D = draw_D_planes(rng, nx, ny, B, Ds, Df, Dg)
+                for plane in D:
+                    plane[rng.random((ny, nx)) < 0.05] = 0.0
+            yield ("vjp", D, CL, CR)
+            lam_lost = False
+        elif op == "sens":
+            yield ("sens",)
+            refused_last = kind in ("3n", "3g")              # (the form without D is refused for a Grid system, then D is given)
         elif op == "stream":
             count = int(rng.integers(B, 3 * B + 2))
             imgs = draw_images(rng, nx, ny, count)
@@ -295,6 +401,7 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             yield ("stream", imgs, Ds, Df, CL, CR, tol, max_iter, int(rng.choice(SOLVE_CE)))
             if not (pre and kset == "explicit"):             # (refused before anything changes: no pre-scaled explicit sweeps)
                 kind, have_x, fill, after_stream = "2p", True, False, True
+                lam_lost, lam_valid, adj_since = lam_lost or lam_valid, False, False
         elif op == "slot":
             yield ("slot", int(rng.integers(B)))
         elif op == "stamps":
@@ -404,6 +511,13 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
         import sensitivity_model as sens_model
     if options.get("prescaled"):
         import prescaled_model as pre_model
+    adjoint = bool(options.get("adjoint"))
+    if adjoint:
+        import field_vjp_model as vjp_model
+        from test_cg_host import decoupled_of
+    # the adjoint's side of the model: lambda per image as the context last returned or took it, whether deff_amd.h's lifetime
+    # rule says it is valid, and the device buffers of the last pass and of the last gradient as they read when they were made
+    m.lam, m.lam_valid, m.vjp_dev, m.sens_dev = None, False, None, None
 
     def distinct_rows():
         return len(np.unique(np.column_stack([np.concatenate(m.A), np.concatenate(m.b)]), axis=0))
@@ -422,6 +536,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 log[-1] += " refused"
                 if m.x is not None:
                     fields_equal()
+                lam_unchanged()
                 return True
             assert not refuse, (seed, log, "a pre-scaled call that should have been refused")
             assert s.plan_value("prescaled") == 1, (seed, log)
@@ -456,6 +571,63 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
             _capi.check(_capi.load().deff_get_slot_field(s._ctx, k, x))
             assert np.array_equal(x, m.x[k]), (seed, log, "field of slot %d" % k)
 
+        def lam_unchanged():
+            """After a call that must leave lambda alone (a refusal, the pass): deff_get_adjoint returns the same bits."""
+            if adjoint and m.lam_valid:
+                got = s.get_adjoint()
+                for k in range(B):
+                    assert np.array_equal(got[k * ny:(k + 1) * ny], m.lam[k]), (seed, log, "lambda of image %d" % k)
+
+        def maps_unchanged(vjp=True, sens=True):
+            """The device buffers of the last pass and of the last gradient read as they did when they were written."""
+            if vjp and m.vjp_dev is not None:
+                p, pitch = s.device_field_vjp_ptr()
+                assert np.array_equal(device_rows(p, B * ny, pitch), m.vjp_dev), (seed, log, "the pass's device map")
+            if sens and m.sens_dev is not None:
+                p, pitch = s.device_sensitivity_ptr()
+                assert np.array_equal(device_rows(p, B * ny, pitch), m.sens_dev), (seed, log, "the gradient's device map")
+
+        def lam_invalidated():
+            m.lam_valid, m.sens_dev = False, None            # (deff_device_sensitivity: "valid until ... an assembly")
+
+        def adjoint_refused(*calls):
+            """While lambda is invalid (or no field exists, for the pass): DEFF_ESTATE, and nothing else changes."""
+            for call in calls:
+                with pytest.raises(pkg.DeffError) as e:
+                    call()
+                assert e.value.code == -5, (seed, log, e.value)
+            log[-1] += " refused"
+            if m.x is not None:
+                fields_equal()
+            maps_unchanged()
+            lam_unchanged()
+
+        def field_vjp_checked(D, CL, CR):
+            """deff_field_vjp_D of the model's field and lambda against tests/field_vjp_model.py: host copy, device map, pad
+            column, Euler sums (check_map's bar in test_gpu_field_vjp.py); the field, lambda and the gradient's map stay."""
+            planes = m.D if D is None else D
+            if not (m.lam_valid and m.x is not None):
+                adjoint_refused(lambda: s.field_vjp(m.stacked(planes), CL, CR))
+                return
+            g, euler = s.field_vjp(m.stacked(planes), CL, CR)
+            g, euler = g.reshape(B, ny, nx), np.atleast_1d(euler)
+            p, pitch = s.device_field_vjp_ptr()
+            assert pitch == 8 * (nx + (nx & 1)), (seed, log, pitch)
+            dev = device_rows(p, B * ny, pitch)
+            for k in range(B):
+                want, want_euler = vjp_model.field_vjp(m.x[k], m.lam[k], planes[k], CL, CR)
+                assert np.array_equal(g[k], want), (seed, log, "field vjp of image %d" % k, np.argwhere(g[k] != want)[:4].tolist())
+                assert np.array_equal(dev[k * ny:(k + 1) * ny, :nx], want), (seed, log, "device map of the pass, image %d" % k)
+                size = float(np.sum(np.abs(planes[k] * want)))
+                assert euler[k] == float(want_euler) or abs(float(np.longdouble(euler[k]) - want_euler)) <= 1e-13 * size, \
+                    (seed, log, k, euler[k], want_euler, size)
+            if nx & 1:
+                assert np.array_equal(dev[:, nx], np.zeros(B * ny)), (seed, log, "pad column of the pass's map")
+            m.vjp_dev = dev
+            maps_unchanged(vjp=False)
+            fields_equal()
+            lam_unchanged()
+
         if use_fma:
             s.set_tuning("fma", 1)
             log.append("fma 1")
@@ -464,12 +636,14 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
         for op, *args in draw:
             if op == "image":
                 m.pix, m.kind, m.fill_fresh = args[0], None, False
+                lam_invalidated()
                 s.set_image(np.stack(m.pix))
                 log.append("image")
             elif op == "assemble":
                 kind, Ds, Df, Dg, CL, CR, D, *base = args
                 m.assemble(kind, Ds, Df, Dg, CL, CR, D, *base)
                 m.phases = (Ds, Df, Dg)
+                lam_invalidated()
                 log.append(f"assemble {kind} {Ds} {Df} {CL}")
                 if kind == "2p":
                     s.assemble_2phase(Ds, Df, CL, CR)
@@ -499,6 +673,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 log.append(f"stage {Ds} {Df} {Dg} {CL}")
                 m.assemble("3n", Ds, Df, Dg, CL, CR)
                 m.phases = (Ds, Df, Dg)
+                lam_invalidated()
                 s.assemble_3phase_native(Ds, Df, Dg, CL, CR)
                 native_counters()
             elif op == "grid":
@@ -575,6 +750,9 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                     log[-1] += " then slots"
                     for k in range(B):
                         slot_field_equal(k)
+                elif reader == "vjp":                        # (the pass consolidates the frozen images itself)
+                    log[-1] += " then vjp"
+                    field_vjp_checked(None, m.CL, m.CR)
                 else:
                     fields_equal()
             elif op == "cg":
@@ -595,6 +773,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                         assert e.code == -1 and "no row dictionary" in str(e) and rows > 511 and planes_key == 0, (seed, log, e, rows)
                     log[-1] += " refused"
                     fields_equal()
+                    lam_unchanged()
                     continue
                 assert m.kind != "Sw", (seed, log, "CG ran on an explicit-only system")
                 has_dict = True
@@ -694,6 +873,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 else:
                     res = s.solve_stream(imgs, Ds, Df, CL, CR, tol, max_iter, check_every=ce, want_fields=True)
                 m.fill_fresh = False
+                lam_invalidated()
                 assert len(res) == len(imgs)
                 want = []
                 for i, pix in enumerate(imgs):
@@ -725,6 +905,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                     with pytest.raises(pkg.DeffError) as e:
                         s.sensitivity()
                     assert e.value.code == -1 and "Grid" in str(e.value), (seed, log, e.value)
+                    lam_unchanged()
                 g, euler = s.sensitivity() if m.kind in ("2p", "3p") else s.sensitivity(m.stacked(m.D), m.CL, m.CR)
                 g, euler = g.reshape(B, ny, nx), np.atleast_1d(euler)
                 p, pitch = s.device_sensitivity_ptr()
@@ -733,10 +914,14 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 for k in range(B):
                     want, want_euler = sens_model.sensitivity(m.x[k], m.D[k], m.CL, m.CR)
                     assert np.array_equal(g[k], want), (seed, log, "sensitivity of image %d" % k)
-                    assert abs(float(np.longdouble(euler[k]) - want_euler)) <= 1e-13 * abs(float(want_euler)), (seed, log, k, euler[k], want_euler)
+                    # (a field that CG blew up on a system with b = 0 overflows both sums alike: inf - inf is no distance)
+                    assert euler[k] == float(want_euler) or \
+                        abs(float(np.longdouble(euler[k]) - want_euler)) <= 1e-13 * abs(float(want_euler)), (seed, log, k, euler[k], want_euler)
                     assert np.array_equal(dev[k * ny:(k + 1) * ny, :nx], want), (seed, log, "device map of image %d" % k)
                 if nx & 1:
                     assert np.array_equal(dev[:, nx], np.zeros(B * ny)), (seed, log, "pad column of the map")
+                m.sens_dev = dev
+                maps_unchanged(sens=False)                   # (the gradient writes its own map, not the pass's)
             elif op == "cgstream":
                 # deff_solve_cg_stream: every image is solved from the linear guess "exactly as a one-image deff_solve_cg call
                 # would" (deff_amd.h) -- compared with that call on a fresh one-image context under the same cg_onchip key --
@@ -755,9 +940,11 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                             assert s.plan_value("fill_runs") == m.fill_count, (seed, log)
                     if m.x is not None:
                         fields_equal()
+                    lam_unchanged()
                     continue
                 res = s.solve_cg_stream(imgs, Ds, Df, CL, CR, rtol=rtol, max_iter=max_iter, check_every=ce, want_fields=True)
                 m.fill_fresh = False
+                lam_invalidated()
                 assert len(res) == len(imgs)
                 assert [r.slot for r in res[:B]] == list(range(B)) and all(0 <= r.slot < B for r in res), (seed, log, [r.slot for r in res])
                 want = []
@@ -788,6 +975,80 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 m.x = [want[last[k]][3] for k in range(B)]
                 m.CL, m.CR, m.kind, m.phases = CL, CR, "2p", (Ds, Df, None)
                 fields_equal()
+            elif op == "adj":
+                # deff_solve_adjoint: every image against a twin -- a fresh one-image context that is given the image's matrix
+                # with w' (w zeroed where the FORWARD system decouples the cell) as its right-hand side and solves it as a
+                # forward system on the planes from a zero field, unfolded, under the OTHER check interval (deff_amd.h: "the
+                # same work items, recurrence and summation order", "results independent of check_every").  The field, the
+                # kernel in use and the Jacobi plan stay; refused on wall-column links, lambda then stays what it was.
+                w, rtol, max_iter, ce = args
+                log.append(f"adj {rtol} {max_iter} {ce}")
+                kernel_before = s.kernel_in_use()
+                tb_before = {k: v for k, v in s.plan().items() if k.startswith("tb_")}
+                if m.kind == "Sw":
+                    with pytest.raises(pkg.DeffError) as e:
+                        s.solve_adjoint(m.stacked(w), rtol=rtol, max_iter=max_iter, check_every=ce)
+                    assert e.value.code == -1 and "wall column" in str(e.value), (seed, log, e.value)
+                    log[-1] += " refused"
+                    if m.x is not None:
+                        fields_equal()
+                    lam_unchanged()
+                    continue
+                res = s.solve_adjoint(m.stacked(w), rtol=rtol, max_iter=max_iter, check_every=ce)
+                res = [res] if B == 1 else res
+                lam = s.get_adjoint()
+                assert s.plan_value("cg_impl") == 3 and s.plan_value("cg_fold") == min(fold_key, 1), (seed, log, fold_key)
+                assert s.kernel_in_use() == kernel_before, (seed, log, kernel_before, s.kernel_in_use())
+                assert {k: v for k, v in s.plan().items() if k.startswith("tb_")} == tb_before, (seed, log, tb_before)
+                m.lam = []
+                for k in range(B):
+                    dec = decoupled_of(m.A[k], m.b[k]).reshape(ny, nx)
+                    wp = np.where(dec, 0.0, w[k])
+                    lk = lam[k * ny:(k + 1) * ny].copy()
+                    got = (res[k].iters, res[k].rel_residual, res[k].converged)
+                    assert np.all(lk[dec] == 0.0) and res[k].deff_raw == 0.0, (seed, log, k)
+                    if not wp.any():
+                        log[-1] += " zero %d" % k
+                        assert got == (0, 0.0, True) and not lk.any(), (seed, log, k, got)
+                    with pkg.Solver(nx, ny) as f:
+                        f.set_tuning("cg_planes", 2)
+                        f.set_tuning("cg_fold", 0)
+                        f.set_system(m.A[k], wp.ravel(), m.D[k], m.CL, m.CR)
+                        f.set_field(np.zeros((ny, nx)))
+                        one = f.solve_cg(rtol=rtol, max_iter=max_iter, check_every=1 if ce == 64 else 64)
+                        assert f.plan_value("cg_impl") == 3 and f.plan_value("cg_fold") == 0, (seed, log)
+                        assert (one.iters, one.rel_residual, one.converged) == got, (seed, log, k, got, (one.iters, one.rel_residual, one.converged))
+                        assert np.array_equal(f.get_field(), lk), (seed, log, "lambda of image %d against its twin" % k)
+                    assert res[k].iters <= max_iter and res[k].converged == (res[k].rel_residual <= rtol), (seed, log, k, got)
+                    if res[k].converged:                     # the bar of test_gpu_cg.py::assert_honest, as for "cg"
+                        rn = residual_np(m.A[k], wp.ravel(), lk, nx, ny)
+                        assert rn <= rtol * (1 + 1e-6) + 1e-13, (seed, log, k, rn)
+                    m.lam.append(lk)
+                m.lam_valid = True
+                log[-1] += " iters %s" % [r.iters for r in res]
+                if m.x is not None:
+                    fields_equal()
+            elif op == "setadj":
+                log.append("setadj")
+                m.lam, m.lam_valid = args[0], True
+                s.set_adjoint(m.stacked(m.lam))
+            elif op == "getadj":
+                log.append("getadj")
+                if not m.lam_valid:
+                    adjoint_refused(s.get_adjoint, s.device_adjoint_ptr)
+                    continue
+                lam_unchanged()
+                p, pitch = s.device_adjoint_ptr()
+                assert pitch == 8 * (nx + (nx & 1)), (seed, log, pitch)
+                dev = device_rows(p, B * ny, pitch)
+                for k in range(B):
+                    assert np.array_equal(dev[k * ny:(k + 1) * ny, :nx], m.lam[k]), (seed, log, "device lambda of image %d" % k)
+                if nx & 1:
+                    assert np.array_equal(dev[:, nx], np.zeros(B * ny)), (seed, log, "pad column of lambda")
+            elif op == "vjp":
+                D, CL, CR = args
+                log.append(f"vjp {'D' if D is not None else 'model'} {CL} {CR}")
+                field_vjp_checked(D, CL, CR)
             elif op == "ptr":
                 log.append("ptr")
                 device_field_equal()
@@ -855,6 +1116,11 @@ CGKEY_SEEDS = dict(first=8000, count=40, with_cg=True, shapes=CGKEY_SHAPES, stac
                    cgstream=True, native3=True, system=True)
 PRESCALED_SEEDS = dict(first=9000, count=40, shapes=NATIVE_SHAPES, stacks=(1, 2, 3), steps=40, prescaled=True, native3=True,
                        system=True, stream=True)
+# ... and the field adjoint, among everything it shares buffers, planes built on demand, scratch and plan keys with: the three CG
+# forms and the CG stream, native and caller's systems, the gradient (whose tune draws lead to resident tiles), streams and
+# the readers of frozen images.
+ADJOINT_SEEDS = dict(first=10000, count=40, with_cg=True, shapes=CGKEY_SHAPES, stacks=(1, 2, 2, 3), steps=40, onchip=True, cgkeys=True,
+                     cgstream=True, native3=True, system=True, sens=True, stream=True, ptr=True, slot=True, adjoint=True)
 
 
 def seed_options(group):
@@ -874,6 +1140,11 @@ def test_random_call_sequences_with_cg_keys_and_cg_streams(pkg, oracle, seed):
 @pytest.mark.parametrize("seed", range(PRESCALED_SEEDS["count"]))
 def test_random_call_sequences_with_prescaled_sweeps(pkg, oracle, seed):
     run_sequence(pkg, oracle, PRESCALED_SEEDS["first"] + seed, **seed_options(PRESCALED_SEEDS))
+
+
+@pytest.mark.parametrize("seed", range(ADJOINT_SEEDS["count"]))
+def test_random_call_sequences_with_the_field_adjoint(pkg, oracle, seed):
+    run_sequence(pkg, oracle, ADJOINT_SEEDS["first"] + seed, **seed_options(ADJOINT_SEEDS))
 
 
 @pytest.mark.parametrize("seed", range(ONCHIP_SEEDS["count"]))

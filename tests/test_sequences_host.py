@@ -11,7 +11,9 @@ for -- an option nobody draws, or a stream nobody reads after, would leave the G
 The seeds of those option groups are pinned in turn (tests/golden/sequence_draws_option_seeds.json, written with draw_log()
 below before the draw gained its later options), and the later groups -- the native 3-phase assembly, a caller's system, the
 Deff gradient, the CG keys and the CG stream, the pre-scaled sweeps -- have a census of their own: every op, kind and key value
-they add, and the call orders they are there for."""
+they add, and the call orders they are there for.  Those three groups are pinned as well
+(tests/golden/sequence_draws_later_seeds.json, recorded before the draw gained `adjoint`, with the images and arguments of
+every stream in the digest and the log), and the field adjoint's group has its census at the end of this file."""
 import hashlib
 import json
 import os
@@ -32,9 +34,12 @@ def seeds_of(group):
     return [(g["first"] + i, seq.seed_options(g)) for i in range(g["count"])]
 
 
-def draw_log(seed, **options):
+def draw_log(seed, every_array=False, **options):
     """The op log run_sequence() writes (without what only a run can add: "refused", the CG form, the stream's early slots, the
-    stamps' sweeps) and the digest of the arrays in the order the solver receives them."""
+    stamps' sweeps) and the digest of the arrays in the order the solver receives them.  The two older golden files were
+    recorded while a "stream" was logged by its name alone and its images were left out of the digest; `every_array` (the
+    later groups' file and every one after it) logs and hashes a stream as a CG stream is, and logs the arguments the older
+    form leaves out (a solve's reader, the slot read, the stamps' omega)."""
     draw = seq.draw_sequence(seed, **options)
     _, nx, ny, B, fma = next(draw)
     h = hashlib.sha1(repr((nx, ny, B)).encode())
@@ -58,12 +63,26 @@ def draw_log(seed, **options):
         elif op == "sweeps":
             log.append(f"sweeps {a[0]} {a[1]:.3f}")
         elif op in ("solve", "cg"):
-            log.append(f"{op} {a[0]} {a[1]} {a[2]}")
+            log.append(f"{op} {a[0]} {a[1]} {a[2]}" + (f" then {a[3]}" if every_array and op == "solve" else ""))
         elif op == "stage":
             log.append(f"stage {a[0]} {a[1]} {a[2]} {a[3]}")
-        elif op == "cgstream":
+        elif op == "cgstream" or (op == "stream" and every_array):
             h.update(np.stack(a[0]).tobytes())
-            log.append(f"cgstream {len(a[0])} {a[1]} {a[2]} {a[3]} {a[5]} {a[6]} {a[7]}")
+            log.append(f"{op} {len(a[0])} {a[1]} {a[2]} {a[3]} {a[5]} {a[6]} {a[7]}")
+        elif op == "slot" and every_array:
+            log.append(f"slot {a[0]}")
+        elif op == "stamps" and every_array:
+            log.append(f"stamps {a[0]:.3f}")
+        elif op == "adj":                                    # w, rtol, max_iter, check_every
+            h.update(np.concatenate(a[0], axis=0).tobytes())
+            log.append(f"adj {a[1]} {a[2]} {a[3]}")
+        elif op == "setadj":
+            h.update(np.concatenate(a[0], axis=0).tobytes())
+            log.append("setadj")
+        elif op == "vjp":                                    # a drawn D plane or None (the model's), CL, CR
+            if a[0] is not None:
+                h.update(np.concatenate(a[0], axis=0).tobytes())
+            log.append(f"vjp {'D' if a[0] is not None else 'model'} {a[1]} {a[2]}")
         else:
             log.append(op)
     return log, h.hexdigest()
@@ -88,6 +107,20 @@ def test_the_option_seeds_draw_what_they_drew_before_the_later_options():
     assert len(recorded) == len(seeds) == 120
     for seed, options in seeds:
         log, digest = draw_log(seed, **options)
+        assert "|".join(log) == recorded[str(seed)]["log"], seed
+        assert digest == recorded[str(seed)]["data"], seed
+
+
+def test_the_later_seeds_draw_what_they_drew_before_the_adjoint():
+    """The native, CG-key and pre-scaled groups, recorded (draw_log with every_array) before the draw gained `adjoint`: with
+    that option off the generator is consumed as it was, streams' images and arguments included."""
+    with open(os.path.join(GOLDEN, "sequence_draws_later_seeds.json")) as f:
+        recorded = json.load(f)
+    seeds = [(g["first"] + i, seq.seed_options(g)) for g in (seq.NATIVE_SEEDS, seq.CGKEY_SEEDS, seq.PRESCALED_SEEDS)
+             for i in range(g["count"])]
+    assert len(recorded) == len(seeds) == 120
+    for seed, options in seeds:
+        log, digest = draw_log(seed, every_array=True, **options)
         assert "|".join(log) == recorded[str(seed)]["log"], seed
         assert digest == recorded[str(seed)]["data"], seed
 
@@ -357,3 +390,190 @@ def test_the_later_option_seeds_reach_what_they_were_added_for(oracle):
     # ny rows of ceil(nx / 64) words within FILL_LARGE_WORDS = 8192); and nothing is larger than 256 x 130 cells
     for nx, ny in set(seq.NATIVE_SHAPES + seq.CGKEY_SHAPES):
         assert ny * ((nx + 63) // 64) <= 8192 and nx * ny <= 256 * 130, (nx, ny)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The field adjoint's group.  Lambda's validity is worked out here from deff_amd.h's lifetime rule alone, independently of the
+# draw's own bookkeeping, and the two have to agree: the draw offers the pass as a solve's first reader only while it is valid.
+
+ADJ_INVALIDATORS = ("image", "native", "D/S", "stage", "stream", "cgstream")
+ADJ_KINDS = ["adj", "adj on Sw", "adj max_iter 0", "adj max_iter 3", "adj zero image", "setadj", "getadj", "vjp", "vjp refused",
+             "getadj refused"]
+ADJ_ORDERS = (["A1"] + ["A2 " + k for k in ADJ_INVALIDATORS] + ["A3 cgstream refused", "A3 adj on Sw"]
+              + ["A4 impl 1", "A4 impl 2", "A4 impl 3", "A4 cg adj cg", "A5", "A6", "A7 setadj adj", "A7 adj setadj vjp",
+                 "A8 vjp sens", "A8 sens vjp"])
+
+
+def adjoint_census(oracle):
+    """Per seed of ADJOINT_SEEDS: `kinds` = which of ADJ_KINDS it draws, `orders` = which of ADJ_ORDERS it reaches."""
+    out = {}
+    g = seq.ADJOINT_SEEDS
+    for i in range(g["count"]):
+        seed, options = g["first"] + i, seq.seed_options(g)
+        draw = seq.draw_sequence(seed, **options)
+        _, nx, ny, B, _ = next(draw)
+        pix = next(draw)[1]
+        kinds, orders = set(), set()
+        kind, asm, nrows = None, None, None
+        keys = dict(cg_onchip=0, cg_planes=0, cg_fold=0, tb_impl=0, tb_launch=0)
+        kset, keys_at_sweeps = "auto", None
+        have_x = lam_valid = False
+        planes_built = False                                 # of a native "2p" / "3n" system
+        a1 = None                                            # after an adj that built those planes: what has followed it
+        lost_by = refused = None                             # the invalidator that took a valid lambda / the refusal that left one
+        a4 = None                                            # the CG forms that ran since the last adj, lambda still its
+        hist = []                                            # every op drawn: (name, accepted)
+
+        def rows():
+            nonlocal nrows
+            if nrows is None:
+                nrows = distinct_rows(oracle, pix, *asm)
+            return nrows
+
+        def invalidate(by):
+            nonlocal lam_valid, lost_by, a4, planes_built, a1
+            if lam_valid:
+                lost_by = by
+            lam_valid, a4 = False, None
+            if by != "image":
+                planes_built, a1 = False, None
+
+        for op, *a in draw:
+            ok = True
+            was_refused, refused = refused, None
+            if op == "tune":
+                if a[0] in keys:
+                    keys[a[0]] = a[1]
+                hist.append((op, True))
+                refused = was_refused                        # (a key in between does not touch lambda)
+                continue
+            if op == "kernel":
+                kset = a[0]
+            elif op == "image":
+                pix, kind = a[0], None
+                invalidate("image")
+            elif op in ("assemble", "stage"):
+                if op == "stage":
+                    a = ["3n"] + a + [None]
+                invalidate("stage" if op == "stage" else "native" if a[0] in ("2p", "3p", "3n", "3g") else "D/S")
+                if a[0] in ("D", "S", "Sw"):
+                    kset = "auto"
+                kind, asm, nrows = a[0], (a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7] if len(a) > 7 else None), None
+            elif op in ("stream", "cgstream"):
+                ok = not (op == "cgstream" and a[2] < 0)
+                if ok:
+                    invalidate(op)
+                    kind, nrows, asm, have_x = "2p", 1, None, True
+                elif lam_valid:
+                    refused = "cgstream refused"
+            elif op in ("init", "set_field"):
+                have_x = True
+            elif op == "cg":
+                has_dict = kind in ("2p", "3n") or (kind != "Sw" and rows() <= 511)
+                ok = kind != "Sw" and (has_dict or keys["cg_planes"] > 0)
+                if ok:
+                    impl = 3 if keys["cg_planes"] == 2 or not has_dict else seq.expected_cg_impl(nx, ny, keys["cg_onchip"])
+                    if kind in ("2p", "3n") and impl == 3:
+                        planes_built = True
+                    if a4 is not None:
+                        a4.add(impl)
+                    if hist[-2:] == [("cg", True), ("adj", True)]:
+                        orders.add("A4 cg adj cg")
+                    if a1 is not None and impl in (1, 2):
+                        a1.add("table")
+                elif lam_valid:
+                    refused = "cg on Sw" if kind == "Sw" else "cg without a dictionary"
+            elif op == "sens":
+                if lam_valid and kind in ("3n", "3g"):
+                    refused = "sens on a Grid system"
+                if hist[-1:] == [("vjp", True)]:
+                    orders.add("A8 vjp sens")
+            elif op == "getsys":
+                if kind in ("2p", "3n"):
+                    planes_built = True
+                if a1 is not None:
+                    a1.add("getsys")
+            elif op in ("sweeps", "solve"):
+                if kind in ("2p", "3n") and kset == "explicit":
+                    planes_built = True
+                if a1 is not None and kset != "explicit":
+                    a1.add("table")
+                if op == "sweeps":
+                    keys_at_sweeps = (keys["tb_impl"], keys["tb_launch"])
+                elif a[3] == "vjp":
+                    assert lam_valid, (seed, "the pass drawn as a reader without a valid lambda")
+                    kinds.add("vjp")
+                    if B >= 2:
+                        orders.add("A5")
+                if op == "solve" and len(hist) >= 2 and hist[-2] == ("sweeps", True) and hist[-1] in (("adj", True), ("vjp", True)) \
+                        and (keys["tb_impl"], keys["tb_launch"]) == (2, 0) and kset in ("auto", "matfree_tb") and kind != "Sw" \
+                        and keys_at_sweeps == (2, 0):
+                    orders.add("A6")
+            elif op == "adj":
+                ok = kind != "Sw"
+                if not ok:
+                    kinds.add("adj on Sw")
+                    if lam_valid:
+                        refused = "adj on Sw"
+                else:
+                    kinds.add("adj")
+                    if a[2] in (0, 3):
+                        kinds.add(f"adj max_iter {a[2]}")
+                    if B >= 2 and any(not w.any() for w in a[0]):
+                        kinds.add("adj zero image")
+                    if kind in ("2p", "3n") and not planes_built:
+                        planes_built, a1 = True, set()
+                    if hist[-1:] == [("setadj", True)]:
+                        orders.add("A7 setadj adj")
+                    lam_valid, lost_by, a4 = True, None, set()
+            elif op == "setadj":
+                kinds.add("setadj")
+                lam_valid, lost_by, a4 = True, None, None
+            elif op == "getadj":
+                ok = lam_valid
+                kinds.add("getadj" if ok else "getadj refused")
+                if ok and was_refused in ("cgstream refused", "adj on Sw"):
+                    orders.add("A3 " + was_refused)
+                if ok and a4:
+                    orders.update("A4 impl %d" % k for k in a4)
+                if not ok and lost_by:
+                    orders.add("A2 " + lost_by)
+                    lost_by = None
+            elif op == "vjp":
+                ok = lam_valid and have_x
+                kinds.add("vjp" if ok else "vjp refused")
+                if ok and hist[-2:] == [("adj", True), ("setadj", True)]:
+                    orders.add("A7 adj setadj vjp")
+                if ok and hist[-1:] == [("sens", True)]:
+                    orders.add("A8 sens vjp")
+                if not lam_valid and lost_by:
+                    orders.add("A2 " + lost_by)
+                    lost_by = None
+            if a1 is not None and a1 == {"table", "getsys"}:
+                orders.add("A1")
+            hist.append((op, ok))
+        out[seed] = dict(kinds=kinds, orders=orders, shape=(nx, ny), B=B)
+    return out
+
+
+def test_the_adjoint_seeds_reach_what_they_were_added_for(oracle):
+    """Every kind of the adjoint's ops is drawn by at least 8 seeds and at least 4 seeds reach each of
+    A1  adj is the first call that needs the planes of a native "2p" / "3n" system; a sweep, solve or CG on the row table and
+        deff_get_system follow on that system
+    A2  a valid lambda, an invalidator (counted per kind: a new image, a native assembly, a caller's plane or system, a
+        continuation stage, a stream, a CG stream), then getadj or vjp, refused
+    A3  a valid lambda, a refused call (a CG stream with Df = -1; adj on wall-column links), then getadj
+    A4  adj, CG (counted per form), then getadj with lambda still that solve's; and cg, adj, cg in a row
+    A5  a solve of a stack (B >= 2) whose first reader is the pass
+    A6  sweeps, adj or vjp, a solve in a row under tb_impl 2 / tb_launch 0, with the conditions of order 6 above
+    A7  setadj then adj; adj, setadj, vjp in a row
+    A8  vjp then the gradient (which reads the pass's device map afterwards); the gradient then vjp (which reads the gradient's)."""
+    c = adjoint_census(oracle)
+    drawn = {k: sum(1 for v in c.values() if k in v["kinds"]) for k in ADJ_KINDS}
+    reached = {k: sum(1 for v in c.values() if k in v["orders"]) for k in ADJ_ORDERS}
+    print(f"adjoint: seeds that draw {drawn}; seeds that reach the orders {reached}")
+    assert all(n >= 8 for n in drawn.values()), drawn
+    assert all(n >= 4 for n in reached.values()), reached
+    assert any(v["shape"][0] % 2 == 0 for v in c.values()) and any(v["shape"][0] % 2 == 1 for v in c.values())
+    for nx, ny in seq.CGKEY_SHAPES:
+        assert nx * ny <= 256 * 130, (nx, ny)
