@@ -8,7 +8,7 @@
 // produced on the device; sweeps are enqueued back to back with pointer
 // ping-pong (no per-sweep sync or D2D copy, unlike cuh:1239/cuh:1281); a
 // convergence check moves 16*ny bytes, not the field (cuh:1245).
-#include "ctx.hpp"
+#include "cell_pass.hpp"
 #include <algorithm>
 #include "driver/jpeg_gray.hpp"
 #include "flood_fill.hpp"
@@ -128,7 +128,6 @@ try {
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (c->mf_host) (void)hipHostFree(c->mf_host);
     if (c->q) (void)hipFree(c->q);
-    if (c->resid) (void)hipFree(c->resid);
     if (c->tb_dealt) (void)hipFree(c->tb_dealt);
     if (c->tb_chain_nbrs) (void)hipFree(c->tb_chain_nbrs);
     if (c->res_flags) (void)hipFree(c->res_flags);
@@ -141,16 +140,9 @@ try {
     if (c->cgs_dev) (void)hipFree(c->cgs_dev);
     if (c->cgs_pin) (void)hipHostFree(c->cgs_pin);
     for (hipEvent_t e : c->cgs_ev) if (e) (void)hipEventDestroy(e);
-    if (c->resid_ev0) (void)hipEventDestroy(c->resid_ev0);
-    if (c->resid_ev1) (void)hipEventDestroy(c->resid_ev1);
-    if (c->sens_g) (void)hipFree(c->sens_g);
-    if (c->sens_part) (void)hipFree(c->sens_part);
-    if (c->sens_ev0) (void)hipEventDestroy(c->sens_ev0);
-    if (c->sens_ev1) (void)hipEventDestroy(c->sens_ev1);
-    void *adj_bufs[] = {c->adj_lam, c->adj_w, c->vjp_g, c->vjp_part};
-    for (void *p : adj_bufs) if (p) (void)hipFree(p);
-    if (c->vjp_ev0) (void)hipEventDestroy(c->vjp_ev0);
-    if (c->vjp_ev1) (void)hipEventDestroy(c->vjp_ev1);
+    for (CellPass *p : {&c->pass_res, &c->pass_sens, &c->pass_vjp}) cell_pass_free(*p);
+    if (c->adj_lam) (void)hipFree(c->adj_lam);
+    if (c->adj_w) (void)hipFree(c->adj_w);
     if (c->q_host) (void)hipHostFree(c->q_host);
     if (c->chain_counted) resident_chain_ctx_destroyed(c->device);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -277,9 +269,9 @@ try {
     else if (!strcmp(key, "tb_R")) c->tb_R = value;
     else if (!strcmp(key, "tb_debug_stall")) c->tb_debug_stall = value;
     else if (!strcmp(key, "tb_debug_stall_skip")) c->tb_debug_stall_skip = value;
-    else if (!strcmp(key, "res_kt")) c->res_kt = value;
-    else if (!strcmp(key, "sens_kt")) c->sens_kt = value;
-    else if (!strcmp(key, "vjp_kt")) c->vjp_kt = value;
+    else if (!strcmp(key, "res_kt")) c->pass_res.kt = value;
+    else if (!strcmp(key, "sens_kt")) c->pass_sens.kt = value;
+    else if (!strcmp(key, "vjp_kt")) c->pass_vjp.kt = value;
     else if (!strcmp(key, "tb_sym")) c->tb_sym = value;
     else if (!strcmp(key, "tb_launch")) {            // 0: resident passes where possible; 1: one launch per pass
         if (value > 1) return fail(DEFF_EINVAL, "tb_launch takes 0 (resident passes where the tiles fit the chip) or 1 (one launch per pass)");
@@ -364,12 +356,12 @@ try {
     else if (!strcmp(key, "cgs_intervals")) *value = c->cgs_intervals;
     else if (!strcmp(key, "cgs_launches")) *value = c->cgs_launches;
     else if (!strcmp(key, "cgs_waits")) *value = c->cgs_waits;
-    else if (!strcmp(key, "res_kt")) *value = c->res_plan_kt;
-    else if (!strcmp(key, "res_items")) *value = c->res_plan_items;
-    else if (!strcmp(key, "sens_kt")) *value = c->sens_plan_kt;
-    else if (!strcmp(key, "sens_items")) *value = c->sens_plan_items;
-    else if (!strcmp(key, "vjp_kt")) *value = c->vjp_plan_kt;
-    else if (!strcmp(key, "vjp_items")) *value = c->vjp_plan_items;
+    else if (!strcmp(key, "res_kt")) *value = c->pass_res.plan_kt;
+    else if (!strcmp(key, "res_items")) *value = c->pass_res.plan_items;
+    else if (!strcmp(key, "sens_kt")) *value = c->pass_sens.plan_kt;
+    else if (!strcmp(key, "sens_items")) *value = c->pass_sens.plan_items;
+    else if (!strcmp(key, "vjp_kt")) *value = c->pass_vjp.plan_kt;
+    else if (!strcmp(key, "vjp_items")) *value = c->pass_vjp.plan_items;
     else if (!strcmp(key, "fill_impl")) *value = c->fill_plan_impl;
     else if (!strcmp(key, "fill_launches")) *value = c->fill_plan_launches;
     else if (!strcmp(key, "fill_rounds")) *value = c->fill_plan_rounds;

@@ -1,9 +1,8 @@
 // api_residual.hip -- deff_residual / deff_residual_D: the reference's Residual() (Deff2DGPU/Deff2D.cuh:451-494) of the
 // context's current field, reduced on the device (kernels_residual.hpp).
-#include "ctx.hpp"
+#include "cell_pass.hpp"
 #include "kernels_residual.hpp"
-#include <algorithm>
-#include <vector>
+static_assert(RES_ROWS == CELL_PASS_ROWS && RES_COLS == CELL_PASS_COLS, "cell_pass_items plans the class kernel's tiles");
 
 // (dy/dx) * H per class pair, the wall conductance and the "no face" zero -- the reference's expressions, evaluated once on
 // the host (this file is built with -ffp-contract=off like the rest of the library)
@@ -19,41 +18,14 @@ static ResTable residual_table(const deff_ctx *c)
     return t;
 }
 
-static int residual_buffers(deff_ctx *c, size_t partials)
+// sums -> means: R / (numCols * numRows), cuh:491.  The residual's own event pair (pass_res), so a residual taken inside a
+// solve loop's callback leaves the loop's ev0 / ev1 -- and with them loop_ms -- alone.
+static int residual_finish(deff_ctx *c, const CellItems &it, double *r, float *ms)
 {
-    const size_t want = partials + (size_t)c->nimg;
-    if (c->resid_cap < want) {
-        if (c->resid) { HIP_TRY(hipFree(c->resid)); c->resid = nullptr; c->resid_cap = 0; }
-        HIP_TRY(hipMalloc((void **)&c->resid, want * sizeof(double)));
-        c->resid_cap = want;
-    }
-    return DEFF_OK;
-}
-
-// Opens the timed window of a call that asked for `ms` (the slot variant never does): the residual's own event pair, so a
-// residual taken inside a solve loop's callback leaves the loop's ev0 / ev1 -- and with them loop_ms -- alone.
-static int residual_start(deff_ctx *c, const float *ms)
-{
-    if (!ms) return DEFF_OK;
-    if (!c->resid_ev0) HIP_TRY(hipEventCreate(&c->resid_ev0));
-    if (!c->resid_ev1) HIP_TRY(hipEventCreate(&c->resid_ev1));
-    HIP_TRY(hipEventRecord(c->resid_ev0, c->stream));
-    return DEFF_OK;
-}
-
-// sums -> means: R / (numCols * numRows), cuh:491
-static int residual_finish(deff_ctx *c, size_t per_img, int nimg, double *r, float *ms)
-{
-    double *out = c->resid + per_img * nimg;
-    hipLaunchKernelGGL(k_residual_final, dim3(nimg), dim3(1024), 0, c->stream, c->resid, per_img, out);
-    HIP_TRY(hipGetLastError());
-    if (ms) HIP_TRY(hipEventRecord(c->resid_ev1, c->stream));
-    std::vector<double> sums(nimg);
-    HIP_TRY(hipMemcpyAsync(sums.data(), out, sizeof(double) * nimg, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, c->resid_ev0, c->resid_ev1));
+    std::vector<double> sums(it.nimg);
+    TRY(cell_pass_finish(c, c->pass_res, k_residual_final, it, sums.data(), nullptr, ms));
     const double cells = (double)((int64_t)c->nxt * (int64_t)c->ny);
-    for (int k = 0; k < nimg; ++k) r[k] = sums[k] / cells;
+    for (int k = 0; k < it.nimg; ++k) r[k] = sums[k] / cells;
     return DEFF_OK;
 }
 
@@ -67,7 +39,7 @@ static int residual_common(deff_ctx *c, const double *r)
     return DEFF_OK;
 }
 
-// the class kernel over `nimg` stacked images starting at field `x` / pixels `pix`; sums -> c->resid (after the partials)
+// the class kernel over `nimg` stacked images starting at field `x` / pixels `pix`; sums -> pass_res.part (after the partials)
 static int residual_classes(deff_ctx *c, const double *x, const uint8_t *pix, int nimg, double *r, float *ms)
 {
     if (!c->phase_mode || !c->have_image)
@@ -75,33 +47,21 @@ static int residual_classes(deff_ctx *c, const double *x, const uint8_t *pix, in
                                  "pass the diffusivities to deff_residual_D() otherwise");
     if ((uint64_t)c->ny * (uint64_t)c->nx * 8u >= ((uint64_t)1 << 32))
         return fail(DEFF_EINVAL, "deff_residual: an image of more than 512 Mi cells (use deff_residual_D)");
-    // work items: column strips of 128, cut into runs of kt tiles of RES_ROWS rows that one wave streams top to bottom (the two
-    // halo rows of a tile are then loaded once per run).  kt: about 4 096 items in the launch -- one round of waves on 256 CUs;
-    // measured at 4096^2, reduction included: kt = 1 42.0 us, 2 34.4, 4 32.0, 8 31.7 -- and at most 16 384 items per image
-    // (k_residual_final adds an image's partial sums with ONE workgroup); tuning "res_kt" overrides
-    const int ntx = (c->nxt + RES_COLS - 1) / RES_COLS, tiles_y = (c->ny + RES_ROWS - 1) / RES_ROWS;
-    int kt = c->res_kt;
-    if (kt <= 0) {
-        kt = (int)std::min<size_t>(64, std::max<size_t>(1, (size_t)ntx * tiles_y * nimg / 4096));
-        kt = std::max(kt, (int)(((size_t)ntx * tiles_y + 16383) / 16384));
-    }
-    if (kt > tiles_y) kt = tiles_y;
-    const int cpi = (tiles_y + kt - 1) / kt;
-    const size_t per_img = (size_t)ntx * cpi, tiles = per_img * nimg;
-    TRY(residual_buffers(c, tiles));
+    CellPass &p = c->pass_res;
+    const CellItems it = cell_pass_items(c->nxt, c->ny, nimg, p.kt);
+    TRY(cell_pass_room(c, p, false, it.items));
     const ResTable tab = residual_table(c);
     const bool fast = c->ampX == 1 && c->ampY == 1 && (c->W % 2) == 0;
-    const dim3 grid((unsigned)((tiles + 3) / 4));
-    TRY(residual_start(c, ms));
+    const dim3 grid((unsigned)((it.items + 3) / 4));
+    TRY(cell_pass_start(c, p, ms));
 #define LAUNCH_RES(P_, F_)                                                                                              \
     hipLaunchKernelGGL((k_residual_classes<P_, F_>), grid, dim3(256), 0, c->stream, x, pix, c->W, c->ampX,              \
-                       c->ampY, c->nx, c->nxt, c->ny, nimg, ntx, cpi, kt, c->CL, c->CR, tab, c->resid)
+                       c->ampY, c->nx, c->nxt, c->ny, nimg, it.ntx, it.cpi, it.kt, c->CL, c->CR, tab, p.part)
     if (c->phase_mode == 2) { if (fast) LAUNCH_RES(2, true); else LAUNCH_RES(2, false); }
     else { if (fast) LAUNCH_RES(3, true); else LAUNCH_RES(3, false); }
 #undef LAUNCH_RES
     HIP_TRY(hipGetLastError());
-    c->res_plan_kt = kt; c->res_plan_items = (int)per_img;       // deff_get_plan "res_kt" / "res_items": what was launched
-    return residual_finish(c, per_img, nimg, r, ms);
+    return residual_finish(c, it, r, ms);
 }
 
 extern "C" int deff_residual(deff_ctx *c, double *r, float *ms)
@@ -129,18 +89,17 @@ try {
     TRY(residual_common(c, r));
     if (!D) return fail(DEFF_EINVAL, "D is NULL");
     TRY(consolidate(c));
+    CellPass &p = c->pass_res;
     const int segs = (c->nxt + 255) / 256;
     const size_t per_img = (size_t)c->ny * segs;
-    TRY(residual_buffers(c, per_img * c->nimg));
-    TRY(ensure_scratch(c, sizeof(double) * c->n));
-    double *dD = (double *)c->scratch;
-    if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(dD, 0, sizeof(double) * c->n, c->stream));
-    TRY(rows_h2d(c, dD, D, (size_t)c->rows));
-    TRY(residual_start(c, ms));
+    const CellItems it{segs, 0, c->ny, c->nimg, per_img, per_img * c->nimg};   // no runs (kt 0): one partial sum per row segment
+    TRY(cell_pass_room(c, p, false, it.items));
+    const double *dD;
+    TRY(cell_pass_upload_D(c, D, &dD));
+    TRY(cell_pass_start(c, p, ms));
     hipLaunchKernelGGL(k_residual_plane, dim3((unsigned)(c->rows * segs)), dim3(256), 0, c->stream, c->x[c->cur], dD, c->nx,
-                       c->nxt, c->ny, c->nimg, segs, c->dx, c->dy, CL, CR, c->resid);
+                       c->nxt, c->ny, c->nimg, segs, c->dx, c->dy, CL, CR, p.part);
     HIP_TRY(hipGetLastError());
-    c->res_plan_kt = 0; c->res_plan_items = (int)per_img;        // no runs: one partial sum per row segment
-    return residual_finish(c, per_img, c->nimg, r, ms);
+    return residual_finish(c, it, r, ms);
 }
 DEFF_API_CATCH

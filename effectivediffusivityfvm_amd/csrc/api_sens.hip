@@ -1,10 +1,25 @@
 // api_sens.hip -- deff_sensitivity / deff_sensitivity_D / deff_device_sensitivity: the per-cell gradient dDeff_raw / dD of the
-// context's current field and its Euler sum, one pass on the device (kernels_sens.hpp).  Reads the field; changes nothing but
-// the map, its partial sums and the shared upload scratch.
-#include "ctx.hpp"
-#include "kernels_sens.hpp"
-#include <algorithm>
-#include <vector>
+// context's current field and its Euler sum, one pass on the device (kernels_facepass.hpp: the walk with SensPass).  Reads the
+// field; changes nothing but the map, its partial sums and the shared upload scratch.
+#include "cell_pass.hpp"
+#include "kernels_facepass.hpp"
+static_assert(FP_ROWS == CELL_PASS_ROWS && FP_COLS == CELL_PASS_COLS, "cell_pass_items plans the face walk's tiles");
+
+namespace deff {
+
+__global__ __launch_bounds__(256) void k_sens(const double *__restrict__ x, const double *__restrict__ D, int nx, int nxt, int ny,
+                                              int nimg, int ntx, int cpi, int kt, double wx, double wy, double ww, double CL,
+                                              double CR, double den, double *__restrict__ g, double *__restrict__ partial)
+{
+    face_pass(SensPass{den}, {x}, D, nx, nxt, ny, nimg, ntx, cpi, kt, wx, wy, ww, CL, CR, g, partial);
+}
+
+__global__ __launch_bounds__(1024) void k_sens_final(const double *__restrict__ partial, size_t per_img, double *__restrict__ out)
+{
+    partials_sum_body(partial, per_img, out);
+}
+
+}  // namespace deff
 
 // Everything that can refuse the call, before anything is touched.
 static int sens_common(deff_ctx *c, const char *who, double CL, double CR)
@@ -19,46 +34,17 @@ static int sens_common(deff_ctx *c, const char *who, double CL, double CR)
 // the map of the stack's newest fields (x[cur] after consolidate) for the D plane `dD` on the device (pitch nx, pad column 0)
 static int sens_launch(deff_ctx *c, const double *dD, double CL, double CR, double *g, double *euler, float *ms)
 {
-    // work items as the residual's (api_residual.hip): column strips of 128, cut into runs of kt tiles of SENS_ROWS rows, about
-    // 4 096 items in a launch and at most 16 384 per image; tuning "sens_kt" overrides
-    const int ntx = (c->nxt + SENS_COLS - 1) / SENS_COLS, tiles_y = (c->ny + SENS_ROWS - 1) / SENS_ROWS;
-    int kt = c->sens_kt;
-    if (kt <= 0) {
-        kt = (int)std::min<size_t>(64, std::max<size_t>(1, (size_t)ntx * tiles_y * c->nimg / 4096));
-        kt = std::max(kt, (int)(((size_t)ntx * tiles_y + 16383) / 16384));
-    }
-    if (kt > tiles_y) kt = tiles_y;
-    const int cpi = (tiles_y + kt - 1) / kt;
-    const size_t per_img = (size_t)ntx * cpi, items = per_img * c->nimg;
-    if ((items + 3) / 4 > 0x7fffffffu) return fail(DEFF_EINVAL, "deff_sensitivity: too many work items");
-    TRY(dev_alloc(&c->sens_g, c->n));
-    const size_t want = items + (size_t)c->nimg;
-    if (c->sens_part_cap < want) {
-        if (c->sens_part) { HIP_TRY(hipFree(c->sens_part)); c->sens_part = nullptr; c->sens_part_cap = 0; }
-        HIP_TRY(hipMalloc((void **)&c->sens_part, want * sizeof(double)));
-        c->sens_part_cap = want;
-    }
-    if (ms) {                                                      // the call's own pair: ev0 / ev1 belong to the solve loops
-        if (!c->sens_ev0) HIP_TRY(hipEventCreate(&c->sens_ev0));
-        if (!c->sens_ev1) HIP_TRY(hipEventCreate(&c->sens_ev1));
-        HIP_TRY(hipEventRecord(c->sens_ev0, c->stream));
-    }
+    CellPass &p = c->pass_sens;
+    const CellItems it = cell_pass_items(c->nxt, c->ny, c->nimg, p.kt);
+    if ((it.items + 3) / 4 > 0x7fffffffu) return fail(DEFF_EINVAL, "deff_sensitivity: too many work items");
+    TRY(cell_pass_room(c, p, true, it.items));
+    TRY(cell_pass_start(c, p, ms));
     const double dx = c->dx, dy = c->dy;
     const double wx = dy / dx, wy = dx / dy, ww = dy / (dx / 2.0), den = (CR - CL) * (CR - CL);
-    double *out = c->sens_part + items;
-    hipLaunchKernelGGL(k_sens, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, c->x[c->cur], dD, c->nx, c->nxt, c->ny,
-                       c->nimg, ntx, cpi, kt, wx, wy, ww, CL, CR, den, c->sens_g, c->sens_part);
+    hipLaunchKernelGGL(k_sens, dim3((unsigned)((it.items + 3) / 4)), dim3(256), 0, c->stream, c->x[c->cur], dD, c->nx, c->nxt,
+                       c->ny, c->nimg, it.ntx, it.cpi, it.kt, wx, wy, ww, CL, CR, den, p.map, p.part);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sens_final, dim3(c->nimg), dim3(1024), 0, c->stream, c->sens_part, per_img, out);
-    HIP_TRY(hipGetLastError());
-    if (ms) HIP_TRY(hipEventRecord(c->sens_ev1, c->stream));
-    c->sens_have = true;
-    c->sens_plan_kt = kt; c->sens_plan_items = (int)per_img;     // deff_get_plan "sens_kt" / "sens_items": what was launched
-    if (g) TRY(rows_d2h(c, g, (const double *)c->sens_g, (size_t)c->rows));
-    if (euler) HIP_TRY(hipMemcpyAsync(euler, out, sizeof(double) * c->nimg, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, c->sens_ev0, c->sens_ev1));
-    return DEFF_OK;
+    return cell_pass_finish(c, p, k_sens_final, it, euler, g, ms);
 }
 
 extern "C" int deff_sensitivity_D(deff_ctx *c, const double *D, double CL, double CR, double *g, double *euler, float *ms)
@@ -67,10 +53,8 @@ try {
     if (!D) return fail(DEFF_EINVAL, "D is NULL");
     TRY(sens_common(c, "deff_sensitivity_D", CL, CR));
     TRY(consolidate(c));                                           // every image's newest field in x[cur]
-    TRY(ensure_scratch(c, sizeof(double) * c->n));
-    double *dD = (double *)c->scratch;
-    if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(dD, 0, sizeof(double) * c->n, c->stream));
-    TRY(rows_h2d(c, dD, D, (size_t)c->rows));
+    const double *dD;
+    TRY(cell_pass_upload_D(c, D, &dD));
     return sens_launch(c, dD, CL, CR, g, euler, ms);
 }
 DEFF_API_CATCH
@@ -102,10 +86,7 @@ DEFF_API_CATCH
 
 extern "C" int deff_device_sensitivity(deff_ctx *c, void **d_g, size_t *row_pitch_bytes)
 try {
-    if (!c || !d_g) return fail(DEFF_EINVAL, "NULL argument");
-    if (!c->sens_have) return fail(DEFF_ESTATE, "no sensitivity map yet (deff_sensitivity / deff_sensitivity_D)");
-    *d_g = c->sens_g;
-    if (row_pitch_bytes) *row_pitch_bytes = sizeof(double) * c->nx;
-    return DEFF_OK;
+    return cell_pass_device_map(c, &deff_ctx::pass_sens, d_g, row_pitch_bytes,
+                                "no sensitivity map yet (deff_sensitivity / deff_sensitivity_D)");
 }
 DEFF_API_CATCH

@@ -11,9 +11,13 @@
 //   api_solve.hip  wall fluxes and the Jacobi solve loops (one image, batch, streaming batch); no sweep kernel
 //   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg) and through refilled slots (deff_solve_cg_stream);
 //                  every CG kernel, the slab forms included: their launches for one slab (cg_slab.hpp)
+//   api_residual.hip  the reference's Residual() of the current field (deff_residual, deff_residual_slot, deff_residual_D)
 //   api_sens.hip   the Deff gradient dDeff/dD per cell and its Euler sum (deff_sensitivity, deff_sensitivity_D)
 //   api_vjp.hip    the field adjoint: lambda's buffer (deff_set_adjoint, deff_get_adjoint, deff_device_adjoint) and the pass
 //                  (x, lambda, D) -> dL/dD (deff_field_vjp_D); deff_solve_adjoint itself is in api_cg.hip, beside the loop it runs
+//   cell_pass.hpp  the host path those three share (CellPass below): work-item planner, partial sums, the call's own event
+//                  pair, the D upload, the device-map getter; k_sens and k_vjp are one walk (kernels_facepass.hpp), the three
+//                  final sums one body (wave_reduce.hpp)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
 //                  RCCL or a caller-supplied transport with one process per GPU); conjugate gradients over the slabs
@@ -62,6 +66,23 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
     } while (0)
 
 // ------------------------------------------------------------ context -----
+
+// What one pass over the cells of the current field keeps between calls (the residual, the Deff gradient, the field adjoint's
+// pass; cell_pass.hpp has what they do with it).
+struct CellPass {
+    double *map = nullptr;          // device: the last per-cell map (pitch nx), kept until the next call; the residual has none
+    double *part = nullptr;         // device: the work items' partial sums + one sum per image, grow-only
+    size_t part_cap = 0;
+    bool have = false;              // map holds a result
+    // The call's own event pair, created by the first call that asks for `ms`: ev0 / ev1 of the context belong to the solve
+    // loops alone, which read them at every check and may call a pass in between (a deff_set_progress or deff_image_done_fn
+    // callback).
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int kt = 0;                     // tuning "res_kt" / "sens_kt" / "vjp_kt": tiles of 8 rows a wave streams through (0 = planner)
+    // deff_get_plan "*_kt" / "*_items" of the last call that launched: the run length used (planner, override and clip
+    // applied) and the partial sums the final kernel adds per image
+    int plan_kt = 0, plan_items = 0;
+};
 
 struct deff_ctx {
     int device = 0;
@@ -130,12 +151,6 @@ struct deff_ctx {
     // from a caller's D plane or matrix) and their diffusivities {fluid, solid, gas}
     int phase_mode = 0;
     double phase_D[3] = {0, 0, 0};
-    double *resid = nullptr;        // device: partial sums of the residual reduction + one sum per image
-    size_t resid_cap = 0;
-    int res_kt = 0;                 // tuning: tiles of 8 rows a wave of the residual kernel streams through (0 = planner)
-    // deff_get_plan "res_kt" / "res_items" of the last residual call that launched: the run length the class kernel used
-    // (planner, override and clip applied; 0 for deff_residual_D) and the partial sums k_residual_final adds per image
-    int res_plan_kt = 0, res_plan_items = 0;
 
     // wall data for the flux evaluation
     double *Dl = nullptr, *Dr = nullptr;
@@ -279,34 +294,19 @@ struct deff_ctx {
     hipEvent_t cgs_ev[2] = {nullptr, nullptr};   // a snapshot has arrived
     int cgs_intervals = 0, cgs_launches = 0, cgs_waits = 0;   // deff_get_plan: figures of the last stream
 
-    // deff_residual / deff_residual_D time themselves with their own pair, created by the first call that asks for `ms`:
-    // ev0 / ev1 belong to the solve loops alone, which read them at every check and may call the residual in between
-    // (a deff_set_progress or deff_image_done_fn callback)
-    hipEvent_t resid_ev0 = nullptr, resid_ev1 = nullptr;
-
-    // deff_sensitivity / deff_sensitivity_D (api_sens.hip): the last map (pitch nx, kept until the next call: deff_device_sensitivity),
-    // the work items' Euler sums + one sum per image, and the calls' own event pair, all allocated by the first call.
-    // sens_kt: tuning, tiles of 8 rows a wave streams through (0 = planner); sens_plan_*: deff_get_plan "sens_kt" / "sens_items"
-    double *sens_g = nullptr, *sens_part = nullptr;
-    size_t sens_part_cap = 0;
-    bool sens_have = false;
-    hipEvent_t sens_ev0 = nullptr, sens_ev1 = nullptr;
-    int sens_kt = 0, sens_plan_kt = 0, sens_plan_items = 0;
+    // The passes over the cells of the current field (cell_pass.hpp), everything allocated by the first call that needs it:
+    //   pass_res   deff_residual / deff_residual_slot / deff_residual_D (api_residual.hip): no map; plan_kt is 0 after deff_residual_D
+    //   pass_sens  deff_sensitivity / deff_sensitivity_D (api_sens.hip): the map dDeff/dD, handed out by deff_device_sensitivity
+    //   pass_vjp   deff_field_vjp_D (api_vjp.hip): the map dL/dD, handed out by deff_device_field_vjp
+    CellPass pass_res, pass_sens, pass_vjp;
     bool grid_given = false;        // the last deff_assemble_3phase was given a Grid (deff_sensitivity refuses such a system)
 
     // The field adjoint (api_vjp.hip; the solve itself is api_cg.hip's loop).  adj_lam: lambda of A lambda = w (pitch nx, pad
     // column 0), adj_w: the right-hand side w' = w with the forward system's decoupled cells zeroed; both allocated by the
     // first deff_solve_adjoint / deff_set_adjoint.  adj_valid: lambda belongs to the current system and image (adjoint_reset
     // below: every call that replaces either clears it).
-    // deff_field_vjp_D: the last map dL/dD (pitch nx, kept until the next call: deff_device_field_vjp), the work items' Euler sums
-    // + one sum per image, the call's own event pair; vjp_kt: tuning "vjp_kt"; vjp_plan_*: deff_get_plan "vjp_kt" / "vjp_items"
     double *adj_lam = nullptr, *adj_w = nullptr;
     bool adj_valid = false;
-    double *vjp_g = nullptr, *vjp_part = nullptr;
-    size_t vjp_part_cap = 0;
-    bool vjp_have = false;
-    hipEvent_t vjp_ev0 = nullptr, vjp_ev1 = nullptr;
-    int vjp_kt = 0, vjp_plan_kt = 0, vjp_plan_items = 0;
 
     // Native 3-phase system (kernels_fill.hpp, api_fill.hip): the flood fill of the pore space as bitmaps -- one `open` and
     // one `reach` word per 64 columns of a row, fill_nw words per row --, its status words and the tiled form's `changed` words.

@@ -242,29 +242,11 @@ __global__ __launch_bounds__(256) void k_residual_plane(const double *__restrict
 // image adds them up in this same fixed order: 33.6 against 32.0 us at 4096^2, 21.7 against 14.0 at 2048^2, 126.8 against 114 at
 // 8192^2.  The acknowledged store and the atomic's round trip keep every workgroup's slot on its CU ~2 us longer, which costs
 // more than the second launch saves.)
-// One workgroup of 16 waves per image: thread t adds the partial sums t, t + 1024, ... of its image in that order, the wave
-// tree combines the 64 thread sums of a wave, thread 0 adds the 16 wave sums in wave order.  out[img] = sum.
+// One workgroup of 16 waves per image adds the image's partial sums (wave_reduce.hpp).  out[img] = sum.
 __global__ __launch_bounds__(1024) void k_residual_final(const double *__restrict__ partial, size_t per_img,
                                                          double *__restrict__ out)
 {
-    __shared__ double ws[16];
-    const double *p = partial + (size_t)blockIdx.x * per_img;
-    double acc = 0.0;
-    size_t i = threadIdx.x;
-    for (; i + 3 * 1024 < per_img; i += 4 * 1024) {               // four loads in flight, added in index order
-        const double a = p[i], b = p[i + 1024], c = p[i + 2048], d = p[i + 3072];
-        acc += a; acc += b; acc += c; acc += d;
-    }
-    for (; i < per_img; i += 1024) acc += p[i];
-    const double s = wave_sum_to_lane63(acc);
-    if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = ws[0];
-#pragma unroll
-        for (int w = 1; w < 16; ++w) t += ws[w];
-        out[blockIdx.x] = t;
-    }
+    partials_sum_body(partial, per_img, out);
 }
 
 }  // namespace deff

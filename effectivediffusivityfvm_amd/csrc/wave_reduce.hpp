@@ -1,5 +1,6 @@
 // wave_reduce.hpp -- wavefront-level (wave64) lane shifts and the fixed-order DPP sum tree shared by the residual
-// (kernels_residual.hpp) and conjugate-gradient (kernels_cg.hpp) reductions.
+// (kernels_residual.hpp), conjugate-gradient (kernels_cg.hpp) and gradient-pass (kernels_facepass.hpp) reductions, and the
+// final sum of an image's partial sums that the residual and the gradient passes end with.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +40,31 @@ __device__ __forceinline__ double wave_sum_to_lane63(double v)
     t = t + dpp_f64<0x142, 0xa, 0xf>(t);                         // row_bcast:15 into rows 1 and 3
     t = t + dpp_f64<0x143, 0xc, 0xf>(t);                         // row_bcast:31 into rows 2 and 3
     return t;
+}
+
+// The body of a __global__ __launch_bounds__(1024) kernel, one workgroup of 16 waves per image: thread t adds the partial sums
+// t, t + 1024, ... of its image in that order, the wave tree combines the 64 thread sums of a wave, thread 0 adds the 16 wave
+// sums in wave order.  out[img] = sum.  (k_residual_final, k_sens_final, k_vjp_final: one order, one text.)
+__device__ __forceinline__ void partials_sum_body(const double *__restrict__ partial, size_t per_img, double *__restrict__ out)
+{
+    __shared__ double ws[16];
+    const double *p = partial + (size_t)blockIdx.x * per_img;
+    double acc = 0.0;
+    size_t i = threadIdx.x;
+    for (; i + 3 * 1024 < per_img; i += 4 * 1024) {               // four loads in flight, added in index order
+        const double a = p[i], b = p[i + 1024], c = p[i + 2048], d = p[i + 3072];
+        acc += a; acc += b; acc += c; acc += d;
+    }
+    for (; i < per_img; i += 1024) acc += p[i];
+    const double s = wave_sum_to_lane63(acc);
+    if ((threadIdx.x & 63) == 63) ws[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = ws[0];
+#pragma unroll
+        for (int w = 1; w < 16; ++w) t += ws[w];
+        out[blockIdx.x] = t;
+    }
 }
 
 }  // namespace deff
