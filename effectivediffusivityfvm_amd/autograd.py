@@ -2,6 +2,8 @@
 the backward pass the library's one-pass gradient (deff_sensitivity_D) -- no second solve, the problem is self-adjoint.
 The concentration field as one: the same forward solve; the backward pass is one adjoint solve with the incoming gradient as
 right-hand side (deff_solve_adjoint) and one pass over (x, lambda, D) (deff_field_vjp_D), for any loss on the field.
+Both ops have a jvp for torch.autograd.forward_ad: Deff's is a sum over its gradient map, the field's one pass over (x, D, dD)
+(deff_tangent_rhs_D) and one solve (deff_solve_tangent).  torch.func transforms are not supported (no setup_context).
 
 torch is imported inside the functions only: importing the package does not import it.  D makes a host round trip (plumbing;
 the solve and the gradient run in the library's HIP kernels)."""
@@ -44,7 +46,9 @@ def _function():
                 if solver is None:
                     s.close()
             deff = np.array([r.deff_raw for r in rs], dtype=np.float64)
-            ctx.save_for_backward(torch.from_numpy(np.ascontiguousarray(g).reshape(Dh.shape)).to(D.device))
+            g = torch.from_numpy(np.ascontiguousarray(g).reshape(Dh.shape)).to(D.device)
+            ctx.save_for_backward(g)
+            ctx.save_for_forward(g)
             out = torch.from_numpy(deff).to(D.device)
             return out if stack else out[0]
 
@@ -52,6 +56,12 @@ def _function():
         def backward(ctx, grad_out):
             (g,) = ctx.saved_tensors
             return grad_out[..., None, None] * g, None, None, None, None, None
+
+        @staticmethod
+        def jvp(ctx, tD, *_):
+            # forward mode (torch.autograd.forward_ad): the map is the whole Jacobian, one row per image
+            (g,) = ctx.saved_tensors
+            return (g * tD).sum((-2, -1))
 
     _FN = _EffectiveDiffusivity
     return _FN
@@ -128,6 +138,26 @@ def _field_function():
             g = torch.from_numpy(np.ascontiguousarray(g).reshape(Dh.shape)).to(grad_out.device)
             return g, None, None, None, None, None
 
+        @staticmethod
+        def jvp(ctx, tD, *_):
+            # forward mode (torch.autograd.forward_ad): A dx = db - dA x along tD, one pass and one solve
+            Dh, x, CL, CR, rtol, max_iter, solver = ctx.deff_args
+            nimg = Dh.shape[0] if Dh.ndim == 3 else 1
+            ny, nx = Dh.shape[-2:]
+            d = np.ascontiguousarray(tD.detach().cpu().numpy(), dtype=np.float64)
+            s = solver if solver is not None else Solver(nx, ny, nimg=nimg)
+            try:
+                # as in backward: the solver's system and field are set again
+                s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
+                s.set_field(x.reshape(nimg * ny, nx))
+                s.tangent_rhs(Dh.reshape(nimg * ny, nx), d.reshape(nimg * ny, nx), CL, CR)
+                _converged("concentration_field (tangent)", s.solve_tangent(rtol=rtol, max_iter=max_iter), rtol, max_iter)
+                dx = s.get_tangent()
+            finally:
+                if solver is None:
+                    s.close()
+            return torch.from_numpy(dx.reshape(Dh.shape)).to(tD.device)
+
     _FIELD_FN = _ConcentrationField
     return _FIELD_FN
 
@@ -140,7 +170,9 @@ def concentration_field(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, solve
     again and the saved x set as its field -- on `solver` when one was passed, otherwise on a Solver created and closed for the
     backward pass --, then one adjoint solve A lambda = w to rtol (deff_solve_adjoint; RuntimeError if it does not converge)
     and one pass over (x, lambda, D) (deff_field_vjp_D) give dL/dD.  D and w make a host round trip.  `solver`: a Solver of the
-    same shape to reuse (its system, field, adjoint field and the tuning key "cg_planes" are overwritten, in both passes)."""
+    same shape to reuse (its system, field, adjoint field and the tuning key "cg_planes" are overwritten, in both passes).
+    Under torch.autograd.forward_ad the tangent of x along D's tangent is computed the same way: system and field set again,
+    then deff_tangent_rhs_D and deff_solve_tangent to rtol (RuntimeError if it does not converge)."""
     import torch
     if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() not in (2, 3):
         raise TypeError("D must be a float64 tensor of shape (ny, nx) or (nimg, ny, nx)")

@@ -6,7 +6,8 @@
 // deff_solve, in far fewer iterations.  Nothing of the Jacobi path is touched: its tables (lut, c0 plane), plans and knobs
 // stay as they are (the "fma" knob does not apply here: CG's arithmetic is written-order FP64 only).
 // The launches of one iteration, in every form and under every fold key, are CgIteration::enqueue's, for both solves.
-// deff_solve_adjoint (A lambda = w for the gradient of a loss on the field, api_vjp.hip) runs deff_solve_cg's host loop,
+// deff_solve_adjoint (A lambda = w for the gradient of a loss on the field, api_vjp.hip) and deff_solve_tangent (A dx = r for
+// the field's derivative along a direction, api_tangent.hip) run deff_solve_cg's host loop,
 // cg_host_loop, on the coefficient planes with its own solution and right-hand side buffers.
 #include "ctx.hpp"
 #include "kernels_cg.hpp"
@@ -311,25 +312,32 @@ try {
 }
 DEFF_API_CATCH
 
-// ---- deff_solve_adjoint -------------------------------------------------------------------------------------------------
+// ---- deff_solve_adjoint, deff_solve_tangent -----------------------------------------------------------------------------
 //
 // A lambda = w on the current matrix (symmetric: the adjoint system of A x = b is the same A), for the gradient of a loss on
-// the field (api_vjp.hip).  The plane form of deff_solve_cg with two pointers changed: the solution is adj_lam instead of the
-// field, the right-hand side adj_w (w, zeroed where the FORWARD system's row is decoupled: cg_inv == 0) instead of the b
-// plane.  cg_inv and the admissibility verdict are k_cgp_prepare's on the forward planes, b included.  Nothing the forward
-// solve or the Jacobi path reads is written.
-extern "C" int deff_solve_adjoint(deff_ctx *c, const double *w, double rtol, int64_t max_iter, int64_t check_every,
-                                  deff_cg_result *out)
-try {
-    if (!c || !w || !out) return fail(DEFF_EINVAL, "NULL argument");
-    if (!(rtol >= 0.0) || !std::isfinite(rtol)) return fail(DEFF_EINVAL, "deff_solve_adjoint: rtol must be finite and >= 0");
-    if (max_iter < 0) return fail(DEFF_EINVAL, "deff_solve_adjoint: negative max_iter");
+// the field (api_vjp.hip), and A dx = r on it for the field's derivative along a direction of D (api_tangent.hip).  The plane
+// form of deff_solve_cg with two pointers changed: the solution is adj_lam (tan_dx) instead of the field, the right-hand side
+// adj_w (tan_w) -- w (r), zeroed where the FORWARD system's row is decoupled: cg_inv == 0 -- instead of the b plane.  cg_inv
+// and the admissibility verdict are k_cgp_prepare's on the forward planes, b included.  Nothing the forward solve or the Jacobi
+// path reads is written.  The two entry points differ in where the right-hand side comes from (the host; the last
+// deff_tangent_rhs_D's map on the device) and in the buffers.
+
+// the arguments and the context's form: before any device work
+static int side_solve_args(deff_ctx *c, const char *who, double rtol, int64_t max_iter, int64_t check_every)
+{
+    if (!(rtol >= 0.0) || !std::isfinite(rtol)) return fail(DEFF_EINVAL, "%s: rtol must be finite and >= 0", who);
+    if (max_iter < 0) return fail(DEFF_EINVAL, "%s: negative max_iter", who);
     if (check_every < 1) return fail(DEFF_EINVAL, "check_every must be >= 1");
-    if (c->slab)
-        return fail(DEFF_EINVAL, "deff_solve_adjoint: not for row-slab contexts (the rows of the image live on several devices)");
+    if (c->slab) return fail(DEFF_EINVAL, "%s: not for row-slab contexts (the rows of the image live on several devices)", who);
     if (c->wrap_links)
-        return fail(DEFF_EINVAL, "deff_solve_adjoint: the system links a wall column to the neighbouring row (explicit-only system)");
+        return fail(DEFF_EINVAL, "%s: the system links a wall column to the neighbouring row (explicit-only system)", who);
     if (!c->have_explicit && !c->have_matfree) return fail(DEFF_ESTATE, "no system assembled");
+    return DEFF_OK;
+}
+
+// the planes, the CG buffers, cg_inv and the verdict on the matrix; a refusal has changed nothing a caller can see
+static int side_solve_prepare(deff_ctx *c, const char *who, CgGeom *geom)
+{
     TRY(use_device(c));
     TRY(resident_check(c));                                          // the scratch and the stream are about to be used
     TRY(explicit_from_image(c));                                     // a native system's planes; nothing to do for any other
@@ -337,8 +345,6 @@ try {
     const size_t items = (size_t)g.per_img * c->nimg;
     TRY(cg_buffers(c, items));
     TRY(cgp_buffers(c));
-    TRY(dev_alloc(&c->adj_lam, c->n));
-    TRY(dev_alloc(&c->adj_w, c->n));
     const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, c->b};
 
     unsigned flags[2] = {0, 0};
@@ -350,14 +356,18 @@ try {
     HIP_TRY(hipMemcpyAsync(flags, c->cg_flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (flags[0] & CGP_FLAG_ROW)
-        return fail(DEFF_EINVAL, "deff_solve_adjoint: a matrix row is not admissible: an active row needs a finite A0 > 0 and "
-                                 "finite links");
+        return fail(DEFF_EINVAL, "%s: a matrix row is not admissible: an active row needs a finite A0 > 0 and finite links", who);
     if (flags[0])
-        return fail(DEFF_EINVAL, "deff_solve_adjoint: the system is not symmetric (a link between two active cells differs from "
-                                 "its partner, or an active row links out of its image)");
+        return fail(DEFF_EINVAL, "%s: the system is not symmetric (a link between two active cells differs from its partner, or "
+                                 "an active row links out of its image)", who);
+    *geom = g;
+    return DEFF_OK;
+}
 
-    // from here on lambda is the new call's
-    c->adj_valid = false;
+// the "cg_*" plan keys, and what every such solve does once its right-hand side is in `rhs`: the mask, the guess 0, the loop
+static int side_solve_run(deff_ctx *c, double *x, double *rhs, const CgGeom &g, double rtol, int64_t max_iter,
+                          int64_t check_every, deff_cg_result *out)
+{
     c->cg_plan_kr = g.kr;
     c->cg_plan_ntx = g.ntx;
     c->cg_plan_items = (int)g.per_img;
@@ -365,23 +375,59 @@ try {
     c->cg_plan_impl = 3;
     const int fold = c->cg_fold == 2 ? 1 : c->cg_fold;
     c->cg_plan_fold = fold;
-    if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(c->adj_w, 0, sizeof(double) * c->n, c->stream));
-    TRY(rows_h2d(c, c->adj_w, w, (size_t)c->rows));
-    hipLaunchKernelGGL(k_cgp_mask_rhs, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, c->cg_inv, c->n, c->adj_w);
+    hipLaunchKernelGGL(k_cgp_mask_rhs, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, c->cg_inv, c->n, rhs);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(c->adj_lam, 0, sizeof(double) * c->n, c->stream));     // the guess, always
+    HIP_TRY(hipMemsetAsync(x, 0, sizeof(double) * c->n, c->stream));              // the guess, always
 
     std::vector<CgScal> hs;
     float ms = 0;
-    TRY(cg_host_loop(c, c->adj_lam, c->adj_w, true, false, fold, g, rtol, max_iter, check_every, hs, &ms));
-    c->adj_valid = true;
+    TRY(cg_host_loop(c, x, rhs, true, false, fold, g, rtol, max_iter, check_every, hs, &ms));
     for (int i = 0; i < c->nimg; ++i) {
         out[i].iters = hs[i].iters;
         out[i].rel_residual = hs[i].rel;
-        out[i].deff_raw = 0.0;                                       // lambda has no flux
+        out[i].deff_raw = 0.0;                                       // neither lambda nor dx has a flux
         out[i].loop_ms = ms;
         out[i].converged = hs[i].rel <= rtol;
     }
+    return DEFF_OK;
+}
+
+extern "C" int deff_solve_adjoint(deff_ctx *c, const double *w, double rtol, int64_t max_iter, int64_t check_every,
+                                  deff_cg_result *out)
+try {
+    if (!c || !w || !out) return fail(DEFF_EINVAL, "NULL argument");
+    TRY(side_solve_args(c, "deff_solve_adjoint", rtol, max_iter, check_every));
+    CgGeom g;
+    TRY(side_solve_prepare(c, "deff_solve_adjoint", &g));
+    TRY(dev_alloc(&c->adj_lam, c->n));
+    TRY(dev_alloc(&c->adj_w, c->n));
+    // from here on lambda is the new call's
+    c->adj_valid = false;
+    if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(c->adj_w, 0, sizeof(double) * c->n, c->stream));
+    TRY(rows_h2d(c, c->adj_w, w, (size_t)c->rows));
+    TRY(side_solve_run(c, c->adj_lam, c->adj_w, g, rtol, max_iter, check_every, out));
+    c->adj_valid = true;
+    return DEFF_OK;
+}
+DEFF_API_CATCH
+
+// The right-hand side is the last deff_tangent_rhs_D's map, copied on the device into tan_w (the map itself stays as it was:
+// the mask is applied to the copy).  With the same numbers in w this is deff_solve_adjoint's arithmetic, bit for bit.
+extern "C" int deff_solve_tangent(deff_ctx *c, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out)
+try {
+    if (!c || !out) return fail(DEFF_EINVAL, "NULL argument");
+    TRY(side_solve_args(c, "deff_solve_tangent", rtol, max_iter, check_every));
+    if (!c->pass_tan.have || !c->tan_rhs)
+        return fail(DEFF_ESTATE, "deff_solve_tangent: no right-hand side for the current system (deff_tangent_rhs_D)");
+    CgGeom g;
+    TRY(side_solve_prepare(c, "deff_solve_tangent", &g));
+    TRY(dev_alloc(&c->tan_dx, c->n));
+    TRY(dev_alloc(&c->tan_w, c->n));
+    // from here on dx is the new call's
+    c->tan_valid = false;
+    HIP_TRY(hipMemcpyAsync(c->tan_w, c->pass_tan.map, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
+    TRY(side_solve_run(c, c->tan_dx, c->tan_w, g, rtol, max_iter, check_every, out));
+    c->tan_valid = true;
     return DEFF_OK;
 }
 DEFF_API_CATCH

@@ -15,8 +15,10 @@
 //   api_sens.hip   the Deff gradient dDeff/dD per cell and its Euler sum (deff_sensitivity, deff_sensitivity_D)
 //   api_vjp.hip    the field adjoint: lambda's buffer (deff_set_adjoint, deff_get_adjoint, deff_device_adjoint) and the pass
 //                  (x, lambda, D) -> dL/dD (deff_field_vjp_D); deff_solve_adjoint itself is in api_cg.hip, beside the loop it runs
-//   cell_pass.hpp  the host path those three share (CellPass below): work-item planner, partial sums, the call's own event
-//                  pair, the D upload, the device-map getter; k_sens and k_vjp are one walk (kernels_facepass.hpp), the three
+//   api_tangent.hip  the field tangent: the pass (x, D, dD) -> r = db - dA x (deff_tangent_rhs_D) and dx's buffer
+//                  (deff_get_tangent, deff_device_tangent); deff_solve_tangent is in api_cg.hip, beside deff_solve_adjoint
+//   cell_pass.hpp  the host path those four share (CellPass below): work-item planner, partial sums, the call's own event
+//                  pair, the D upload, the device-map getter; k_sens, k_vjp and k_tan are one walk (kernels_facepass.hpp), the
 //                  final sums one body (wave_reduce.hpp)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
@@ -78,7 +80,7 @@ struct CellPass {
     // loops alone, which read them at every check and may call a pass in between (a deff_set_progress or deff_image_done_fn
     // callback).
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int kt = 0;                     // tuning "res_kt" / "sens_kt" / "vjp_kt": tiles of 8 rows a wave streams through (0 = planner)
+    int kt = 0;                     // tuning "res_kt" / "sens_kt" / "vjp_kt" / "tan_kt": tiles of 8 rows a wave streams through (0 = planner)
     // deff_get_plan "*_kt" / "*_items" of the last call that launched: the run length used (planner, override and clip
     // applied) and the partial sums the final kernel adds per image
     int plan_kt = 0, plan_items = 0;
@@ -298,7 +300,8 @@ struct deff_ctx {
     //   pass_res   deff_residual / deff_residual_slot / deff_residual_D (api_residual.hip): no map; plan_kt is 0 after deff_residual_D
     //   pass_sens  deff_sensitivity / deff_sensitivity_D (api_sens.hip): the map dDeff/dD, handed out by deff_device_sensitivity
     //   pass_vjp   deff_field_vjp_D (api_vjp.hip): the map dL/dD, handed out by deff_device_field_vjp
-    CellPass pass_res, pass_sens, pass_vjp;
+    //   pass_tan   deff_tangent_rhs_D (api_tangent.hip): the map r = db - dA x, handed out by deff_device_tangent_rhs
+    CellPass pass_res, pass_sens, pass_vjp, pass_tan;
     bool grid_given = false;        // the last deff_assemble_3phase was given a Grid (deff_sensitivity refuses such a system)
 
     // The field adjoint (api_vjp.hip; the solve itself is api_cg.hip's loop).  adj_lam: lambda of A lambda = w (pitch nx, pad
@@ -307,6 +310,13 @@ struct deff_ctx {
     // below: every call that replaces either clears it).
     double *adj_lam = nullptr, *adj_w = nullptr;
     bool adj_valid = false;
+
+    // The field tangent (api_tangent.hip; the solve is api_cg.hip's loop).  tan_dx: dx of A dx = r' (pitch nx, pad column 0),
+    // tan_w: r' = pass_tan's map with the forward system's decoupled cells zeroed; both allocated by the first
+    // deff_solve_tangent.  tan_rhs: pass_tan's map was computed since the current system and image were set, so it may serve
+    // as a right-hand side; tan_valid: dx belongs to them.  adjoint_reset clears both.
+    double *tan_dx = nullptr, *tan_w = nullptr;
+    bool tan_rhs = false, tan_valid = false;
 
     // Native 3-phase system (kernels_fill.hpp, api_fill.hip): the flood fill of the pore space as bitmaps -- one `open` and
     // one `reach` word per 64 columns of a row, fill_nw words per row --, its status words and the tiled form's `changed` words.
@@ -400,8 +410,10 @@ static inline CoefSoA soa_of(deff_ctx *c) { return CoefSoA{c->a0, c->aW, c->aE, 
 // a new system: no dictionary was looked for in it yet
 static inline void dict_reset(deff_ctx *c) { c->dict_tried = false; c->dict_outcome = 0; c->dict_rows = 0; }
 
-// a new system or image: the adjoint field was the old one's (deff_get_adjoint, deff_device_adjoint, deff_field_vjp_D: DEFF_ESTATE)
-static inline void adjoint_reset(deff_ctx *c) { c->adj_valid = false; }
+// a new system or image: the adjoint field was the old one's (deff_get_adjoint, deff_device_adjoint, deff_field_vjp_D:
+// DEFF_ESTATE), and so were the tangent and the map that was its right-hand side (deff_solve_tangent, deff_get_tangent,
+// deff_device_tangent: DEFF_ESTATE)
+static inline void adjoint_reset(deff_ctx *c) { c->adj_valid = false; c->tan_rhs = false; c->tan_valid = false; }
 
 // No C++ exception may unwind through the C ABI: every `extern "C" int` entry point is a
 // function-try-block ending in DEFF_API_CATCH, which turns std::bad_alloc (host vectors sized by the

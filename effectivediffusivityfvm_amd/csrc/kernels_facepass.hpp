@@ -3,22 +3,24 @@
 // written once; a policy P says what a face and a wall contribute and what is done with the cell's sum:
 //   SensPass   the Deff gradient dDeff_raw / dD from (x, D)              k_sens, api_sens.hip
 //   VjpPass    the field adjoint's dL/dD from (x, lambda, D)             k_vjp, api_vjp.hip
-// Both kernels are this one text, so the order of operations per cell, the launch geometry and the order of the Euler sum are
+//   TanPass    the field tangent's right-hand side from (x, dD, D)       k_tan, api_tangent.hip
+// All kernels are this one text, so the order of operations per cell, the launch geometry and the order of the final sum are
 // the same by construction.
 //
 // Per cell p, one term per face (weights as the assembly's, fvm_row.hpp: W / E faces carry wx = dy / dx, N / S faces
 // wy = dx / dy, a wall ww = dy / (dx / 2)).  The chain rule through the harmonic mean H = 2 Dp Dq / (Dp + Dq) is local:
-// dH / dDp = 2 (Dq / (Dp + Dq))^2.  With d[k] = the difference of plane k across the face, v[k] = the cell's own values:
-//   interior face to q   s = Dp + Dq;  t = (s == 0) ? 0 : Dq / s;  c = (2.0 * (t * t)) * (w * P::pair(d))
+// dH / dDp = 2 (Dq / (Dp + Dq))^2.  With v[k] = a cell's own value of plane k:
+//   interior face to q   s = Dp + Dq;  tq = (s == 0) ? 0 : Dq / s;  tp likewise with Dp;  P::face(p, q, w, tq, tp, cp, cq)
 //   left / right wall    e = xp - CL (CR);  c = ww * P::wall(e, v)
 //   no face (an image's first and last row)   c = +0.0
 //   g[p] = P::finish(((cW + cE) + cN) + cS),  and g[p] = 0 where D[p] == 0.  The pad column of an odd mesh width gets 0.
-// s, w and P::pair(d) are the same value seen from either cell of a face, so w * pair(d) is evaluated ONCE per face and gives
-// the term of both cells with one division each (fp_face).
+// A face is evaluated ONCE and gives the term of both its cells with one division each (fp_face): P::face sees both cells
+// and both quotients.  The gradient passes' term is (2.0 * (t * t)) * (w * pair(d)) with d[k] = the difference of plane k
+// across the face, a value that is the same from either cell (fp_pair_face); the tangent's is antisymmetric (TanPass).
 //
-// The second output, euler[img] = sum over the image's cells of D[p] * g[p], is a check that needs no reference (each policy
-// says what it equals).  ORDER of that sum: a lane adds its cells top to bottom through its work item (first cell of its pair,
-// then the second), the 64 lane sums of a wave are combined by wave_reduce.hpp's fixed DPP tree (row_shr 1, 2, 3, 4, 8, then
+// The second output, sum[img] = sum over the image's cells of P::term(D[p], g[p]) -- D[p] * g[p] for the gradient passes, the
+// Euler sum -- is a check that needs no reference (each policy says what it equals).  ORDER of that sum: a lane adds its
+// cells top to bottom through its work item (first cell of its pair, then the second), the 64 lane sums of a wave are combined by wave_reduce.hpp's fixed DPP tree (row_shr 1, 2, 3, 4, 8, then
 // row_bcast 15 and 31: lane 63 holds the sum), and the final kernel (partials_sum_body, one workgroup of 16 waves per image)
 // has thread t add the work items' sums t, t + 1024, ... in that order, the same tree per wave, and thread 0 the 16 wave sums
 // in wave order.  The order depends on the launch geometry only: the same bits on every call.
@@ -33,6 +35,23 @@ constexpr int FP_ROWS = 8;                       // rows per tile
 constexpr int FP_COLS = 128;                     // columns per strip: 2 per lane
 template <bool V> struct FpTag { static constexpr bool value = V; };
 
+// what a lane holds of one row: two cells (.x = a, .y = b) of D and of the policy's planes; and one cell of it
+template <int NF> struct FpRow { double2 v[NF], D; };
+template <int NF> struct FpCell { double v[NF], D; };
+
+// The face of the gradient passes: P::pair(d) of the planes' differences is one value for both cells.
+template <class P>
+__device__ __forceinline__ void fp_pair_face(const FpCell<P::NF> &p, const FpCell<P::NF> &q, double w, double tq, double tp,
+                                             double &cp, double &cq)
+{
+    double d[P::NF];
+#pragma unroll
+    for (int k = 0; k < P::NF; ++k) d[k] = p.v[k] - q.v[k];
+    const double wd = w * P::pair(d);
+    cp = (2.0 * (tq * tq)) * wd;
+    cq = (2.0 * (tp * tp)) * wd;
+}
+
 // The Deff gradient (k_sens).  The system is self-adjoint: Deff_raw = 2E / (CR - CL)^2 with E = 1/2 sum over faces of
 // g_f (dx_f)^2 (the two wall half-faces included), and at the solution dDeff_raw / dg_f = (dx_f)^2 / (CR - CL)^2.  So with
 // e = xp - xq a face gives w * (e * e), a wall ww * (e * e), and g[p] = (((cW + cE) + cN) + cS) / ((CR - CL) * (CR - CL));
@@ -44,8 +63,14 @@ struct SensPass {
     static constexpr int NF = 1;                 // planes besides D: x
     double den;                                  // (CR - CL) * (CR - CL)
     __device__ __forceinline__ static double pair(const double (&d)[1]) { return d[0] * d[0]; }
+    __device__ __forceinline__ static void face(const FpCell<1> &p, const FpCell<1> &q, double w, double tq, double tp, double &cp,
+                                                double &cq)
+    {
+        fp_pair_face<SensPass>(p, q, w, tq, tp, cp, cq);
+    }
     __device__ __forceinline__ static double wall(double e, const double (&)[1]) { return e * e; }
     __device__ __forceinline__ double finish(double s) const { return s / den; }
+    __device__ __forceinline__ static double term(double D, double g) { return D * g; }
 };
 
 // The field adjoint's pass (k_vjp), planes x and l with A l = dL/dx.  dL/dD[p] = -l^T (dA/dD[p] x - db/dD[p]), and over faces
@@ -59,13 +84,44 @@ struct SensPass {
 struct VjpPass {
     static constexpr int NF = 2;                 // planes besides D: x, lambda
     __device__ __forceinline__ static double pair(const double (&d)[2]) { return d[0] * d[1]; }
+    __device__ __forceinline__ static void face(const FpCell<2> &p, const FpCell<2> &q, double w, double tq, double tp, double &cp,
+                                                double &cq)
+    {
+        fp_pair_face<VjpPass>(p, q, w, tq, tp, cp, cq);
+    }
     __device__ __forceinline__ static double wall(double e, const double (&v)[2]) { return e * v[1]; }
     __device__ __forceinline__ double finish(double s) const { return -s; }
+    __device__ __forceinline__ static double term(double D, double g) { return D * g; }
 };
 
-// what a lane holds of one row: two cells (.x = a, .y = b) of D and of the policy's planes; and one cell of it
-template <int NF> struct FpRow { double2 v[NF], D; };
-template <int NF> struct FpCell { double v[NF], D; };
+// The field tangent's right-hand side (k_tan), planes x and dD: for A(D) x = b(D) and a direction dD, A dx = db - dA x =: r.
+// Over the faces of cell p, (dA x - db)[p] = sum over faces da_f (x_p - x_q) + ww dD_p (x_p - C_wall), and da_f = w dH with
+// dH = 2 (Dq / s)^2 dD_p + 2 (Dp / s)^2 dD_q.  With d[p] = (D[p] == 0) ? 0 : dD[p] (a cell that cannot diffuse has no
+// direction), e = xp - xq:
+//   interior face   h = (2.0 * (tq * tq)) * dp + (2.0 * (tp * tp)) * dq;   c = w * (h * e)
+//   wall            c = ww * (dp * (xp - CL (CR)))
+//   r[p] = -(((cW + cE) + cN) + cS).
+// h has the same bits seen from either cell (the two products change places and the addition commutes) and e changes sign
+// exactly, so the other cell's term is -c: one evaluation per face, as in the gradient passes.
+// tests/tangent_model.py states the same expressions in numpy, in this order: the map is compared bit for bit.
+// sum[img] is the squared norm of r: for dD = D it is that of the forward residual b - A x (x is of degree 0 in D).
+// Byte model: x, dD, D read and r written, 32 B per cell.
+struct TanPass {
+    static constexpr int NF = 2;                 // planes besides D: x, dD
+    __device__ __forceinline__ static void face(const FpCell<2> &p, const FpCell<2> &q, double w, double tq, double tp, double &cp,
+                                                double &cq)
+    {
+        const double dp = (p.D == 0) ? 0 : p.v[1], dq = (q.D == 0) ? 0 : q.v[1];
+        const double h = (2.0 * (tq * tq)) * dp + (2.0 * (tp * tp)) * dq;
+        cp = w * (h * (p.v[0] - q.v[0]));
+        cq = -cp;
+    }
+    // (the wall cell's own D == 0 needs no test here: the walk sets its r to 0)
+    __device__ __forceinline__ static double wall(double e, const double (&v)[2]) { return v[1] * e; }
+    __device__ __forceinline__ double finish(double s) const { return -s; }
+    __device__ __forceinline__ static double term(double, double g) { return g * g; }
+};
+
 template <int NF> __device__ __forceinline__ FpCell<NF> fp_a(const FpRow<NF> &r)
 {
     FpCell<NF> c;
@@ -88,14 +144,9 @@ template <class P>
 __device__ __forceinline__ void fp_face(const FpCell<P::NF> &p, const FpCell<P::NF> &q, double w, double &cp, double &cq)
 {
     const double s = p.D + q.D;
-    double d[P::NF];
-#pragma unroll
-    for (int k = 0; k < P::NF; ++k) d[k] = p.v[k] - q.v[k];
-    const double wd = w * P::pair(d);
     const double tq = (s == 0) ? 0 : q.D / s;
     const double tp = (s == 0) ? 0 : p.D / s;
-    cp = (2.0 * (tq * tq)) * wd;
-    cq = (2.0 * (tp * tp)) * wd;
+    P::face(p, q, w, tq, tp, cp, cq);
 }
 
 __device__ __forceinline__ double fp_readlane(double v, int l)
@@ -120,7 +171,7 @@ __device__ __forceinline__ double fp_readlane(double v, int l)
 //    shifts, no per-row selects.  The next tile's outer cells are loaded a tile ahead.
 //  - Only the last strip (EDGE) knows the right wall, the cells beyond it and the pad column, by per-lane selects.
 // Addresses are 64-bit (image base + row base are wave-uniform, the lane adds its column).  No LDS, no waiting.
-// partial[img * per_img + tx * cpi + chunk] = the work item's sum of D * g (cpi = work items per strip and image).
+// partial[img * per_img + tx * cpi + chunk] = the work item's sum of P::term (cpi = work items per strip and image).
 template <class P>
 __device__ __forceinline__ void face_pass(const P &pol, const double *const (&planes)[P::NF], const double *D, int nx, int nxt,
                                           int ny, int nimg, int ntx, int cpi, int kt, double wx, double wy, double ww, double CL,
@@ -219,8 +270,8 @@ __device__ __forceinline__ void face_pass(const P &pol, const double *const (&pl
                 double gb = pol.finish(((mB + eB) + nB) + sB);
                 if (!va || ca.D == 0) ga = 0.0;
                 if (!vb || cb.D == 0) gb = 0.0;
-                if (va) acc += ca.D * ga;
-                if (vb) acc += cb.D * gb;
+                if (va) acc += P::term(ca.D, ga);
+                if (vb) acc += P::term(cb.D, gb);
                 if (st) *reinterpret_cast<double2 *>(gi + (size_t)r * (size_t)nx + col) = make_double2(ga, gb);
                 nA = nA2; nB = nB2;
                 c = n; n = f;

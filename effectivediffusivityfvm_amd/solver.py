@@ -479,6 +479,74 @@ class Solver:
         check(self._L.deff_device_field_vjp(self._ctx, C.byref(p), C.byref(pitch)))
         return p.value, pitch.value
 
+    # -- field tangent: dx along a direction dD ---------------------------
+    def tangent_rhs(self, D, dD, CL, CR, timing=False):
+        """r = db - dA x along the direction dD, from the current field and the diffusivity plane D, both (rows, nx), in one
+        pass (deff_tangent_rhs_D): (r, norm2) with r as (ny, nx), or (nimg, ny, nx) for a stack, and norm2 = sum of r * r per
+        image (a float, or an array); for dD = D it is the forward residual's.  timing=True appends the device time in ms."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        dD = np.ascontiguousarray(dD, dtype=np.float64)
+        assert D.size == self.nx * self.rows and dD.size == D.size
+        r = np.empty((self.rows, self.nx), dtype=np.float64)
+        n2 = (C.c_double * self.nimg)()
+        ms = C.c_float()
+        check(self._L.deff_tangent_rhs_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p), float(CL),
+                                         float(CR), r.ctypes.data_as(C.c_void_p), n2, C.byref(ms) if timing else None))
+        r = r if self.nimg == 1 else r.reshape(self.nimg, self.ny, self.nx)
+        norm2 = n2[0] if self.nimg == 1 else np.array(n2[:])
+        return (r, norm2, ms.value) if timing else (r, norm2)
+
+    def device_tangent_rhs_ptr(self):
+        """(device pointer, row pitch in bytes) of the last tangent_rhs map; valid until the next one or close()."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_device_tangent_rhs(self._ctx, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+    def solve_tangent(self, rtol=1e-10, max_iter=1_000_000, check_every=64):
+        """A dx = r on the current matrix with homogeneous walls (deff_solve_tangent), r the last tangent_rhs map, read on the
+        device: solve_adjoint's iteration into a buffer of its own -- the field, the system, lambda and the map stay as they
+        are.  One image: a CGResult (deff_raw 0.0, MFL / MFR None); a stack: a list, one per image."""
+        res = (CGResultC * self.nimg)()
+        check(self._L.deff_solve_tangent(self._ctx, float(rtol), int(max_iter), int(check_every), res))
+        outs = []
+        for k in range(self.nimg):
+            out = CGResult()
+            out.iters, out.rel_residual, out.deff_raw = res[k].iters, res[k].rel_residual, res[k].deff_raw
+            out.converged, out.loop_ms = bool(res[k].converged), res[k].loop_ms
+            out.MFL = out.MFR = None
+            outs.append(out)
+        return outs[0] if self.nimg == 1 else outs
+
+    def get_tangent(self):
+        """The tangent field dx as (rows, nx); DeffError (DEFF_ESTATE) while none is valid for the current system."""
+        dx = np.empty((self.rows, self.nx), dtype=np.float64)
+        check(self._L.deff_get_tangent(self._ctx, dx.ctypes.data_as(C.c_void_p)))
+        return dx
+
+    def device_tangent_ptr(self):
+        """(device pointer, row pitch in bytes) of the tangent field; the pitch is device_field_ptr's."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_device_tangent(self._ctx, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+    def field_jvp(self, D, dD, CL, CR, rtol=1e-10, max_iter=1_000_000, check_every=64):
+        """dx = (dx/dD) dD of the current field: tangent_rhs + solve_tangent + get_tangent, as (rows, nx).  RuntimeError if the
+        solve does not reach rtol."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        dD = np.ascontiguousarray(dD, dtype=np.float64)
+        assert D.size == self.nx * self.rows and dD.size == D.size
+        check(self._L.deff_tangent_rhs_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p), float(CL),
+                                         float(CR), None, None, None))         # the map stays on the device
+        rs = self.solve_tangent(rtol=rtol, max_iter=max_iter, check_every=check_every)
+        rs = rs if isinstance(rs, list) else [rs]
+        bad = [k for k, r in enumerate(rs) if not r.converged]
+        if bad:
+            raise RuntimeError(f"field_jvp: CG did not converge to rtol {rtol} for image(s) {bad} "
+                               f"(rel_residual {[rs[k].rel_residual for k in bad]}, max_iter {max_iter})")
+        return self.get_tangent()
+
     def set_progress(self, fn):
         """fn(iter, deff_raw, change) after every convergence check, or None."""
         if fn is None:

@@ -100,6 +100,7 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  *   about 4 096 work items per launch; clipped to the image's tile rows; deff_get_plan "res_kt"),
  * "sens_kt" (deff_sensitivity / deff_sensitivity_D: the same for the gradient pass; deff_get_plan "sens_kt"),
  * "vjp_kt" (deff_field_vjp_D: the same for the field adjoint's pass; deff_get_plan "vjp_kt"),
+ * "tan_kt" (deff_tangent_rhs_D: the same for the field tangent's pass; deff_get_plan "tan_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
  *   run every pass between two checks in ONE launch, neighbouring tiles synchronised by flags: 1 = one launch per
  *   pass instead; a resident launch that cannot make progress -- another process holds part of the GPU -- gives up
@@ -139,7 +140,8 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * 0 after deff_residual_D, which has no runs) and "res_items" (partial sums added per image by the final reduction:
  * strips of 128 columns x ceil(tile rows / res_kt), or for deff_residual_D rows x segments of 256 columns).  Of the last
  * deff_sensitivity / deff_sensitivity_D that launched: "sens_kt" and "sens_items", with the same meaning; of the last
- * deff_field_vjp_D that launched: "vjp_kt" and "vjp_items", likewise.  Of the flood fill
+ * deff_field_vjp_D that launched: "vjp_kt" and "vjp_items", and of the last deff_tangent_rhs_D: "tan_kt" and "tan_items",
+ * likewise.  Of the flood fill
  * on the device (deff_assemble_3phase_native): "fill_impl" (form of the last fill: 1 = one workgroup per image, 2 = row tiles),
  * "fill_launches" (kernel launches of the last fill), "fill_rounds" (most rounds one workgroup of it took), "fill_runs" (fills
  * computed since the context was created: a continuation stage on the same image computes none), "fill_fallbacks" (images
@@ -437,6 +439,55 @@ int deff_device_adjoint(deff_ctx *ctx, void **d_lam, size_t *row_pitch_bytes);
 int deff_field_vjp_D(deff_ctx *ctx, const double *D, double CL, double CR,
                      double *g /* nimg*ny*nx, may be NULL */, double *euler /* [nimg], may be NULL */, float *ms);
 int deff_device_field_vjp(deff_ctx *ctx, void **d_g, size_t *row_pitch_bytes);
+/* ---- field tangent: dx = (dx/dD) dD, the field's derivative along a direction dD of the diffusivity map, one pass and one
+ * solve (nothing like it in the reference): the forward-mode counterpart of the field adjoint, J v where that gives J^T w.
+ * Differentiating A(D) x = b(D) along dD:  A dx = db - dA x =: r  with homogeneous walls, the same matrix again.
+ *
+ * deff_tangent_rhs_D: r[p] from the current field x, D and dD, in one pass.  With dx, dy of deff_mesh, wx = dy / dx,
+ * wy = dx / dy, ww = dy / (dx / 2.0), d[p] = (D[p] == 0) ? 0 : dD[p], x and d of cell p and of its neighbour q:
+ *   interior face of p towards q (weight w = wx for W / E, wy for N / S):
+ *       s = Dp + Dq;  tq = (s == 0) ? 0 : Dq / s;  tp = (s == 0) ? 0 : Dp / s;
+ *       h = (2.0 * (tq * tq)) * dp + (2.0 * (tp * tp)) * dq;  e = xp - xq;  c = w * (h * e)
+ *   left / right wall:  c = ww * (dp * (xp - CL (CR)))          no face (first / last row of an image):  c = +0.0
+ *   r[p] = -(((cW + cE) + cN) + cS),   and r[p] = 0 where D[p] == 0.
+ * These doubles, in this order (tests/tangent_model.py states them in numpy; the library is built without contraction).  h is
+ * the change of the face's harmonic mean; it has the same bits seen from either cell and e changes sign exactly, so a face
+ * is evaluated once for both.  norm2[k] = sum over image k of r[p] * r[p], a wave-level reduction in a fixed order
+ * (csrc/kernels_facepass.hpp), the same bits on every call.  x is of degree 0 in D, so for dD = D the pass returns the
+ * forward residual b - A x and norm2 its squared norm: ~0 for a converged x, a check that needs no reference.  r
+ * (nimg*ny*nx, true width) and norm2 ([nimg]) may each be NULL; *ms (may be NULL) = device time of the pass, on an event
+ * pair of its own.
+ *   D and dD [nimg*ny*nx] on the host, as deff_field_vjp_D takes D.  CR == CL is allowed.
+ *   Plain and stack contexts; row slabs: DEFF_EINVAL; NULL ctx, D or dD: DEFF_EINVAL; no field: DEFF_ESTATE.  Needs no system.
+ *   Pending work is settled first and every image's newest field is read.  The call writes only its own map, its partial sums
+ *   and the upload scratch (which holds both planes: 2 n doubles); a refused call leaves the previous map alone.  Negative or
+ *   non-finite D or dD: unspecified values, never a fault.
+ * Tuning "tan_kt" and deff_get_plan "tan_kt" / "tan_items": as "vjp_kt" / "vjp_items", the same planner.
+ * deff_device_tangent_rhs: the device buffer of the last map (row pitch as deff_device_field, the pad column of an odd width
+ *   holds 0), valid until the next deff_tangent_rhs_D or deff_destroy; DEFF_ESTATE before one exists.
+ *
+ * deff_solve_tangent: A dx = r' on the context's CURRENT matrix, r' = the last deff_tangent_rhs_D's map with the forward
+ *   system's decoupled rows zeroed, read on the device (no host round trip); dx goes into a buffer of the context's own.
+ *   Everything else is deff_solve_adjoint with w = r, bit for bit: the iteration on the coefficient planes from the guess 0,
+ *   "cg_fold", the stop, the true-residual rounds, out[k] (deff_raw 0.0).
+ *   Writes: dx, r' (a copy: the map stays as it was), the CG work vectors and the "cg_*" plan keys.  Left as they are: lambda
+ *   and its validity, the field, the system, the row dictionary, the Jacobi plans, the sensitivity and field-adjoint maps.
+ *   Refusals, each changing nothing: those of deff_solve_adjoint, and DEFF_ESTATE while there is no right-hand side map for
+ *   the current system.
+ * The tangent's lifetime: deff_solve_tangent makes dx valid; every call that invalidates the adjoint field (see there)
+ *   invalidates dx and the map's use as a right-hand side -- a new deff_tangent_rhs_D is needed; deff_device_tangent_rhs still
+ *   hands the old map out.  While dx is invalid deff_get_tangent and deff_device_tangent return DEFF_ESTATE.
+ * deff_get_tangent: dx[nimg*ny*nx] to the host, true width.  deff_device_tangent: its device buffer, row pitch as
+ *   deff_device_field; valid until the context is destroyed, its contents until the next deff_solve_tangent.  NULL arguments
+ *   and row-slab contexts: DEFF_EINVAL.
+ * A Gauss-Newton product J^T (J v): deff_tangent_rhs_D(v), deff_solve_tangent, deff_get_tangent, deff_solve_adjoint(w = dx),
+ *   deff_field_vjp_D. */
+int deff_tangent_rhs_D(deff_ctx *ctx, const double *D, const double *dD, double CL, double CR,
+                       double *r /* nimg*ny*nx, may be NULL */, double *norm2 /* [nimg], may be NULL */, float *ms);
+int deff_device_tangent_rhs(deff_ctx *ctx, void **d_r, size_t *row_pitch_bytes);
+int deff_solve_tangent(deff_ctx *ctx, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out /* [nimg] */);
+int deff_get_tangent(deff_ctx *ctx, double *dx);
+int deff_device_tangent(deff_ctx *ctx, void **d_dx, size_t *row_pitch_bytes);
 /* sweep-kernel launches issued by the last deff_sweeps()/deff_solve() and the sweeps one
  * temporally blocked launch performs (1 for the single-sweep kernels).  A chained launch of the streaming kernel
  * (deff_get_plan "tb_chain" = 1: several passes of *sweeps_per_pass sweeps in one launch) counts its PASSES, so that
