@@ -3,7 +3,10 @@ the backward pass the library's one-pass gradient (deff_sensitivity_D) -- no sec
 The concentration field as one: the same forward solve; the backward pass is one adjoint solve with the incoming gradient as
 right-hand side (deff_solve_adjoint) and one pass over (x, lambda, D) (deff_field_vjp_D), for any loss on the field.
 Both ops have a jvp for torch.autograd.forward_ad: Deff's is a sum over its gradient map, the field's one pass over (x, D, dD)
-(deff_tangent_rhs_D) and one solve (deff_solve_tangent).  torch.func transforms are not supported (no setup_context).
+(deff_tangent_rhs_D) and one solve (deff_solve_tangent).  Deff is twice differentiable: under create_graph its backward hands
+the gradient map out through a second Function whose backward is the Hessian-vector product -- the forward solve again, one
+tangent solve and one pass over (x, dx, dD, D) (deff_sensitivity_hvp_D).  torch.func transforms are not supported (no
+setup_context).
 
 torch is imported inside the functions only: importing the package does not import it.  D makes a host round trip (plumbing;
 the solve and the gradient run in the library's HIP kernels)."""
@@ -12,6 +15,66 @@ import numpy as np
 from .solver import Solver
 
 _FN = None
+_GRAD_FN = None
+
+
+def _grad_function():
+    """The torch.autograd.Function that carries Deff's gradient map through a graph -- the second derivative of
+    effective_diffusivity -- and the one its backward pass applies, the Hessian-vector product.  Created at first use."""
+    global _GRAD_FN
+    if _GRAD_FN is not None:
+        return _GRAD_FN
+    import torch
+
+    class _DeffHessVec(torch.autograd.Function):
+        """w -> H w per image, H the Hessian of deff_raw at D.  Linear in w and H is symmetric, so its own vjp is itself:
+        torch.autograd.functional.hvp differentiates the backward pass with respect to the incoming gradient.  D is a
+        constant here: third derivatives are not computed."""
+        @staticmethod
+        def forward(ctx, D, w, CL, CR, rtol, max_iter, solver):
+            Dh = np.ascontiguousarray(D.detach().cpu().numpy(), dtype=np.float64)
+            nimg = Dh.shape[0] if Dh.ndim == 3 else 1
+            ny, nx = Dh.shape[-2:]
+            wh = np.ascontiguousarray(w.detach().cpu().numpy(), dtype=np.float64)
+            s = solver if solver is not None else Solver(nx, ny, nimg=nimg)
+            try:
+                # the forward pass's own calls: the same bits of x, whatever happened to the solver since
+                s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
+                s.init_linear(CL, CR)
+                s.set_tuning("cg_planes", 1)
+                _converged("effective_diffusivity (second order)", s.solve_cg(rtol=rtol, max_iter=max_iter), rtol, max_iter)
+                try:
+                    hv, _ = s.deff_hvp(Dh.reshape(nimg * ny, nx), wh.reshape(nimg * ny, nx), CL, CR, rtol=rtol, max_iter=max_iter)
+                except RuntimeError as e:
+                    raise RuntimeError(f"effective_diffusivity (second order): {e}") from None
+            finally:
+                if solver is None:
+                    s.close()
+            ctx.save_for_backward(D)
+            ctx.deff_args = (CL, CR, rtol, max_iter, solver)
+            return torch.from_numpy(np.ascontiguousarray(hv).reshape(Dh.shape)).to(w.device)
+
+        @staticmethod
+        def backward(ctx, u):
+            (D,) = ctx.saved_tensors
+            return None, _DeffHessVec.apply(D, u, *ctx.deff_args), None, None, None, None, None
+
+    class _DeffGradient(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, D, g, CL, CR, rtol, max_iter, solver):
+            # g(D) was computed by effective_diffusivity's forward pass: nothing is solved or copied here
+            ctx.save_for_backward(D)
+            ctx.deff_args = (CL, CR, rtol, max_iter, solver)
+            return g.view_as(g)
+
+        @staticmethod
+        def backward(ctx, w):
+            # H is symmetric: the vjp of the gradient map is the Hessian-vector product H w, per image
+            (D,) = ctx.saved_tensors
+            return _DeffHessVec.apply(D.detach(), w, *ctx.deff_args), None, None, None, None, None, None
+
+    _GRAD_FN = _DeffGradient
+    return _GRAD_FN
 
 
 def _function():
@@ -47,20 +110,24 @@ def _function():
                     s.close()
             deff = np.array([r.deff_raw for r in rs], dtype=np.float64)
             g = torch.from_numpy(np.ascontiguousarray(g).reshape(Dh.shape)).to(D.device)
-            ctx.save_for_backward(g)
+            ctx.save_for_backward(g, D)
             ctx.save_for_forward(g)
+            ctx.deff_args = (CL, CR, rtol, max_iter, solver)
             out = torch.from_numpy(deff).to(D.device)
             return out if stack else out[0]
 
         @staticmethod
         def backward(ctx, grad_out):
-            (g,) = ctx.saved_tensors
+            g, D = ctx.saved_tensors
+            if torch.is_grad_enabled() and D.requires_grad:
+                # create_graph: the map as a function of D, whose backward is the Hessian-vector product
+                g = _grad_function().apply(D, g, *ctx.deff_args)
             return grad_out[..., None, None] * g, None, None, None, None, None
 
         @staticmethod
         def jvp(ctx, tD, *_):
             # forward mode (torch.autograd.forward_ad): the map is the whole Jacobian, one row per image
-            (g,) = ctx.saved_tensors
+            g = ctx.saved_tensors[0]
             return (g * tD).sum((-2, -1))
 
     _FN = _EffectiveDiffusivity
@@ -72,7 +139,16 @@ def effective_diffusivity(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, sol
     tensor on D's device, shape () or (nimg,), differentiable with respect to D.  Forward: deff_assemble_from_D, the linear
     guess, conjugate gradients on the coefficient planes to rtol (raises RuntimeError if they do not converge), then the
     gradient map of the converged field; backward: grad_out[..., None, None] * g.  `solver`: a Solver of the same shape to
-    reuse (its system, field and the tuning key "cg_planes" are overwritten); otherwise one is created and closed."""
+    reuse (its system, field and the tuning key "cg_planes" are overwritten); otherwise one is created and closed.
+    Twice differentiable: under create_graph=True the backward pass returns the same numbers with g as a function of D, and a
+    backward pass through that (torch.autograd.functional.hvp, Newton-CG, a penalty on the gradient) gets H w, H the Hessian of
+    deff_raw, per image: the system is assembled from D again, the linear guess taken and the forward pass's CG run again
+    (the same bits of x), then Solver.deff_hvp -- one pass over (x, D, w), one tangent solve to rtol, one pass over
+    (x, dx, w, D) -- on `solver` when one was passed (its system, field, tangent right-hand side map, tangent field, the
+    Hessian-vector map and "cg_planes" are overwritten), otherwise on a Solver created and closed for that pass; RuntimeError
+    if a solve does not converge.  H w is in turn differentiable with respect to w (by H again: functional.hvp's double
+    backward needs it); D is a constant there, so third derivatives come out as zero, and a jvp of the gradient map and
+    torch.func are not supported.  First-order use pays nothing for this: no extra solve or copy, the same bits."""
     import torch
     if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() not in (2, 3):
         raise TypeError("D must be a float64 tensor of shape (ny, nx) or (nimg, ny, nx)")

@@ -68,7 +68,7 @@ DEFF_API_CATCH
 static int tangent_common(deff_ctx *c, const char *who)
 {
     if (c->slab) return fail(DEFF_EINVAL, "%s: not for row-slab contexts (the rows of the image live on several devices)", who);
-    if (!c->tan_valid) return fail(DEFF_ESTATE, "%s: no tangent field for the current system (deff_solve_tangent)", who);
+    if (!c->tan_valid) return fail(DEFF_ESTATE, "%s: no tangent field for the current system (deff_solve_tangent / deff_set_tangent)", who);
     return DEFF_OK;
 }
 

@@ -17,8 +17,10 @@
 //                  (x, lambda, D) -> dL/dD (deff_field_vjp_D); deff_solve_adjoint itself is in api_cg.hip, beside the loop it runs
 //   api_tangent.hip  the field tangent: the pass (x, D, dD) -> r = db - dA x (deff_tangent_rhs_D) and dx's buffer
 //                  (deff_get_tangent, deff_device_tangent); deff_solve_tangent is in api_cg.hip, beside deff_solve_adjoint
-//   cell_pass.hpp  the host path those four share (CellPass below): work-item planner, partial sums, the call's own event
-//                  pair, the D upload, the device-map getter; k_sens, k_vjp and k_tan are one walk (kernels_facepass.hpp), the
+//   api_hvp.hip    the Deff Hessian-vector product: the pass (x, dx, dD, D) -> H dD (deff_sensitivity_hvp_D) and a caller's
+//                  own tangent (deff_set_tangent)
+//   cell_pass.hpp  the host path those five share (CellPass below): work-item planner, partial sums, the call's own event
+//                  pair, the D upload, the device-map getter; k_sens, k_vjp, k_tan and k_hvp are one walk (kernels_facepass.hpp), the
 //                  final sums one body (wave_reduce.hpp)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
@@ -80,7 +82,7 @@ struct CellPass {
     // loops alone, which read them at every check and may call a pass in between (a deff_set_progress or deff_image_done_fn
     // callback).
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int kt = 0;                     // tuning "res_kt" / "sens_kt" / "vjp_kt" / "tan_kt": tiles of 8 rows a wave streams through (0 = planner)
+    int kt = 0;                     // tuning "res_kt" / "sens_kt" / "vjp_kt" / "tan_kt" / "hvp_kt": tiles of 8 rows a wave streams through (0 = planner)
     // deff_get_plan "*_kt" / "*_items" of the last call that launched: the run length used (planner, override and clip
     // applied) and the partial sums the final kernel adds per image
     int plan_kt = 0, plan_items = 0;
@@ -301,7 +303,8 @@ struct deff_ctx {
     //   pass_sens  deff_sensitivity / deff_sensitivity_D (api_sens.hip): the map dDeff/dD, handed out by deff_device_sensitivity
     //   pass_vjp   deff_field_vjp_D (api_vjp.hip): the map dL/dD, handed out by deff_device_field_vjp
     //   pass_tan   deff_tangent_rhs_D (api_tangent.hip): the map r = db - dA x, handed out by deff_device_tangent_rhs
-    CellPass pass_res, pass_sens, pass_vjp, pass_tan;
+    //   pass_hvp   deff_sensitivity_hvp_D (api_hvp.hip): the map H dD, handed out by deff_device_sensitivity_hvp
+    CellPass pass_res, pass_sens, pass_vjp, pass_tan, pass_hvp;
     bool grid_given = false;        // the last deff_assemble_3phase was given a Grid (deff_sensitivity refuses such a system)
 
     // The field adjoint (api_vjp.hip; the solve itself is api_cg.hip's loop).  adj_lam: lambda of A lambda = w (pitch nx, pad
@@ -313,8 +316,9 @@ struct deff_ctx {
 
     // The field tangent (api_tangent.hip; the solve is api_cg.hip's loop).  tan_dx: dx of A dx = r' (pitch nx, pad column 0),
     // tan_w: r' = pass_tan's map with the forward system's decoupled cells zeroed; both allocated by the first
-    // deff_solve_tangent.  tan_rhs: pass_tan's map was computed since the current system and image were set, so it may serve
-    // as a right-hand side; tan_valid: dx belongs to them.  adjoint_reset clears both.
+    // deff_solve_tangent (tan_dx by deff_set_tangent too: api_hvp.hip, whose pass reads it).  tan_rhs: pass_tan's map was
+    // computed since the current system and image were set, so it may serve as a right-hand side; tan_valid: dx belongs to
+    // them.  adjoint_reset clears both.
     double *tan_dx = nullptr, *tan_w = nullptr;
     bool tan_rhs = false, tan_valid = false;
 

@@ -4,6 +4,7 @@
 //   SensPass   the Deff gradient dDeff_raw / dD from (x, D)              k_sens, api_sens.hip
 //   VjpPass    the field adjoint's dL/dD from (x, lambda, D)             k_vjp, api_vjp.hip
 //   TanPass    the field tangent's right-hand side from (x, dD, D)       k_tan, api_tangent.hip
+//   HvpPass    the Deff Hessian-vector product from (x, dx, dD, D)       k_hvp, api_hvp.hip
 // All kernels are this one text, so the order of operations per cell, the launch geometry and the order of the final sum are
 // the same by construction.
 //
@@ -18,7 +19,7 @@
 // and both quotients.  The gradient passes' term is (2.0 * (t * t)) * (w * pair(d)) with d[k] = the difference of plane k
 // across the face, a value that is the same from either cell (fp_pair_face); the tangent's is antisymmetric (TanPass).
 //
-// The second output, sum[img] = sum over the image's cells of P::term(D[p], g[p]) -- D[p] * g[p] for the gradient passes, the
+// The second output, sum[img] = sum over the image's cells of P::term(cell p, g[p]) -- D[p] * g[p] for the gradient passes, the
 // Euler sum -- is a check that needs no reference (each policy says what it equals).  ORDER of that sum: a lane adds its
 // cells top to bottom through its work item (first cell of its pair, then the second), the 64 lane sums of a wave are combined by wave_reduce.hpp's fixed DPP tree (row_shr 1, 2, 3, 4, 8, then
 // row_bcast 15 and 31: lane 63 holds the sum), and the final kernel (partials_sum_body, one workgroup of 16 waves per image)
@@ -70,7 +71,7 @@ struct SensPass {
     }
     __device__ __forceinline__ static double wall(double e, const double (&)[1]) { return e * e; }
     __device__ __forceinline__ double finish(double s) const { return s / den; }
-    __device__ __forceinline__ static double term(double D, double g) { return D * g; }
+    __device__ __forceinline__ static double term(const FpCell<1> &c, double g) { return c.D * g; }
 };
 
 // The field adjoint's pass (k_vjp), planes x and l with A l = dL/dx.  dL/dD[p] = -l^T (dA/dD[p] x - db/dD[p]), and over faces
@@ -91,7 +92,7 @@ struct VjpPass {
     }
     __device__ __forceinline__ static double wall(double e, const double (&v)[2]) { return e * v[1]; }
     __device__ __forceinline__ double finish(double s) const { return -s; }
-    __device__ __forceinline__ static double term(double D, double g) { return D * g; }
+    __device__ __forceinline__ static double term(const FpCell<2> &c, double g) { return c.D * g; }
 };
 
 // The field tangent's right-hand side (k_tan), planes x and dD: for A(D) x = b(D) and a direction dD, A dx = db - dA x =: r.
@@ -119,7 +120,42 @@ struct TanPass {
     // (the wall cell's own D == 0 needs no test here: the walk sets its r to 0)
     __device__ __forceinline__ static double wall(double e, const double (&v)[2]) { return v[1] * e; }
     __device__ __forceinline__ double finish(double s) const { return -s; }
-    __device__ __forceinline__ static double term(double, double g) { return g * g; }
+    __device__ __forceinline__ static double term(const FpCell<2> &, double g) { return g * g; }
+};
+
+// The Deff Hessian-vector product (k_hvp), planes x, y = dx (the field tangent along dD) and dD.  g = dDeff_raw / dD is
+// SensPass's map, a function of (x, D), so H dD = dg/dD . dD + dg/dx . dx.  Both parts are face-local: a face gives cell p
+// (2 tq^2) w e^2 with tq = Dq / s, and along dD the quotient moves by u = (tp dq - tq dp) / s, the difference e by f = yp - yq.
+// With d[p] = (D[p] == 0) ? 0 : dD[p] (a cell that cannot diffuse has no direction):
+//   interior face   u = (s == 0) ? 0 : (tp * dq - tq * dp) / s;  e = xp - xq;  f = yp - yq;
+//                   c = w * ((4.0 * tq) * (u * (e * e)) + (4.0 * (tq * tq)) * (e * f))
+//   wall            e = xp - CL (CR);  c = ww * (2.0 * (e * yp))
+//   hv[p] = (((cW + cE) + cN) + cS) / ((CR - CL) * (CR - CL)),  hv[p] = 0 where D[p] == 0.
+// Seen from q, u is exactly -u (the two products change places in a subtraction) and e * e, e * f have the same bits (both
+// factors change sign exactly; a zero may differ in sign, which no comparison of doubles sees), so
+//   cq = w * ((4.0 * tp) * ((-u) * (e * e)) + (4.0 * (tp * tp)) * (e * f)):
+// one evaluation per face, three FP64 divisions per face (tq, tp, u) where the other policies have two.
+// tests/sens_hvp_model.py states the same expressions in numpy, in this order: the map is compared bit for bit.
+// sum[img] = sum of d[p] * hv[p] = dD^T H dD, the curvature of Deff_raw along dD: never positive at a converged field with
+// its own tangent (Deff is a minimum over fields of functions linear in D, hence concave).
+// Byte model: x, dx, dD, D read and hv written, 40 B per cell.
+struct HvpPass {
+    static constexpr int NF = 3;                 // planes besides D: x, dx, dD
+    double den;                                  // (CR - CL) * (CR - CL)
+    __device__ __forceinline__ static void face(const FpCell<3> &p, const FpCell<3> &q, double w, double tq, double tp, double &cp,
+                                                double &cq)
+    {
+        const double s = p.D + q.D;
+        const double dp = (p.D == 0) ? 0 : p.v[2], dq = (q.D == 0) ? 0 : q.v[2];
+        const double u = (s == 0) ? 0 : (tp * dq - tq * dp) / s;
+        const double e = p.v[0] - q.v[0], f = p.v[1] - q.v[1];
+        const double ee = e * e, ef = e * f;
+        cp = w * ((4.0 * tq) * (u * ee) + (4.0 * (tq * tq)) * ef);
+        cq = w * ((4.0 * tp) * ((-u) * ee) + (4.0 * (tp * tp)) * ef);
+    }
+    __device__ __forceinline__ static double wall(double e, const double (&v)[3]) { return 2.0 * (e * v[1]); }
+    __device__ __forceinline__ double finish(double s) const { return s / den; }
+    __device__ __forceinline__ static double term(const FpCell<3> &c, double g) { return ((c.D == 0) ? 0 : c.v[2]) * g; }
 };
 
 template <int NF> __device__ __forceinline__ FpCell<NF> fp_a(const FpRow<NF> &r)
@@ -168,7 +204,9 @@ __device__ __forceinline__ double fp_readlane(double v, int l)
 //  - The strip's outer neighbours: per tile, lanes 0...7 load the cell west of the strip for one row each (and the strip's
 //    own first cell) and evaluate that face, or the left wall's term; lanes 8...15 load the cell east of it.  A row takes
 //    them from there with v_readlane: lane 0's W term and lane 63's E neighbour enter as the `old` operand of the lane
-//    shifts, no per-row selects.  The next tile's outer cells are loaded a tile ahead.
+//    shifts, no per-row selects.  The next tile's outer cells are loaded a tile ahead -- with three planes (HvpPass) into the
+//    same registers during the tile's last row, once that row has taken its own: a second set would cost 16 VGPRs and the
+//    fourth wave per SIMD.
 //  - Only the last strip (EDGE) knows the right wall, the cells beyond it and the pad column, by per-lane selects.
 // Addresses are 64-bit (image base + row base are wave-uniform, the lane adds its column).  No LDS, no waiting.
 // partial[img * per_img + tx * cpi + chunk] = the work item's sum of P::term (cpi = work items per strip and image).
@@ -180,6 +218,7 @@ __device__ __forceinline__ void face_pass(const P &pol, const double *const (&pl
     constexpr int NF = P::NF;
     using Row = FpRow<NF>;
     using Cell = FpCell<NF>;
+    constexpr bool OUTER_IN_PLACE = NF >= 3;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const size_t gy = (size_t)nimg * (size_t)cpi;
@@ -239,7 +278,7 @@ __device__ __forceinline__ void face_pass(const P &pol, const double *const (&pl
         double acc = 0.0;
 #pragma unroll 1
         for (int l = l_begin; l < l_end; l += FP_ROWS) {
-            load_outer(l + FP_ROWS, o2);
+            if constexpr (!OUTER_IN_PLACE) load_outer(l + FP_ROWS, o2);
             double hw;                                           // lanes 0...7: the W term of the strip's first cell in row l + lane
             if (wwall) hw = ww * P::wall(o.a.v[0] - CL, o.a.v);
             else fp_face<P>(o.a, o.h, wx, hw, unused);
@@ -254,6 +293,9 @@ __device__ __forceinline__ void face_pass(const P &pol, const double *const (&pl
 #pragma unroll
                 for (int k = 0; k < NF; ++k) ce.v[k] = dpp_f64_keep<0x130>(ca.v[k], fp_readlane(o.h.v[k], 8 + q));   // wave_shl:1
                 ce.D = dpp_f64_keep<0x130>(ca.D, fp_readlane(o.h.D, 8 + q));
+                if constexpr (OUTER_IN_PLACE) {
+                    if (q == FP_ROWS - 1) load_outer(l + FP_ROWS, o);
+                }
                 double mA, mB, eB, eQ, sA, sB, nA2, nB2;
                 fp_face<P>(ca, cb, wx, mA, mB);                      // a | b
                 fp_face<P>(cb, ce, wx, eB, eQ);                      // b | the next lane's a
@@ -270,13 +312,13 @@ __device__ __forceinline__ void face_pass(const P &pol, const double *const (&pl
                 double gb = pol.finish(((mB + eB) + nB) + sB);
                 if (!va || ca.D == 0) ga = 0.0;
                 if (!vb || cb.D == 0) gb = 0.0;
-                if (va) acc += P::term(ca.D, ga);
-                if (vb) acc += P::term(cb.D, gb);
+                if (va) acc += P::term(ca, ga);
+                if (vb) acc += P::term(cb, gb);
                 if (st) *reinterpret_cast<double2 *>(gi + (size_t)r * (size_t)nx + col) = make_double2(ga, gb);
                 nA = nA2; nB = nB2;
                 c = n; n = f;
             }
-            o = o2;
+            if constexpr (!OUTER_IN_PLACE) o = o2;
         }
         const double s = wave_sum_to_lane63(acc);
         if (lane == 63) partial[(size_t)img * ((size_t)ntx * cpi) + (size_t)tx * cpi + chunk] = s;

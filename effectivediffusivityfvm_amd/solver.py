@@ -537,15 +537,61 @@ class Solver:
         D = np.ascontiguousarray(D, dtype=np.float64)
         dD = np.ascontiguousarray(dD, dtype=np.float64)
         assert D.size == self.nx * self.rows and dD.size == D.size
+        self._tangent_along("field_jvp", D, dD, CL, CR, rtol, max_iter, check_every)
+        return self.get_tangent()
+
+    def _tangent_along(self, who, D, dD, CL, CR, rtol, max_iter, check_every):
+        """tangent_rhs with the map left on the device, then solve_tangent; RuntimeError if the solve does not reach rtol."""
         check(self._L.deff_tangent_rhs_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p), float(CL),
-                                         float(CR), None, None, None))         # the map stays on the device
+                                         float(CR), None, None, None))
         rs = self.solve_tangent(rtol=rtol, max_iter=max_iter, check_every=check_every)
         rs = rs if isinstance(rs, list) else [rs]
         bad = [k for k, r in enumerate(rs) if not r.converged]
         if bad:
-            raise RuntimeError(f"field_jvp: CG did not converge to rtol {rtol} for image(s) {bad} "
+            raise RuntimeError(f"{who}: CG did not converge to rtol {rtol} for image(s) {bad} "
                                f"(rel_residual {[rs[k].rel_residual for k in bad]}, max_iter {max_iter})")
-        return self.get_tangent()
+
+    # -- Deff Hessian-vector product: H dD ---------------------------------
+    def set_tangent(self, dx):
+        """A caller's own dx as the tangent field (deff_set_tangent); needs a system."""
+        dx = np.ascontiguousarray(dx, dtype=np.float64)
+        assert dx.size == self.nx * self.rows
+        check(self._L.deff_set_tangent(self._ctx, dx.ctypes.data_as(C.c_void_p)))
+
+    def sens_hvp(self, D, dD, CL, CR, timing=False):
+        """hv = H dD, H the Hessian of deff_raw with respect to the diffusivity map, from the current field, the current tangent
+        field and the planes D and dD, both (rows, nx), in one pass (deff_sensitivity_hvp_D): (hv, curv) with hv as (ny, nx), or
+        (nimg, ny, nx) for a stack, and curv = dD^T H dD per image (a float, or an array).  The tangent has to be the one along
+        this dD (tangent_rhs + solve_tangent, or set_tangent): deff_hvp does all three.  timing=True appends the device time in
+        ms."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        dD = np.ascontiguousarray(dD, dtype=np.float64)
+        assert D.size == self.nx * self.rows and dD.size == D.size
+        hv = np.empty((self.rows, self.nx), dtype=np.float64)
+        cv = (C.c_double * self.nimg)()
+        ms = C.c_float()
+        check(self._L.deff_sensitivity_hvp_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p), float(CL),
+                                             float(CR), hv.ctypes.data_as(C.c_void_p), cv, C.byref(ms) if timing else None))
+        hv = hv if self.nimg == 1 else hv.reshape(self.nimg, self.ny, self.nx)
+        curv = cv[0] if self.nimg == 1 else np.array(cv[:])
+        return (hv, curv, ms.value) if timing else (hv, curv)
+
+    def device_sens_hvp_ptr(self):
+        """(device pointer, row pitch in bytes) of the last sens_hvp map; valid until the next one or close()."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_device_sensitivity_hvp(self._ctx, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+    def deff_hvp(self, D, dD, CL, CR, rtol=1e-10, max_iter=1_000_000, check_every=64):
+        """(hv, curv) = sens_hvp of the current (converged) field along dD with the tangent computed here: tangent_rhs with the
+        map left on the device, solve_tangent to rtol (RuntimeError if it does not get there), then sens_hvp.  Overwrites the
+        tangent's right-hand side map and the tangent field."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        dD = np.ascontiguousarray(dD, dtype=np.float64)
+        assert D.size == self.nx * self.rows and dD.size == D.size
+        self._tangent_along("deff_hvp", D, dD, CL, CR, rtol, max_iter, check_every)
+        return self.sens_hvp(D, dD, CL, CR)
 
     def set_progress(self, fn):
         """fn(iter, deff_raw, change) after every convergence check, or None."""

@@ -101,6 +101,7 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  * "sens_kt" (deff_sensitivity / deff_sensitivity_D: the same for the gradient pass; deff_get_plan "sens_kt"),
  * "vjp_kt" (deff_field_vjp_D: the same for the field adjoint's pass; deff_get_plan "vjp_kt"),
  * "tan_kt" (deff_tangent_rhs_D: the same for the field tangent's pass; deff_get_plan "tan_kt"),
+ * "hvp_kt" (deff_sensitivity_hvp_D: the same for the Hessian-vector pass; deff_get_plan "hvp_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
  *   run every pass between two checks in ONE launch, neighbouring tiles synchronised by flags: 1 = one launch per
  *   pass instead; a resident launch that cannot make progress -- another process holds part of the GPU -- gives up
@@ -140,8 +141,8 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * 0 after deff_residual_D, which has no runs) and "res_items" (partial sums added per image by the final reduction:
  * strips of 128 columns x ceil(tile rows / res_kt), or for deff_residual_D rows x segments of 256 columns).  Of the last
  * deff_sensitivity / deff_sensitivity_D that launched: "sens_kt" and "sens_items", with the same meaning; of the last
- * deff_field_vjp_D that launched: "vjp_kt" and "vjp_items", and of the last deff_tangent_rhs_D: "tan_kt" and "tan_items",
- * likewise.  Of the flood fill
+ * deff_field_vjp_D that launched: "vjp_kt" and "vjp_items", of the last deff_tangent_rhs_D: "tan_kt" and "tan_items", and of
+ * the last deff_sensitivity_hvp_D: "hvp_kt" and "hvp_items", likewise.  Of the flood fill
  * on the device (deff_assemble_3phase_native): "fill_impl" (form of the last fill: 1 = one workgroup per image, 2 = row tiles),
  * "fill_launches" (kernel launches of the last fill), "fill_rounds" (most rounds one workgroup of it took), "fill_runs" (fills
  * computed since the context was created: a continuation stage on the same image computes none), "fill_fallbacks" (images
@@ -474,7 +475,7 @@ int deff_device_field_vjp(deff_ctx *ctx, void **d_g, size_t *row_pitch_bytes);
  *   and its validity, the field, the system, the row dictionary, the Jacobi plans, the sensitivity and field-adjoint maps.
  *   Refusals, each changing nothing: those of deff_solve_adjoint, and DEFF_ESTATE while there is no right-hand side map for
  *   the current system.
- * The tangent's lifetime: deff_solve_tangent makes dx valid; every call that invalidates the adjoint field (see there)
+ * The tangent's lifetime: deff_solve_tangent and deff_set_tangent (below) make dx valid; every call that invalidates the adjoint field (see there)
  *   invalidates dx and the map's use as a right-hand side -- a new deff_tangent_rhs_D is needed; deff_device_tangent_rhs still
  *   hands the old map out.  While dx is invalid deff_get_tangent and deff_device_tangent return DEFF_ESTATE.
  * deff_get_tangent: dx[nimg*ny*nx] to the host, true width.  deff_device_tangent: its device buffer, row pitch as
@@ -488,6 +489,47 @@ int deff_device_tangent_rhs(deff_ctx *ctx, void **d_r, size_t *row_pitch_bytes);
 int deff_solve_tangent(deff_ctx *ctx, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out /* [nimg] */);
 int deff_get_tangent(deff_ctx *ctx, double *dx);
 int deff_device_tangent(deff_ctx *ctx, void **d_dx, size_t *row_pitch_bytes);
+/* ---- Deff Hessian-vector product: hv = H dD, H the Hessian of deff_raw with respect to the diffusivity map, one tangent
+ * solve and one pass (nothing like it in the reference): what Newton-CG, trust-region steps and curvature checks on a
+ * diffusivity map need.  g(D) = d deff_raw / dD at the converged field is deff_sensitivity_D's map, a function of (x, D); along
+ * a direction dD,  H dD = dg/dD . dD + dg/dx . dx  with dx the field tangent along dD (deff_tangent_rhs_D(dD), then
+ * deff_solve_tangent).  Both parts are face-local.
+ *
+ * deff_sensitivity_hvp_D: hv[p] from the current field x, the current tangent y = dx, D and dD, in one pass.  With dx, dy of
+ * deff_mesh, wx = dy / dx, wy = dx / dy, ww = dy / (dx / 2.0), d[p] = (D[p] == 0) ? 0 : dD[p], x, y and d of cell p and of its
+ * neighbour q:
+ *   interior face of p towards q (weight w = wx for W / E, wy for N / S):
+ *       s = Dp + Dq;  tq = (s == 0) ? 0 : Dq / s;  tp = (s == 0) ? 0 : Dp / s;  u = (s == 0) ? 0 : (tp * dq - tq * dp) / s;
+ *       e = xp - xq;  f = yp - yq;  c = w * ((4.0 * tq) * (u * (e * e)) + (4.0 * (tq * tq)) * (e * f))
+ *   left / right wall:  e = xp - CL (CR);  c = ww * (2.0 * (e * yp))          no face (first / last row of an image):  c = +0.0
+ *   hv[p] = (((cW + cE) + cN) + cS) / ((CR - CL) * (CR - CL)),   and hv[p] = 0 where D[p] == 0.
+ * These doubles, in this order (tests/sens_hvp_model.py states them in numpy; the library is built without contraction).  u is
+ * the change of the quotient tq along dD; seen from q it is exactly -u, and e * e and e * f have the same bits from either
+ * side, so a face is evaluated once for both cells:  cq = w * ((4.0 * tp) * ((-u) * (e * e)) + (4.0 * (tp * tp)) * (e * f)).
+ * Only the sign of a zero can differ from the expressions above, which no comparison of doubles sees.
+ * curv[k] = sum over image k of d[p] * hv[p] = dD^T H dD, the curvature of deff_raw along dD, a wave-level reduction in a
+ * fixed order (csrc/kernels_facepass.hpp), the same bits on every call.  Checks that need no reference: deff_raw is
+ * homogeneous of degree 1 in D, so g is of degree 0 and H D = 0; H is symmetric; and deff_raw is a minimum over fields of
+ * functions linear in D, hence concave: curv <= 0 for a converged x and its own dx.  hv (nimg*ny*nx, true width) and curv
+ * ([nimg]) may each be NULL; *ms (may be NULL) = device time of the pass, on an event pair of its own.
+ *   D and dD [nimg*ny*nx] on the host, as deff_tangent_rhs_D takes them.  The call reads the newest field and the current
+ *   tangent dx; that dx belongs to THIS dD (and to this D and field) is the caller's responsibility: the pass cannot tell.
+ *   Plain and stack contexts; NULL ctx, D or dD, a row-slab context, CR == CL: DEFF_EINVAL; no field, or no valid tangent:
+ *   DEFF_ESTATE.  Pending work is settled first and every image's newest field is read.  The call writes only its own map, its
+ *   partial sums and the upload scratch (which holds both planes: 2 n doubles); a refused call leaves the previous map alone.
+ *   Negative or non-finite D, dD or dx: unspecified values, never a fault.
+ * Tuning "hvp_kt" and deff_get_plan "hvp_kt" / "hvp_items": as "tan_kt" / "tan_items", the same planner.
+ * deff_device_sensitivity_hvp: the device buffer of the last map (row pitch as deff_device_field, the pad column of an odd
+ *   width holds 0), valid until the next deff_sensitivity_hvp_D or deff_destroy; DEFF_ESTATE before one exists.
+ * deff_set_tangent: dx[nimg*ny*nx] (host, true width) becomes the tangent field and is valid -- a caller's own dx, the
+ *   counterpart of deff_set_adjoint: for a dx computed elsewhere, and for the pass on arbitrary planes without a solve.  The
+ *   same lifetime and invalidation as after deff_solve_tangent; the map's use as a right-hand side is not touched.  Allocates
+ *   the tangent's buffer if needed.  NULL arguments and row-slab contexts: DEFF_EINVAL; no system: DEFF_ESTATE.
+ * The whole product: deff_tangent_rhs_D(dD), deff_solve_tangent, deff_sensitivity_hvp_D(dD). */
+int deff_sensitivity_hvp_D(deff_ctx *ctx, const double *D, const double *dD, double CL, double CR,
+                           double *hv /* nimg*ny*nx, may be NULL */, double *curv /* [nimg], may be NULL */, float *ms);
+int deff_device_sensitivity_hvp(deff_ctx *ctx, void **d_hv, size_t *row_pitch_bytes);
+int deff_set_tangent(deff_ctx *ctx, const double *dx);
 /* sweep-kernel launches issued by the last deff_sweeps()/deff_solve() and the sweeps one
  * temporally blocked launch performs (1 for the single-sweep kernels).  A chained launch of the streaming kernel
  * (deff_get_plan "tb_chain" = 1: several passes of *sweeps_per_pass sweeps in one launch) counts its PASSES, so that
