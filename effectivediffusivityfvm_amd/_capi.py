@@ -33,6 +33,8 @@ SYMBOLS = [
     "deff_solve_adjoint", "deff_set_adjoint", "deff_get_adjoint", "deff_device_adjoint", "deff_field_vjp_D", "deff_device_field_vjp",
     "deff_tangent_rhs_D", "deff_device_tangent_rhs", "deff_solve_tangent", "deff_get_tangent", "deff_device_tangent",
     "deff_sensitivity_hvp_D", "deff_device_sensitivity_hvp", "deff_set_tangent",
+    "deff_adjoint_tangent_rhs_D", "deff_solve_adjoint_tangent", "deff_get_adjoint_tangent", "deff_device_adjoint_tangent",
+    "deff_set_adjoint_tangent", "deff_field_vjp_hvp_D", "deff_device_field_vjp_hvp",
     "deff_set_progress", "deff_last_launches", "deff_device_field", "deff_synchronize",
 ]
 
@@ -146,6 +148,15 @@ def load():
                                              C.POINTER(C.c_float)]
         L.deff_device_sensitivity_hvp.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.deff_set_tangent.argtypes = [ctx, C.c_void_p]
+    if hasattr(L, "deff_field_vjp_hvp_D"):               # DEFF_AMD_LIB may name a build from before the second-order field adjoint
+        L.deff_adjoint_tangent_rhs_D.argtypes = [ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.deff_solve_adjoint_tangent.argtypes = [ctx, C.c_double, C.c_int64, C.c_int64, C.POINTER(CGResultC)]
+        L.deff_get_adjoint_tangent.argtypes = [ctx, C.c_void_p]
+        L.deff_device_adjoint_tangent.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.deff_set_adjoint_tangent.argtypes = [ctx, C.c_void_p]
+        L.deff_field_vjp_hvp_D.argtypes = [ctx, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_float)]
+        L.deff_device_field_vjp_hvp.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.deff_set_progress.argtypes = [ctx, PROGRESS_FN, C.c_void_p]
     L.deff_last_launches.argtypes = [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     ip = C.POINTER(C.c_int)

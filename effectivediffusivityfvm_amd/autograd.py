@@ -6,7 +6,9 @@ Both ops have a jvp for torch.autograd.forward_ad: Deff's is a sum over its grad
 (deff_tangent_rhs_D) and one solve (deff_solve_tangent).  Deff is twice differentiable: under create_graph its backward hands
 the gradient map out through a second Function whose backward is the Hessian-vector product -- the forward solve again, one
 tangent solve and one pass over (x, dx, dD, D) (deff_sensitivity_hvp_D).  torch.func transforms are not supported (no
-setup_context).
+setup_context).  The field is twice differentiable too: under create_graph its backward is a Function (D, w) -> g whose own
+backward gives S_w v -- the Hessian of w^T x(D) along v: the adjoint solve again, two tangent solves and one pass over
+(x, lambda, dx, dlambda, v, D) (deff_field_vjp_hvp_D) -- for D and J v for w.
 
 torch is imported inside the functions only: importing the package does not import it.  D makes a host round trip (plumbing;
 the solve and the gradient run in the library's HIP kernels)."""
@@ -166,6 +168,102 @@ def _converged(who, rs, rtol, max_iter):
                            f"(rel_residual {[rs[k].rel_residual for k in bad]}, max_iter {max_iter})")
 
 
+_FIELD_GRAD_FN = None
+
+
+def _field_grad_function():
+    """The torch.autograd.Function (D, w) -> g = J^T w that carries the field adjoint's map through a graph -- the second
+    derivative of concentration_field -- and the two its backward pass applies.  Created at first use."""
+    global _FIELD_GRAD_FN
+    if _FIELD_GRAD_FN is not None:
+        return _FIELD_GRAD_FN
+    import torch
+
+    def on_solver(Dh, x, CL, CR, solver, fn):
+        """fn(s, D2) on `solver`, or on a Solver created and closed here, with the system of Dh assembled and x as its field."""
+        nimg = Dh.shape[0] if Dh.ndim == 3 else 1
+        ny, nx = Dh.shape[-2:]
+        s = solver if solver is not None else Solver(nx, ny, nimg=nimg)
+        try:
+            # whatever happened to the solver since the forward pass: its system and field are set again
+            D2 = Dh.reshape(nimg * ny, nx)
+            s.assemble_from_D(D2, CL, CR)
+            s.set_field(x.reshape(nimg * ny, nx))
+            return fn(s, D2)
+        finally:
+            if solver is None:
+                s.close()
+
+    def host(t, Dh):
+        return np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float64).reshape(-1, Dh.shape[-1])
+
+    def tensor(a, Dh, like):
+        return torch.from_numpy(np.ascontiguousarray(a).reshape(Dh.shape)).to(like.device)
+
+    class _FieldHessVec(torch.autograd.Function):
+        """v -> S_w v, S_w the Hessian of w^T x(D) with w fixed.  Linear in v and S_w is symmetric, so its own vjp is itself:
+        torch.autograd.functional.hvp differentiates the backward pass with respect to the incoming gradient.  D and w are
+        constants here: third derivatives and the w-derivative of S_w v are not computed."""
+        @staticmethod
+        def forward(ctx, v, Dh, x, w, CL, CR, rtol, max_iter, solver):
+            def run(s, D2):
+                _converged("concentration_field (second order, adjoint)",
+                           s.solve_adjoint(w, rtol=rtol, max_iter=max_iter), rtol, max_iter)
+                try:
+                    return s.field_hvp(D2, host(v, Dh), CL, CR, rtol=rtol, max_iter=max_iter)[0]
+                except RuntimeError as e:
+                    raise RuntimeError(f"concentration_field (second order): {e}") from None
+            ctx.deff_args = (Dh, x, w, CL, CR, rtol, max_iter, solver)
+            return tensor(on_solver(Dh, x, CL, CR, solver, run), Dh, v)
+
+        @staticmethod
+        def backward(ctx, u):
+            return (_FieldHessVec.apply(u, *ctx.deff_args),) + (None,) * 8
+
+    class _FieldJvp(torch.autograd.Function):
+        """v -> J v, J = dx/dD.  Linear in v; its vjp is J^T, the field adjoint's map with D held constant."""
+        @staticmethod
+        def forward(ctx, v, Dh, x, CL, CR, rtol, max_iter, solver):
+            def run(s, D2):
+                try:
+                    return s.field_jvp(D2, host(v, Dh), CL, CR, rtol=rtol, max_iter=max_iter)
+                except RuntimeError as e:
+                    raise RuntimeError(f"concentration_field (second order): {e}") from None
+            ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver)
+            return tensor(on_solver(Dh, x, CL, CR, solver, run), Dh, v)
+
+        @staticmethod
+        def backward(ctx, u):
+            Dh = ctx.deff_args[0]
+            return (_FieldVjp.apply(tensor(Dh, Dh, u), u, *ctx.deff_args),) + (None,) * 7
+
+    class _FieldVjp(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, D, w, Dh, x, CL, CR, rtol, max_iter, solver):
+            # concentration_field's first-order backward pass, call for call
+            wh = host(w, Dh)
+
+            def run(s, D2):
+                _converged("concentration_field (adjoint)", s.solve_adjoint(wh, rtol=rtol, max_iter=max_iter), rtol, max_iter)
+                return s.field_vjp(D2, CL, CR)[0]
+            ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver)
+            ctx.deff_w = wh
+            return tensor(on_solver(Dh, x, CL, CR, solver, run), Dh, w)
+
+        @staticmethod
+        def backward(ctx, v):
+            Dh, x, CL, CR, rtol, max_iter, solver = ctx.deff_args
+            gD = gw = None
+            if ctx.needs_input_grad[0]:
+                gD = _FieldHessVec.apply(v, Dh, x, ctx.deff_w, CL, CR, rtol, max_iter, solver)
+            if ctx.needs_input_grad[1]:
+                gw = _FieldJvp.apply(v, *ctx.deff_args)
+            return (gD, gw) + (None,) * 7
+
+    _FIELD_GRAD_FN = _FieldVjp
+    return _FIELD_GRAD_FN
+
+
 def _field_function():
     """The torch.autograd.Function of concentration_field, created at first use."""
     global _FIELD_FN
@@ -192,11 +290,16 @@ def _field_function():
                 if solver is None:
                     s.close()
             ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver)
+            ctx.save_for_backward(D)
             return torch.from_numpy(x.copy()).to(D.device)
 
         @staticmethod
         def backward(ctx, grad_out):
             Dh, x, CL, CR, rtol, max_iter, solver = ctx.deff_args
+            (D,) = ctx.saved_tensors
+            if torch.is_grad_enabled() and (D.requires_grad or grad_out.requires_grad):
+                # create_graph: the same calls inside a Function of (D, w), whose backward is the second order
+                return (_field_grad_function().apply(D, grad_out, *ctx.deff_args),) + (None,) * 5
             nimg = Dh.shape[0] if Dh.ndim == 3 else 1
             ny, nx = Dh.shape[-2:]
             w = np.ascontiguousarray(grad_out.detach().cpu().numpy(), dtype=np.float64)
@@ -248,7 +351,18 @@ def concentration_field(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, solve
     and one pass over (x, lambda, D) (deff_field_vjp_D) give dL/dD.  D and w make a host round trip.  `solver`: a Solver of the
     same shape to reuse (its system, field, adjoint field and the tuning key "cg_planes" are overwritten, in both passes).
     Under torch.autograd.forward_ad the tangent of x along D's tangent is computed the same way: system and field set again,
-    then deff_tangent_rhs_D and deff_solve_tangent to rtol (RuntimeError if it does not converge)."""
+    then deff_tangent_rhs_D and deff_solve_tangent to rtol (RuntimeError if it does not converge).
+    Twice differentiable: under create_graph=True the backward pass makes the same calls and returns the same numbers, as a
+    function g(D, w) of D and the incoming gradient.  A backward pass through that with a cotangent v (functional.hvp,
+    Newton-CG, a penalty on the gradient) gets, for D, S_w v -- S_w the Hessian of w^T x(D) with w fixed, the term that makes the
+    Gauss-Newton product J^T L'' J into the Hessian: system and field set again, deff_solve_adjoint(w), then Solver.field_hvp
+    (deff_tangent_rhs_D, deff_solve_tangent, deff_adjoint_tangent_rhs_D, deff_solve_adjoint_tangent, deff_field_vjp_hvp_D) --
+    and, for w, J v (Solver.field_jvp); each on `solver` when one was passed (its system, field, adjoint field, both tangents'
+    right-hand side maps, the tangent field, the adjoint's tangent and the second-order map are overwritten), otherwise on a
+    Solver created and closed for that pass; RuntimeError if a solve does not converge.  S_w v and J v are in turn
+    differentiable with respect to v (by S_w again, and by J^T: functional.hvp's double backward needs both); D and w are
+    constants there, so third derivatives and the w-derivative of S_w v come out as None / zero, and a jvp of the gradient map and
+    torch.func are not supported.  First-order use pays nothing for this: the same calls, the same bits, no graph."""
     import torch
     if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() not in (2, 3):
         raise TypeError("D must be a float64 tensor of shape (ny, nx) or (nimg, ny, nx)")

@@ -401,8 +401,9 @@ try {
     TRY(side_solve_prepare(c, "deff_solve_adjoint", &g));
     TRY(dev_alloc(&c->adj_lam, c->n));
     TRY(dev_alloc(&c->adj_w, c->n));
-    // from here on lambda is the new call's
+    // from here on lambda is the new call's, and dlambda (api_fhvp.hip) belonged to the old one
     c->adj_valid = false;
+    adjoint_tangent_reset(c);
     if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(c->adj_w, 0, sizeof(double) * c->n, c->stream));
     TRY(rows_h2d(c, c->adj_w, w, (size_t)c->rows));
     TRY(side_solve_run(c, c->adj_lam, c->adj_w, g, rtol, max_iter, check_every, out));
@@ -428,6 +429,28 @@ try {
     HIP_TRY(hipMemcpyAsync(c->tan_w, c->pass_tan.map, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
     TRY(side_solve_run(c, c->tan_dx, c->tan_w, g, rtol, max_iter, check_every, out));
     c->tan_valid = true;
+    return DEFF_OK;
+}
+DEFF_API_CATCH
+
+// A dlambda = q' for the second-order field adjoint (api_fhvp.hip): deff_solve_tangent with the last
+// deff_adjoint_tangent_rhs_D's map as the right-hand side, copied into adj_dw, and adj_dl as the solution.
+extern "C" int deff_solve_adjoint_tangent(deff_ctx *c, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out)
+try {
+    if (!c || !out) return fail(DEFF_EINVAL, "NULL argument");
+    TRY(side_solve_args(c, "deff_solve_adjoint_tangent", rtol, max_iter, check_every));
+    if (!c->pass_atan.have || !c->atan_rhs)
+        return fail(DEFF_ESTATE, "deff_solve_adjoint_tangent: no right-hand side for the current system and adjoint field "
+                                 "(deff_adjoint_tangent_rhs_D)");
+    CgGeom g;
+    TRY(side_solve_prepare(c, "deff_solve_adjoint_tangent", &g));
+    TRY(dev_alloc(&c->adj_dl, c->n));
+    TRY(dev_alloc(&c->adj_dw, c->n));
+    // from here on dlambda is the new call's
+    c->atan_valid = false;
+    HIP_TRY(hipMemcpyAsync(c->adj_dw, c->pass_atan.map, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
+    TRY(side_solve_run(c, c->adj_dl, c->adj_dw, g, rtol, max_iter, check_every, out));
+    c->atan_valid = true;
     return DEFF_OK;
 }
 DEFF_API_CATCH

@@ -140,11 +140,13 @@ try {
     if (c->cgs_dev) (void)hipFree(c->cgs_dev);
     if (c->cgs_pin) (void)hipHostFree(c->cgs_pin);
     for (hipEvent_t e : c->cgs_ev) if (e) (void)hipEventDestroy(e);
-    for (CellPass *p : {&c->pass_res, &c->pass_sens, &c->pass_vjp, &c->pass_tan, &c->pass_hvp}) cell_pass_free(*p);
+    for (CellPass *p : {&c->pass_res, &c->pass_sens, &c->pass_vjp, &c->pass_tan, &c->pass_hvp, &c->pass_atan, &c->pass_fhvp}) cell_pass_free(*p);
     if (c->adj_lam) (void)hipFree(c->adj_lam);
     if (c->adj_w) (void)hipFree(c->adj_w);
     if (c->tan_dx) (void)hipFree(c->tan_dx);
     if (c->tan_w) (void)hipFree(c->tan_w);
+    if (c->adj_dl) (void)hipFree(c->adj_dl);
+    if (c->adj_dw) (void)hipFree(c->adj_dw);
     if (c->q_host) (void)hipHostFree(c->q_host);
     if (c->chain_counted) resident_chain_ctx_destroyed(c->device);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -276,6 +278,7 @@ try {
     else if (!strcmp(key, "vjp_kt")) c->pass_vjp.kt = value;
     else if (!strcmp(key, "tan_kt")) c->pass_tan.kt = value;
     else if (!strcmp(key, "hvp_kt")) c->pass_hvp.kt = value;
+    else if (!strcmp(key, "fhvp_kt")) c->pass_fhvp.kt = value;
     else if (!strcmp(key, "tb_sym")) c->tb_sym = value;
     else if (!strcmp(key, "tb_launch")) {            // 0: resident passes where possible; 1: one launch per pass
         if (value > 1) return fail(DEFF_EINVAL, "tb_launch takes 0 (resident passes where the tiles fit the chip) or 1 (one launch per pass)");
@@ -370,6 +373,8 @@ try {
     else if (!strcmp(key, "tan_items")) *value = c->pass_tan.plan_items;
     else if (!strcmp(key, "hvp_kt")) *value = c->pass_hvp.plan_kt;
     else if (!strcmp(key, "hvp_items")) *value = c->pass_hvp.plan_items;
+    else if (!strcmp(key, "fhvp_kt")) *value = c->pass_fhvp.plan_kt;
+    else if (!strcmp(key, "fhvp_items")) *value = c->pass_fhvp.plan_items;
     else if (!strcmp(key, "fill_impl")) *value = c->fill_plan_impl;
     else if (!strcmp(key, "fill_launches")) *value = c->fill_plan_launches;
     else if (!strcmp(key, "fill_rounds")) *value = c->fill_plan_rounds;

@@ -1,7 +1,8 @@
 // api_tangent.hip -- the field tangent's pass and buffer: deff_tangent_rhs_D / deff_device_tangent_rhs: r = db - dA x per cell
 // for a direction dD and its squared norm per image, from the current field, D and dD, one pass on the device
 // (kernels_facepass.hpp: the walk with TanPass); deff_get_tangent / deff_device_tangent: dx of A dx = r' (deff_solve_tangent,
-// which computes it, is in api_cg.hip beside the loop it runs).  Reads the field; changes nothing but the map, its partial
+// which computes it, is in api_cg.hip beside the loop it runs); deff_adjoint_tangent_rhs_D: the same pass on lambda, the
+// right-hand side of the adjoint's tangent (api_fhvp.hip).  Reads the field (lambda); changes nothing but the map, its partial
 // sums and the shared upload scratch.
 #include "cell_pass.hpp"
 #include "kernels_facepass.hpp"
@@ -24,22 +25,21 @@ __global__ __launch_bounds__(1024) void k_tan_final(const double *__restrict__ p
 
 }  // namespace deff
 
-// the map of the stack's newest fields (x[cur] after consolidate) for the planes `dD` and `ddD` on the device (pitch nx, pad column 0)
-static int tan_launch(deff_ctx *c, const double *dD, const double *ddD, double CL, double CR, double *r, double *norm2, float *ms)
+// the map of `field` -- the stack's newest fields (x[cur] after consolidate) into pass_tan, or lambda into pass_atan -- for the
+// planes `dD` and `ddD` on the device (pitch nx, pad column 0); both passes are planned by tuning "tan_kt"
+static int tan_launch(deff_ctx *c, CellPass &p, const char *who, const double *field, const double *dD, const double *ddD, double CL,
+                      double CR, double *r, double *norm2, float *ms)
 {
-    CellPass &p = c->pass_tan;
-    const CellItems it = cell_pass_items(c->nxt, c->ny, c->nimg, p.kt);
-    if ((it.items + 3) / 4 > 0x7fffffffu) return fail(DEFF_EINVAL, "deff_tangent_rhs_D: too many work items");
+    const CellItems it = cell_pass_items(c->nxt, c->ny, c->nimg, c->pass_tan.kt);
+    if ((it.items + 3) / 4 > 0x7fffffffu) return fail(DEFF_EINVAL, "%s: too many work items", who);
     TRY(cell_pass_room(c, p, true, it.items));
     TRY(cell_pass_start(c, p, ms));
     const double dx = c->dx, dy = c->dy;
     const double wx = dy / dx, wy = dx / dy, ww = dy / (dx / 2.0);
-    hipLaunchKernelGGL(k_tan, dim3((unsigned)((it.items + 3) / 4)), dim3(256), 0, c->stream, c->x[c->cur], ddD, dD, c->nx, c->nxt,
+    hipLaunchKernelGGL(k_tan, dim3((unsigned)((it.items + 3) / 4)), dim3(256), 0, c->stream, field, ddD, dD, c->nx, c->nxt,
                        c->ny, c->nimg, it.ntx, it.cpi, it.kt, wx, wy, ww, CL, CR, p.map, p.part);
     HIP_TRY(hipGetLastError());
-    TRY(cell_pass_finish(c, p, k_tan_final, it, norm2, r, ms));
-    c->tan_rhs = true;                                             // a right-hand side for the current system
-    return DEFF_OK;
+    return cell_pass_finish(c, p, k_tan_final, it, norm2, r, ms);
 }
 
 extern "C" int deff_tangent_rhs_D(deff_ctx *c, const double *D, const double *dD, double CL, double CR, double *r, double *norm2,
@@ -55,7 +55,33 @@ try {
     const double *d0, *d1;
     TRY(cell_pass_upload_D(c, D, &d0, 0, 2));
     TRY(cell_pass_upload_D(c, dD, &d1, 1, 2));
-    return tan_launch(c, d0, d1, CL, CR, r, norm2, ms);
+    TRY(tan_launch(c, c->pass_tan, "deff_tangent_rhs_D", c->x[c->cur], d0, d1, CL, CR, r, norm2, ms));
+    c->tan_rhs = true;                                             // a right-hand side for the current system
+    return DEFF_OK;
+}
+DEFF_API_CATCH
+
+// The right-hand side of lambda's own tangent (the second-order field adjoint, api_fhvp.hip): differentiating A lambda = w along
+// dD with w fixed, A dlambda = -dA lambda =: q -- the pass above with lambda in the place of the field and both wall values 0
+// (db is the walls' part: lambda has none).  Into pass_atan: pass_tan's map, which deff_solve_tangent reads, stays.
+extern "C" int deff_adjoint_tangent_rhs_D(deff_ctx *c, const double *D, const double *dD, double *q, double *norm2, float *ms)
+try {
+    if (!c) return fail(DEFF_EINVAL, "ctx is NULL");
+    if (!D) return fail(DEFF_EINVAL, "D is NULL");
+    if (!dD) return fail(DEFF_EINVAL, "dD is NULL");
+    if (c->slab)
+        return fail(DEFF_EINVAL, "deff_adjoint_tangent_rhs_D: not for row-slab contexts (the rows of the image live on several devices)");
+    if (!c->adj_valid)
+        return fail(DEFF_ESTATE, "deff_adjoint_tangent_rhs_D: no adjoint field for the current system (deff_solve_adjoint / deff_set_adjoint)");
+    TRY(use_device(c));
+    TRY(resident_check(c));                                        // the scratch and the stream are about to be used
+    const double *d0, *d1;
+    TRY(cell_pass_upload_D(c, D, &d0, 0, 2));
+    TRY(cell_pass_upload_D(c, dD, &d1, 1, 2));
+    TRY(tan_launch(c, c->pass_atan, "deff_adjoint_tangent_rhs_D", c->adj_lam, d0, d1, 0.0, 0.0, q, norm2, ms));
+    c->atan_rhs = true;                                            // a right-hand side for the current system and lambda
+    c->atan_valid = false;                                         // dlambda belonged to the previous one
+    return DEFF_OK;
 }
 DEFF_API_CATCH
 

@@ -31,6 +31,7 @@ try {
     TRY(use_device(c));
     TRY(dev_alloc(&c->adj_lam, c->n));
     c->adj_valid = false;
+    adjoint_tangent_reset(c);                                      // dlambda (api_fhvp.hip) belonged to the old lambda
     if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(c->adj_lam, 0, sizeof(double) * c->n, c->stream));
     TRY(rows_h2d(c, c->adj_lam, lam, (size_t)c->rows));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -1,6 +1,7 @@
 // cell_pass.hpp -- the host path of a pass over the cells of the current field that ends in one sum per image: the residual
 // (api_residual.hip), the Deff gradient (api_sens.hip), the field adjoint's pass (api_vjp.hip), the field tangent's
-// (api_tangent.hip) and the Deff Hessian-vector product's (api_hvp.hip).  Each entry point keeps its
+// (api_tangent.hip), the Deff Hessian-vector product's (api_hvp.hip) and the field adjoint's second-order passes
+// (api_fhvp.hip).  Each entry point keeps its
 // own refusals and its own kernel launch; what is here is what they did alike: the work-item planner, the buffers, the call's
 // own event pair, the final sum and the copies out, the upload of a caller's D plane, and the device-map getter.
 #pragma once
@@ -17,7 +18,7 @@ struct CellItems {
 // and below a run are then loaded once per run).  kt: about 4 096 items in the launch -- one round of waves on 256 CUs;
 // measured with the residual's class kernel at 4096^2, reduction included: kt = 1 42.0 us, 2 34.4, 4 32.0, 8 31.7 -- and at most
 // 16 384 items per image (the final kernel adds an image's partial sums with ONE workgroup); `tuned` > 0 (tuning "res_kt" /
-// "sens_kt" / "vjp_kt" / "tan_kt" / "hvp_kt") overrides; clipped to the image.
+// "sens_kt" / "vjp_kt" / "tan_kt" / "hvp_kt" / "fhvp_kt") overrides; clipped to the image.
 static inline CellItems cell_pass_items(int nxt, int ny, int nimg, int tuned)
 {
     const int ntx = (nxt + CELL_PASS_COLS - 1) / CELL_PASS_COLS, tiles_y = (ny + CELL_PASS_ROWS - 1) / CELL_PASS_ROWS;

@@ -19,8 +19,11 @@
 //                  (deff_get_tangent, deff_device_tangent); deff_solve_tangent is in api_cg.hip, beside deff_solve_adjoint
 //   api_hvp.hip    the Deff Hessian-vector product: the pass (x, dx, dD, D) -> H dD (deff_sensitivity_hvp_D) and a caller's
 //                  own tangent (deff_set_tangent)
-//   cell_pass.hpp  the host path those five share (CellPass below): work-item planner, partial sums, the call's own event
-//                  pair, the D upload, the device-map getter; k_sens, k_vjp, k_tan and k_hvp are one walk (kernels_facepass.hpp), the
+//   api_fhvp.hip   the field adjoint's second order: dlambda's buffer and setter (its right-hand side, deff_adjoint_tangent_rhs_D,
+//                  is k_tan on lambda, in api_tangent.hip; deff_solve_adjoint_tangent is in api_cg.hip) and the pass
+//                  (x, lambda, dx, dlambda, dD, D) -> S_w dD (deff_field_vjp_hvp_D)
+//   cell_pass.hpp  the host path those six share (CellPass below): work-item planner, partial sums, the call's own event
+//                  pair, the D upload, the device-map getter; k_sens, k_vjp, k_tan, k_hvp and k_fhvp are one walk (kernels_facepass.hpp), the
 //                  final sums one body (wave_reduce.hpp)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
@@ -82,7 +85,7 @@ struct CellPass {
     // loops alone, which read them at every check and may call a pass in between (a deff_set_progress or deff_image_done_fn
     // callback).
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int kt = 0;                     // tuning "res_kt" / "sens_kt" / "vjp_kt" / "tan_kt" / "hvp_kt": tiles of 8 rows a wave streams through (0 = planner)
+    int kt = 0;                     // tuning "res_kt" / "sens_kt" / "vjp_kt" / "tan_kt" / "hvp_kt" / "fhvp_kt": tiles of 8 rows a wave streams through (0 = planner)
     // deff_get_plan "*_kt" / "*_items" of the last call that launched: the run length used (planner, override and clip
     // applied) and the partial sums the final kernel adds per image
     int plan_kt = 0, plan_items = 0;
@@ -304,7 +307,10 @@ struct deff_ctx {
     //   pass_vjp   deff_field_vjp_D (api_vjp.hip): the map dL/dD, handed out by deff_device_field_vjp
     //   pass_tan   deff_tangent_rhs_D (api_tangent.hip): the map r = db - dA x, handed out by deff_device_tangent_rhs
     //   pass_hvp   deff_sensitivity_hvp_D (api_hvp.hip): the map H dD, handed out by deff_device_sensitivity_hvp
-    CellPass pass_res, pass_sens, pass_vjp, pass_tan, pass_hvp;
+    //   pass_atan  deff_adjoint_tangent_rhs_D (api_tangent.hip): the map q = -dA lambda, k_tan's on lambda; a map of its own, so
+    //              that pass_tan's stays
+    //   pass_fhvp  deff_field_vjp_hvp_D (api_fhvp.hip): the map S_w dD, handed out by deff_device_field_vjp_hvp
+    CellPass pass_res, pass_sens, pass_vjp, pass_tan, pass_hvp, pass_atan, pass_fhvp;
     bool grid_given = false;        // the last deff_assemble_3phase was given a Grid (deff_sensitivity refuses such a system)
 
     // The field adjoint (api_vjp.hip; the solve itself is api_cg.hip's loop).  adj_lam: lambda of A lambda = w (pitch nx, pad
@@ -321,6 +327,14 @@ struct deff_ctx {
     // them.  adjoint_reset clears both.
     double *tan_dx = nullptr, *tan_w = nullptr;
     bool tan_rhs = false, tan_valid = false;
+
+    // The adjoint's tangent (api_fhvp.hip; its right-hand side is api_tangent.hip's pass, the solve api_cg.hip's loop).  adj_dl: dlambda of A dlambda = q' (pitch nx, pad
+    // column 0), adj_dw: q' = pass_atan's map with the forward system's decoupled cells zeroed; both allocated by the first
+    // deff_solve_adjoint_tangent (adj_dl by deff_set_adjoint_tangent too).  atan_rhs: pass_atan's map was computed since the
+    // current system, image and lambda were set; atan_valid: dlambda belongs to them.  adjoint_reset clears both, and so does
+    // every call that replaces lambda (deff_solve_adjoint, deff_set_adjoint).
+    double *adj_dl = nullptr, *adj_dw = nullptr;
+    bool atan_rhs = false, atan_valid = false;
 
     // Native 3-phase system (kernels_fill.hpp, api_fill.hip): the flood fill of the pore space as bitmaps -- one `open` and
     // one `reach` word per 64 columns of a row, fill_nw words per row --, its status words and the tiled form's `changed` words.
@@ -417,7 +431,8 @@ static inline void dict_reset(deff_ctx *c) { c->dict_tried = false; c->dict_outc
 // a new system or image: the adjoint field was the old one's (deff_get_adjoint, deff_device_adjoint, deff_field_vjp_D:
 // DEFF_ESTATE), and so were the tangent and the map that was its right-hand side (deff_solve_tangent, deff_get_tangent,
 // deff_device_tangent: DEFF_ESTATE)
-static inline void adjoint_reset(deff_ctx *c) { c->adj_valid = false; c->tan_rhs = false; c->tan_valid = false; }
+static inline void adjoint_tangent_reset(deff_ctx *c) { c->atan_rhs = false; c->atan_valid = false; }   // a new lambda
+static inline void adjoint_reset(deff_ctx *c) { c->adj_valid = false; c->tan_rhs = false; c->tan_valid = false; adjoint_tangent_reset(c); }
 
 // No C++ exception may unwind through the C ABI: every `extern "C" int` entry point is a
 // function-try-block ending in DEFF_API_CATCH, which turns std::bad_alloc (host vectors sized by the

@@ -5,6 +5,7 @@
 //   VjpPass    the field adjoint's dL/dD from (x, lambda, D)             k_vjp, api_vjp.hip
 //   TanPass    the field tangent's right-hand side from (x, dD, D)       k_tan, api_tangent.hip
 //   HvpPass    the Deff Hessian-vector product from (x, dx, dD, D)       k_hvp, api_hvp.hip
+//   FieldHvpPass  the field adjoint's second order from (x, lambda, dx, dlambda, dD, D)   k_fhvp, api_fhvp.hip
 // All kernels are this one text, so the order of operations per cell, the launch geometry and the order of the final sum are
 // the same by construction.
 //
@@ -158,6 +159,42 @@ struct HvpPass {
     __device__ __forceinline__ static double term(const FpCell<3> &c, double g) { return ((c.D == 0) ? 0 : c.v[2]) * g; }
 };
 
+// The second-order field adjoint (k_fhvp), planes x, l (A l = w), y = dx and m = dl along dD, and dD.  g = grad of w^T x(D) is
+// VjpPass's map, a function of (x, l, D) with w held fixed, so S_w dD = dg/dD . dD + dg/dx . y + dg/dl . m: y is the field
+// tangent (A y = db - dA x), m the adjoint's (A m = -dA l: TanPass on l with both wall values 0).  All three parts are
+// face-local: a face gives cell p (2 tq^2) w e fl, the quotient moves by u as in HvpPass, e by ed, fl by fm.
+// With d[p] = (D[p] == 0) ? 0 : dD[p]:
+//   interior face   u = (s == 0) ? 0 : (tp * dq - tq * dp) / s;  e = xp - xq;  fl = lp - lq;  ed = yp - yq;  fm = mp - mq;
+//                   ef = e * fl;  k = ed * fl + e * fm;
+//                   c = w * ((4.0 * tq) * (u * ef) + (2.0 * (tq * tq)) * k)
+//   wall            e = xp - CL (CR);  c = ww * (yp * lp + e * mp)
+//   hv[p] = -(((cW + cE) + cN) + cS),  hv[p] = 0 where D[p] == 0.
+// Seen from q, u is exactly -u and ef, k have the same bits (every difference changes sign exactly, so each product keeps
+// its bits and the addition its operands; a zero may differ in sign), so
+//   cq = w * ((4.0 * tp) * ((-u) * ef) + (2.0 * (tp * tp)) * k):
+// one evaluation per face, three FP64 divisions per face as in HvpPass.
+// tests/field_hvp_model.py states the same expressions in numpy, in this order: the map is compared bit for bit.
+// sum[img] = sum of d[p] * hv[p] = dD^T S_w dD.  It has no sign; w^T x is homogeneous of degree 0 in D, so S_w D = -g.
+// Byte model: x, l, dx, dl, dD, D read and hv written, 56 B per cell.
+struct FieldHvpPass {
+    static constexpr int NF = 5;                 // planes besides D: x, lambda, dx, dlambda, dD
+    __device__ __forceinline__ static void face(const FpCell<5> &p, const FpCell<5> &q, double w, double tq, double tp, double &cp,
+                                                double &cq)
+    {
+        const double s = p.D + q.D;
+        const double dp = (p.D == 0) ? 0 : p.v[4], dq = (q.D == 0) ? 0 : q.v[4];
+        const double u = (s == 0) ? 0 : (tp * dq - tq * dp) / s;
+        const double e = p.v[0] - q.v[0], fl = p.v[1] - q.v[1], ed = p.v[2] - q.v[2], fm = p.v[3] - q.v[3];
+        const double ef = e * fl, k = ed * fl + e * fm;
+        cp = w * ((4.0 * tq) * (u * ef) + (2.0 * (tq * tq)) * k);
+        cq = w * ((4.0 * tp) * ((-u) * ef) + (2.0 * (tp * tp)) * k);
+    }
+    // (e is plane 0's value against the wall: x)
+    __device__ __forceinline__ static double wall(double e, const double (&v)[5]) { return v[2] * v[1] + e * v[3]; }
+    __device__ __forceinline__ double finish(double s) const { return -s; }
+    __device__ __forceinline__ static double term(const FpCell<5> &c, double g) { return ((c.D == 0) ? 0 : c.v[4]) * g; }
+};
+
 template <int NF> __device__ __forceinline__ FpCell<NF> fp_a(const FpRow<NF> &r)
 {
     FpCell<NF> c;
@@ -204,7 +241,7 @@ __device__ __forceinline__ double fp_readlane(double v, int l)
 //  - The strip's outer neighbours: per tile, lanes 0...7 load the cell west of the strip for one row each (and the strip's
 //    own first cell) and evaluate that face, or the left wall's term; lanes 8...15 load the cell east of it.  A row takes
 //    them from there with v_readlane: lane 0's W term and lane 63's E neighbour enter as the `old` operand of the lane
-//    shifts, no per-row selects.  The next tile's outer cells are loaded a tile ahead -- with three planes (HvpPass) into the
+//    shifts, no per-row selects.  The next tile's outer cells are loaded a tile ahead -- with three planes or more (HvpPass, FieldHvpPass) into the
 //    same registers during the tile's last row, once that row has taken its own: a second set would cost 16 VGPRs and the
 //    fourth wave per SIMD.
 //  - Only the last strip (EDGE) knows the right wall, the cells beyond it and the pad column, by per-lane selects.

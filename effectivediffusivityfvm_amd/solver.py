@@ -593,6 +593,103 @@ class Solver:
         self._tangent_along("deff_hvp", D, dD, CL, CR, rtol, max_iter, check_every)
         return self.sens_hvp(D, dD, CL, CR)
 
+    # -- second-order field adjoint: S_w dD, the Hessian of w^T x(D) -------
+    def adjoint_tangent_rhs(self, D, dD, timing=False):
+        """q = -dA lambda along the direction dD, from the current adjoint field and the diffusivity plane D, both (rows, nx),
+        in one pass (deff_adjoint_tangent_rhs_D: tangent_rhs's pass on lambda with both wall values 0, into a map of its own):
+        (q, norm2) with q as (ny, nx), or (nimg, ny, nx) for a stack, and norm2 = sum of q * q per image.  timing=True appends
+        the device time in ms."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        dD = np.ascontiguousarray(dD, dtype=np.float64)
+        assert D.size == self.nx * self.rows and dD.size == D.size
+        q = np.empty((self.rows, self.nx), dtype=np.float64)
+        n2 = (C.c_double * self.nimg)()
+        ms = C.c_float()
+        check(self._L.deff_adjoint_tangent_rhs_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p),
+                                                 q.ctypes.data_as(C.c_void_p), n2, C.byref(ms) if timing else None))
+        q = q if self.nimg == 1 else q.reshape(self.nimg, self.ny, self.nx)
+        norm2 = n2[0] if self.nimg == 1 else np.array(n2[:])
+        return (q, norm2, ms.value) if timing else (q, norm2)
+
+    def solve_adjoint_tangent(self, rtol=1e-10, max_iter=1_000_000, check_every=64):
+        """A dlambda = q on the current matrix with homogeneous walls (deff_solve_adjoint_tangent), q the last
+        adjoint_tangent_rhs map, read on the device: solve_tangent's iteration into a buffer of its own -- the field, the
+        system, lambda, dx and the maps stay as they are.  One image: a CGResult (deff_raw 0.0, MFL / MFR None); a stack: a
+        list, one per image."""
+        res = (CGResultC * self.nimg)()
+        check(self._L.deff_solve_adjoint_tangent(self._ctx, float(rtol), int(max_iter), int(check_every), res))
+        outs = []
+        for k in range(self.nimg):
+            out = CGResult()
+            out.iters, out.rel_residual, out.deff_raw = res[k].iters, res[k].rel_residual, res[k].deff_raw
+            out.converged, out.loop_ms = bool(res[k].converged), res[k].loop_ms
+            out.MFL = out.MFR = None
+            outs.append(out)
+        return outs[0] if self.nimg == 1 else outs
+
+    def get_adjoint_tangent(self):
+        """dlambda as (rows, nx); DeffError (DEFF_ESTATE) while none is valid for the current system and adjoint field."""
+        dl = np.empty((self.rows, self.nx), dtype=np.float64)
+        check(self._L.deff_get_adjoint_tangent(self._ctx, dl.ctypes.data_as(C.c_void_p)))
+        return dl
+
+    def set_adjoint_tangent(self, dl):
+        """A caller's own dlambda (deff_set_adjoint_tangent); needs a system."""
+        dl = np.ascontiguousarray(dl, dtype=np.float64)
+        assert dl.size == self.nx * self.rows
+        check(self._L.deff_set_adjoint_tangent(self._ctx, dl.ctypes.data_as(C.c_void_p)))
+
+    def device_adjoint_tangent_ptr(self):
+        """(device pointer, row pitch in bytes) of dlambda; the pitch is device_field_ptr's."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_device_adjoint_tangent(self._ctx, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+    def field_vjp_hvp(self, D, dD, CL, CR, timing=False):
+        """hv = S_w dD, S_w the Hessian of w^T x(D) with w = A lambda held fixed, from the current field, adjoint field,
+        tangent field and dlambda and the planes D and dD, both (rows, nx), in one pass (deff_field_vjp_hvp_D): (hv, curv) with
+        hv as (ny, nx), or (nimg, ny, nx) for a stack, and curv = dD^T S_w dD per image (a float, or an array).  The tangent
+        and dlambda have to be the ones along this dD: field_hvp does all five steps.  timing=True appends the device time in
+        ms."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        dD = np.ascontiguousarray(dD, dtype=np.float64)
+        assert D.size == self.nx * self.rows and dD.size == D.size
+        hv = np.empty((self.rows, self.nx), dtype=np.float64)
+        cv = (C.c_double * self.nimg)()
+        ms = C.c_float()
+        check(self._L.deff_field_vjp_hvp_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p), float(CL),
+                                           float(CR), hv.ctypes.data_as(C.c_void_p), cv, C.byref(ms) if timing else None))
+        hv = hv if self.nimg == 1 else hv.reshape(self.nimg, self.ny, self.nx)
+        curv = cv[0] if self.nimg == 1 else np.array(cv[:])
+        return (hv, curv, ms.value) if timing else (hv, curv)
+
+    def device_field_vjp_hvp_ptr(self):
+        """(device pointer, row pitch in bytes) of the last field_vjp_hvp map; valid until the next one or close()."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_device_field_vjp_hvp(self._ctx, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+    def field_hvp(self, D, dD, CL, CR, rtol=1e-10, max_iter=1_000_000, check_every=64):
+        """(hv, curv) = field_vjp_hvp of the current (converged) field and adjoint field along dD with both tangents computed
+        here: tangent_rhs and adjoint_tangent_rhs with their maps left on the device, solve_tangent and solve_adjoint_tangent
+        to rtol (RuntimeError if one does not get there), then field_vjp_hvp.  Overwrites both right-hand side maps, the
+        tangent field and dlambda."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        dD = np.ascontiguousarray(dD, dtype=np.float64)
+        assert D.size == self.nx * self.rows and dD.size == D.size
+        self._tangent_along("field_hvp", D, dD, CL, CR, rtol, max_iter, check_every)
+        check(self._L.deff_adjoint_tangent_rhs_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p),
+                                                 None, None, None))
+        rs = self.solve_adjoint_tangent(rtol=rtol, max_iter=max_iter, check_every=check_every)
+        rs = rs if isinstance(rs, list) else [rs]
+        bad = [k for k, r in enumerate(rs) if not r.converged]
+        if bad:
+            raise RuntimeError(f"field_hvp (adjoint tangent): CG did not converge to rtol {rtol} for image(s) {bad} "
+                               f"(rel_residual {[rs[k].rel_residual for k in bad]}, max_iter {max_iter})")
+        return self.field_vjp_hvp(D, dD, CL, CR)
+
     def set_progress(self, fn):
         """fn(iter, deff_raw, change) after every convergence check, or None."""
         if fn is None:

@@ -102,6 +102,7 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  * "vjp_kt" (deff_field_vjp_D: the same for the field adjoint's pass; deff_get_plan "vjp_kt"),
  * "tan_kt" (deff_tangent_rhs_D: the same for the field tangent's pass; deff_get_plan "tan_kt"),
  * "hvp_kt" (deff_sensitivity_hvp_D: the same for the Hessian-vector pass; deff_get_plan "hvp_kt"),
+ * "fhvp_kt" (deff_field_vjp_hvp_D: the same for the field adjoint's second-order pass; deff_get_plan "fhvp_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
  *   run every pass between two checks in ONE launch, neighbouring tiles synchronised by flags: 1 = one launch per
  *   pass instead; a resident launch that cannot make progress -- another process holds part of the GPU -- gives up
@@ -142,7 +143,8 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * strips of 128 columns x ceil(tile rows / res_kt), or for deff_residual_D rows x segments of 256 columns).  Of the last
  * deff_sensitivity / deff_sensitivity_D that launched: "sens_kt" and "sens_items", with the same meaning; of the last
  * deff_field_vjp_D that launched: "vjp_kt" and "vjp_items", of the last deff_tangent_rhs_D: "tan_kt" and "tan_items", and of
- * the last deff_sensitivity_hvp_D: "hvp_kt" and "hvp_items", likewise.  Of the flood fill
+ * the last deff_sensitivity_hvp_D: "hvp_kt" and "hvp_items", of the last deff_field_vjp_hvp_D: "fhvp_kt" and "fhvp_items",
+ * likewise.  Of the flood fill
  * on the device (deff_assemble_3phase_native): "fill_impl" (form of the last fill: 1 = one workgroup per image, 2 = row tiles),
  * "fill_launches" (kernel launches of the last fill), "fill_rounds" (most rounds one workgroup of it took), "fill_runs" (fills
  * computed since the context was created: a continuation stage on the same image computes none), "fill_fallbacks" (images
@@ -530,6 +532,63 @@ int deff_sensitivity_hvp_D(deff_ctx *ctx, const double *D, const double *dD, dou
                            double *hv /* nimg*ny*nx, may be NULL */, double *curv /* [nimg], may be NULL */, float *ms);
 int deff_device_sensitivity_hvp(deff_ctx *ctx, void **d_hv, size_t *row_pitch_bytes);
 int deff_set_tangent(deff_ctx *ctx, const double *dx);
+/* ---- second-order field adjoint: hv = S_w dD, S_w the Hessian of phi_w(D) = w^T x(D) with the incoming gradient w = dL/dx held
+ * fixed, two side solves and one pass (nothing like it in the reference): the term that makes the Gauss-Newton product
+ * J^T L'' J of a loss on the field into its Hessian.  g = grad phi_w is deff_field_vjp_D's map, a function of (x, lambda, D);
+ * along dD, x moves by y = dx (the field tangent: deff_tangent_rhs_D, deff_solve_tangent), lambda by m = dlambda with
+ * A dlambda = -dA lambda =: q, and the quotient tq = Dq / s by u.  All three parts are face-local.
+ *
+ * deff_adjoint_tangent_rhs_D: q[p] from the current lambda, D and dD: deff_tangent_rhs_D's pass and expressions with lambda in
+ *   the place of the field and both wall values 0 (bit for bit tests/tangent_model.tangent_rhs(lambda, D, dD, 0, 0)), into a map
+ *   of its own -- deff_device_tangent_rhs's map stays.  norm2[k] = the squared norm of q per image.  q, norm2, ms may be NULL.
+ *   Needs a valid lambda (DEFF_ESTATE otherwise); NULL ctx, D or dD and row-slab contexts: DEFF_EINVAL.  Launch geometry: tuning
+ *   "tan_kt" (the plan keys "tan_kt" / "tan_items" stay those of the last deff_tangent_rhs_D).  Makes the map a right-hand side
+ *   and dlambda invalid.
+ * deff_solve_adjoint_tangent: A dlambda = q', q' the map above with the forward system's decoupled rows zeroed, read on the
+ *   device; deff_solve_tangent with other buffers, bit for bit the same arithmetic for the same numbers.  Leaves the field,
+ *   the system, lambda, dx and every map as they are.  Refusals: those of deff_solve_tangent; DEFF_ESTATE while there is no
+ *   right-hand side for the current system and lambda.
+ * dlambda's lifetime: deff_solve_adjoint_tangent and deff_set_adjoint_tangent make it valid; every call that invalidates the
+ *   adjoint field, and every call that replaces it (deff_solve_adjoint, deff_set_adjoint: a new lambda makes dlambda stale),
+ *   invalidates dlambda and the map's use as a right-hand side.  While it is invalid deff_get_adjoint_tangent,
+ *   deff_device_adjoint_tangent and deff_field_vjp_hvp_D return DEFF_ESTATE.
+ * deff_get_adjoint_tangent / deff_device_adjoint_tangent / deff_set_adjoint_tangent: as deff_get_tangent / deff_device_tangent
+ *   / deff_set_tangent (the setter needs a system; it lets the pass run on arbitrary planes).
+ *
+ * deff_field_vjp_hvp_D: hv[p] from the current field x, lambda l, tangent y, dlambda m, D and dD, in one pass.  With dx, dy of
+ * deff_mesh, wx = dy / dx, wy = dx / dy, ww = dy / (dx / 2.0), d[p] = (D[p] == 0) ? 0 : dD[p]:
+ *   interior face of p towards q (weight w = wx for W / E, wy for N / S):
+ *       s = Dp + Dq;  tq = (s == 0) ? 0 : Dq / s;  tp = (s == 0) ? 0 : Dp / s;  u = (s == 0) ? 0 : (tp * dq - tq * dp) / s;
+ *       e = xp - xq;  fl = lp - lq;  ed = yp - yq;  fm = mp - mq;  ef = e * fl;  k = ed * fl + e * fm;
+ *       c = w * ((4.0 * tq) * (u * ef) + (2.0 * (tq * tq)) * k)
+ *   left / right wall:  e = xp - CL (CR);  c = ww * (yp * lp + e * mp)        no face (first / last row of an image):  c = +0.0
+ *   hv[p] = -(((cW + cE) + cN) + cS),   and hv[p] = 0 where D[p] == 0.
+ * These doubles, in this order (tests/field_hvp_model.py states them in numpy; the library is built without contraction).
+ * Seen from q, u is exactly -u and ef, k have the same bits, so a face is evaluated once for both cells:
+ *   cq = w * ((4.0 * tp) * ((-u) * ef) + (2.0 * (tp * tp)) * k).  Only the sign of a zero can differ from the expressions above.
+ * curv[k] = sum over image k of d[p] * hv[p] = dD^T S_w dD, a wave-level reduction in a fixed order
+ * (csrc/kernels_facepass.hpp), the same bits on every call; it has no sign.  Checks that need no reference: phi_w is
+ * homogeneous of degree 0 in D, so g is of degree -1 and S_w D = -g; S_w is symmetric; S_w is linear in w.  hv (nimg*ny*nx,
+ * true width) and curv ([nimg]) may each be NULL; *ms (may be NULL) = device time of the pass, on an event pair of its own.
+ *   D and dD [nimg*ny*nx] on the host.  CR == CL is allowed (nothing is divided by it).  That lambda, dx and dlambda belong to
+ *   THIS dD, D and field is the caller's responsibility: the pass cannot tell.
+ *   Plain and stack contexts; NULL ctx, D or dD, a row-slab context: DEFF_EINVAL; no field, no valid lambda, no valid tangent,
+ *   no valid dlambda: DEFF_ESTATE, the message names which.  The call writes only its own map, its partial sums and the upload
+ *   scratch (2 n doubles); a refused call leaves the previous map alone.  Non-finite planes: unspecified values, never a fault.
+ * Tuning "fhvp_kt" and deff_get_plan "fhvp_kt" / "fhvp_items": as "hvp_kt" / "hvp_items", the same planner.
+ * deff_device_field_vjp_hvp: the device buffer of the last map (row pitch as deff_device_field, the pad column of an odd width
+ *   holds 0), valid until the next deff_field_vjp_hvp_D or deff_destroy; DEFF_ESTATE before one exists.
+ * The whole product, on a converged field with a valid lambda: deff_tangent_rhs_D(dD), deff_solve_tangent,
+ *   deff_adjoint_tangent_rhs_D(dD), deff_solve_adjoint_tangent, deff_field_vjp_hvp_D(dD). */
+int deff_adjoint_tangent_rhs_D(deff_ctx *ctx, const double *D, const double *dD,
+                               double *q /* nimg*ny*nx, may be NULL */, double *norm2 /* [nimg], may be NULL */, float *ms);
+int deff_solve_adjoint_tangent(deff_ctx *ctx, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out /* [nimg] */);
+int deff_get_adjoint_tangent(deff_ctx *ctx, double *dl);
+int deff_device_adjoint_tangent(deff_ctx *ctx, void **d_dl, size_t *row_pitch_bytes);
+int deff_set_adjoint_tangent(deff_ctx *ctx, const double *dl);
+int deff_field_vjp_hvp_D(deff_ctx *ctx, const double *D, const double *dD, double CL, double CR,
+                         double *hv /* nimg*ny*nx, may be NULL */, double *curv /* [nimg], may be NULL */, float *ms);
+int deff_device_field_vjp_hvp(deff_ctx *ctx, void **d_hv, size_t *row_pitch_bytes);
 /* sweep-kernel launches issued by the last deff_sweeps()/deff_solve() and the sweeps one
  * temporally blocked launch performs (1 for the single-sweep kernels).  A chained launch of the streaming kernel
  * (deff_get_plan "tb_chain" = 1: several passes of *sweeps_per_pass sweeps in one launch) counts its PASSES, so that
