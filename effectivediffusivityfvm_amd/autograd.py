@@ -20,6 +20,13 @@ _FN = None
 _GRAD_FN = None
 
 
+def _tune(s, onchip):
+    """The tuning keys every pass sets on its Solver: with `onchip` the solves on the coefficient planes iterate images of at
+    most 16 384 cells on one compute unit each ("cg_onchip_planes" 1); without it the key is left as it is."""
+    if onchip:
+        s.set_tuning("cg_onchip_planes", 1)
+
+
 def _grad_function():
     """The torch.autograd.Function that carries Deff's gradient map through a graph -- the second derivative of
     effective_diffusivity -- and the one its backward pass applies, the Hessian-vector product.  Created at first use."""
@@ -33,7 +40,7 @@ def _grad_function():
         torch.autograd.functional.hvp differentiates the backward pass with respect to the incoming gradient.  D is a
         constant here: third derivatives are not computed."""
         @staticmethod
-        def forward(ctx, D, w, CL, CR, rtol, max_iter, solver):
+        def forward(ctx, D, w, CL, CR, rtol, max_iter, solver, onchip):
             Dh = np.ascontiguousarray(D.detach().cpu().numpy(), dtype=np.float64)
             nimg = Dh.shape[0] if Dh.ndim == 3 else 1
             ny, nx = Dh.shape[-2:]
@@ -44,6 +51,7 @@ def _grad_function():
                 s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
                 s.init_linear(CL, CR)
                 s.set_tuning("cg_planes", 1)
+                _tune(s, onchip)
                 _converged("effective_diffusivity (second order)", s.solve_cg(rtol=rtol, max_iter=max_iter), rtol, max_iter)
                 try:
                     hv, _ = s.deff_hvp(Dh.reshape(nimg * ny, nx), wh.reshape(nimg * ny, nx), CL, CR, rtol=rtol, max_iter=max_iter)
@@ -53,27 +61,27 @@ def _grad_function():
                 if solver is None:
                     s.close()
             ctx.save_for_backward(D)
-            ctx.deff_args = (CL, CR, rtol, max_iter, solver)
+            ctx.deff_args = (CL, CR, rtol, max_iter, solver, onchip)
             return torch.from_numpy(np.ascontiguousarray(hv).reshape(Dh.shape)).to(w.device)
 
         @staticmethod
         def backward(ctx, u):
             (D,) = ctx.saved_tensors
-            return None, _DeffHessVec.apply(D, u, *ctx.deff_args), None, None, None, None, None
+            return None, _DeffHessVec.apply(D, u, *ctx.deff_args), None, None, None, None, None, None
 
     class _DeffGradient(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, D, g, CL, CR, rtol, max_iter, solver):
+        def forward(ctx, D, g, CL, CR, rtol, max_iter, solver, onchip):
             # g(D) was computed by effective_diffusivity's forward pass: nothing is solved or copied here
             ctx.save_for_backward(D)
-            ctx.deff_args = (CL, CR, rtol, max_iter, solver)
+            ctx.deff_args = (CL, CR, rtol, max_iter, solver, onchip)
             return g.view_as(g)
 
         @staticmethod
         def backward(ctx, w):
             # H is symmetric: the vjp of the gradient map is the Hessian-vector product H w, per image
             (D,) = ctx.saved_tensors
-            return _DeffHessVec.apply(D.detach(), w, *ctx.deff_args), None, None, None, None, None, None
+            return _DeffHessVec.apply(D.detach(), w, *ctx.deff_args), None, None, None, None, None, None, None
 
     _GRAD_FN = _DeffGradient
     return _GRAD_FN
@@ -88,7 +96,7 @@ def _function():
 
     class _EffectiveDiffusivity(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, D, CL, CR, rtol, max_iter, solver):
+        def forward(ctx, D, CL, CR, rtol, max_iter, solver, onchip):
             Dh = np.ascontiguousarray(D.detach().cpu().numpy(), dtype=np.float64)
             stack = Dh.ndim == 3
             nimg = Dh.shape[0] if stack else 1
@@ -100,6 +108,7 @@ def _function():
                 s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
                 s.init_linear(CL, CR)
                 s.set_tuning("cg_planes", 1)
+                _tune(s, onchip)
                 rs = s.solve_cg(rtol=rtol, max_iter=max_iter)
                 rs = rs if isinstance(rs, list) else [rs]
                 bad = [k for k, r in enumerate(rs) if not r.converged]
@@ -114,7 +123,7 @@ def _function():
             g = torch.from_numpy(np.ascontiguousarray(g).reshape(Dh.shape)).to(D.device)
             ctx.save_for_backward(g, D)
             ctx.save_for_forward(g)
-            ctx.deff_args = (CL, CR, rtol, max_iter, solver)
+            ctx.deff_args = (CL, CR, rtol, max_iter, solver, onchip)
             out = torch.from_numpy(deff).to(D.device)
             return out if stack else out[0]
 
@@ -124,7 +133,7 @@ def _function():
             if torch.is_grad_enabled() and D.requires_grad:
                 # create_graph: the map as a function of D, whose backward is the Hessian-vector product
                 g = _grad_function().apply(D, g, *ctx.deff_args)
-            return grad_out[..., None, None] * g, None, None, None, None, None
+            return grad_out[..., None, None] * g, None, None, None, None, None, None
 
         @staticmethod
         def jvp(ctx, tD, *_):
@@ -136,7 +145,7 @@ def _function():
     return _FN
 
 
-def effective_diffusivity(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, solver=None):
+def effective_diffusivity(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, solver=None, onchip=False):
     """deff_raw of the diffusivity map D -- a float64 tensor (ny, nx), or (nimg, ny, nx) for a stack, on any device -- as a
     tensor on D's device, shape () or (nimg,), differentiable with respect to D.  Forward: deff_assemble_from_D, the linear
     guess, conjugate gradients on the coefficient planes to rtol (raises RuntimeError if they do not converge), then the
@@ -150,11 +159,15 @@ def effective_diffusivity(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, sol
     Hessian-vector map and "cg_planes" are overwritten), otherwise on a Solver created and closed for that pass; RuntimeError
     if a solve does not converge.  H w is in turn differentiable with respect to w (by H again: functional.hvp's double
     backward needs it); D is a constant there, so third derivatives come out as zero, and a jvp of the gradient map and
-    torch.func are not supported.  First-order use pays nothing for this: no extra solve or copy, the same bits."""
+    torch.func are not supported.  First-order use pays nothing for this: no extra solve or copy, the same bits.
+    `onchip`: True sets the tuning key "cg_onchip_planes" to 1 on the Solver of every pass, first and second order, created
+    here or passed (the key is overwritten, like "cg_planes", and stays set on a passed solver): images of at most 16 384
+    cells (pitch x ny) iterate on one compute unit each (plan "cg_impl" 4), larger ones as without it.  The results agree with
+    onchip=False to the solves' rtol, not bit for bit.  False (default) leaves the key alone: the same calls and bits as ever."""
     import torch
     if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() not in (2, 3):
         raise TypeError("D must be a float64 tensor of shape (ny, nx) or (nimg, ny, nx)")
-    return _function().apply(D, float(CL), float(CR), float(rtol), int(max_iter), solver)
+    return _function().apply(D, float(CL), float(CR), float(rtol), int(max_iter), solver, bool(onchip))
 
 
 _FIELD_FN = None
@@ -179,7 +192,7 @@ def _field_grad_function():
         return _FIELD_GRAD_FN
     import torch
 
-    def on_solver(Dh, x, CL, CR, solver, fn):
+    def on_solver(Dh, x, CL, CR, solver, onchip, fn):
         """fn(s, D2) on `solver`, or on a Solver created and closed here, with the system of Dh assembled and x as its field."""
         nimg = Dh.shape[0] if Dh.ndim == 3 else 1
         ny, nx = Dh.shape[-2:]
@@ -189,6 +202,7 @@ def _field_grad_function():
             D2 = Dh.reshape(nimg * ny, nx)
             s.assemble_from_D(D2, CL, CR)
             s.set_field(x.reshape(nimg * ny, nx))
+            _tune(s, onchip)
             return fn(s, D2)
         finally:
             if solver is None:
@@ -205,7 +219,7 @@ def _field_grad_function():
         torch.autograd.functional.hvp differentiates the backward pass with respect to the incoming gradient.  D and w are
         constants here: third derivatives and the w-derivative of S_w v are not computed."""
         @staticmethod
-        def forward(ctx, v, Dh, x, w, CL, CR, rtol, max_iter, solver):
+        def forward(ctx, v, Dh, x, w, CL, CR, rtol, max_iter, solver, onchip):
             def run(s, D2):
                 _converged("concentration_field (second order, adjoint)",
                            s.solve_adjoint(w, rtol=rtol, max_iter=max_iter), rtol, max_iter)
@@ -213,52 +227,52 @@ def _field_grad_function():
                     return s.field_hvp(D2, host(v, Dh), CL, CR, rtol=rtol, max_iter=max_iter)[0]
                 except RuntimeError as e:
                     raise RuntimeError(f"concentration_field (second order): {e}") from None
-            ctx.deff_args = (Dh, x, w, CL, CR, rtol, max_iter, solver)
-            return tensor(on_solver(Dh, x, CL, CR, solver, run), Dh, v)
+            ctx.deff_args = (Dh, x, w, CL, CR, rtol, max_iter, solver, onchip)
+            return tensor(on_solver(Dh, x, CL, CR, solver, onchip, run), Dh, v)
 
         @staticmethod
         def backward(ctx, u):
-            return (_FieldHessVec.apply(u, *ctx.deff_args),) + (None,) * 8
+            return (_FieldHessVec.apply(u, *ctx.deff_args),) + (None,) * 9
 
     class _FieldJvp(torch.autograd.Function):
         """v -> J v, J = dx/dD.  Linear in v; its vjp is J^T, the field adjoint's map with D held constant."""
         @staticmethod
-        def forward(ctx, v, Dh, x, CL, CR, rtol, max_iter, solver):
+        def forward(ctx, v, Dh, x, CL, CR, rtol, max_iter, solver, onchip):
             def run(s, D2):
                 try:
                     return s.field_jvp(D2, host(v, Dh), CL, CR, rtol=rtol, max_iter=max_iter)
                 except RuntimeError as e:
                     raise RuntimeError(f"concentration_field (second order): {e}") from None
-            ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver)
-            return tensor(on_solver(Dh, x, CL, CR, solver, run), Dh, v)
+            ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver, onchip)
+            return tensor(on_solver(Dh, x, CL, CR, solver, onchip, run), Dh, v)
 
         @staticmethod
         def backward(ctx, u):
             Dh = ctx.deff_args[0]
-            return (_FieldVjp.apply(tensor(Dh, Dh, u), u, *ctx.deff_args),) + (None,) * 7
+            return (_FieldVjp.apply(tensor(Dh, Dh, u), u, *ctx.deff_args),) + (None,) * 8
 
     class _FieldVjp(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, D, w, Dh, x, CL, CR, rtol, max_iter, solver):
+        def forward(ctx, D, w, Dh, x, CL, CR, rtol, max_iter, solver, onchip):
             # concentration_field's first-order backward pass, call for call
             wh = host(w, Dh)
 
             def run(s, D2):
                 _converged("concentration_field (adjoint)", s.solve_adjoint(wh, rtol=rtol, max_iter=max_iter), rtol, max_iter)
                 return s.field_vjp(D2, CL, CR)[0]
-            ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver)
+            ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver, onchip)
             ctx.deff_w = wh
-            return tensor(on_solver(Dh, x, CL, CR, solver, run), Dh, w)
+            return tensor(on_solver(Dh, x, CL, CR, solver, onchip, run), Dh, w)
 
         @staticmethod
         def backward(ctx, v):
-            Dh, x, CL, CR, rtol, max_iter, solver = ctx.deff_args
+            Dh, x, CL, CR, rtol, max_iter, solver, onchip = ctx.deff_args
             gD = gw = None
             if ctx.needs_input_grad[0]:
-                gD = _FieldHessVec.apply(v, Dh, x, ctx.deff_w, CL, CR, rtol, max_iter, solver)
+                gD = _FieldHessVec.apply(v, Dh, x, ctx.deff_w, CL, CR, rtol, max_iter, solver, onchip)
             if ctx.needs_input_grad[1]:
                 gw = _FieldJvp.apply(v, *ctx.deff_args)
-            return (gD, gw) + (None,) * 7
+            return (gD, gw) + (None,) * 8
 
     _FIELD_GRAD_FN = _FieldVjp
     return _FIELD_GRAD_FN
@@ -273,7 +287,7 @@ def _field_function():
 
     class _ConcentrationField(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, D, CL, CR, rtol, max_iter, solver):
+        def forward(ctx, D, CL, CR, rtol, max_iter, solver, onchip):
             Dh = np.ascontiguousarray(D.detach().cpu().numpy(), dtype=np.float64)
             nimg = Dh.shape[0] if Dh.ndim == 3 else 1
             ny, nx = Dh.shape[-2:]
@@ -284,22 +298,23 @@ def _field_function():
                 s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
                 s.init_linear(CL, CR)
                 s.set_tuning("cg_planes", 1)
+                _tune(s, onchip)
                 _converged("concentration_field", s.solve_cg(rtol=rtol, max_iter=max_iter, fluxes=False), rtol, max_iter)
                 x = s.get_field().reshape(Dh.shape)
             finally:
                 if solver is None:
                     s.close()
-            ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver)
+            ctx.deff_args = (Dh, x, CL, CR, rtol, max_iter, solver, onchip)
             ctx.save_for_backward(D)
             return torch.from_numpy(x.copy()).to(D.device)
 
         @staticmethod
         def backward(ctx, grad_out):
-            Dh, x, CL, CR, rtol, max_iter, solver = ctx.deff_args
+            Dh, x, CL, CR, rtol, max_iter, solver, onchip = ctx.deff_args
             (D,) = ctx.saved_tensors
             if torch.is_grad_enabled() and (D.requires_grad or grad_out.requires_grad):
                 # create_graph: the same calls inside a Function of (D, w), whose backward is the second order
-                return (_field_grad_function().apply(D, grad_out, *ctx.deff_args),) + (None,) * 5
+                return (_field_grad_function().apply(D, grad_out, *ctx.deff_args),) + (None,) * 6
             nimg = Dh.shape[0] if Dh.ndim == 3 else 1
             ny, nx = Dh.shape[-2:]
             w = np.ascontiguousarray(grad_out.detach().cpu().numpy(), dtype=np.float64)
@@ -308,6 +323,7 @@ def _field_function():
                 # whatever happened to the solver since the forward pass: its system and field are set again
                 s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
                 s.set_field(x.reshape(nimg * ny, nx))
+                _tune(s, onchip)
                 _converged("concentration_field (adjoint)",
                            s.solve_adjoint(w.reshape(nimg * ny, nx), rtol=rtol, max_iter=max_iter), rtol, max_iter)
                 g, _ = s.field_vjp(Dh.reshape(nimg * ny, nx), CL, CR)
@@ -315,12 +331,12 @@ def _field_function():
                 if solver is None:
                     s.close()
             g = torch.from_numpy(np.ascontiguousarray(g).reshape(Dh.shape)).to(grad_out.device)
-            return g, None, None, None, None, None
+            return g, None, None, None, None, None, None
 
         @staticmethod
         def jvp(ctx, tD, *_):
             # forward mode (torch.autograd.forward_ad): A dx = db - dA x along tD, one pass and one solve
-            Dh, x, CL, CR, rtol, max_iter, solver = ctx.deff_args
+            Dh, x, CL, CR, rtol, max_iter, solver, onchip = ctx.deff_args
             nimg = Dh.shape[0] if Dh.ndim == 3 else 1
             ny, nx = Dh.shape[-2:]
             d = np.ascontiguousarray(tD.detach().cpu().numpy(), dtype=np.float64)
@@ -329,6 +345,7 @@ def _field_function():
                 # as in backward: the solver's system and field are set again
                 s.assemble_from_D(Dh.reshape(nimg * ny, nx), CL, CR)
                 s.set_field(x.reshape(nimg * ny, nx))
+                _tune(s, onchip)
                 s.tangent_rhs(Dh.reshape(nimg * ny, nx), d.reshape(nimg * ny, nx), CL, CR)
                 _converged("concentration_field (tangent)", s.solve_tangent(rtol=rtol, max_iter=max_iter), rtol, max_iter)
                 dx = s.get_tangent()
@@ -341,7 +358,7 @@ def _field_function():
     return _FIELD_FN
 
 
-def concentration_field(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, solver=None):
+def concentration_field(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, solver=None, onchip=False):
     """The concentration field x of the diffusivity map D -- a float64 tensor (ny, nx), or (nimg, ny, nx) for a stack, on any
     device -- as a tensor of D's shape on D's device, differentiable with respect to D for ANY loss on x.  Forward, as
     effective_diffusivity: deff_assemble_from_D, the linear guess, conjugate gradients on the coefficient planes to rtol
@@ -362,8 +379,11 @@ def concentration_field(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, solve
     Solver created and closed for that pass; RuntimeError if a solve does not converge.  S_w v and J v are in turn
     differentiable with respect to v (by S_w again, and by J^T: functional.hvp's double backward needs both); D and w are
     constants there, so third derivatives and the w-derivative of S_w v come out as None / zero, and a jvp of the gradient map and
-    torch.func are not supported.  First-order use pays nothing for this: the same calls, the same bits, no graph."""
+    torch.func are not supported.  First-order use pays nothing for this: the same calls, the same bits, no graph.
+    `onchip`: as in effective_diffusivity -- True sets "cg_onchip_planes" to 1 on the Solver of the forward pass, the backward
+    pass, the jvp and every second-order pass (created or passed; the key is overwritten), so the forward solve and the
+    adjoint and tangent solves iterate eligible images on one compute unit each; False (default) leaves the key alone."""
     import torch
     if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() not in (2, 3):
         raise TypeError("D must be a float64 tensor of shape (ny, nx) or (nimg, ny, nx)")
-    return _field_function().apply(D, float(CL), float(CR), float(rtol), int(max_iter), solver)
+    return _field_function().apply(D, float(CL), float(CR), float(rtol), int(max_iter), solver, bool(onchip))

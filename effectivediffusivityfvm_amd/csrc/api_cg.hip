@@ -8,12 +8,14 @@
 // The launches of one iteration, in every form and under every fold key, are CgIteration::enqueue's, for both solves.
 // deff_solve_adjoint (A lambda = w for the gradient of a loss on the field, api_vjp.hip) and deff_solve_tangent (A dx = r for
 // the field's derivative along a direction, api_tangent.hip) run deff_solve_cg's host loop,
-// cg_host_loop, on the coefficient planes with its own solution and right-hand side buffers.
+// cg_host_loop, on the coefficient planes with its own solution and right-hand side buffers.  Under the tuning key
+// "cg_onchip_planes" every solve on the planes iterates small images on one compute unit each (kernels_cg_image_planes.hpp).
 #include "ctx.hpp"
 #include "kernels_cg.hpp"
 #include "kernels_cg_planes.hpp"
 #include "kernels_cg_fold.hpp"
 #include "kernels_cg_image.hpp"
+#include "kernels_cg_image_planes.hpp"
 #include "kernels_cg_stream.hpp"
 #include "kernels_cg_slab.hpp"
 #include "cg_slab.hpp"
@@ -67,6 +69,13 @@ static CgGeom cg_geometry(const deff_ctx *c)
     g.cpi = (c->ny + g.kr - 1) / g.kr;
     g.per_img = (unsigned)((size_t)g.ntx * g.cpi);
     return g;
+}
+
+// one workgroup per image (kernels_cg_image.hpp, kernels_cg_image_planes.hpp): the form's own tuning key is set and an image's
+// cells fit a compute unit
+static bool cg_onchip_form(const deff_ctx *c, bool planes)
+{
+    return (planes ? c->cg_onchip_planes : c->cg_onchip) && (size_t)c->nx * c->ny <= (size_t)CGI_CELLS;
 }
 
 static int cg_buffers(deff_ctx *c, size_t items)
@@ -204,10 +213,15 @@ static int cg_host_loop(deff_ctx *c, double *x, const double *rhs, bool planes, 
         }
         if (onchip) {
             // up to check_every iterations of every running image, p in cg_p[0] throughout (the streaming loop below starts
-            // every call at cg_p[0] with the restart flag set, so the two forms never read each other's p)
-            hipLaunchKernelGGL(k_cg_image, dim3((unsigned)std::min(c->nimg, c->cg_cus)), dim3(CGI_THREADS), 0, c->stream,
-                               c->cg_tab, c->lut_nrows, c->code, x, c->cg_r, c->cg_p[0], sc, c->nx, c->ny, c->nimg,
-                               (long long)check_every, tol2, (long long)max_iter);
+            // every call at cg_p[0] with the restart flag set, so the forms never read each other's p); on the planes
+            // (tuning "cg_onchip_planes") the same launch of k_cgp_image, which reads the matrix planes and cg_inv only
+            const dim3 wgs((unsigned)std::min(c->nimg, c->cg_cus));
+            if (planes)
+                hipLaunchKernelGGL(k_cgp_image, wgs, dim3(CGI_THREADS), 0, c->stream, P, c->cg_inv, x, c->cg_r, c->cg_p[0], sc, c->nx,
+                                   c->ny, c->nimg, (long long)check_every, tol2, (long long)max_iter);
+            else
+                hipLaunchKernelGGL(k_cg_image, wgs, dim3(CGI_THREADS), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, x, c->cg_r,
+                                   c->cg_p[0], sc, c->nx, c->ny, c->nimg, (long long)check_every, tol2, (long long)max_iter);
             HIP_TRY(hipGetLastError());
             continue;
         }
@@ -256,7 +270,8 @@ try {
     const size_t items = (size_t)g.per_img * c->nimg;
     // on chip (tuning "cg_onchip"): an image whose arrays fit one compute unit's LDS and registers iterates there, one
     // launch per check_every iterations instead of four per iteration; larger images keep the streaming kernels
-    const bool onchip = !planes && c->cg_onchip && (size_t)c->nx * c->ny <= (size_t)CGI_CELLS;
+    // (on the planes: tuning "cg_onchip_planes", k_cgp_image)
+    const bool onchip = cg_onchip_form(c, planes);
     if (onchip && !c->cg_cus) HIP_TRY(hipDeviceGetAttribute(&c->cg_cus, hipDeviceAttributeMultiprocessorCount, c->device));
     TRY(cg_buffers(c, items));
     if (planes) TRY(cgp_buffers(c));
@@ -264,7 +279,7 @@ try {
     c->cg_plan_ntx = g.ntx;
     c->cg_plan_items = (int)g.per_img;
     c->cg_plan_restarts = 0;
-    c->cg_plan_impl = planes ? 3 : onchip ? 2 : 1;
+    c->cg_plan_impl = planes ? (onchip ? 4 : 3) : onchip ? 2 : 1;
     // two launches per iteration (tuning "cg_fold", kernels_cg_fold.hpp); the plane form's direction kernel loads ahead already
     const int fold = onchip ? 0 : (planes && c->cg_fold == 2) ? 1 : c->cg_fold;
     c->cg_plan_fold = fold;
@@ -372,8 +387,10 @@ static int side_solve_run(deff_ctx *c, double *x, double *rhs, const CgGeom &g, 
     c->cg_plan_ntx = g.ntx;
     c->cg_plan_items = (int)g.per_img;
     c->cg_plan_restarts = 0;
-    c->cg_plan_impl = 3;
-    const int fold = c->cg_fold == 2 ? 1 : c->cg_fold;
+    const bool onchip = cg_onchip_form(c, true);
+    if (onchip && !c->cg_cus) HIP_TRY(hipDeviceGetAttribute(&c->cg_cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    c->cg_plan_impl = onchip ? 4 : 3;
+    const int fold = onchip ? 0 : c->cg_fold == 2 ? 1 : c->cg_fold;
     c->cg_plan_fold = fold;
     hipLaunchKernelGGL(k_cgp_mask_rhs, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, c->cg_inv, c->n, rhs);
     HIP_TRY(hipGetLastError());
@@ -381,7 +398,7 @@ static int side_solve_run(deff_ctx *c, double *x, double *rhs, const CgGeom &g, 
 
     std::vector<CgScal> hs;
     float ms = 0;
-    TRY(cg_host_loop(c, x, rhs, true, false, fold, g, rtol, max_iter, check_every, hs, &ms));
+    TRY(cg_host_loop(c, x, rhs, true, onchip, fold, g, rtol, max_iter, check_every, hs, &ms));
     for (int i = 0; i < c->nimg; ++i) {
         out[i].iters = hs[i].iters;
         out[i].rel_residual = hs[i].rel;

@@ -309,6 +309,12 @@ try {
         if (value > 1) return fail(DEFF_EINVAL, "cg_onchip takes 0 (streaming kernels) or 1 (small images iterate on one compute unit each)");
         c->cg_onchip = value;
     }
+    else if (!strcmp(key, "cg_onchip_planes")) {
+        if (value > 1)
+            return fail(DEFF_EINVAL, "cg_onchip_planes takes 0 (streaming kernels on the coefficient planes) or 1 (small images "
+                                     "iterate on one compute unit each)");
+        c->cg_onchip_planes = value;
+    }
     else if (!strcmp(key, "cg_planes")) {
         if (value > 2)
             return fail(DEFF_EINVAL, "cg_planes takes 0 (CG on the row dictionary only), 1 (on the coefficient planes when the system "

@@ -285,6 +285,10 @@ struct deff_ctx {
     // system that has no row dictionary, 2 = for every system (tests: the bits are the table form's); 0 (default) = never.
     // cg_inv (1 / a0 per cell, 0 on decoupled cells) and cg_q (A p) are allocated by the first call that takes that form
     int cg_planes = 0;
+    // tuning "cg_onchip_planes": 1 = a solve on the coefficient planes (deff_solve_cg where it takes that form, and the side
+    // solves deff_solve_adjoint / _tangent / _adjoint_tangent) iterates images of at most 16 384 cells on one compute unit each
+    // (kernels_cg_image_planes.hpp; cg_plan_impl 4); 0 (default) = the streaming plane kernels for every size
+    int cg_onchip_planes = 0;
     double *cg_inv = nullptr, *cg_q = nullptr;
     // tuning "cg_fold": 1 = an iteration of the streaming forms is two launches, the image's last workgroup to arrive does what
     // k_cg_alpha / k_cg_beta do (kernels_cg_fold.hpp); 2 = as 1, the table form's direction kernel with loads a row ahead;

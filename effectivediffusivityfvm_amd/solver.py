@@ -98,7 +98,8 @@ class Solver:
     def plan(self):
         """What the temporally blocked kernel's last launch plan chose (zeros before any sweep), and "cg_impl": the form of
         the last solve_cg (1 streaming kernels, 2 one image per compute unit: set_tuning("cg_onchip", 1), 3 on the coefficient
-        planes: set_tuning("cg_planes", 1 or 2); 0 before one).  "prescaled": 1 when the last sweeps ran the pre-scaled five-FMA
+        planes: set_tuning("cg_planes", 1 or 2), 4 one image per compute unit on the coefficient planes:
+        set_tuning("cg_onchip_planes", 1); 0 before one).  "prescaled": 1 when the last sweeps ran the pre-scaled five-FMA
         arithmetic (set_tuning("prescaled", 1): opt-in, not bit-identical to the reference's written order)."""
         out = {}
         for key in ("tb_T", "tb_LY", "tb_strips", "tb_chunks_per_image", "tb_blocks", "tb_impl", "tb_R", "tb_NW", "tb_resident", "tb_sym", "tb_ranked", "tb_aged", "cg_impl", "prescaled"):
@@ -236,6 +237,10 @@ class Solver:
         explicit coefficient planes; set_tuning("cg_planes", 2) takes that form for every system (the bits of the table
         form where a dictionary exists).  plan_value("cg_impl") is 3 after such a call.  Explicit-only systems (a wall link
         into the neighbouring row) and row slabs stay refused.
+        set_tuning("cg_onchip_planes", 1) (0 or 1; anything else raises DeffError) lets a call that takes the plane form
+        iterate images of at most 16 384 cells (pitch x ny) on one compute unit each, as "cg_onchip" does for the table form:
+        plan_value("cg_impl") is 4 then, and a system that has a dictionary gets the bits of "cg_onchip" 1.  The key also
+        applies to solve_adjoint, solve_tangent and solve_adjoint_tangent, which always run on the planes.
         set_tuning("cg_fold", 1) makes an iteration of the streaming forms (cg_impl 1 and 3) two launches instead of four: the
         per-image sums are taken by the last workgroup to arrive; 2 also lets the table form's direction kernel load a row
         ahead.  The results are those of 0 bit for bit; plan_value("cg_fold") is what the last call ran (0 on chip)."""
@@ -423,6 +428,8 @@ class Solver:
         """A lambda = w on the current matrix with homogeneous walls (deff_solve_adjoint), w = dL/dx as (rows, nx): the
         iteration of solve_cg on the coefficient planes from lambda = 0, into a buffer of the context's own -- the field, the
         system and its dictionary stay as they are.  Cells the forward system decouples ignore w and get lambda = 0.
+        With set_tuning("cg_onchip_planes", 1) images of at most 16 384 cells iterate on one compute unit each
+        (plan_value("cg_impl") 4), here and in solve_tangent and solve_adjoint_tangent.
         One image: a CGResult (deff_raw 0.0, MFL / MFR None); a stack: a list, one per image."""
         w = np.ascontiguousarray(w, dtype=np.float64)
         assert w.size == self.nx * self.rows

@@ -90,6 +90,9 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  * "cg_onchip" (deff_solve_cg: 1 = images of at most 16 384 cells iterate on one compute unit each, see there),
  * "cg_planes" (deff_solve_cg on the explicit coefficient planes: 1 = for a system without a row dictionary, 2 = always;
  *   values above 2 are DEFF_EINVAL; see there),
+ * "cg_onchip_planes" (CG solves on the coefficient planes -- deff_solve_cg where it takes that form, deff_solve_adjoint,
+ *   deff_solve_tangent, deff_solve_adjoint_tangent: 1 = images of at most 16 384 cells iterate on one compute unit each; values
+ *   above 1 are DEFF_EINVAL; see deff_solve_cg),
  * "cg_fold" (deff_solve_cg / deff_solve_cg_stream: 1 = two launches per iteration instead of four, 2 = as 1 with loads a row
  *   ahead; values above 2 are DEFF_EINVAL; see deff_solve_cg),
  * "fill_impl" (deff_assemble_3phase_native: form of the flood fill on the device, 0 = by size, 1 = one workgroup per image,
@@ -134,7 +137,8 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * passes of a batch run as one resident launch; workgroup tiles only), "tb_chain" (1: the streaming kernel chains its passes), "tb_chunk_min" / "tb_chunk_max" (dealt tiles: rows of the shortest and of the tallest chunk), "tb_fallbacks" (resident intervals that gave up and were redone with
  * one launch per pass); 0 before any sweep.  Of the last deff_solve_cg (0 before one): "cg_kr" (rows per work item),
  * "cg_strips" (strips of 128 columns), "cg_items" (work items per image), "cg_restarts" (true-residual rounds that
- * sent an image back into the iteration), "cg_impl" (1 = streaming kernels, 2 = on chip, 3 = on the coefficient planes) and
+ * sent an image back into the iteration), "cg_impl" (1 = streaming kernels, 2 = on chip, 3 = on the coefficient planes,
+ * 4 = on chip on the coefficient planes: tuning key "cg_onchip_planes") and
  * "cg_fold" (the fold the call ran: 0, 1 or 2, see the tuning key); of the last
  * deff_solve_cg_stream, which also sets the "cg_" keys: "cgs_intervals", "cgs_launches", "cgs_waits" (see there).  Of the
  * last deff_residual / deff_residual_slot / deff_residual_D that launched (0 before one; a refused call leaves them alone):
@@ -266,6 +270,17 @@ int deff_solve_batch(deff_ctx *ctx, double omega, double tol, int64_t max_iter, 
  * dictionary and every plan of the Jacobi path are left as they are.  Still refused whatever the key: explicit-only systems
  * (a wall link into the neighbouring row) and row-slab contexts; the key has no effect on deff_slab_*_solve_cg (a slab's
  * system needs a dictionary) nor on deff_solve_cg_stream (a native 2-phase system always has one).
+ * Tuning key "cg_onchip_planes" (0 default: nothing changes anywhere; values above 1 are DEFF_EINVAL): 1 = a solve that takes
+ * the plane form -- this call when the system has no dictionary under "cg_planes" 1 or under "cg_planes" 2, and
+ * deff_solve_adjoint, deff_solve_tangent and deff_solve_adjoint_tangent always -- iterates every image by one workgroup on one
+ * compute unit, as "cg_onchip" does for the table form, when an image has at most 16 384 cells (row pitch x ny, the same rule).
+ * r and A p stay in registers and p in LDS; a pair's matrix row and 1 / A0 are read from the coefficient planes and the
+ * field is read and written in place in every iteration (72 B per cell through L2 / Infinity Cache).  The start, the admissibility check, the flag reads every check_every
+ * iterations, the true-residual rounds and the fluxes are the streaming plane form's; the mapping and the order of the sums
+ * are the table on-chip form's, so a system that has a dictionary gives the bits of "cg_onchip" 1, and any system bits that
+ * do not depend on check_every or on the stack an image is in.  deff_get_plan "cg_impl" = 4 and "cg_fold" = 0 after such a
+ * call.  Larger images, and every call under 0, run exactly as without the key.  Independent of "cg_onchip", which keeps its
+ * meaning for systems that run on the row table.  No effect on row slabs nor on deff_solve_cg_stream.
  * Tuning key "cg_fold" (0 default: four launches per iteration -- two that stream over the field, two that run one
  * workgroup per image to add its partial sums and set alpha / beta and the stop flags): 1 = two launches per iteration.
  * Every work item counts itself in when its partial sum is stored, and the last workgroup to arrive for an image adds the
@@ -392,7 +407,8 @@ int deff_device_sensitivity(deff_ctx *ctx, void **d_g, size_t *row_pitch_bytes);
  *   Reads: the system (its coefficient planes; a native 2- / 3-phase system's are built from its image first, as under the
  *   tuning key "cg_planes" 2) and w[nimg*ny*nx] on the host, true width.  Needs neither a field nor wall diffusivities.
  *   The iteration is deff_solve_cg's on the coefficient planes, whatever "cg_planes" and "cg_onchip" are set to ("cg_fold"
- *   applies as it does to that form): the same work items, recurrence and summation order, the same stop on the device
+ *   applies as it does to that form; under "cg_onchip_planes" 1 images of at most 16 384 cells iterate on one compute unit
+ *   each, "cg_impl" 4, here and in deff_solve_tangent and deff_solve_adjoint_tangent): the same work items, recurrence and summation order, the same stop on the device
  *   (||r|| <= rtol ||w'||), the same true-residual rounds and restart limit, results independent of check_every.  The guess
  *   is always lambda = 0.  Which cells are decoupled is decided by the FORWARD system (four zero links and forward b == 0):
  *   there w is ignored (w' = 0) and lambda = 0; everywhere else w' = w.  An image with ||w'|| = 0 returns at once: iters 0,

@@ -49,6 +49,14 @@ fold_profile   the per-kernel split of keys 0 / 1 / 2 at 1024^2 and at 4096^2: o
               own per size (child processes); --stats-out keeps the two tables in one file
   python tools/measure_cg.py --cases fold_iter,fold_profile --out profiles/cg_fold_results.json \
                              --stats-out profiles/cg_fold_kernel_stats.csv
+onchip_planes  systems on coefficient planes at 128^2 (a seeded per-cell D, uniform 0.5 ... 2, reproducible without any image):
+              one image, a stack of 32 and a stack of 256; solve_cg and solve_adjoint to --rtol at check_every 64 and 512; the
+              streaming plane kernels ("cg_onchip_planes" 0: the code path every earlier revision runs) against one image per
+              compute unit (1), alternating run by run on fresh contexts, at least 3 runs each; every run's loop_ms and
+              iterations, per-iteration time, ratio fastest key 0 / slowest key 1
+onchip_planes_profile  k_cgp_image's share of loop_ms on the 256-image stack from a `rocprofv3 --kernel-trace --stats` run of its
+              own (a child process), and the bytes it moves per compute unit against the 72 B/cell model
+  python tools/measure_cg.py --cases onchip_planes,onchip_planes_profile --out profiles/cg_onchip_planes_results.json
 The bytes model of one iteration is 68 B/cell; "model_us" is that traffic at 6.3 TB/s."""
 import argparse
 import json
@@ -600,6 +608,87 @@ def fold_profile(stats_out):
     return out
 
 
+ONCHIP_PLANES_BYTES_PER_CELL = 72      # k_cgp_image: (A) inv 8 | (B) five planes 40 | (C) inv 8, x 8 read + 8 written
+
+
+def onchip_planes_D(B, n=128):
+    """The seeded per-cell diffusivity of a stack of B images (uniform 0.5 ... 2) and the adjoint's right-hand side."""
+    rng = np.random.default_rng(4200 + B)
+    return rng.uniform(0.5, 2.0, (B * n, n)), rng.standard_normal((B * n, n))
+
+
+def onchip_planes(rtol, max_iter, runs, stacks=(1, 32, 256), only_key1=False, check_everys=(64, 512)):
+    """Systems on coefficient planes (a per-cell D, assemble_from_D, "cg_planes" 1) at 128^2: the streaming plane kernels
+    ("cg_onchip_planes" 0: the code path every earlier revision runs) against one image per compute unit (1), on fresh
+    contexts, the two alternating run by run; solve_cg from the linear guess and solve_adjoint of a seeded w, both to rtol."""
+    n = 128
+    out = {"mesh": [n, n], "rtol": rtol, "bytes_per_cell_model_key1": ONCHIP_PLANES_BYTES_PER_CELL,
+           "bytes_per_cell_model_key0": PLANES_BYTES_PER_CELL}
+    for B in stacks:
+        D, w = onchip_planes_D(B, n)
+        case = {}
+        for ce in check_everys:
+            rows = {f"{what}_key{k}": [] for what in ("solve_cg", "solve_adjoint") for k in (0, 1)}
+            for _ in range(max(runs, 3)):
+                for key in (0, 1):
+                    if only_key1 and not key:
+                        continue
+                    with pkg.Solver(n, n, nimg=B) as s:
+                        s.set_tuning("cg_planes", 1)
+                        s.set_tuning("cg_onchip_planes", key)
+                        s.assemble_from_D(D, 0.0, 1.0)
+                        s.init_linear(0.0, 1.0)
+                        for what in ("solve_cg", "solve_adjoint"):
+                            if what == "solve_cg":
+                                rs = s.solve_cg(rtol=rtol, max_iter=max_iter, check_every=ce, fluxes=False)
+                            else:
+                                rs = s.solve_adjoint(w, rtol=rtol, max_iter=max_iter, check_every=ce)
+                            rs = rs if isinstance(rs, list) else [rs]
+                            assert s.plan_value("cg_impl") == 3 + key and all(r.converged for r in rs)
+                            its = [int(r.iters) for r in rs]
+                            rows[f"{what}_key{key}"].append({"loop_ms": rs[0].loop_ms, "max_iters": max(its), "mean_iters": sum(its) / B,
+                                                             "per_iter_us": 1e3 * rs[0].loop_ms / max(its)})
+            if not only_key1:
+                for what in ("solve_cg", "solve_adjoint"):
+                    fast_old = min(r["loop_ms"] for r in rows[f"{what}_key0"])
+                    slow_new = max(r["loop_ms"] for r in rows[f"{what}_key1"])
+                    rows[f"{what}_ratio_fastest_key0_over_slowest_key1"] = fast_old / slow_new
+                    rows[f"{what}_per_iter_us_best"] = {f"key{k}": min(r["per_iter_us"] for r in rows[f"{what}_key{k}"]) for k in (0, 1)}
+            case[f"check_every_{ce}"] = rows
+        out[f"stack{B}"] = case
+    return out
+
+
+def onchip_planes_profile(rtol):
+    """k_cgp_image's share of loop_ms: one key-1 run of the 256-image stack (check_every 512) in a child process of its own
+    under `rocprofv3 --kernel-trace --stats`."""
+    import csv
+    import glob
+    with tempfile.TemporaryDirectory() as d:
+        run = os.path.join(d, "run.json")
+        p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(d, "prof"), "-o", "run", "--",
+                            sys.executable, os.path.abspath(__file__), "--cases", "onchip_planes", "--only-onchip", "--rtol", repr(rtol),
+                            "--out", run], capture_output=True, text=True, timeout=600)
+        if p.returncode != 0 or not os.path.exists(run):
+            return {"error": (p.stderr or p.stdout)[-1500:]}
+        rows = json.load(open(run))["onchip_planes"]["stack256"]["check_every_512"]
+        loop_ms = sum(r["loop_ms"] for what in ("solve_cg", "solve_adjoint") for r in rows[f"{what}_key1"])
+        iters = sum(r["max_iters"] for what in ("solve_cg", "solve_adjoint") for r in rows[f"{what}_key1"])
+        out = {"loop_ms_all_runs": loop_ms, "max_iters_all_runs": iters, "kernels": {}}
+        files = glob.glob(os.path.join(d, "prof", "**", "*kernel_stats*.csv"), recursive=True)
+        if not files:
+            return {**out, "error": "no kernel stats written"}
+        for k in csv.DictReader(open(files[0])):
+            out["kernels"][k["Name"].split("(")[0]] = {"calls": int(k["Calls"]), "total_ms": float(k["TotalDurationNs"]) / 1e6}
+        img = [v for n_, v in out["kernels"].items() if "k_cgp_image" in n_]
+        if img:
+            out["k_cgp_image_ms"] = img[0]["total_ms"]
+            out["k_cgp_image_share_of_loop"] = img[0]["total_ms"] / loop_ms
+            out["k_cgp_image_us_per_iteration"] = 1e3 * img[0]["total_ms"] / iters
+            out["k_cgp_image_GBs_per_CU"] = ONCHIP_PLANES_BYTES_PER_CELL * 128 * 128 / (1e3 * img[0]["total_ms"] / iters * 1e-6) / 1e9
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="config1,config2,bench4096,stack16x1024,shipped00042")
@@ -654,6 +743,11 @@ def main():
             out[case] = fold_iter(a.runs, a.only_fold.split(",") if a.only_fold else None)
         elif case == "fold_profile":
             out[case] = fold_profile(a.stats_out)
+        elif case == "onchip_planes":
+            out[case] = (onchip_planes(a.rtol, a.max_iter, 1, (256,), True, (512,)) if a.only_onchip
+                         else onchip_planes(a.rtol, a.max_iter, a.runs))
+        elif case == "onchip_planes_profile":
+            out[case] = onchip_planes_profile(a.rtol)
         elif case == "stream_profile":
             out[case] = stream_profile(a.rtol, a.images)
         elif case == "stream_driver":
