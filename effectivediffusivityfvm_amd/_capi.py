@@ -35,6 +35,7 @@ SYMBOLS = [
     "deff_sensitivity_hvp_D", "deff_device_sensitivity_hvp", "deff_set_tangent",
     "deff_adjoint_tangent_rhs_D", "deff_solve_adjoint_tangent", "deff_get_adjoint_tangent", "deff_device_adjoint_tangent",
     "deff_set_adjoint_tangent", "deff_field_vjp_hvp_D", "deff_device_field_vjp_hvp",
+    "deff_flux_field_D", "deff_flux_field", "deff_device_flux_field",
     "deff_set_progress", "deff_last_launches", "deff_device_field", "deff_synchronize",
 ]
 
@@ -157,6 +158,11 @@ def load():
         L.deff_field_vjp_hvp_D.argtypes = [ctx, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                            C.POINTER(C.c_float)]
         L.deff_device_field_vjp_hvp.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    if hasattr(L, "deff_flux_field_D"):                  # DEFF_AMD_LIB may name a build from before the flux field
+        L.deff_flux_field_D.argtypes = [ctx, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_float)]
+        L.deff_flux_field.argtypes = [ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.deff_device_flux_field.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.deff_set_progress.argtypes = [ctx, PROGRESS_FN, C.c_void_p]
     L.deff_last_launches.argtypes = [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     ip = C.POINTER(C.c_int)

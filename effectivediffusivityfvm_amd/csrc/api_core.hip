@@ -141,6 +141,7 @@ try {
     if (c->cgs_pin) (void)hipHostFree(c->cgs_pin);
     for (hipEvent_t e : c->cgs_ev) if (e) (void)hipEventDestroy(e);
     for (CellPass *p : {&c->pass_res, &c->pass_sens, &c->pass_vjp, &c->pass_tan, &c->pass_hvp, &c->pass_atan, &c->pass_fhvp}) cell_pass_free(*p);
+    flux_pass_free(c->pass_flux);
     if (c->adj_lam) (void)hipFree(c->adj_lam);
     if (c->adj_w) (void)hipFree(c->adj_w);
     if (c->tan_dx) (void)hipFree(c->tan_dx);
@@ -279,6 +280,7 @@ try {
     else if (!strcmp(key, "tan_kt")) c->pass_tan.kt = value;
     else if (!strcmp(key, "hvp_kt")) c->pass_hvp.kt = value;
     else if (!strcmp(key, "fhvp_kt")) c->pass_fhvp.kt = value;
+    else if (!strcmp(key, "flux_kt")) c->pass_flux.kt = value;
     else if (!strcmp(key, "tb_sym")) c->tb_sym = value;
     else if (!strcmp(key, "tb_launch")) {            // 0: resident passes where possible; 1: one launch per pass
         if (value > 1) return fail(DEFF_EINVAL, "tb_launch takes 0 (resident passes where the tiles fit the chip) or 1 (one launch per pass)");
@@ -381,6 +383,8 @@ try {
     else if (!strcmp(key, "hvp_items")) *value = c->pass_hvp.plan_items;
     else if (!strcmp(key, "fhvp_kt")) *value = c->pass_fhvp.plan_kt;
     else if (!strcmp(key, "fhvp_items")) *value = c->pass_fhvp.plan_items;
+    else if (!strcmp(key, "flux_kt")) *value = c->pass_flux.plan_kt;
+    else if (!strcmp(key, "flux_items")) *value = c->pass_flux.plan_items;
     else if (!strcmp(key, "fill_impl")) *value = c->fill_plan_impl;
     else if (!strcmp(key, "fill_launches")) *value = c->fill_plan_launches;
     else if (!strcmp(key, "fill_rounds")) *value = c->fill_plan_rounds;

@@ -103,3 +103,30 @@ static inline void cell_pass_free(CellPass &p)
     if (p.ev0) (void)hipEventDestroy(p.ev0);
     if (p.ev1) (void)hipEventDestroy(p.ev1);
 }
+
+// The flux field's buffers (api_flux.hip): the two maps, the left wall's rows, the section sums, and room for `chunks` work
+// items' column sums (pitch nx) and left-wall sums.
+static inline int flux_pass_room(deff_ctx *c, FluxPass &p, size_t chunks)
+{
+    TRY(dev_alloc(&p.fx, c->n));
+    TRY(dev_alloc(&p.fy, c->n));
+    TRY(dev_alloc(&p.left, (size_t)c->rows));
+    TRY(dev_alloc(&p.Q, (size_t)c->nimg * ((size_t)c->nxt + 1)));
+    if (p.part_cap < chunks) {
+        if (p.colpart) { HIP_TRY(hipFree(p.colpart)); p.colpart = nullptr; }
+        if (p.wallpart) { HIP_TRY(hipFree(p.wallpart)); p.wallpart = nullptr; }
+        p.part_cap = 0;
+        HIP_TRY(hipMalloc((void **)&p.colpart, chunks * (size_t)c->nx * sizeof(double)));
+        HIP_TRY(hipMalloc((void **)&p.wallpart, chunks * sizeof(double)));
+        p.part_cap = chunks;
+    }
+    return DEFF_OK;
+}
+
+static inline void flux_pass_free(FluxPass &p)
+{
+    for (double *d : {p.fx, p.fy, p.left, p.colpart, p.wallpart, p.Q})
+        if (d) (void)hipFree(d);
+    if (p.ev0) (void)hipEventDestroy(p.ev0);
+    if (p.ev1) (void)hipEventDestroy(p.ev1);
+}

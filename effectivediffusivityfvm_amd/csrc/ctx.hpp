@@ -22,6 +22,8 @@
 //   api_fhvp.hip   the field adjoint's second order: dlambda's buffer and setter (its right-hand side, deff_adjoint_tangent_rhs_D,
 //                  is k_tan on lambda, in api_tangent.hip; deff_solve_adjoint_tangent is in api_cg.hip) and the pass
 //                  (x, lambda, dx, dlambda, dD, D) -> S_w dD (deff_field_vjp_hvp_D)
+//   api_flux.hip   the flux field: the pass (x, D) -> fx, fy, left and the section sums (deff_flux_field, deff_flux_field_D),
+//                  kernels_flux.hpp
 //   cell_pass.hpp  the host path those six share (CellPass below): work-item planner, partial sums, the call's own event
 //                  pair, the D upload, the device-map getter; k_sens, k_vjp, k_tan, k_hvp and k_fhvp are one walk (kernels_facepass.hpp), the
 //                  final sums one body (wave_reduce.hpp)
@@ -89,6 +91,19 @@ struct CellPass {
     // deff_get_plan "*_kt" / "*_items" of the last call that launched: the run length used (planner, override and clip
     // applied) and the partial sums the final kernel adds per image
     int plan_kt = 0, plan_items = 0;
+};
+
+// What the flux-field pass keeps between calls (api_flux.hip, kernels_flux.hpp; cell_pass.hpp has its room and its release).
+struct FluxPass {
+    double *fx = nullptr, *fy = nullptr;    // device: the last face-flux maps (pitch nx), kept until the next call
+    double *left = nullptr;                 // device: the left wall's flux per row of the stack
+    double *colpart = nullptr, *wallpart = nullptr;   // device: the work items' column sums (pitch nx) and left-wall sums, grow-only
+    size_t part_cap = 0;                    // chunks (images x work items per strip and image) the two hold
+    double *Q = nullptr;                    // device: nimg x (nxt + 1) section sums
+    bool have = false;                      // the maps hold a result
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;          // the call's own event pair (see CellPass)
+    int kt = 0;                             // tuning "flux_kt": tiles of 8 rows a wave streams through (0 = planner)
+    int plan_kt = 0, plan_items = 0;        // deff_get_plan "flux_kt" / "flux_items" of the last call that launched
 };
 
 struct deff_ctx {
@@ -315,6 +330,8 @@ struct deff_ctx {
     //              that pass_tan's stays
     //   pass_fhvp  deff_field_vjp_hvp_D (api_fhvp.hip): the map S_w dD, handed out by deff_device_field_vjp_hvp
     CellPass pass_res, pass_sens, pass_vjp, pass_tan, pass_hvp, pass_atan, pass_fhvp;
+    //   pass_flux  deff_flux_field / deff_flux_field_D (api_flux.hip): the maps fx, fy, handed out by deff_device_flux_field
+    FluxPass pass_flux;
     bool grid_given = false;        // the last deff_assemble_3phase was given a Grid (deff_sensitivity refuses such a system)
 
     // The field adjoint (api_vjp.hip; the solve itself is api_cg.hip's loop).  adj_lam: lambda of A lambda = w (pitch nx, pad

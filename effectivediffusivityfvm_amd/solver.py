@@ -4,6 +4,7 @@ Thin: every method is one call into the C ABI (include/deff_amd.h).  Array
 conventions are the reference's: row-major (ny, nx) fields, A as (n, 5) =
 P, W, E, S(row+1), N(row-1) (Deff2D.cuh:815-902).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -43,6 +44,23 @@ def _slab_solve_cg(fn, handle, ny, rtol, max_iter, check_every, fluxes):
     out.converged, out.loop_ms = bool(res.converged), res.loop_ms
     out.MFL, out.MFR = MFL, MFR
     return out
+
+
+FluxField = collections.namedtuple("FluxField", "fx fy left sections")
+
+
+def flux_vectors(ff, nx, ny):
+    """Cell-centred physical flux densities (Jx, Jy) of a FluxField of ONE image (or one image of a stack: fx, fy (ny, nx), left
+    (ny,)), numpy only: Jx = -(fxW + fx) / (2 dy), Jy = -(fyN + fy) / (2 dx) with dx = 1 / nx, dy = 1 / ny, fxW the east flux
+    of the west neighbour (left in column 0) and fyN the south flux of the north neighbour (0 in row 0).  The face fluxes are
+    "higher index minus lower" and integrated over the face, hence the sign and the division by the face's length."""
+    fx = np.asarray(ff.fx, dtype=np.float64).reshape(ny, nx)
+    fy = np.asarray(ff.fy, dtype=np.float64).reshape(ny, nx)
+    left = np.asarray(ff.left, dtype=np.float64).reshape(ny)
+    dx, dy = 1.0 / nx, 1.0 / ny
+    fxW = np.concatenate([left[:, None], fx[:, :-1]], axis=1)
+    fyN = np.concatenate([np.zeros((1, nx)), fy[:-1, :]], axis=0)
+    return -(fxW + fx) / (2 * dy), -(fyN + fy) / (2 * dx)
 
 
 def recommended_batch(nx, ny, images, device=0):
@@ -422,6 +440,41 @@ class Solver:
         pitch = C.c_size_t()
         check(self._L.deff_device_sensitivity(self._ctx, C.byref(p), C.byref(pitch)))
         return p.value, pitch.value
+
+    # -- flux field: face fluxes and section sums ---------------------------
+    def flux_field(self, D=None, CL=None, CR=None, timing=False):
+        """The flux through every face of the current field and through every vertical section, in one pass (deff_flux_field /
+        deff_flux_field_D): FluxField(fx, fy, left, sections).  fx[p] is the flux through the E face of cell p (the right
+        wall's in the last column), fy[p] through its S face (row + 1; +0.0 in an image's last row), both as (ny, nx), or
+        (nimg, ny, nx) for a stack; left (nimg, ny) the left wall's; sections (nimg, nx + 1) the sums over the rows of left and
+        of every column of fx -- for a converged field all the same number, and (sections[0] + sections[nx]) / (2 (CR - CL))
+        is deff_raw.  Sign: "higher index minus lower", the physical flux is the negative (flux_vectors).  D = None: the
+        diffusivities of the system assembled from the image (assemble_2phase, or assemble_3phase without a grid) with its CL,
+        CR; otherwise the plane (rows, nx).  timing=True appends the device time in ms."""
+        fx = np.empty((self.rows, self.nx), dtype=np.float64)
+        fy = np.empty((self.rows, self.nx), dtype=np.float64)
+        left = np.empty((self.nimg, self.ny), dtype=np.float64)
+        sec = np.empty((self.nimg, self.nx + 1), dtype=np.float64)
+        ms = C.c_float()
+        out = [a.ctypes.data_as(C.c_void_p) for a in (fx, fy, left, sec)] + [C.byref(ms) if timing else None]
+        if D is None:
+            check(self._L.deff_flux_field(self._ctx, *out))
+        else:
+            D = np.ascontiguousarray(D, dtype=np.float64)
+            assert D.size == self.nx * self.rows
+            check(self._L.deff_flux_field_D(self._ctx, D.ctypes.data_as(C.c_void_p), float(CL), float(CR), *out))
+        if self.nimg > 1:
+            fx, fy = fx.reshape(self.nimg, self.ny, self.nx), fy.reshape(self.nimg, self.ny, self.nx)
+        ff = FluxField(fx, fy, left, sec)
+        return ff + (ms.value,) if timing else ff
+
+    def device_flux_field_ptrs(self):
+        """(device pointer of fx, device pointer of fy, row pitch in bytes) of the last flux_field maps; valid until the next
+        one or close()."""
+        px, py = C.c_void_p(), C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_device_flux_field(self._ctx, C.byref(px), C.byref(py), C.byref(pitch)))
+        return px.value, py.value, pitch.value
 
     # -- field adjoint: dL/dD for a loss on the field ----------------------
     def solve_adjoint(self, w, rtol=1e-10, max_iter=1_000_000, check_every=64):

@@ -106,6 +106,8 @@ int deff_get_kernel(const deff_ctx *ctx, int *kernel_in_use);
  * "tan_kt" (deff_tangent_rhs_D: the same for the field tangent's pass; deff_get_plan "tan_kt"),
  * "hvp_kt" (deff_sensitivity_hvp_D: the same for the Hessian-vector pass; deff_get_plan "hvp_kt"),
  * "fhvp_kt" (deff_field_vjp_hvp_D: the same for the field adjoint's second-order pass; deff_get_plan "fhvp_kt"),
+ * "flux_kt" (deff_flux_field / deff_flux_field_D: the same for the flux-field pass, where it also fixes the order of the
+ *   section sums; deff_get_plan "flux_kt"),
  * "tb_launch" (workgroup tiles whose tiles all fit the chip
  *   run every pass between two checks in ONE launch, neighbouring tiles synchronised by flags: 1 = one launch per
  *   pass instead; a resident launch that cannot make progress -- another process holds part of the GPU -- gives up
@@ -148,6 +150,7 @@ int deff_set_tuning(deff_ctx *ctx, const char *key, int value);
  * deff_sensitivity / deff_sensitivity_D that launched: "sens_kt" and "sens_items", with the same meaning; of the last
  * deff_field_vjp_D that launched: "vjp_kt" and "vjp_items", of the last deff_tangent_rhs_D: "tan_kt" and "tan_items", and of
  * the last deff_sensitivity_hvp_D: "hvp_kt" and "hvp_items", of the last deff_field_vjp_hvp_D: "fhvp_kt" and "fhvp_items",
+ * of the last deff_flux_field / deff_flux_field_D: "flux_kt" and "flux_items" (work items per image),
  * likewise.  Of the flood fill
  * on the device (deff_assemble_3phase_native): "fill_impl" (form of the last fill: 1 = one workgroup per image, 2 = row tiles),
  * "fill_launches" (kernel launches of the last fill), "fill_rounds" (most rounds one workgroup of it took), "fill_runs" (fills
@@ -399,6 +402,47 @@ int deff_sensitivity_D(deff_ctx *ctx, const double *D, double CL, double CR,
                        double *g /* nimg*ny*nx, may be NULL */, double *euler /* [nimg], may be NULL */, float *ms);
 int deff_sensitivity(deff_ctx *ctx, double *g, double *euler, float *ms);
 int deff_device_sensitivity(deff_ctx *ctx, void **d_g, size_t *row_pitch_bytes);
+/* The flux field of the current field: the flux through every face and the total flux through every vertical section, in one
+ * pass over the field and the diffusivities (nothing like it in the reference, which evaluates the two wall columns only,
+ * cuh:1256-1257).  With dx, dy of deff_mesh, whm(w1, w2, x1, x2) = (w1 + w2) / (w1 / x1 + w2 / x2) (cuh:347-360), row 0 the
+ * top row, e the east and s the south (row + 1) neighbour of cell p:
+ *   interior E face:  ke = whm(dx / 2, dx / 2, Dp, De);  fx[p] = ((ke * dy) / dx) * (xe - xp)
+ *   right wall (the last column):  fx[p] = ((Dp * dy) / (dx / 2)) * (CR - xp)
+ *   left wall (column 0):  left[row] = ((Dp * dy) / (dx / 2)) * (xp - CL)
+ *   interior S face:  ks = whm(dy / 2, dy / 2, Ds, Dp);  fy[p] = ((ks * dx) / dy) * (xs - xp)
+ *   last row of an image:  fy[p] = +0.0 (nothing crosses between the images of a stack)
+ * These doubles, in this order (tests/flux_model.py states them in numpy; the library is built without contraction): the
+ * conductances of the assembly (DiscretizeMatrix2D) in its operation order.  With fxW[p] the east flux of the west neighbour
+ * (or left) and fyN[p] the south flux of the north neighbour (or 0), fxW - fx + fyN - fy at cell p equals (A x - b)[p] up to
+ * rounding.  Sign: the reference's Residual(), "higher index minus lower"; the physical flux is the negative.  Weights:
+ * Residual() (cuh:479-485) weights vertical faces with dy / dx, the assembly with dx / dy; this pass follows the ASSEMBLY, so
+ * the identity holds on meshes whose cells are not square.  D == 0 needs no special case (whm returns 0, the flux is 0).
+ * sections: per image W + 1 sums, W the mesh width: Q[0] = sum over the rows of left, Q[j] = sum over the rows of
+ *   fx[row, j - 1], Q[W] the right wall; (Q[0] + Q[W]) / (2 (CR - CL)) is deff_raw up to rounding, and with no-flux top and
+ *   bottom all W + 1 are the same number for a converged field: their spread says how far Deff depends on where it is measured.
+ *   Order of a sum, fixed: the rows of an image are cut into runs of 8 * "flux_kt" rows; within a run a column's terms are
+ *   added top to bottom, starting from the first; the runs are added in order, starting from the first.  The same bits on
+ *   every call.
+ * fx, fy (nimg*ny*nx, true width), left (nimg*ny) and sections (nimg*(nx+1)) may each be NULL; *ms (may be NULL) = device
+ * time of the pass, on an event pair of its own.
+ *   deff_flux_field_D: D[nimg*ny*nx] on the host, as deff_sensitivity_D takes it.  CR == CL is allowed (nothing is divided by it).
+ *   deff_flux_field: D from the context's image system -- deff_assemble_2phase, or deff_assemble_3phase with Grid == NULL --,
+ *     filled on the device from the stored phase diffusivities; CL, CR are the system's.  A system assembled with a Grid
+ *     (ImpSolid rows, deff_assemble_3phase_native) is DEFF_EINVAL; no image system: DEFF_ESTATE.
+ * Plain and stack contexts; row slabs, NULL ctx and NULL D: DEFF_EINVAL; no field: DEFF_ESTATE.  Pending work is settled first
+ * and every image's newest field is read.  A successful call writes only its own buffers and the upload scratch -- not the
+ * field, the system, the plans, the other passes' maps or the solvers' events --, and a refused call changes nothing.
+ * Negative or non-finite D: unspecified values, never a fault.
+ * Tuning "flux_kt": tiles of 8 rows one wave streams through (0 = the planner's choice, clipped to the image);
+ * deff_get_plan "flux_kt" / "flux_items": what the last call used, and its work items per image
+ * (strips of 128 columns x ceil(tile rows / flux_kt)).
+ * deff_device_flux_field: the device buffers of the last maps (row pitch as deff_device_field, the pad column of an odd width
+ * holds +0.0), valid until the next flux-field call or deff_destroy; DEFF_ESTATE before the first call. */
+int deff_flux_field_D(deff_ctx *ctx, const double *D, double CL, double CR,
+                      double *fx, double *fy /* nimg*ny*nx, may be NULL */, double *left /* nimg*ny, may be NULL */,
+                      double *sections /* nimg*(nx+1), may be NULL */, float *ms);
+int deff_flux_field(deff_ctx *ctx, double *fx, double *fy, double *left, double *sections, float *ms);
+int deff_device_flux_field(deff_ctx *ctx, void **d_fx, void **d_fy, size_t *row_pitch_bytes);
 /* ---- field adjoint: dL/dD for ANY loss L(x) on the concentration field, one adjoint solve and one pass (nothing like it in
  * the reference).  The system is A(D) x = b(D) with A symmetric, so for w = dL/dx the adjoint system is the same matrix:
  * A lambda = w with homogeneous walls, and dL/dD[p] = -lambda^T (dA/dD[p] x - db/dD[p]), a face-wise pass over (x, lambda, D).
