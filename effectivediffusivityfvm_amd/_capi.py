@@ -37,6 +37,9 @@ SYMBOLS = [
     "deff_set_adjoint_tangent", "deff_field_vjp_hvp_D", "deff_device_field_vjp_hvp",
     "deff_flux_field_D", "deff_flux_field", "deff_device_flux_field",
     "deff_set_progress", "deff_last_launches", "deff_device_field", "deff_synchronize",
+    "deff_volume_create", "deff_volume_destroy", "deff_volume_mesh", "deff_volume_assemble_from_D", "deff_volume_get_system",
+    "deff_volume_init_linear", "deff_volume_set_field", "deff_volume_get_field", "deff_volume_device_field", "deff_volume_flux",
+    "deff_volume_solve_cg", "deff_volume_get_plan",
 ]
 
 
@@ -163,6 +166,20 @@ def load():
                                         C.POINTER(C.c_float)]
         L.deff_flux_field.argtypes = [ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.deff_device_flux_field.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    if hasattr(L, "deff_volume_create"):                 # DEFF_AMD_LIB may name a build from before the volumes
+        pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        L.deff_volume_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ctx)]
+        L.deff_volume_destroy.argtypes = [ctx]
+        L.deff_volume_mesh.argtypes = [ctx, pi, pi, pi, pd, pd, pd]
+        L.deff_volume_assemble_from_D.argtypes = [ctx, _dp, C.c_double, C.c_double]
+        L.deff_volume_get_system.argtypes = [ctx, _dp, _dp]
+        L.deff_volume_init_linear.argtypes = [ctx, C.c_double, C.c_double]
+        L.deff_volume_set_field.argtypes = [ctx, _dp]
+        L.deff_volume_get_field.argtypes = [ctx, _dp]
+        L.deff_volume_device_field.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.deff_volume_flux.argtypes = [ctx, pd, C.c_void_p, C.c_void_p]
+        L.deff_volume_solve_cg.argtypes = [ctx, C.c_double, C.c_int64, C.c_int64, C.POINTER(CGResultC), C.c_void_p, C.c_void_p]
+        L.deff_volume_get_plan.argtypes = [ctx, C.c_char_p, C.POINTER(C.c_int)]
     L.deff_set_progress.argtypes = [ctx, PROGRESS_FN, C.c_void_p]
     L.deff_last_launches.argtypes = [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     ip = C.POINTER(C.c_int)

@@ -10,9 +10,12 @@
 // the field's derivative along a direction, api_tangent.hip) run deff_solve_cg's host loop,
 // cg_host_loop, on the coefficient planes with its own solution and right-hand side buffers.  Under the tuning key
 // "cg_onchip_planes" every solve on the planes iterates small images on one compute unit each (kernels_cg_image_planes.hpp).
+// A volume (api_volume.hip) is the plane form on one tall image plus the z links: its kernels (kernels_cg_volume.hpp) are
+// launched here, from volume_assemble_planes and volume_solve_cg, and the loop takes them through CgIteration::z.
 #include "ctx.hpp"
 #include "kernels_cg.hpp"
 #include "kernels_cg_planes.hpp"
+#include "kernels_cg_volume.hpp"
 #include "kernels_cg_fold.hpp"
 #include "kernels_cg_image.hpp"
 #include "kernels_cg_image_planes.hpp"
@@ -129,6 +132,7 @@ struct CgIteration {
     double tol2;
     long long max_iter;
     const double *rhs = nullptr;    // plane form: the right-hand side plane (the iteration's kernels read the matrix planes only)
+    CgvLinks z = CgvLinks();        // plane form of a volume (kernels_cg_volume.hpp): the z links and the slice's rows; z.ny = 0 otherwise
 
     int enqueue(const double *p_in, double *p_out) const
     {
@@ -148,7 +152,9 @@ struct CgIteration {
             }
             return 2;
         }
-        if (planes)
+        if (z.ny)
+            hipLaunchKernelGGL(k_cgv_dir, grid, dim3(256), 0, c->stream, P, z, c->cg_inv, c->cg_r, p_in, p_out, c->cg_q, sc, g, part);
+        else if (planes)
             hipLaunchKernelGGL(k_cgp_dir, grid, dim3(256), 0, c->stream, P, c->cg_inv, c->cg_r, p_in, p_out, c->cg_q, sc, g, part);
         else
             hipLaunchKernelGGL(k_cg_dir, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, c->cg_r, p_in, p_out, sc,
@@ -170,8 +176,11 @@ struct CgIteration {
 // rounds at the end.  The caller has prepared the table or cg_inv, zeroed cg_flags and cg_tick and set the "cg_*" plan keys;
 // `planes` reads the matrix from the coefficient planes and the right-hand side from `rhs` (the table form has b in its
 // table and ignores it).  hs[img] = the images' final scalars, *ms = the loop's time on cg_ev0 / cg_ev1.
+// A volume (volume_solve_cg below: planes, neither on chip nor folded) passes its z links: the direction and the residual
+// launch are then the volume's kernels, everything else is as for an image of ny * nz rows.
 static int cg_host_loop(deff_ctx *c, double *x, const double *rhs, bool planes, bool onchip, int fold, const CgGeom &g,
-                        double rtol, int64_t max_iter, int64_t check_every, std::vector<CgScal> &hs, float *ms)
+                        double rtol, int64_t max_iter, int64_t check_every, std::vector<CgScal> &hs, float *ms,
+                        const CgvLinks &z = CgvLinks())
 {
     const size_t items = (size_t)g.per_img * c->nimg;
     const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, rhs};
@@ -181,10 +190,11 @@ static int cg_host_loop(deff_ctx *c, double *x, const double *rhs, bool planes, 
     double *part = c->cg_part, *part_rz = c->cg_part + items, *part_rr = c->cg_part + 2 * items;
     CgScal *sc = (CgScal *)c->cg_scal;
     const CgIteration iteration{c, planes, fold, grid, fin, g, x, part, part_rz, part_rr, c->cg_tick,
-                                c->cg_tick + cgf_ticks(g.per_img, (size_t)c->nimg), tol2, (long long)max_iter, rhs};
+                                c->cg_tick + cgf_ticks(g.per_img, (size_t)c->nimg), tol2, (long long)max_iter, rhs, z};
     hs.resize(c->nimg);
     auto true_residual = [&](int mode, int allow) -> int {
-        if (planes) hipLaunchKernelGGL(k_cgp_resid, grid, dim3(256), 0, c->stream, P, c->cg_inv, x, c->cg_r, g, part);
+        if (z.ny) hipLaunchKernelGGL(k_cgv_resid, grid, dim3(256), 0, c->stream, P, z, c->cg_inv, x, c->cg_r, g, part);
+        else if (planes) hipLaunchKernelGGL(k_cgp_resid, grid, dim3(256), 0, c->stream, P, c->cg_inv, x, c->cg_r, g, part);
         else hipLaunchKernelGGL(k_cg_resid, grid, dim3(256), 0, c->stream, c->cg_tab, c->lut_nrows, c->code, x, c->cg_r, g, part);
         hipLaunchKernelGGL(k_cg_check, fin, dim3(CG_FIN), 0, c->stream, part, g.per_img, sc, tol2, (long long)max_iter, mode,
                            allow, c->cg_flags + 1);
@@ -326,6 +336,71 @@ try {
     return DEFF_OK;
 }
 DEFF_API_CATCH
+
+// ---- volumes (api_volume.hip, kernels_cg_volume.hpp) ---------------------------------------------------------------------
+//
+// A deff_volume's private context is one image of nx x (ny * nz); these two run the volume's kernels on it.  They live here,
+// beside the loop and the plane kernels they share: a kernel header is compiled into one translation unit.
+
+// The eight planes of the 7-point system from the D volume in `dD` (device, pitch c->nx) and the wall diffusivities.
+int volume_assemble_planes(deff_ctx *c, const double *dD, int ny, int nz, double dy, double dz, double CL, double CR, double *aB,
+                           double *aF)
+{
+    hipLaunchKernelGGL(k_assemble_volume_from_D, dim3(grid_for(c->n)), dim3(256), 0, c->stream, dD, c->nx, c->nxt, ny, nz, c->dx, dy,
+                       dz, CL, CR, soa_of(c), aB, aF);
+    hipLaunchKernelGGL(k_wall_D_from_D, dim3((c->rows + 255) / 256), dim3(256), 0, c->stream, dD, c->nx, c->nxt, c->rows, c->Dl,
+                       c->Dr);
+    HIP_TRY(hipGetLastError());
+    return DEFF_OK;
+}
+
+// deff_solve_cg's plane form on a volume: the same checks on the system before the field is touched (k_cgv_prepare), the same
+// loop, Deff and wall fluxes of the final field.  The caller has checked the arguments and the context's state.
+int volume_solve_cg(deff_ctx *c, const double *aB, const double *aF, int ny, double rtol, int64_t max_iter, int64_t check_every,
+                    deff_cg_result *out, double *MFL, double *MFR)
+{
+    TRY(use_device(c));
+    const CgGeom g = cg_geometry(c);
+    TRY(cg_buffers(c, g.per_img));
+    TRY(cgp_buffers(c));
+    c->cg_plan_kr = g.kr;
+    c->cg_plan_ntx = g.ntx;
+    c->cg_plan_items = (int)g.per_img;
+    c->cg_plan_restarts = 0;
+    c->cg_plan_impl = 5;
+    c->cg_plan_fold = 0;
+    const CgpPlanes P{c->a0, c->aW, c->aE, c->aS, c->aN, c->b};
+    CgvLinks z;
+    z.aB = aB;
+    z.aF = aF;
+    z.ny = ny;
+
+    unsigned flags[2] = {0, 0};
+    HIP_TRY(hipMemsetAsync(c->cg_flags, 0, sizeof(unsigned) * 2, c->stream));
+    hipLaunchKernelGGL(k_cgv_prepare, dim3(grid_for(c->n, 2048)), dim3(256), 0, c->stream, P, z, c->nx, c->rows, c->cg_inv,
+                       c->cg_flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(flags, c->cg_flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flags[0] & CGP_FLAG_ROW)
+        return fail(DEFF_EINVAL, "deff_volume_solve_cg: a matrix row is not admissible: an active row needs a finite A0 > 0 and "
+                                 "finite links");
+    if (flags[0])
+        return fail(DEFF_EINVAL, "deff_volume_solve_cg: the system is not symmetric (a link between two active cells differs from "
+                                 "its partner, or an active row links out of the volume)");
+
+    std::vector<CgScal> hs;
+    float ms = 0;
+    TRY(cg_host_loop(c, c->x[c->cur], c->b, true, false, 0, g, rtol, max_iter, check_every, hs, &ms, z));
+    double deff = 0;
+    TRY(deff_flux(c, &deff, MFL, MFR));
+    out->iters = hs[0].iters;
+    out->rel_residual = hs[0].rel;
+    out->deff_raw = deff;
+    out->loop_ms = ms;
+    out->converged = hs[0].rel <= rtol;
+    return DEFF_OK;
+}
 
 // ---- deff_solve_adjoint, deff_solve_tangent -----------------------------------------------------------------------------
 //

@@ -27,6 +27,8 @@
 //   cell_pass.hpp  the host path those six share (CellPass below): work-item planner, partial sums, the call's own event
 //                  pair, the D upload, the device-map getter; k_sens, k_vjp, k_tan, k_hvp and k_fhvp are one walk (kernels_facepass.hpp), the
 //                  final sums one body (wave_reduce.hpp)
+//   api_volume.hip 3-D volumes: deff_volume, a private context of nx x (ny * nz) plus the z-link planes (its kernels and its solve
+//                  are in api_cg.hip, beside the plane form they extend: kernels_cg_volume.hpp)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
 //                  for both forms, which differ in the transport only (peer copies in one process,
 //                  RCCL or a caller-supplied transport with one process per GPU); conjugate gradients over the slabs
@@ -576,3 +578,8 @@ void resident_chain_ctx_created(int device);
 void resident_chain_ctx_destroyed(int device);
 // api_solve.hip
 int flux_rows(deff_ctx *c, bool need_rows = true);
+// api_cg.hip: what a deff_volume (api_volume.hip) runs on its private context of nx x (ny * nz)
+int volume_assemble_planes(deff_ctx *c, const double *dD, int ny, int nz, double dy, double dz, double CL, double CR, double *aB,
+                           double *aF);
+int volume_solve_cg(deff_ctx *c, const double *aB, const double *aF, int ny, double rtol, int64_t max_iter, int64_t check_every,
+                    deff_cg_result *out, double *MFL, double *MFR);

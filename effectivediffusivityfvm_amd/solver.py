@@ -775,6 +775,93 @@ class Solver:
         check(self._L.deff_synchronize(self._ctx))
 
 
+class Volume:
+    """One nx x ny x nz volume on the unit cube (deff_volume_*): the 7-point system from a per-cell D volume, its CG solve and
+    its Deff.  Arrays are (nz, ny, nx); A is (n, 7) = P, W, E, S(row+1), N(row-1), B(slice-1), F(slice+1).  The walls in x are
+    Dirichlet (CL, CR), y and z zero-flux.  Nothing else of Solver exists for volumes yet."""
+
+    def __init__(self, nx, ny, nz, device=0):
+        self._L = _capi.load()
+        self._vol = C.c_void_p()
+        self.nx, self.ny, self.nz = int(nx), int(ny), int(nz)
+        self.rows = self.ny * self.nz
+        check(self._L.deff_volume_create(int(device), self.nx, self.ny, self.nz, C.byref(self._vol)))
+
+    def close(self):
+        if self._vol:
+            self._L.deff_volume_destroy(self._vol)
+            self._vol = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def mesh(self):
+        """(nx, ny, nz, dx, dy, dz)"""
+        n = [C.c_int() for _ in range(3)]
+        d = [C.c_double() for _ in range(3)]
+        check(self._L.deff_volume_mesh(self._vol, *[C.byref(v) for v in n + d]))
+        return tuple(v.value for v in n + d)
+
+    def assemble_from_D(self, D, CL, CR):
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        assert D.size == self.nx * self.rows
+        check(self._L.deff_volume_assemble_from_D(self._vol, D, CL, CR))
+
+    def get_system(self):
+        n = self.nx * self.rows
+        A = np.empty((n, 7), dtype=np.float64)
+        b = np.empty(n, dtype=np.float64)
+        check(self._L.deff_volume_get_system(self._vol, A, b))
+        return A, b
+
+    def init_linear(self, CL, CR):
+        check(self._L.deff_volume_init_linear(self._vol, CL, CR))
+
+    def set_field(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.size == self.nx * self.rows
+        check(self._L.deff_volume_set_field(self._vol, x))
+
+    def get_field(self):
+        x = np.empty((self.nz, self.ny, self.nx), dtype=np.float64)
+        check(self._L.deff_volume_get_field(self._vol, x))
+        return x
+
+    def flux(self):
+        """(deff_raw, MFL, MFR): the wall flux densities of all ny * nz rows, slice after slice."""
+        d = C.c_double()
+        MFL = np.zeros(self.rows)
+        MFR = np.zeros(self.rows)
+        check(self._L.deff_volume_flux(self._vol, C.byref(d), MFL.ctypes.data_as(C.c_void_p), MFR.ctypes.data_as(C.c_void_p)))
+        return d.value, MFL, MFR
+
+    def solve_cg(self, rtol=1e-10, max_iter=1_000_000, check_every=64, fluxes=True):
+        """Jacobi-preconditioned conjugate gradients from the current field to ||b - A x|| <= rtol ||b|| (deff_volume_solve_cg):
+        Solver.solve_cg's rules on the volume's coefficient planes.  A CGResult with the ny * nz wall fluxes."""
+        return _slab_solve_cg(self._L.deff_volume_solve_cg, self._vol, self.rows, rtol, max_iter, check_every, fluxes)
+
+    def plan_value(self, key):
+        """"cg_kr", "cg_items", "cg_restarts" or "cg_impl" (5 = the volume form) of the last solve_cg."""
+        v = C.c_int()
+        check(self._L.deff_volume_get_plan(self._vol, key.encode(), C.byref(v)))
+        return v.value
+
+    def device_field_ptr(self):
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_volume_device_field(self._vol, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+
 class SlabGroup:
     """One image split into row slabs over `devices` (one slab per entry; entries may repeat,
     which is how the multi-GPU path is exercised on a single GPU).  Same call sequence as Solver."""

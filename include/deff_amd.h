@@ -767,6 +767,56 @@ int deff_debug_tb_stamps(deff_ctx *ctx, double omega, unsigned long long *out, i
 int deff_device_field(deff_ctx *ctx, void **d_x, size_t *row_pitch_bytes);
 int deff_synchronize(deff_ctx *ctx);
 
+/* ---- volumes: the 7-point system of an nx x ny x nz mesh from a D volume, its CG solve and its Deff (not in the reference,
+ * whose README lists a 3-D version as upcoming).  A first milestone: a host D volume goes in, a field converged to
+ * ||b - A x||_2 <= rtol ||b||_2 and its Deff come out; everything else that exists for images (Jacobi sweeps, voxel images and
+ * dictionaries, stacks, the on-chip and folded forms, row slabs, the derivative passes, the flux field) does not for volumes.
+ * A volume is a type of its own: no deff_ctx entry point takes it.
+ *   The domain is the unit cube: dx = 1/nx, dy = 1/ny, dz = 1/nz.  The left and right walls (x) are Dirichlet at half a cell
+ * (CL, CR); y and z are zero-flux.  Arrays are D[nz][ny][nx]: cell (k, i, j) at (k*ny + i)*nx + j; slice k - 1 is "back" (B),
+ * slice k + 1 "front" (F), row i - 1 is N and row i + 1 is S as in 2-D.  The row of a cell, with whm(w1, w2, x1, x2) =
+ * (w1 + w2) / (w1/x1 + w2/x2) (cuh:347-360) and every product and quotient evaluated left to right, is DiscretizeMatrix2D's
+ * (cuh:815-902) with the face areas of a volume:
+ *   x block: kw = whm(dx/2, dx/2, Dp, Dw), ke = whm(dx/2, dx/2, Dp, De); aW = -kw*dy*dz/dx, aE = -ke*dy*dz/dx,
+ *     a0 += (ke*dy*dz/dx + kw*dy*dz/dx).  First column: kw = Dp, no aW, a0 += (ke*dy*dz/dx + kw*dy*dz/(dx/2)),
+ *     b += CL*kw*dy*dz/(dx/2).  Last column: ke = Dp, no aE, a0 += (ke*dy*dz/(dx/2) + kw*dy*dz/dx), b += CR*ke*dy*dz/(dx/2).
+ *   y block: kn = whm(dy/2, dy/2, Dp, Dn), ks = whm(dy/2, dy/2, Ds, Dp); aN = -kn*dx*dz/dy, aS = -ks*dx*dz/dy,
+ *     a0 += (kn*dx*dz/dy + ks*dx*dz/dy); the first row of a slice has the S terms alone, the last the N terms alone.
+ *   z block: kb = whm(dz/2, dz/2, Dp, Db), kf = whm(dz/2, dz/2, Df, Dp); aB = -kb*dx*dy/dz, aF = -kf*dx*dy/dz,
+ *     a0 += (kb*dx*dy/dz + kf*dx*dy/dz); the first slice has the F terms alone, the last the B terms alone; nz = 1 has no z
+ *     block, and as x * 1.0 is exact its doubles are those of deff_assemble_from_D on the same D.
+ * deff_volume_create: nx, ny >= 2, nz >= 1 and at most 2^31 cells (the width rounded up to even), else DEFF_EINVAL. */
+typedef struct deff_volume deff_volume;
+int deff_volume_create(int device, int nx, int ny, int nz, deff_volume **out);
+int deff_volume_destroy(deff_volume *v);
+int deff_volume_mesh(const deff_volume *v, int *nx, int *ny, int *nz, double *dx, double *dy, double *dz);   /* any may be NULL */
+/* the system above from D[nz*ny*nx] on the host (true width); also sets the wall diffusivities the flux evaluation reads
+ * (column 0 and column nx - 1 of every row).  The field is left as it is. */
+int deff_volume_assemble_from_D(deff_volume *v, const double *D, double CL, double CR);
+/* the assembled coefficients: A[n*7] = a0, aW, aE, aS, aN, aB, aF per cell, b[n], n = nz*ny*nx; DEFF_ESTATE before an assembly */
+int deff_volume_get_system(deff_volume *v, double *A, double *b);
+/* the field, x[nz*ny*nx]: as deff_init_linear (the ramp in x of every row), deff_set_field, deff_get_field, deff_device_field
+ * (rows of the pitch deff_device_field describes, slice after slice) */
+int deff_volume_init_linear(deff_volume *v, double CL, double CR);
+int deff_volume_set_field(deff_volume *v, const double *x);
+int deff_volume_get_field(deff_volume *v, double *x);
+int deff_volume_device_field(deff_volume *v, void **d_x, size_t *row_pitch_bytes);
+/* deff_flux on the volume: the wall flux densities of all ny*nz rows (MFL, MFR: ny*nz values each, may be NULL) and
+ * *deff_raw = their mean over both walls / (CR - CL), summed in row order */
+int deff_volume_flux(deff_volume *v, double *deff_raw, double *MFL, double *MFR);
+/* deff_solve_cg on the volume's coefficient planes: the argument checks, the DEFF_ESTATE cases (no field, no system), the
+ * stop rule on the device, the results' independence of check_every, the true-residual rounds (up to 8 restarts),
+ * rel_residual recomputed from x, decoupled cells (all six links and b zero) at x = 0 and the b = 0 behaviour are
+ * deff_solve_cg's; so is the admissibility check before the field is touched, which also compares aB with the back cell's aF
+ * and aF with the front cell's aB bit for bit and refuses a z link out of the volume (DEFF_EINVAL; a refusal changes
+ * nothing).  out: one result; MFL / MFR: ny*nz values each, may be NULL.  The iteration is the plane form's with the back and
+ * front rows added: a volume of one slice gives the bits of deff_solve_cg under "cg_planes" on the same D. */
+int deff_volume_solve_cg(deff_volume *v, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out,
+                         double *MFL, double *MFR);
+/* of the last deff_volume_solve_cg: "cg_kr", "cg_items", "cg_restarts" as deff_get_plan gives them for an image of ny*nz rows,
+ * and "cg_impl" (5 = the volume form; 0 before a solve); any other key: DEFF_EINVAL */
+int deff_volume_get_plan(deff_volume *v, const char *key, int *value);
+
 #ifdef __cplusplus
 }
 #endif
