@@ -425,6 +425,7 @@ try {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_image = true;
     c->have_matfree = false;
+    c->phase_mode = 0;                               // the phase diffusivities belonged to the old image's system
     adjoint_reset(c);
     return DEFF_OK;
 }
@@ -442,6 +443,7 @@ try {
     HIP_TRY(hipGetLastError());
     c->have_image = true;
     c->have_matfree = false;
+    c->phase_mode = 0;                               // the phase diffusivities belonged to the old image's system
     adjoint_reset(c);
     return DEFF_OK;
 }

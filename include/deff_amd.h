@@ -428,7 +428,8 @@ int deff_device_sensitivity(deff_ctx *ctx, void **d_g, size_t *row_pitch_bytes);
  *   deff_flux_field_D: D[nimg*ny*nx] on the host, as deff_sensitivity_D takes it.  CR == CL is allowed (nothing is divided by it).
  *   deff_flux_field: D from the context's image system -- deff_assemble_2phase, or deff_assemble_3phase with Grid == NULL --,
  *     filled on the device from the stored phase diffusivities; CL, CR are the system's.  A system assembled with a Grid
- *     (ImpSolid rows, deff_assemble_3phase_native) is DEFF_EINVAL; no image system: DEFF_ESTATE.
+ *     (ImpSolid rows, deff_assemble_3phase_native) is DEFF_EINVAL; no image system: DEFF_ESTATE.  A new image
+ *     (deff_set_image, deff_synth_image) leaves none until the next assembly, here and for deff_sensitivity and deff_residual.
  * Plain and stack contexts; row slabs, NULL ctx and NULL D: DEFF_EINVAL; no field: DEFF_ESTATE.  Pending work is settled first
  * and every image's newest field is read.  A successful call writes only its own buffers and the upload scratch -- not the
  * field, the system, the plans, the other passes' maps or the solvers' events --, and a refused call changes nothing.

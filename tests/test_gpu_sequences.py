@@ -123,17 +123,36 @@ ASSEMBLE_C = [(0.0, 1.0), (0.25, 0.75)]
 #             plane with zero cells, walls drawn anew, + deff_device_field_vjp; also the first reader of some solves).  The draw
 #             follows one more fact: whether lambda is valid -- deff_amd.h's lifetime rule applied to the ops drawn so far
 
+#
+# ... and the second-order calls, which share five validity flags, one upload scratch of two planes, the CG work vectors and the
+# field ping-pong with everything above.  The draw follows five facts by deff_amd.h's lifetime rules applied to the ops drawn so
+# far -- lambda, the tangent's right-hand side and dx, dlambda's right-hand side and dlambda -- and whether flux maps exist:
+#
+#   tangent   "trhs" (deff_tangent_rhs_D on the model's planes or on a drawn plane with zero cells; dD drawn, dD = D and a dD that
+#             is non-zero where D == 0 included; walls drawn anew, CR == CL included), "tan" (deff_solve_tangent, max_iter 0 / 3 /
+#             large), "settan", "gettan" (deff_get_tangent + deff_device_tangent) and "hvp" (deff_sensitivity_hvp_D; CR == CL is
+#             refused)
+#   second    "arhs", "atan", "setatan", "getatan" and "fhvp": the same five for dlambda and deff_field_vjp_hvp_D
+#   fluxfield "ff" (deff_flux_field_D, then deff_flux_field, whose outcome follows the kind of system), "ffptr"
+#             (deff_device_flux_field) and the key "flux_kt"
+#   onchip_planes  the key "cg_onchip_planes" (also "opflip": the key flipped between a right-hand side and its solve); after every
+#             side solve and every plane-form cg the form that ran is asserted
+
 # (key, values) pairs the tune draw gains per option; "cg keys" sets both CG keys in one draw, "prescaled" mostly toggles
-TUNE_EXTRA = dict(native3=[("fill_impl", [0, 1, 2])] * 3 + [("fill_tile_rows", [0, 8, 16])] * 4,
+TUNE_EXTRA = dict(fluxfield=[("flux_kt", [0, 1, 2])] * 8,
+                  onchip_planes=[("cg_onchip_planes", [0, 1, 1])] * 6,
+                  native3=[("fill_impl", [0, 1, 2])] * 3 + [("fill_tile_rows", [0, 8, 16])] * 4,
                   cgkeys=[("cg keys", None)] * 12,
                   prescaled=[("prescaled", None)] * 10,
                   sens=[("tb_impl", [2])] * 8 + [("tb_launch", [0])] * 2)     # (towards resident tiles: a gradient inside a pending interval)
 CG_PLANES_DRAW, CG_FOLD_DRAW = [0, 0, 1, 2], [0, 1, 1, 2, 2]
+PASS_WALLS = ASSEMBLE_C + [(0.5, 0.5)]                       # the walls of a drawn pass: CR == CL is allowed by all but "hvp"
+PASSES = ("trhs", "arhs", "vjp", "hvp", "fhvp", "sens", "ff")       # every one uploads its planes into the one scratch
 
 
 def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30, onchip=False, stream=False, ptr=False,
                   slot=False, stamps=False, fma=False, native3=False, system=False, cgkeys=False, cgstream=False, sens=False,
-                  prescaled=False, adjoint=False):
+                  prescaled=False, adjoint=False, tangent=False, second=False, fluxfield=False, onchip_planes=False):
     """Generator of (op, arguments...) tuples; the first is ("open", nx, ny, B, fma) and the second the first image."""
     assert not (fma and with_cg)                             # CG's arithmetic has no contracted form to compare with
     assert not (prescaled and (fma or stamps))
@@ -156,7 +175,14 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
     tb_keys = {"tb_impl": 0, "tb_launch": 0}                 # (followed under `adjoint` only: towards resident tiles)
     sw = "Sw" if nx % 2 == 0 else "S"                        # (an odd width cannot represent a wall-column link: refused)
     kinds = ["2p", "2p", "3p", "D"] + (["3n", "3n", "3g"] if native3 else []) + (["S", sw, sw] if system else [])
-    extra = [kv for name, on in (("native3", native3), ("cgkeys", cgkeys), ("prescaled", prescaled), ("sens", sens)) if on for kv in TUNE_EXTRA[name]]
+    extra = [kv for name, on in (("native3", native3), ("cgkeys", cgkeys), ("prescaled", prescaled), ("sens", sens),
+                                 ("fluxfield", fluxfield), ("onchip_planes", onchip_planes)) if on for kv in TUNE_EXTRA[name]]
+    newer = tangent or second or fluxfield or onchip_planes
+    assert not newer or (adjoint and not prescaled)          # (the later options extend the adjoint's bookkeeping)
+    tan_rhs = tan_valid = atan_rhs = atan_valid = False      # the tangent's right-hand side and dx, dlambda's and dlambda
+    dx_lost = dl_lost = False                                # dx / dlambda was valid and an invalidator has just run
+    op_key = 0                                               # "cg_onchip_planes"
+    hist = []                                                # every op drawn so far (followed under the later options only)
     for step in range(steps):
         ops = ["image", "assemble", "tune"]
         if kind is not None:
@@ -245,11 +271,106 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
                     # the invalidators that even weights would leave rare while a lambda is there to lose
                     ops += (["stream"] * 2 if stream and B >= 2 else []) + (["cgstream"] * 5 if cgstream and B >= 2 else [])
                     ops += ["stage"] * 24 if native3 and kind == "3n" else []
+        if newer:
+            # The later options' ops and the weights of the orders they are drawn for (T1 ... T12 in test_sequences_host.py).  As
+            # for the adjoint: every read and pass is offered at a low weight whatever the state (refused while what it needs is
+            # missing), and at a high one where it continues a chain -- a right-hand side is followed by its solve, a solve by a
+            # read and a pass, a lost vector by the calls that must now be refused.
+            tb2 = (tb_keys["tb_impl"], tb_keys["tb_launch"]) == (2, 0) and kset in ("auto", "matfree_tb") and kind != "Sw"
+            sysok = kind is not None
+            h3 = tuple(hist[-3:])
+            if tangent:
+                ops += ["trhs", "trhs", "gettan", "hvp"] + (["trhs"] * 25 if have_x and sysok and kind != "Sw" and not tan_rhs else [])
+                # (with no system the solve is drawn only where it is refused for lack of a right-hand side, and the setter not
+                # at all: whether a context without a system still has one to solve on is not specified)
+                ops += ["tan", "settan"] if sysok else [] if tan_rhs else ["tan"]
+                if dx_lost:
+                    ops += ["gettan"] * 40 + ["hvp"] * 40 + ["tan"] * 40
+                if prev == "trhs" and sysok and tan_rhs:
+                    ops += ["tan"] * 1000 + (["opflip"] * 150 if onchip_planes else [])
+                if h3[-2:] == ("trhs", "opflip"):
+                    ops += ["tan"] * 2000
+                if prev == "tan" and tan_valid:
+                    ops += ["gettan"] * 600 + ["hvp"] * 60 + (["cgform"] * 150 + ["cg"] * 20 if have_x and with_cg else []) + ["adj"] * 20
+                    ops += ["atan"] * 150 if atan_rhs and second else []
+                if h3[-2:] == ("tan", "gettan") and have_x:
+                    ops += ["hvp"] * 1500
+                if h3[-2:] == ("tan", "cgform") and have_x and with_cg:
+                    ops += ["cg"] * 1500
+                if h3 == ("tan", "cgform", "cg") and tan_valid:
+                    ops += ["gettan"] * 1500
+                if prev == "cg" and tan_rhs and sysok:
+                    ops += ["tan"] * 300
+                if h3[-2:] == ("cg", "tan") and have_x and with_cg:
+                    ops += ["cg"] * 1500
+                if prev == "settan" and have_x:
+                    ops += ["hvp"] * 40
+                if tan_valid:
+                    ops += ["gettan", "hvp"] + (["adj"] * 200 if sysok and not lam_valid and kind != "Sw" else [])
+                    if refused_last:
+                        ops += ["gettan"] * 40
+                    # the invalidators that even weights would leave rare while a dx is there to lose
+                    ops += (["stream"] * 2 if stream and B >= 2 else []) + (["cgstream"] * 5 if cgstream and B >= 2 else [])
+                    ops += ["stage"] * 24 if native3 and kind == "3n" else []
+                    ops += ["image"] * 2 + ["assemble"] * 4
+                if kind == "Sw":                             # (the side solves are refused: with a caller's dx in place)
+                    ops += ["tan"] * 20 if tan_valid else ["settan"] * 20
+            if second:
+                ops += ["arhs", "getatan", "fhvp"] + (["atan", "setatan"] if sysok else [] if atan_rhs else ["atan"])
+                if dl_lost:
+                    ops += ["getatan"] * 40 + ["fhvp"] * 40 + ["atan"] * 40
+                if lam_valid and prev in ("adj", "setadj") and not atan_valid and not dl_lost:
+                    ops += ["arhs"] * 1000
+                if prev == "arhs" and sysok and atan_rhs:
+                    ops += ["atan"] * 1000 + (["opflip"] * 150 if onchip_planes else [])
+                if h3[-2:] == ("arhs", "opflip"):
+                    ops += ["atan"] * 2000
+                if prev == "atan" and atan_valid:
+                    ops += ["fhvp"] * 1000 + ["getatan"] * 60 + (["tan"] * 60 if tan_rhs else ["trhs"] * 30) + ["adj"] * 30 + ["setadj"] * 30
+                if prev == "setatan" and have_x:
+                    ops += ["fhvp"] * (300 if lam_valid and tan_valid else 40) + (["settan"] * 20 if not tan_valid and sysok else [])
+                if lam_valid and tan_valid and have_x and sysok:
+                    ops += ["setatan"] * 10
+                if prev == "hvp" and tan_valid and have_x and sysok and kind != "Sw":       # (the tangent's chain, then dlambda's)
+                    ops += ["adj"] * 1000
+                if atan_valid:
+                    ops += ["getatan", "fhvp"] + (["trhs"] * 4 if not tan_valid else [])
+                    if refused_last:
+                        ops += ["getatan"] * 40
+                if kind == "Sw" and lam_valid:
+                    ops += ["atan"] * 10 if atan_valid else ["setatan"] * 20
+            if fluxfield:
+                ops += ["ff", "ff", "ffptr"] + (["ff"] * 200 if kind == "3n" and have_x and (tan_valid or atan_valid) else [])
+                if prev in ("image", "assemble", "stage") and have_x:
+                    ops += ["ff"] * 60
+                if prev == "ff":
+                    ops += ["ffptr"] * 6
+            if prev in PASSES:                               # three different passes in a row: the one upload scratch
+                ops += [p for p, on in (("trhs", tangent), ("hvp", tangent and tan_valid), ("arhs", second and lam_valid),
+                                        ("fhvp", second and atan_valid and tan_valid and lam_valid), ("ff", fluxfield),
+                                        ("vjp", lam_valid), ("sens", sens and sysok and have_x)) if on and p != prev] * 5
+            if have_x and sysok:
+                # a pass inside a resident interval that no check has settled (sweeps, the pass, a solve in a row), and a
+                # stack's solve whose first reader is the pass
+                first = (["trhs"] if tangent else []) + (["ff"] if fluxfield else [])
+                if tb2 and prev != "sweeps":
+                    ops += ["sweeps"] * 60
+                if prev == "sweeps":
+                    ops += first * (100 if tb2 else 6) + (["ff"] * 80 if tb2 and fluxfield else [])
+                if prev2 == "sweeps" and prev in ("trhs", "ff"):
+                    ops += ["solve"] * (4000 if tb2 else 10)
+                if onchip_planes and op_key == 1 and with_cg:    # (the plane form of the forward solve under the key)
+                    ops += ["cgform"] * 10 + ["cg"] * (200 if prev == "cgform" else 4)
         op = ops[rng.integers(len(ops))]
         prev2, prev = prev, op
+        hist.append(op)
         refused_on_3n = False
         refused_last = False
+        dx_lost = dx_lost and op in ("tune", "kernel", "cgform", "opflip")       # (the boost lasts for one call that is no key)
+        dl_lost = dl_lost and op in ("tune", "kernel", "cgform", "opflip")
         if op in ("image", "assemble", "stage"):             # (a new image or system: lambda was the old one's)
+            dx_lost, dl_lost = tan_valid, atan_valid
+            tan_rhs = tan_valid = atan_rhs = atan_valid = False
             lam_lost, lam_valid, adj_since = lam_lost or lam_valid, False, False
         if op == "image":
             yield ("image", draw_images(rng, nx, ny, B))
@@ -284,11 +405,13 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             rtol = float(rng.choice([1e-6, 1e-10]))
             max_iter = int(rng.choice([3, 100000, 100000]))
             ce = int(rng.choice([1, 64]))
-            refused = bool(rng.random() < (0.5 if kind == "3n" or (adjoint and lam_valid) else 0.2))       # (about one in four over a group)
+            refused = bool(rng.random() < (0.5 if kind == "3n" or (adjoint and lam_valid) or tan_valid or atan_valid else 0.2))       # (about one in four over a group)
             yield ("cgstream", imgs, Ds, -1.0 if refused else Df, CL, CR, rtol, max_iter, ce)
             if not refused:
                 kind, have_x, fill, after_stream = "2p", True, False, True
                 lam_lost, lam_valid, adj_since = lam_lost or lam_valid, False, False
+                dx_lost, dl_lost = tan_valid, atan_valid
+                tan_rhs = tan_valid = atan_rhs = atan_valid = False
             refused_on_3n = refused and kind == "3n"
             refused_last = refused
         elif op == "prescaled":
@@ -308,6 +431,8 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
                     v = int(rng.choice(values))
                     if key in tb_keys:
                         tb_keys[key] = v
+                    if key == "cg_onchip_planes":
+                        op_key = v
                     yield ("tune", key, v)
             elif what == 0:
                 yield ("tune", "tb_T", int(rng.choice([0, 2, 4, 8])))
@@ -346,7 +471,10 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             readers = ["get"] + (["ptr"] if ptr else []) + (["slot"] if slot else [])
             if adjoint and lam_valid:                        # ... and deff_field_vjp_D, which consolidates itself
                 readers += ["vjp"] * 8
-            yield ("solve", tol, max_iter, ce, readers[rng.integers(len(readers))] if len(readers) > 1 else "get")
+            readers += (["trhs"] * 6 if tangent else []) + (["ff"] * 6 if fluxfield else [])       # ... and so do these two
+            reader = readers[rng.integers(len(readers))] if len(readers) > 1 else "get"
+            yield ("solve", tol, max_iter, ce, reader)
+            tan_rhs = tan_rhs or reader == "trhs"
         elif op == "cg":
             rtol = float(rng.choice([1e-6, 1e-10]))
             max_iter = int(rng.choice([0, 3, 100000]))
@@ -364,15 +492,20 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
                 refused_last = True                          # (an explicit-only system; lambda stays what it was)
             else:
                 lam_valid, lam_lost, adj_since = True, False, True
+                dl_lost, atan_rhs, atan_valid = atan_valid, False, False         # (a new lambda: dlambda was the old one's)
         elif op == "cgform":                                 # the keys of one of CG's three forms, set together
             # (on chip where the system surely has a dictionary; elsewhere the form that never needs one is likelier)
-            form = int(rng.choice([0, 1, 1, 1, 2] if kind in ("2p", "3n") else [0, 1, 2, 2]))
+            forms = [0, 1, 1, 1, 2] if kind in ("2p", "3n") else [0, 1, 2, 2]
+            if onchip_planes and op_key == 1:
+                forms = forms + [2, 2, 2]                    # (towards the plane form, which the key moves on chip)
+            form = int(rng.choice(forms))
             yield ("tune", "cg_onchip", 1 if form == 1 else 0)
             yield ("tune", "cg_planes", 2 if form == 2 else 0)
             yield ("tune", "cg_fold", int(rng.choice(CG_FOLD_DRAW)))
         elif op == "setadj":
             yield ("setadj", [rng.standard_normal((ny, nx)) for _ in range(B)])
             lam_valid, lam_lost = True, False
+            dl_lost, atan_rhs, atan_valid = atan_valid, False, False
         elif op == "getadj":
             yield ("getadj",)
             lam_lost = False
@@ -391,6 +524,56 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
         elif op == "sens":
             yield ("sens",)
             refused_last = kind in ("3n", "3g")              # (the form without D is refused for a Grid system, then D is given)
+        elif op in ("trhs", "arhs", "hvp", "fhvp", "ff"):
+            # the model's planes, or a plane of the caller's with zero cells; the direction: random (non-zero where D == 0 too),
+            # or D itself; the walls are drawn independently of the system's (the right-hand side of dlambda has none)
+            own = kind is None or bool(rng.random() < 1.0 / 3.0)
+            D = None
+            if own:
+                Ds, Df, Dg = ASSEMBLE_D[rng.integers(3)]
+                D = draw_D_planes(rng, nx, ny, B, Ds, Df, Dg)
+                for plane in D:
+                    plane[rng.random((ny, nx)) < 0.05] = 0.0
+            # (None: the direction D itself -- never for "hvp": H D = 0, and the bar of its curv is relative to the sum itself)
+            dD = None
+            if op != "ff" and (rng.random() < 0.8 or op == "hvp"):
+                dD = [rng.standard_normal((ny, nx)) for _ in range(B)]
+            CL, CR = PASS_WALLS[rng.integers(3)] if op != "arhs" else (0.0, 0.0)
+            yield (op, D, dD, CL, CR)
+            if op == "trhs":
+                tan_rhs = tan_rhs or have_x
+            elif op == "arhs" and lam_valid:
+                dl_lost, atan_rhs, atan_valid = False, True, False
+            elif op == "hvp":
+                refused_last = not (have_x and tan_valid) or CL == CR
+                dx_lost = False
+            elif op == "fhvp":
+                refused_last = not (have_x and tan_valid and lam_valid and atan_valid)
+                dx_lost = dl_lost = False
+            elif op == "ff":
+                refused_last = kind in ("3n", "3g")          # (the form without D; the one with D went through)
+        elif op in ("tan", "atan"):
+            rtol = float(rng.choice([1e-6, 1e-10]))
+            max_iter = int(rng.choice([0, 3, 100000, 100000]))
+            yield (op, rtol, max_iter, int(rng.choice([1, 64])))
+            ok = kind not in (None, "Sw") and (tan_rhs if op == "tan" else atan_rhs)
+            refused_last = not ok
+            if ok and op == "tan":
+                tan_valid = True
+            elif ok:
+                atan_valid = True
+            dx_lost, dl_lost = dx_lost and op != "tan", dl_lost and op != "atan"
+        elif op in ("settan", "setatan"):
+            yield (op, [rng.standard_normal((ny, nx)) for _ in range(B)])
+            if op == "settan":
+                tan_valid, dx_lost = True, False
+            else:
+                atan_valid, dl_lost = True, False
+        elif op in ("gettan", "getatan"):
+            yield (op,)
+        elif op == "opflip":
+            op_key = 1 - op_key
+            yield ("tune", "cg_onchip_planes", op_key)
         elif op == "stream":
             count = int(rng.integers(B, 3 * B + 2))
             imgs = draw_images(rng, nx, ny, count)
@@ -402,6 +585,8 @@ def draw_sequence(seed, with_cg=False, shapes=SHAPES, stacks=(1, 1, 3), steps=30
             if not (pre and kset == "explicit"):             # (refused before anything changes: no pre-scaled explicit sweeps)
                 kind, have_x, fill, after_stream = "2p", True, False, True
                 lam_lost, lam_valid, adj_since = lam_lost or lam_valid, False, False
+                dx_lost, dl_lost = tan_valid, atan_valid
+                tan_rhs = tan_valid = atan_rhs = atan_valid = False
         elif op == "slot":
             yield ("slot", int(rng.integers(B)))
         elif op == "stamps":
@@ -503,7 +688,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
     flavour = "fma" if use_fma else None
     m = Model(ob, nx, ny, B, None)
     log = []
-    onchip_key = planes_key = fold_key = pre_key = 0
+    onchip_key = planes_key = fold_key = pre_key = op_key = 0
     kernel_set = "auto"
     m.fill_fresh, m.fill_count = False, 0                    # the device fill: of the current image? / how many were computed
     sens_model = pre_model = None
@@ -518,6 +703,19 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
     # the adjoint's side of the model: lambda per image as the context last returned or took it, whether deff_amd.h's lifetime
     # rule says it is valid, and the device buffers of the last pass and of the last gradient as they read when they were made
     m.lam, m.lam_valid, m.vjp_dev, m.sens_dev = None, False, None, None
+    # ... and the second-order side: dx and dlambda the same way, the two right-hand side maps as the model computed them (what
+    # a twin solves from), whether each may serve as one, the device maps of the other passes, and "cg_onchip_planes"
+    m.dx, m.tan_valid, m.r, m.tan_rhs = None, False, None, False
+    m.dl, m.atan_valid, m.q, m.atan_rhs = None, False, None, False
+    m.dev = {}
+    if any(options.get(k) for k in ("tangent", "second", "fluxfield")):
+        import field_hvp_model
+        import flux_model
+        import sens_hvp_model
+        import tangent_model
+        from test_gpu_field_hvp import CURV_MASS_BAR
+        from test_gpu_sens_hvp import CURV_BAR
+        from test_gpu_tangent import NORM2_BAR
 
     def distinct_rows():
         return len(np.unique(np.column_stack([np.concatenate(m.A), np.concatenate(m.b)]), axis=0))
@@ -577,18 +775,35 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 got = s.get_adjoint()
                 for k in range(B):
                     assert np.array_equal(got[k * ny:(k + 1) * ny], m.lam[k]), (seed, log, "lambda of image %d" % k)
+            # ... and so do deff_get_tangent and deff_get_adjoint_tangent, each while the model says it is valid
+            for valid, vec, get, what in ((m.tan_valid, m.dx, s.get_tangent, "dx"), (m.atan_valid, m.dl, s.get_adjoint_tangent, "dlambda")):
+                if valid:
+                    got = get()
+                    for k in range(B):
+                        assert np.array_equal(got[k * ny:(k + 1) * ny], vec[k]), (seed, log, "%s of image %d" % (what, k))
 
-        def maps_unchanged(vjp=True, sens=True):
-            """The device buffers of the last pass and of the last gradient read as they did when they were written."""
+        def maps_unchanged(vjp=True, sens=True, skip=()):
+            """The device buffers of the last pass and of the last gradient read as they did when they were written -- and those
+            of the tangent's right-hand side (which deff_device_tangent_rhs hands out even after an invalidation), of the two
+            Hessian-vector passes and of the flux field."""
             if vjp and m.vjp_dev is not None:
                 p, pitch = s.device_field_vjp_ptr()
                 assert np.array_equal(device_rows(p, B * ny, pitch), m.vjp_dev), (seed, log, "the pass's device map")
             if sens and m.sens_dev is not None:
                 p, pitch = s.device_sensitivity_ptr()
                 assert np.array_equal(device_rows(p, B * ny, pitch), m.sens_dev), (seed, log, "the gradient's device map")
+            for name, ptr in (("trhs", s.device_tangent_rhs_ptr), ("hvp", s.device_sens_hvp_ptr), ("fhvp", s.device_field_vjp_hvp_ptr)):
+                if name not in skip and m.dev.get(name) is not None:
+                    p, pitch = ptr()
+                    assert np.array_equal(device_rows(p, B * ny, pitch), m.dev[name], equal_nan=True), (seed, log, "device map of " + name)
+            if "ff" not in skip and m.dev.get("ff") is not None:
+                px, py, pitch = s.device_flux_field_ptrs()
+                for p, want, what in ((px, m.dev["ff"][0], "fx"), (py, m.dev["ff"][1], "fy")):
+                    assert np.array_equal(device_rows(p, B * ny, pitch), want, equal_nan=True), (seed, log, "device map of " + what)
 
         def lam_invalidated():
             m.lam_valid, m.sens_dev = False, None            # (deff_device_sensitivity: "valid until ... an assembly")
+            m.tan_rhs = m.tan_valid = m.atan_rhs = m.atan_valid = False
 
         def adjoint_refused(*calls):
             """While lambda is invalid (or no field exists, for the pass): DEFF_ESTATE, and nothing else changes."""
@@ -628,6 +843,218 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
             fields_equal()
             lam_unchanged()
 
+        # ---- the second-order calls ------------------------------------------------------------------------------------
+        def refused(reasons, *calls):
+            """Every call is refused for one of `reasons` -- (code, keyword of deff_amd.h's message); where the model knows of
+            one reason only, that one -- and nothing changes: the field, every valid vector and every map read as before."""
+            for call in calls:
+                with pytest.raises(pkg.DeffError) as e:
+                    call()
+                assert any(e.value.code == code and word in str(e.value) for code, word in reasons), (seed, log, reasons, e.value)
+            log[-1] += " refused"
+            if m.x is not None:
+                fields_equal()
+            maps_unchanged()
+            lam_unchanged()
+
+        def side_impl():
+            """deff_get_plan "cg_impl" after a solve on the coefficient planes (deff_amd.h, "cg_onchip_planes")."""
+            return 4 if op_key == 1 and (nx + (nx & 1)) * ny <= ONCHIP_LIMIT else 3
+
+        def map_checked(what, g, ptr, want):
+            """The host copy and the device map of a pass equal the model's bit for bit; the pad column of an odd width is 0."""
+            g = np.asarray(g).reshape(B, ny, nx)
+            p, pitch = ptr()
+            assert pitch == 8 * (nx + (nx & 1)), (seed, log, what, pitch)
+            dev = device_rows(p, B * ny, pitch)
+            for k in range(B):
+                assert np.array_equal(g[k], want[k], equal_nan=True), (seed, log, "%s of image %d" % (what, k), np.argwhere(g[k] != want[k])[:4].tolist())
+                assert np.array_equal(dev[k * ny:(k + 1) * ny, :nx], want[k], equal_nan=True), (seed, log, "device map of %s, image %d" % (what, k))
+            if nx & 1:
+                assert np.array_equal(dev[:, nx], np.zeros(B * ny)), (seed, log, "pad column of " + what)
+            return dev
+
+        def sum_checked(what, k, got, want, bar):
+            """A per-image sum against the model's long-double one, within the bar of the pass's own directed test."""
+            off = abs(float(np.longdouble(got) - want))
+            print(f"seed {seed} {what} image {k}: {got!r}, off the model's by {off:.3e}, bar {bar:.3e}")
+            assert got == float(want) or off <= bar, (seed, log, what, k, got, float(want), off, bar)
+
+        def after_pass(name):
+            maps_unchanged(skip=(name,))
+            if m.x is not None:
+                fields_equal()
+            lam_unchanged()
+
+        def planes_of(D, dD):
+            planes = m.D if D is None else D
+            return planes, (planes if dD is None else dD)
+
+        def trhs_checked(D, dD, CL, CR):
+            """deff_tangent_rhs_D of the model's field against tests/tangent_model.py; norm2 within check_map's bar in
+            test_gpu_tangent.py.  The map becomes a right-hand side for the current system."""
+            planes, dirs = planes_of(D, dD)
+            call = lambda: s.tangent_rhs(m.stacked(planes), m.stacked(dirs), CL, CR)     # noqa: E731
+            if m.x is None:
+                return refused([(-5, "no field")], call)
+            r, n2 = call()
+            want = [tangent_model.tangent_rhs(m.x[k], planes[k], dirs[k], CL, CR) for k in range(B)]
+            m.dev["trhs"] = map_checked("the tangent's right-hand side", r, s.device_tangent_rhs_ptr, [w[0] for w in want])
+            for k in range(B):
+                sum_checked("norm2 of r", k, np.atleast_1d(n2)[k], want[k][1], NORM2_BAR * abs(float(want[k][1])))
+            m.r, m.tan_rhs = [w[0] for w in want], True
+            after_pass("trhs")
+
+        def arhs_checked(D, dD):
+            """deff_adjoint_tangent_rhs_D: the tangent's model on lambda with both wall values 0; a new right-hand side makes
+            dlambda invalid.  The map has no device getter: the twin of the next "atan" solves from the model's copy."""
+            planes, dirs = planes_of(D, dD)
+            call = lambda: s.adjoint_tangent_rhs(m.stacked(planes), m.stacked(dirs))     # noqa: E731
+            if not m.lam_valid:
+                return refused([(-5, "no adjoint field")], call)
+            q, n2 = call()
+            q = np.asarray(q).reshape(B, ny, nx)
+            want = [tangent_model.tangent_rhs(m.lam[k], planes[k], dirs[k], 0.0, 0.0) for k in range(B)]
+            for k in range(B):
+                assert np.array_equal(q[k], want[k][0], equal_nan=True), (seed, log, "q of image %d" % k, np.argwhere(q[k] != want[k][0])[:4].tolist())
+                sum_checked("norm2 of q", k, np.atleast_1d(n2)[k], want[k][1], NORM2_BAR * abs(float(want[k][1])))
+            m.q, m.atan_rhs, m.atan_valid = [w[0] for w in want], True, False
+            with pytest.raises(pkg.DeffError) as e:          # (dlambda belonged to the previous right-hand side)
+                s.get_adjoint_tangent()
+            assert e.value.code == -5, (seed, log, e.value)
+            after_pass("arhs")
+
+        def hvp_checked(D, dD, CL, CR):
+            """deff_sensitivity_hvp_D of the model's field and dx against tests/sens_hvp_model.py; curv within check_map's bar in
+            test_gpu_sens_hvp.py."""
+            planes, dirs = planes_of(D, dD)
+            call = lambda: s.sens_hvp(m.stacked(planes), m.stacked(dirs), CL, CR)        # noqa: E731
+            reasons = ([(-1, "CR == CL")] if CL == CR else []) + ([(-5, "no field")] if m.x is None else []) + \
+                ([(-5, "no tangent field")] if not m.tan_valid else [])
+            if reasons:
+                return refused(reasons, call)
+            hv, cv = call()
+            want = [sens_hvp_model.sens_hvp(m.x[k], m.dx[k], planes[k], dirs[k], CL, CR) for k in range(B)]
+            m.dev["hvp"] = map_checked("the Deff Hessian-vector product", hv, s.device_sens_hvp_ptr, [w[0] for w in want])
+            for k in range(B):
+                sum_checked("curv", k, np.atleast_1d(cv)[k], want[k][1], CURV_BAR * abs(float(want[k][1])))
+            after_pass("hvp")
+
+        def fhvp_checked(D, dD, CL, CR):
+            """deff_field_vjp_hvp_D of the model's field, lambda, dx and dlambda against tests/field_hvp_model.py; curv within
+            check_map's bar in test_gpu_field_hvp.py.  A refusal names what is missing."""
+            planes, dirs = planes_of(D, dD)
+            call = lambda: s.field_vjp_hvp(m.stacked(planes), m.stacked(dirs), CL, CR)   # noqa: E731
+            reasons = [(-5, word) for word, have in (("no field", m.x is not None), ("no adjoint field", m.lam_valid),
+                                                     ("no tangent field", m.tan_valid), ("no adjoint tangent", m.atan_valid)) if not have]
+            if reasons:
+                return refused(reasons, call)
+            hv, cv = call()
+            want = [field_hvp_model.field_hvp(m.x[k], m.lam[k], m.dx[k], m.dl[k], planes[k], dirs[k], CL, CR) for k in range(B)]
+            m.dev["fhvp"] = map_checked("the field Hessian-vector product", hv, s.device_field_vjp_hvp_ptr, [w[0] for w in want])
+            for k in range(B):
+                mass = float(np.sum(np.abs(np.where(planes[k] == 0.0, 0.0, dirs[k]) * want[k][0])))
+                sum_checked("curv of S_w", k, np.atleast_1d(cv)[k], want[k][1], CURV_MASS_BAR * mass)
+            after_pass("fhvp")
+
+        def flux_maps_checked(ff, planes, CL, CR):
+            kt = s.plan_value("flux_kt")
+            want = [flux_model.flux_field(m.x[k], planes[k], CL, CR) for k in range(B)]
+            px, py, pitch = s.device_flux_field_ptrs()
+            devx = map_checked("fx", ff.fx, lambda: (px, pitch), [w[0] for w in want])
+            devy = map_checked("fy", ff.fy, lambda: (py, pitch), [w[1] for w in want])
+            for k in range(B):
+                assert np.array_equal(ff.left[k], want[k][2], equal_nan=True), (seed, log, "left wall of image %d" % k)
+                Q = flux_model.sections(want[k][0], want[k][2], ny, kt)
+                assert np.array_equal(ff.sections[k], Q, equal_nan=True), (seed, log, "sections of image %d under flux_kt %d" % (k, kt),
+                                                                           np.flatnonzero(ff.sections[k] != Q)[:4].tolist())
+            m.dev["ff"] = (devx, devy)
+            after_pass("ff")
+
+        def ff_checked(D, CL, CR):
+            """deff_flux_field_D against tests/flux_model.py (sections in the order of the "flux_kt" the plan reports), then
+            deff_flux_field, whose outcome follows how the current system was assembled (deff_amd.h)."""
+            planes = m.D if D is None else D
+            with_D = lambda: s.flux_field(m.stacked(planes), CL, CR)                     # noqa: E731
+            image_form = {"2p": [], "3p": [], "3n": [(-1, "Grid")], "3g": [(-1, "Grid")]}.get(m.kind, [(-5, "assembled from the image")])
+            if m.x is None:
+                refused([(-5, "no field")], with_D)
+                return refused(image_form + [(-5, "no field")], s.flux_field)
+            flux_maps_checked(with_D(), planes, CL, CR)
+            if image_form:
+                return refused(image_form, s.flux_field)
+            flux_maps_checked(s.flux_field(), m.D, m.CL, m.CR)
+
+        def vector_read(which):
+            """deff_get_tangent + deff_device_tangent (deff_get_adjoint_tangent + deff_device_adjoint_tangent)."""
+            valid, vec, get, ptr, word = (m.tan_valid, m.dx, s.get_tangent, s.device_tangent_ptr, "no tangent field") if which == "gettan" \
+                else (m.atan_valid, m.dl, s.get_adjoint_tangent, s.device_adjoint_tangent_ptr, "no adjoint tangent")
+            if not valid:
+                return refused([(-5, word)], get, ptr)
+            lam_unchanged()
+            p, pitch = ptr()
+            assert pitch == 8 * (nx + (nx & 1)), (seed, log, pitch)
+            dev = device_rows(p, B * ny, pitch)
+            for k in range(B):
+                assert np.array_equal(dev[k * ny:(k + 1) * ny, :nx], vec[k]), (seed, log, "device %s of image %d" % (which[3:], k))
+            if nx & 1:
+                assert np.array_equal(dev[:, nx], np.zeros(B * ny)), (seed, log, "pad column of " + which[3:])
+
+        def side_solve_checked(which, rtol, max_iter, ce):
+            """deff_solve_tangent / deff_solve_adjoint_tangent: "deff_solve_adjoint with w = r, bit for bit" (deff_amd.h).  The
+            twin is a fresh context of the same stack size that is given the model's system through deff_set_system, the same
+            "cg_fold" and "cg_onchip_planes" and the OTHER check interval, and solves deff_solve_adjoint(w = the model's map)."""
+            solve, rhs_ok, rhs, get = (s.solve_tangent, m.tan_rhs, m.r, s.get_tangent) if which == "tan" \
+                else (s.solve_adjoint_tangent, m.atan_rhs, m.q, s.get_adjoint_tangent)
+            call = lambda: solve(rtol=rtol, max_iter=max_iter, check_every=ce)           # noqa: E731
+            # (after a new image the context has no system of its own; the header leaves open whether the old one's wall-column
+            # links still speak: the draw asks for a solve there only where there is no right-hand side either)
+            reasons = ([(-1, "wall column")] if m.kind == "Sw" else []) + ([(-5, "right-hand side")] if not rhs_ok else []) + \
+                ([(-5, "no system"), (-1, "wall column")] if m.kind is None else [])
+            if reasons:
+                return refused(reasons, call)
+            kernel_before = s.kernel_in_use()
+            tb_before = {k: v for k, v in s.plan().items() if k.startswith("tb_")}
+            res = call()
+            res = [res] if B == 1 else res
+            got = get()
+            impl = side_impl()
+            want_fold = 0 if impl == 4 else min(fold_key, 1)
+            assert (s.plan_value("cg_impl"), s.plan_value("cg_fold")) == (impl, want_fold), (seed, log, op_key, fold_key, s.plan_value("cg_impl"))
+            assert s.kernel_in_use() == kernel_before, (seed, log, kernel_before, s.kernel_in_use())
+            assert {k: v for k, v in s.plan().items() if k.startswith("tb_")} == tb_before, (seed, log, tb_before)
+            with pkg.Solver(nx, ny, nimg=B) as f:
+                f.set_tuning("cg_fold", fold_key)
+                f.set_tuning("cg_onchip_planes", op_key)
+                f.set_system(m.stacked(m.A), m.stacked(m.b), m.stacked(m.D), m.CL, m.CR)
+                twin = f.solve_adjoint(m.stacked(rhs), rtol=rtol, max_iter=max_iter, check_every=1 if ce == 64 else 64)
+                twin = [twin] if B == 1 else twin
+                assert (f.plan_value("cg_impl"), f.plan_value("cg_fold")) == (impl, want_fold), (seed, log, "the twin's form")
+                lam_f = f.get_adjoint()
+            mine = [(r.iters, r.rel_residual, r.converged) for r in res]
+            assert mine == [(r.iters, r.rel_residual, r.converged) for r in twin], (seed, log, mine, [(r.iters, r.rel_residual) for r in twin])
+            assert np.array_equal(got, lam_f, equal_nan=True), (seed, log, which + " against solve_adjoint of the map on a fresh context",
+                                                                  np.argwhere(got != lam_f)[:4].tolist())
+            vec = []
+            for k in range(B):
+                dec = decoupled_of(m.A[k], m.b[k]).reshape(ny, nx)
+                v = got[k * ny:(k + 1) * ny].copy()
+                assert np.all(v[dec] == 0.0) and res[k].deff_raw == 0.0, (seed, log, k)
+                assert res[k].iters <= max_iter and res[k].converged == (res[k].rel_residual <= rtol), (seed, log, k, mine[k])
+                if res[k].converged:                         # the bar of test_gpu_cg.py::assert_honest, as for "adj"
+                    rn = residual_np(m.A[k], np.where(dec, 0.0, rhs[k]).ravel(), v, nx, ny)
+                    assert rn <= rtol * (1 + 1e-6) + 1e-13, (seed, log, k, rn)
+                vec.append(v)
+            if which == "tan":
+                m.dx, m.tan_valid = vec, True
+            else:
+                m.dl, m.atan_valid = vec, True
+            log[-1] += " impl %d iters %s" % (impl, [r.iters for r in res])
+            if m.x is not None:
+                fields_equal()
+            maps_unchanged()
+            lam_unchanged()                                  # (the other two vectors stay)
+
         if use_fma:
             s.set_tuning("fma", 1)
             log.append("fma 1")
@@ -639,6 +1066,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 lam_invalidated()
                 s.set_image(np.stack(m.pix))
                 log.append("image")
+                maps_unchanged()                             # (every other map stays until its own next call)
             elif op == "assemble":
                 kind, Ds, Df, Dg, CL, CR, D, *base = args
                 m.assemble(kind, Ds, Df, Dg, CL, CR, D, *base)
@@ -667,6 +1095,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                     s.assemble_from_D(m.stacked(m.D), CL, CR)
                 if kind != "3n" and options.get("native3"):
                     assert s.plan_value("native3_rows") == 0, (seed, log)
+                maps_unchanged()
             elif op == "stage":
                 Ds, Df, Dg, CL, CR = args
                 assert m.kind == "3n" and m.fill_fresh
@@ -676,6 +1105,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 lam_invalidated()
                 s.assemble_3phase_native(Ds, Df, Dg, CL, CR)
                 native_counters()
+                maps_unchanged()
             elif op == "grid":
                 log.append("grid")
                 g, path = s.grid()
@@ -697,6 +1127,8 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                     fold_key = v
                 elif key == "prescaled":
                     pre_key = v
+                elif key == "cg_onchip_planes":
+                    op_key = v
                 log.append(f"{key} {v}")
             elif op == "kernel":
                 s.set_kernel(args[0]); log.append(f"kernel {args[0]}")
@@ -753,6 +1185,12 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 elif reader == "vjp":                        # (the pass consolidates the frozen images itself)
                     log[-1] += " then vjp"
                     field_vjp_checked(None, m.CL, m.CR)
+                elif reader == "trhs":                       # (and so do these two; the direction D: the forward residual)
+                    log[-1] += " then trhs"
+                    trhs_checked(None, None, m.CL, m.CR)
+                elif reader == "ff":
+                    log[-1] += " then ff"
+                    ff_checked(None, m.CL, m.CR)
                 else:
                     fields_equal()
             elif op == "cg":
@@ -781,12 +1219,14 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                     has_dict = distinct_rows() <= 511
                     assert has_dict or planes_key, (seed, log, "CG ran without a dictionary and without cg_planes")
                 want_impl = 3 if planes_key == 2 or not has_dict else expected_cg_impl(nx, ny, onchip_key)
+                if want_impl == 3:                           # the plane form: on chip under "cg_onchip_planes" where an image fits
+                    want_impl = side_impl()
                 if options.get("onchip"):
                     assert s.plan_value("cg_impl") == want_impl, (seed, log, onchip_key, planes_key)
                     log[-1] += " impl %d" % want_impl
                 if options.get("cgkeys"):
                     # the fold that ran: the key on the streaming forms (on the planes 2 means 1, deff_amd.h), 0 on chip
-                    want_fold = {1: fold_key, 2: 0, 3: min(fold_key, 1)}[want_impl]
+                    want_fold = {1: fold_key, 2: 0, 3: min(fold_key, 1), 4: 0}[want_impl]
                     assert s.plan_value("cg_fold") == want_fold, (seed, log, fold_key, want_impl, s.plan_value("cg_fold"))
                     log[-1] += " fold %d" % want_fold
                 res = [res] if B == 1 else res
@@ -798,10 +1238,14 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                     # With "cgkeys" the fresh context also runs four launches per iteration (cg_fold 0) and, where the system
                     # has a dictionary, on the table (cg_planes 0): the same bits in both cases (deff_amd.h; the plane form has
                     # the work items and summation order of the STREAMING table form, so that is the form it is compared with).
-                    fresh_onchip = 0 if want_impl == 3 else onchip_key
-                    fresh_impl = 3 if not has_dict else expected_cg_impl(nx, ny, fresh_onchip)
+                    # The plane form on chip ("cg_impl" 4): "a system that has a dictionary gives the bits of "cg_onchip" 1" -- the
+                    # fresh context runs the table form on chip --, and one without has the same form to run on the planes.
+                    fresh_onchip = 0 if want_impl == 3 else 1 if want_impl == 4 else onchip_key
+                    fresh_impl = (4 if want_impl == 4 else 3) if not has_dict else expected_cg_impl(nx, ny, fresh_onchip)
                     with pkg.Solver(nx, ny, nimg=B) as f:
                         f.set_tuning("cg_onchip", fresh_onchip)
+                        if want_impl == 4 and not has_dict:
+                            f.set_tuning("cg_onchip_planes", 1)
                         f.set_tuning("cg_planes", 0 if has_dict else planes_key)
                         f.set_image(np.stack(m.pix))
                         if m.kind == "2p":
@@ -897,6 +1341,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 m.x = [want[last[k]][3] for k in range(B)]
                 m.CL, m.CR, m.kind, m.phases = CL, CR, "2p", (Ds, Df, None)
                 fields_equal()
+                maps_unchanged()
             elif op == "sens":
                 # the Deff gradient of the current field: it uses the upload scratch and events of its own and changes nothing
                 # else -- the closing fields_equal() and every later op show that
@@ -975,6 +1420,7 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 m.x = [want[last[k]][3] for k in range(B)]
                 m.CL, m.CR, m.kind, m.phases = CL, CR, "2p", (Ds, Df, None)
                 fields_equal()
+                maps_unchanged()
             elif op == "adj":
                 # deff_solve_adjoint: every image against a twin -- a fresh one-image context that is given the image's matrix
                 # with w' (w zeroed where the FORWARD system decouples the cell) as its right-hand side and solves it as a
@@ -997,7 +1443,8 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                 res = s.solve_adjoint(m.stacked(w), rtol=rtol, max_iter=max_iter, check_every=ce)
                 res = [res] if B == 1 else res
                 lam = s.get_adjoint()
-                assert s.plan_value("cg_impl") == 3 and s.plan_value("cg_fold") == min(fold_key, 1), (seed, log, fold_key)
+                want_fold = 0 if side_impl() == 4 else min(fold_key, 1)
+                assert (s.plan_value("cg_impl"), s.plan_value("cg_fold")) == (side_impl(), want_fold), (seed, log, fold_key, op_key)
                 assert s.kernel_in_use() == kernel_before, (seed, log, kernel_before, s.kernel_in_use())
                 assert {k: v for k, v in s.plan().items() if k.startswith("tb_")} == tb_before, (seed, log, tb_before)
                 m.lam = []
@@ -1013,10 +1460,11 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                     with pkg.Solver(nx, ny) as f:
                         f.set_tuning("cg_planes", 2)
                         f.set_tuning("cg_fold", 0)
+                        f.set_tuning("cg_onchip_planes", op_key)
                         f.set_system(m.A[k], wp.ravel(), m.D[k], m.CL, m.CR)
                         f.set_field(np.zeros((ny, nx)))
                         one = f.solve_cg(rtol=rtol, max_iter=max_iter, check_every=1 if ce == 64 else 64)
-                        assert f.plan_value("cg_impl") == 3 and f.plan_value("cg_fold") == 0, (seed, log)
+                        assert f.plan_value("cg_impl") == side_impl() and f.plan_value("cg_fold") == 0, (seed, log)
                         assert (one.iters, one.rel_residual, one.converged) == got, (seed, log, k, got, (one.iters, one.rel_residual, one.converged))
                         assert np.array_equal(f.get_field(), lk), (seed, log, "lambda of image %d against its twin" % k)
                     assert res[k].iters <= max_iter and res[k].converged == (res[k].rel_residual <= rtol), (seed, log, k, got)
@@ -1025,13 +1473,50 @@ def run_sequence(pkg, ob, seed, with_cg=False, **options):
                         assert rn <= rtol * (1 + 1e-6) + 1e-13, (seed, log, k, rn)
                     m.lam.append(lk)
                 m.lam_valid = True
+                m.atan_rhs = m.atan_valid = False            # (a new lambda: dlambda and its right-hand side were the old one's)
                 log[-1] += " iters %s" % [r.iters for r in res]
                 if m.x is not None:
                     fields_equal()
+                lam_unchanged()                              # (dx stays)
             elif op == "setadj":
                 log.append("setadj")
                 m.lam, m.lam_valid = args[0], True
+                m.atan_rhs = m.atan_valid = False
                 s.set_adjoint(m.stacked(m.lam))
+            elif op in ("trhs", "arhs", "hvp", "fhvp", "ff"):
+                D, dD, CL, CR = args
+                log.append(f"{op} {'D' if D is not None else 'model'} {'dD' if dD is not None else 'D'} {CL} {CR}")
+                if op == "trhs":
+                    trhs_checked(D, dD, CL, CR)
+                elif op == "arhs":
+                    arhs_checked(D, dD)
+                elif op == "hvp":
+                    hvp_checked(D, dD, CL, CR)
+                elif op == "fhvp":
+                    fhvp_checked(D, dD, CL, CR)
+                else:
+                    ff_checked(D, CL, CR)
+            elif op in ("tan", "atan"):
+                log.append(f"{op} {args[0]} {args[1]} {args[2]}")
+                side_solve_checked(op, *args)
+            elif op in ("settan", "setatan"):                # the model adopts the caller's plane, as for "setadj"
+                log.append(op)
+                if op == "settan":
+                    m.dx, m.tan_valid = args[0], True
+                    s.set_tangent(m.stacked(m.dx))
+                else:
+                    m.dl, m.atan_valid = args[0], True
+                    s.set_adjoint_tangent(m.stacked(m.dl))
+                lam_unchanged()
+            elif op in ("gettan", "getatan"):
+                log.append(op)
+                vector_read(op)
+            elif op == "ffptr":
+                log.append("ffptr")
+                if m.dev.get("ff") is None:
+                    refused([(-5, "no flux field")], s.device_flux_field_ptrs)
+                else:
+                    maps_unchanged()
             elif op == "getadj":
                 log.append("getadj")
                 if not m.lam_valid:
@@ -1122,6 +1607,13 @@ PRESCALED_SEEDS = dict(first=9000, count=40, shapes=NATIVE_SHAPES, stacks=(1, 2,
 ADJOINT_SEEDS = dict(first=10000, count=40, with_cg=True, shapes=CGKEY_SHAPES, stacks=(1, 2, 2, 3), steps=40, onchip=True, cgkeys=True,
                      cgstream=True, native3=True, system=True, sens=True, stream=True, ptr=True, slot=True, adjoint=True)
 
+# ... and the second-order calls -- the field tangent, the two Hessian-vector products, the on-chip plane form of the side solves
+# and the flux field -- among everything the adjoint's group has: five validity flags, one upload scratch of two planes and one
+# set of CG work vectors are shared by all of it.
+SECOND_ORDER_SEEDS = dict(first=11000, count=48, with_cg=True, shapes=CGKEY_SHAPES, stacks=(1, 2, 2, 3), steps=40, onchip=True,
+                          cgkeys=True, cgstream=True, native3=True, system=True, sens=True, stream=True, ptr=True, slot=True,
+                          adjoint=True, tangent=True, second=True, fluxfield=True, onchip_planes=True)
+
 
 def seed_options(group):
     return {k: v for k, v in group.items() if k not in ("first", "count")}
@@ -1145,6 +1637,11 @@ def test_random_call_sequences_with_prescaled_sweeps(pkg, oracle, seed):
 @pytest.mark.parametrize("seed", range(ADJOINT_SEEDS["count"]))
 def test_random_call_sequences_with_the_field_adjoint(pkg, oracle, seed):
     run_sequence(pkg, oracle, ADJOINT_SEEDS["first"] + seed, **seed_options(ADJOINT_SEEDS))
+
+
+@pytest.mark.parametrize("seed", range(SECOND_ORDER_SEEDS["count"]))
+def test_random_call_sequences_with_tangents_hessian_products_and_the_flux_field(pkg, oracle, seed):
+    run_sequence(pkg, oracle, SECOND_ORDER_SEEDS["first"] + seed, **seed_options(SECOND_ORDER_SEEDS))
 
 
 @pytest.mark.parametrize("seed", range(ONCHIP_SEEDS["count"]))
@@ -1332,6 +1829,62 @@ def test_a_prescaled_stream_refused_for_the_explicit_kernel_changes_nothing(pkg,
             assert np.array_equal(got[k * ny:(k + 1) * ny], oracle.sweeps(sys_[k][0], sys_[k][1], x0[k * ny:(k + 1) * ny], 2)), k
 
 
+def test_the_image_forms_follow_the_assembly_sequence_and_a_new_image(pkg, oracle):
+    """deff_flux_field, deff_sensitivity and deff_residual take D "from the context's image system"; with no image system they
+    are DEFF_ESTATE (deff_amd.h).  A new image without an assembly is no image system: the stored phase diffusivities belonged
+    to the old image's (found by the "ff" op of SECOND_ORDER_SEEDS right after "image": deff_set_image left the phase count in
+    place, and the three calls evaluated the new pixels with the old system's diffusivities).  Held here by construction with
+    the two assembly chains few seeds reach: "2p" -> a caller's D plane, and "3p" -> native 3-phase -> "3p" again."""
+    import flux_model
+    nx, ny = 33, 20
+    rng = np.random.default_rng(909)
+    pix = [rng.choice(np.array([0, 30, 120, 199, 201, 255], dtype=np.uint8), size=(ny, nx)) for _ in range(2)]
+    Ds, Df, Dg, CL, CR = 1e-2, 1.0, 50.0, 0.25, 0.75
+    x0 = rng.random((ny, nx))
+
+    def image_forms_refused(s, code, word):
+        for call in (s.flux_field, s.sensitivity, s.residual):
+            with pytest.raises(pkg.DeffError) as e:
+                call()
+            assert e.value.code == code and word in str(e.value), (call.__name__, e.value)
+        assert np.array_equal(s.get_field(), x0)
+
+    def image_form_matches(s, D):
+        ff = s.flux_field()
+        fx, fy, left = flux_model.flux_field(x0, D, CL, CR)
+        assert np.array_equal(ff.fx, fx) and np.array_equal(ff.fy, fy) and np.array_equal(ff.left[0], left)
+        assert np.array_equal(ff.sections[0], flux_model.sections(fx, left, ny, s.plan_value("flux_kt")))
+        with_D = s.flux_field(D, CL, CR)
+        assert all(np.array_equal(u, v) for u, v in zip(ff, with_D))
+
+    with pkg.Solver(nx, ny) as s:
+        s.set_image(pix[0])
+        s.assemble_2phase(Ds, Df, CL, CR)
+        s.set_field(x0)
+        image_form_matches(s, oracle.fill_D_2phase(pix[0], Df, Ds))
+        s.set_image(pix[1])                                  # a new image, no assembly: the field stays, the image system is gone
+        image_forms_refused(s, -5, "assembled from the image")
+        s.assemble_2phase(Ds, Df, CL, CR)
+        image_form_matches(s, oracle.fill_D_2phase(pix[1], Df, Ds))
+        s.synth_image(7, 0)                                  # ... and so does a synthetic one
+        image_forms_refused(s, -5, "assembled from the image")
+        s.set_image(pix[1])
+        s.assemble_2phase(Ds, Df, CL, CR)
+        D = oracle.fill_D_3phase(pix[1], Df, Ds, Dg)
+        s.assemble_from_D(D, CL, CR)                         # "2p" -> "D": a caller's plane is no image system
+        with pytest.raises(pkg.DeffError) as e:
+            s.flux_field()
+        assert e.value.code == -5 and "assembled from the image" in str(e.value), e.value
+        s.assemble_3phase(Ds, Df, Dg, CL, CR)                # "3p" -> "3n" -> "3p"
+        image_form_matches(s, D)
+        s.assemble_3phase_native(Ds, Df, Dg, CL, CR)
+        with pytest.raises(pkg.DeffError) as e:
+            s.flux_field()
+        assert e.value.code == -1 and "Grid" in str(e.value), e.value
+        s.assemble_3phase(2 * Ds, Df, Dg, CL, CR)
+        image_form_matches(s, oracle.fill_D_3phase(pix[1], Df, 2 * Ds, Dg))
+
+
 @pytest.mark.parametrize("launch,T", [(0, 4), (0, 8), (1, 4), (1, 8)])     # workgroup tiles exist for passes of 4 and 8
 def test_stamps_advance_one_pass_or_three_on_a_resident_plan(pkg, oracle, launch, T):
     """deff_debug_tb_stamps by construction on both kinds of plan, so that the 3 T of deff_amd.h does not rest on what the
@@ -1479,3 +2032,157 @@ def run_slab_sequence(pkg, ob, seed):
 @pytest.mark.parametrize("seed", range(16))
 def test_random_call_sequences_on_row_slabs_match_the_oracle(pkg, oracle, seed):
     run_slab_sequence(pkg, oracle, 5000 + seed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Volumes (deff_volume_*): a second state machine -- a private context, two link planes and a have_system flag.
+
+VOLUME_SHAPES = [(9, 7, 3), (16, 3, 5), (130, 5, 4), (33, 5, 1)]
+
+
+def run_volume_sequence(pkg, seed):
+    """About 20 calls on one Volume against tests/volume_model.py: assemblies from a drawn D (about 10 % zeros), linear guesses
+    and caller's fields, CG (max_iter 0 / 2 / 7 / large, two tolerances, two check intervals), fluxes, reads of the field and
+    of the system, and in between a second Volume of another shape or a 2-D Solver that is opened, solved and closed.  CG is
+    compared with a twin -- a fresh Volume given the same D, the same field through set_field and the OTHER check interval:
+    field, result and wall fluxes bit for bit -- and rel_residual with the model's residual under the bars of
+    test_gpu_volume.py; the model then adopts the field.  The refusals a Volume has (cg before a field, cg before a system,
+    get_system before a system: DEFF_ESTATE) change nothing."""
+    import oracle_binding as ob
+    import volume_model as vm
+    from test_gpu_cg import EPS
+    from test_gpu_volume import ESTATE, RES_BAR, RES_BAR_CONVERGED
+    ob.build()
+    rng = np.random.default_rng(seed)
+    nx, ny, nz = VOLUME_SHAPES[rng.integers(len(VOLUME_SHAPES))]
+    shape = (nz, ny, nx)
+    log = [f"volume {nx} {ny} {nz}"]
+    D = A = b = x = None
+    CL, CR = 0.0, 1.0
+
+    def draw_D(shp):
+        d = rng.uniform(1e-3, 2.0, shp)
+        d[rng.random(shp) < 0.10] = 0.0
+        return d
+
+    with pkg.Volume(nx, ny, nz) as v:
+        def unchanged():
+            if x is not None:
+                assert vm.same_bits(v.get_field(), x), (seed, log, "field")
+            if A is not None:
+                Ag, bg = v.get_system()
+                assert vm.same_bits(Ag, A) and vm.same_bits(bg, b), (seed, log, "system")
+
+        def refused(call, word):
+            with pytest.raises(pkg.DeffError) as e:
+                call()
+            assert e.value.code == ESTATE and word in str(e.value), (seed, log, e.value)
+            log[-1] += " refused"
+            unchanged()
+
+        for step in range(20):
+            ops = ["assemble", "init", "set_field", "cg", "cg", "getsys", "other"]
+            if x is not None:
+                ops += ["get"] + (["flux", "flux", "cg"] if A is not None else [])
+            op = ops[rng.integers(len(ops))]
+            if op == "assemble":
+                D = draw_D(shape)
+                CL, CR = ASSEMBLE_C[rng.integers(2)]
+                log.append(f"assemble {CL} {CR}")
+                v.assemble_from_D(D, CL, CR)
+                A, b = vm.rows3(D, CL, CR)
+                unchanged()                                  # (get_system gives the model's rows bit for bit; the field stays)
+            elif op == "init":
+                log.append("init")
+                v.init_linear(CL, CR)
+                x = v.get_field()
+                # (every row of every slice is the 2-D guess's: test_gpu_volume.py::test_one_slice_is_the_2d_plane_form)
+                assert np.array_equal(x, np.broadcast_to(ob.linear_guess(nx, ny, CL, CR)[0], shape)), (seed, log)
+            elif op == "set_field":
+                log.append("set_field")
+                x = rng.random(shape)
+                v.set_field(x)
+                unchanged()
+            elif op == "getsys":
+                log.append("getsys")
+                if A is None:
+                    refused(v.get_system, "system")
+                else:
+                    unchanged()
+            elif op == "get":
+                log.append("get")
+                unchanged()
+            elif op == "flux":
+                log.append("flux")
+                d, MFL, MFR = v.flux()
+                d2, MFL2, MFR2 = v.flux()
+                assert d == d2 and np.array_equal(MFL, MFL2) and np.array_equal(MFR, MFR2), (seed, log)
+                want = vm.deff_of(x, D, CL, CR)
+                assert abs(d - want) <= 64 * EPS * abs(want), (seed, log, d, want)
+                unchanged()
+            elif op == "cg":
+                rtol = float(rng.choice([1e-6, 1e-10]))
+                max_iter = int(rng.choice([0, 2, 7, 100000]))
+                ce = int(rng.choice([1, 64]))
+                log.append(f"cg {rtol} {max_iter} {ce}")
+                call = lambda: v.solve_cg(rtol=rtol, max_iter=max_iter, check_every=ce)     # noqa: E731
+                if x is None or A is None:
+                    # (with neither, the header names no order of the two checks: either word)
+                    refused(call, "" if x is None and A is None else "field" if x is None else "system")
+                    continue
+                r = call()
+                got = v.get_field()
+                assert v.plan_value("cg_impl") == 5, (seed, log)
+                with pkg.Volume(nx, ny, nz) as f:
+                    f.assemble_from_D(D, CL, CR)
+                    f.set_field(x)
+                    rf = f.solve_cg(rtol=rtol, max_iter=max_iter, check_every=1 if ce == 64 else 64)
+                    assert (rf.iters, rf.rel_residual, rf.converged, rf.deff_raw) == (r.iters, r.rel_residual, r.converged, r.deff_raw), \
+                        (seed, log, r, rf)
+                    assert vm.same_bits(f.get_field(), got), (seed, log, "CG on a fresh volume")
+                    assert np.array_equal(rf.MFL, r.MFL) and np.array_equal(rf.MFR, r.MFR), (seed, log)
+                dec = vm.decoupled3(A, b).reshape(shape)
+                assert np.all(got[dec] == 0.0), (seed, log)
+                assert r.iters <= max_iter and r.converged == (r.rel_residual <= rtol), (seed, log, r)
+                res = vm.residual3(A, b, got, shape)
+                res_ld = vm.residual3(A, b, got, shape, np.longdouble)
+                print(f"seed {seed} {log[-1]}: iters {r.iters} rel_residual {r.rel_residual:.6e}, model {res:.6e}, long double {res_ld:.6e}")
+                if r.converged:
+                    assert res_ld <= rtol * (1 + 1e-6) + 1e-13, (seed, log, res_ld)
+                if not r.converged and res >= 1e-6:
+                    assert abs(r.rel_residual - res) <= RES_BAR * res, (seed, log, r.rel_residual, res)
+                else:
+                    # test_gpu_volume.py holds a converged field to 1e-3 of the long-double residual at rtol = 1e-13, where
+                    # that is 1e-16 absolute.  rel_residual is a float64 evaluation: its rounding error is absolute (it
+                    # does not shrink with the residual), and CG often lands far below a loose rtol, so the same 1e-16 is
+                    # what the bar means for residuals smaller than 1e-13 (seed 12002: 1.666e-15 against 1.654e-15).
+                    assert abs(r.rel_residual - res_ld) <= RES_BAR_CONVERGED * max(res_ld, 1e-13), (seed, log, r.rel_residual, res_ld)
+                x = got
+                d, MFL, MFR = v.flux()
+                assert r.deff_raw == d and np.array_equal(r.MFL, MFL) and np.array_equal(r.MFR, MFR), (seed, log)
+                log[-1] += " iters %d" % r.iters
+                unchanged()
+            else:
+                # something else on the device in between: a second Volume of another shape, or a 2-D Solver
+                if rng.random() < 0.5:
+                    ox, oy, oz = VOLUME_SHAPES[(VOLUME_SHAPES.index((nx, ny, nz)) + 1 + int(rng.integers(3))) % 4]
+                    log.append(f"other volume {ox} {oy} {oz}")
+                    with pkg.Volume(ox, oy, oz) as o:
+                        o.assemble_from_D(draw_D((oz, oy, ox)), 0.0, 1.0)
+                        o.init_linear(0.0, 1.0)
+                        o.solve_cg(rtol=1e-8, max_iter=200)
+                else:
+                    log.append("other solver")
+                    with pkg.Solver(33, 20) as o:
+                        o.set_tuning("cg_planes", 1)
+                        o.assemble_from_D(draw_D((20, 33)), 0.0, 1.0)
+                        o.init_linear(0.0, 1.0)
+                        o.solve_cg(rtol=1e-8, max_iter=200)
+                unchanged()
+        unchanged()
+    return log
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_random_call_sequences_on_volumes(pkg, seed):
+    run_volume_sequence(pkg, 12000 + seed)

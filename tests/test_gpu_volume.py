@@ -15,6 +15,8 @@ pytestmark = pytest.mark.gpu
 
 CL, CR = 0.25, 1.5
 EINVAL, ESTATE = -1, -5
+RES_BAR = 1e-9                 # rel_residual of a field that is not converged against numpy's float64 evaluation, relative
+RES_BAR_CONVERGED = 1e-3       # ... of a converged one against the long-double evaluation (the float64 one is rounding there)
 
 
 @pytest.fixture(scope="module")
@@ -140,7 +142,7 @@ def test_iterations_follow_the_models_cg(pkg, nx, ny, nz):
             xk = v.get_field()
             assert rk.iters == k and not rk.converged and v.plan_value("cg_impl") == 5
             res = vm.residual3(A, b, xk, D.shape)
-            assert abs(rk.rel_residual - res) <= 1e-9 * res, (rk.rel_residual, res)
+            assert abs(rk.rel_residual - res) <= RES_BAR * res, (rk.rel_residual, res)
             gap = rel_l2(xk, fld[k].astype(np.float64))
             bar = PARITY_M * max(g, 4 * EPS)
             print(f"k-parity ({nx},{ny},{nz}) k={k}: g(k) {g:.3e}  GPU gap {gap:.3e}  ratio {gap / max(g, 4 * EPS):.2f}")
@@ -172,7 +174,7 @@ def test_fixed_point_is_the_dense_solve(pkg, nx, ny, nz):
         assert np.all(x.ravel()[dec] == 0.0) and np.all(np.isfinite(x))
         # rel_residual is the returned field's, recomputed on the host in long double
         res = vm.residual3(A, b, x, shape, np.longdouble)
-        assert abs(r.rel_residual - res) <= 1e-3 * res, (r.rel_residual, res)
+        assert abs(r.rel_residual - res) <= RES_BAR_CONVERGED * res, (r.rel_residual, res)
         fields, k = vm.pcg(A, b, x0, shape, 1_000_000, np.float64, rtol=rtol)
         sel = ~dec
         d_ref = rel_l2(fields[k].ravel()[sel], xd[sel])
@@ -204,7 +206,7 @@ def test_stop_paths(pkg):
         assert r.iters == 0 and not r.converged and v.plan_value("cg_impl") == 5 and v.plan_value("cg_restarts") == 0
         assert np.array_equal(x[~dec], x0[~dec]) and np.all(x[dec] == 0.0) and dec.sum() > 0
         res = vm.residual3(A, b, x, D.shape)
-        assert abs(r.rel_residual - res) <= 1e-9 * res, (r.rel_residual, res)
+        assert abs(r.rel_residual - res) <= RES_BAR * res, (r.rel_residual, res)
         # rtol = 0: the stop test never holds, max_iter ends the call
         v.set_field(x0)
         r = v.solve_cg(rtol=0.0, max_iter=4)

@@ -13,7 +13,10 @@ below before the draw gained its later options), and the later groups -- the nat
 Deff gradient, the CG keys and the CG stream, the pre-scaled sweeps -- have a census of their own: every op, kind and key value
 they add, and the call orders they are there for.  Those three groups are pinned as well
 (tests/golden/sequence_draws_later_seeds.json, recorded before the draw gained `adjoint`, with the images and arguments of
-every stream in the digest and the log), and the field adjoint's group has its census at the end of this file."""
+every stream in the digest and the log), and the field adjoint's group has its census below; its draws are pinned too
+(tests/golden/sequence_draws_adjoint_seeds.json, recorded before the draw gained `tangent`, `second`, `fluxfield` and
+`onchip_planes`).  The group of those four options has its census at the end of this file, with a replay under a flipped rule that
+shows the validity checks bite."""
 import hashlib
 import json
 import os
@@ -577,3 +580,325 @@ def test_the_adjoint_seeds_reach_what_they_were_added_for(oracle):
     assert any(v["shape"][0] % 2 == 0 for v in c.values()) and any(v["shape"][0] % 2 == 1 for v in c.values())
     for nx, ny in seq.CGKEY_SHAPES:
         assert nx * ny <= 256 * 130, (nx, ny)
+
+
+def test_the_adjoint_seeds_draw_what_they_drew_before_the_second_order_options():
+    """ADJOINT_SEEDS, recorded (draw_log with every_array) before the draw gained `tangent`, `second`, `fluxfield` and
+    `onchip_planes`: with those off the generator is consumed as it was."""
+    with open(os.path.join(GOLDEN, "sequence_draws_adjoint_seeds.json")) as f:
+        recorded = json.load(f)
+    g = seq.ADJOINT_SEEDS
+    assert len(recorded) == g["count"] == 40
+    for seed in range(g["first"], g["first"] + g["count"]):
+        log, digest = draw_log(seed, every_array=True, **seq.seed_options(g))
+        assert "|".join(log) == recorded[str(seed)]["log"], seed
+        assert digest == recorded[str(seed)]["data"], seed
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The second-order group.  The five validity facts (lambda, the tangent's right-hand side and dx, dlambda's right-hand side and
+# dlambda) and the existence of flux maps are worked out here from deff_amd.h's lifetime rules alone, independently of the
+# draw's own bookkeeping; `predicted` is what the model of run_sequence() will expect of every call (accepted or refused).
+
+KEY_OPS = ("tune", "kernel")
+SIDE_SOLVES = ("adj", "tan", "atan")
+SO_INVALIDATORS = ("image", "native", "D/S", "stage", "stream", "cgstream")
+SO_KINDS = (["trhs", "trhs dD = D", "tan", "tan refused", "tan max_iter 0", "tan max_iter 3", "settan", "gettan", "gettan refused",
+             "hvp", "hvp refused", "hvp CR == CL", "arhs", "arhs refused", "atan", "atan refused", "atan max_iter 0", "atan max_iter 3",
+             "setatan", "getatan", "getatan refused", "fhvp", "fhvp refused", "ff", "ff image ok", "ff image EINVAL", "ff image ESTATE",
+             "ffptr", "ffptr refused", "flux_kt 0", "flux_kt 1", "flux_kt 2", "cg_onchip_planes 0", "cg_onchip_planes 1",
+             "side impl 3", "side impl 4", "side impl 3 under the key", "cg impl 4", "solve then trhs", "solve then ff"])
+SO_ORDERS = (["T1 tangent one image", "T1 tangent stack", "T1 second one image", "T1 second stack"]
+             + ["T2 " + k for k in SO_INVALIDATORS] + ["T2 tan without a right-hand side"]
+             + ["T3 getatan", "T3 fhvp", "T3 atan", "T3 dx stays"]
+             + ["T4 cgstream", "T4 tan on Sw", "T4 adj on Sw", "T4 hvp walls", "T4 ff on 3n"]
+             + ["T5 tan cgform cg gettan", "T5 cg tan cg"]
+             + ["T6 %s %s" % (a, b) for a in SIDE_SOLVES for b in SIDE_SOLVES if a != b]
+             + ["T7", "T8 resident trhs", "T8 resident ff", "T8 stack trhs", "T8 stack ff", "T9 image ff", "T9 2p D ff", "T9 3p 3n 3p ff",
+                "T10 eligible", "T10 ineligible", "T11 settan hvp", "T11 setatan fhvp", "T12 tan", "T12 atan"])
+# orders the weights cannot make common: held by a directed GPU test of test_gpu_sequences.py, by construction
+SO_DIRECTED = {"T9 3p 3n 3p ff": "test_the_image_forms_follow_the_assembly_sequence_and_a_new_image",
+               "T9 2p D ff": "test_the_image_forms_follow_the_assembly_sequence_and_a_new_image"}
+
+
+def second_order_census(oracle, lambda_keeps_dlambda=False):
+    """Per seed of SECOND_ORDER_SEEDS: `kinds` it draws (of SO_KINDS), `orders` it reaches (of SO_ORDERS) and `predicted`, the
+    (step, op, accepted) of every second-order call.  `lambda_keeps_dlambda` flips one rule of the model -- "a new lambda does
+    not invalidate dlambda" -- to show that the flag checks bite: the seeds on which `predicted` then differs are the ones
+    whose GPU run tells the two models apart."""
+    out = {}
+    g = seq.SECOND_ORDER_SEEDS
+    for i in range(g["count"]):
+        seed, options = g["first"] + i, seq.seed_options(g)
+        draw = seq.draw_sequence(seed, **options)
+        _, nx, ny, B, _ = next(draw)
+        pix = next(draw)[1]
+        eligible = (nx + (nx & 1)) * ny <= seq.ONCHIP_LIMIT
+        kinds, orders, predicted = set(), set(), []
+        kind, asm, nrows, prev_asm = None, None, None, None
+        keys = dict(cg_onchip=0, cg_planes=0, cg_fold=0, tb_impl=0, tb_launch=0, cg_onchip_planes=0, flux_kt=0)
+        kset, keys_at_sweeps = "auto", None
+        have_x = lam = tan_rhs = tan = atan_rhs = atan = ff_have = False
+        dx_src = dl_src = None                               # "set", "solve" or "partial": where the valid vector came from
+        lost_by = None                                       # the invalidator that took a valid dx or dlambda
+        t3 = False                                           # a new lambda took a valid dlambda; no new right-hand side yet
+        last_solve = None                                    # the last accepted side solve since an invalidator
+        rhs_key = {}                                         # "cg_onchip_planes" when the right-hand side of tan / atan was made
+        hist = []                                            # (op, accepted, keys set since the op before) of every op that is no key
+        since = set()
+
+        def rows():
+            nonlocal nrows
+            if nrows is None:
+                nrows = distinct_rows(oracle, pix, *asm)
+            return nrows
+
+        def invalidate(by):
+            nonlocal lam, tan_rhs, tan, atan_rhs, atan, lost_by, t3, last_solve, dx_src, dl_src
+            if tan or atan:
+                lost_by = by
+            lam = tan_rhs = tan = atan_rhs = atan = t3 = False
+            last_solve = dx_src = dl_src = None
+
+        def new_lambda():
+            nonlocal atan_rhs, atan, t3, dl_src
+            if lambda_keeps_dlambda:
+                return
+            t3 = t3 or atan
+            atan_rhs = atan = False
+            dl_src = None
+
+        def side_solved(which):
+            nonlocal last_solve
+            impl = 4 if keys["cg_onchip_planes"] == 1 and eligible else 3
+            kinds.add("side impl %d" % impl)
+            if impl == 3 and keys["cg_onchip_planes"] == 1:
+                kinds.add("side impl 3 under the key")
+            if last_solve is not None and last_solve != which:
+                orders.add("T6 %s %s" % (last_solve, which))
+            last_solve = which
+
+        for step, (op, *a) in enumerate(draw):
+            ok = True
+            if op == "tune":
+                if a[0] in keys:
+                    keys[a[0]] = a[1]
+                if a[0] in ("flux_kt", "cg_onchip_planes"):
+                    kinds.add(f"{a[0]} {a[1]}")
+                since.add(a[0])
+                continue
+            if op == "kernel":
+                kset = a[0]
+                continue
+            ops3 = [h[0] for h in hist[-3:]]
+            oks3 = all(h[1] for h in hist[-3:])
+            if op == "image":
+                pix, kind, prev_asm = a[0], None, None
+                invalidate("image")
+            elif op in ("assemble", "stage"):
+                if op == "stage":
+                    a = ["3n"] + a + [None]
+                invalidate("stage" if op == "stage" else "native" if a[0] in ("2p", "3p", "3n", "3g") else "D/S")
+                if a[0] in ("D", "S", "Sw"):
+                    kset = "auto"
+                prev_asm = (prev_asm or ()) + (a[0],)
+                kind, asm, nrows = a[0], (a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7] if len(a) > 7 else None), None
+            elif op in ("stream", "cgstream"):
+                ok = not (op == "cgstream" and a[2] < 0)
+                if ok:
+                    invalidate(op)
+                    kind, nrows, asm, have_x, prev_asm = "2p", 1, None, True, None
+                elif tan or atan:
+                    orders.add("T4 cgstream")
+            elif op in ("init", "set_field"):
+                have_x = True
+            elif op == "cg":
+                has_dict = kind in ("2p", "3n") or (kind != "Sw" and rows() <= 511)
+                ok = kind != "Sw" and (has_dict or keys["cg_planes"] > 0)
+                if ok:
+                    plane = keys["cg_planes"] == 2 or not has_dict
+                    if plane and keys["cg_onchip_planes"] == 1 and eligible:
+                        kinds.add("cg impl 4")
+                    if ops3[-2:] == ["cg", "tan"] and all(h[1] for h in hist[-2:]):
+                        orders.add("T5 cg tan cg")
+            elif op in ("sweeps", "solve"):
+                if op == "sweeps":
+                    keys_at_sweeps = (keys["tb_impl"], keys["tb_launch"])
+                else:
+                    resident = (keys["tb_impl"], keys["tb_launch"]) == (2, 0) and kset in ("auto", "matfree_tb") and kind != "Sw" \
+                        and keys_at_sweeps == (2, 0)
+                    if resident and len(hist) >= 2 and hist[-2][0] == "sweeps" and hist[-1][:2] in (("trhs", True), ("ff", True)):
+                        orders.add("T8 resident " + hist[-1][0])
+                    if a[3] == "vjp":
+                        assert lam, (seed, "the pass drawn as a reader without a valid lambda")
+                    if a[3] in ("trhs", "ff"):
+                        kinds.add("solve then " + a[3])
+                        if B >= 2:
+                            orders.add("T8 stack " + a[3])
+                        if a[3] == "trhs":
+                            tan_rhs, rhs_key["tan"] = True, keys["cg_onchip_planes"]
+                        else:
+                            ff_have = True
+            elif op == "adj":
+                ok = kind != "Sw"
+                if ok:
+                    lam = True
+                    new_lambda()
+                    side_solved("adj")
+                elif tan or atan:
+                    orders.add("T4 adj on Sw")
+            elif op == "setadj":
+                lam = True
+                new_lambda()
+            elif op == "vjp":
+                ok = lam and have_x
+            elif op == "trhs":
+                ok = have_x
+                if ok:
+                    tan_rhs, rhs_key["tan"] = True, keys["cg_onchip_planes"]
+                    if a[1] is None:
+                        kinds.add("trhs dD = D")
+            elif op == "arhs":
+                ok = lam
+                if ok:
+                    atan_rhs, atan, t3, dl_src, rhs_key["atan"] = True, False, False, None, keys["cg_onchip_planes"]
+            elif op in ("tan", "atan"):
+                rhs = tan_rhs if op == "tan" else atan_rhs
+                ok = kind not in (None, "Sw") and rhs
+                if ok:
+                    src = "partial" if a[1] in (0, 3) else "solve"
+                    if a[1] in (0, 3):
+                        kinds.add(f"{op} max_iter {a[1]}")
+                    if op == "tan":
+                        tan, dx_src = True, src
+                    else:
+                        atan, dl_src = True, src
+                    side_solved(op)
+                    if hist and hist[-1][:2] == ({"tan": "trhs", "atan": "arhs"}[op], True) and "cg_onchip_planes" in since \
+                            and rhs_key[op] != keys["cg_onchip_planes"]:
+                        orders.add("T10 eligible" if eligible else "T10 ineligible")
+                else:
+                    if kind == "Sw" and (tan or atan):
+                        orders.add("T4 tan on Sw")
+                    if not rhs and lost_by:
+                        orders.update(["T2 " + lost_by, "T2 tan without a right-hand side"] if op == "tan" else ["T2 " + lost_by])
+                    if op == "atan" and t3 and not rhs:
+                        orders.add("T3 atan")
+            elif op == "settan":
+                tan, dx_src = True, "set"
+            elif op == "setatan":
+                atan, dl_src, t3 = True, "set", False
+            elif op in ("gettan", "getatan"):
+                ok = tan if op == "gettan" else atan
+                if not ok and lost_by:
+                    orders.add("T2 " + lost_by)
+                if op == "getatan" and not ok and t3:
+                    orders.add("T3 getatan")
+                if op == "gettan" and ok and t3:
+                    orders.add("T3 dx stays")
+                if op == "gettan" and ok and ops3[-2:] == ["tan", "cg"] and all(h[1] for h in hist[-2:]) \
+                        and {"cg_onchip", "cg_planes", "cg_fold"} <= hist[-1][2]:
+                    orders.add("T5 tan cgform cg gettan")
+            elif op == "hvp":
+                ok = have_x and tan and a[2] != a[3]
+                if a[2] == a[3]:
+                    kinds.add("hvp CR == CL")
+                    if have_x and tan:
+                        orders.add("T4 hvp walls")
+                if not tan and lost_by:
+                    orders.add("T2 " + lost_by)
+                if ok and ops3 == ["trhs", "tan", "gettan"] and oks3:
+                    orders.add("T1 tangent " + ("one image" if B == 1 else "stack"))
+                if ok and dx_src == "set":
+                    orders.add("T11 settan hvp")
+                if ok and dx_src == "partial":
+                    orders.add("T12 tan")
+            elif op == "fhvp":
+                ok = have_x and lam and tan and atan
+                if not ok and lost_by and not (tan and atan):
+                    orders.add("T2 " + lost_by)
+                if not atan and t3:
+                    orders.add("T3 fhvp")
+                if ok and ops3 == ["adj", "arhs", "atan"] and oks3:
+                    orders.add("T1 second " + ("one image" if B == 1 else "stack"))
+                if ok and dl_src == "set":
+                    orders.add("T11 setatan fhvp")
+                if ok and dx_src == "partial":
+                    orders.add("T12 tan")
+                if ok and dl_src == "partial":
+                    orders.add("T12 atan")
+            elif op == "ff":
+                ok = have_x
+                if ok:
+                    ff_have = True
+                    form = "ok" if kind in ("2p", "3p") else "EINVAL" if kind in ("3n", "3g") else "ESTATE"
+                    kinds.add("ff image " + form)
+                    if kind == "3n" and (tan or atan):
+                        orders.add("T4 ff on 3n")
+                    if kind is None and hist and hist[-1][0] == "image":
+                        orders.add("T9 image ff")
+                    if kind == "D" and prev_asm and prev_asm[-2:] == ("2p", "D"):
+                        orders.add("T9 2p D ff")
+                    if kind == "3p" and prev_asm and prev_asm[-3:] == ("3p", "3n", "3p"):
+                        orders.add("T9 3p 3n 3p ff")
+            elif op == "ffptr":
+                ok = ff_have
+            if op in ("trhs", "tan", "settan", "gettan", "hvp", "arhs", "atan", "setatan", "getatan", "fhvp", "ff", "ffptr"):
+                kinds.add(op if ok else op + " refused")
+                predicted.append((step, op, bool(ok)))
+            if ok and op in seq.PASSES and len(hist) >= 2 and all(h[1] and h[0] in seq.PASSES for h in hist[-2:]) \
+                    and len({op, hist[-1][0], hist[-2][0]}) == 3:
+                orders.add("T7")
+            if lost_by and op in ("tan", "settan", "atan", "setatan") and ok:
+                lost_by = None
+            hist.append((op, bool(ok), since))
+            since = set()
+        out[seed] = dict(kinds=kinds, orders=orders, predicted=predicted, shape=(nx, ny), B=B)
+    return out
+
+
+def test_the_second_order_seeds_reach_what_they_were_added_for(oracle):
+    """Every kind of SO_KINDS is drawn and every order of SO_ORDERS is reached by at least one seed of SECOND_ORDER_SEEDS, or is
+    held by the directed GPU test SO_DIRECTED names:
+    T1   trhs, tan, gettan, hvp in a row, and adj, arhs, atan, fhvp, all accepted; on one image and on a stack
+    T2   a valid dx or dlambda, an invalidator (counted per kind), then a getter, a pass or a side solve refused for it
+    T3   a new lambda (adj, setadj) while dlambda is valid: getatan, fhvp and atan refused, gettan still accepted
+    T4   a refused call while dx or dlambda is valid: a CG stream with Df = -1, tan or adj on wall-column links, hvp with
+         CR == CL, the image form of ff on a native 3-phase system
+    T5   tan, the keys of a CG form, cg, gettan in a row; cg, tan, cg in a row
+    T6   adj, tan and atan as consecutive accepted side solves on one system, in every order of two
+    T7   three different accepted passes in a row (the shared upload scratch of two planes)
+    T8   sweeps, trhs or ff, a solve in a row on resident workgroup tiles; a stack's solve whose first reader is trhs or ff
+    T9   ff right after a new image; ff on a caller's plane assembled after "2p"; ff after "3p", "3n", "3p"
+    T10  "cg_onchip_planes" changed between a right-hand side and its solve, on a shape that fits one compute unit and on one
+         that does not
+    T11  hvp with a caller's dx, fhvp with a caller's dlambda
+    T12  a pass that uses the partial vector of a side solve stopped by max_iter 0 or 3."""
+    c = second_order_census(oracle)
+    drawn = {k: sum(1 for v in c.values() if k in v["kinds"]) for k in SO_KINDS}
+    reached = {k: sum(1 for v in c.values() if k in v["orders"]) for k in SO_ORDERS}
+    print(f"second order: seeds that draw {drawn}; seeds that reach the orders {reached}")
+    assert all(n >= 1 for n in drawn.values()), {k: n for k, n in drawn.items() if n < 1}
+    missing = [k for k, n in reached.items() if n < 1 and k not in SO_DIRECTED]
+    assert not missing, (missing, reached)
+    assert all(callable(getattr(seq, name)) for name in SO_DIRECTED.values())
+    assert any(v["shape"][0] % 2 == 0 for v in c.values()) and any(v["shape"][0] % 2 == 1 for v in c.values())
+    assert {v["B"] for v in c.values()} == {1, 2, 3}
+
+
+# the seeds whose predictions change when the model is told that a new lambda leaves dlambda valid
+FLIPPED_SEEDS = [11008, 11011, 11021, 11026, 11030, 11041]
+
+
+def test_the_validity_checks_bite(oracle):
+    """Without touching the library: a model with one rule flipped -- "a new lambda does not invalidate dlambda" -- predicts
+    other outcomes (getatan, atan and fhvp accepted where deff_amd.h refuses them) on the seeds of FLIPPED_SEEDS, so a library
+    that forgot that rule would fail there, and the library as it is would fail the flipped model."""
+    right, flipped = second_order_census(oracle), second_order_census(oracle, lambda_keeps_dlambda=True)
+    differ = sorted(seed for seed in right if right[seed]["predicted"] != flipped[seed]["predicted"])
+    print(f"seeds that tell the two models apart: {differ}")
+    for seed in differ:
+        a, b = right[seed]["predicted"], flipped[seed]["predicted"]
+        first = next(u for u, v in zip(a, b) if u != v)
+        assert first[1] in ("getatan", "atan", "fhvp") and not first[2], (seed, first)
+    assert differ == FLIPPED_SEEDS, differ
