@@ -6,8 +6,8 @@
 // deff_solve, in far fewer iterations.  Nothing of the Jacobi path is touched: its tables (lut, c0 plane), plans and knobs
 // stay as they are (the "fma" knob does not apply here: CG's arithmetic is written-order FP64 only).
 // The launches of one iteration, in every form and under every fold key, are CgIteration::enqueue's, for both solves.
-// deff_solve_adjoint (A lambda = w for the gradient of a loss on the field, api_vjp.hip) and deff_solve_tangent (A dx = r for
-// the field's derivative along a direction, api_tangent.hip) run deff_solve_cg's host loop,
+// deff_solve_adjoint (A lambda = w for the gradient of a loss on the field) and deff_solve_tangent (A dx = r for
+// the field's derivative along a direction; both read by the passes of api_facepass.hip) run deff_solve_cg's host loop,
 // cg_host_loop, on the coefficient planes with its own solution and right-hand side buffers.  Under the tuning key
 // "cg_onchip_planes" every solve on the planes iterates small images on one compute unit each (kernels_cg_image_planes.hpp).
 // A volume (api_volume.hip) is the plane form on one tall image plus the z links: its kernels (kernels_cg_volume.hpp) are
@@ -402,15 +402,15 @@ int volume_solve_cg(deff_ctx *c, const double *aB, const double *aF, int ny, dou
     return DEFF_OK;
 }
 
-// ---- deff_solve_adjoint, deff_solve_tangent -----------------------------------------------------------------------------
+// ---- deff_solve_adjoint, deff_solve_tangent, deff_solve_adjoint_tangent -----------------------------------------------------
 //
 // A lambda = w on the current matrix (symmetric: the adjoint system of A x = b is the same A), for the gradient of a loss on
-// the field (api_vjp.hip), and A dx = r on it for the field's derivative along a direction of D (api_tangent.hip).  The plane
-// form of deff_solve_cg with two pointers changed: the solution is adj_lam (tan_dx) instead of the field, the right-hand side
-// adj_w (tan_w) -- w (r), zeroed where the FORWARD system's row is decoupled: cg_inv == 0 -- instead of the b plane.  cg_inv
-// and the admissibility verdict are k_cgp_prepare's on the forward planes, b included.  Nothing the forward solve or the Jacobi
-// path reads is written.  The two entry points differ in where the right-hand side comes from (the host; the last
-// deff_tangent_rhs_D's map on the device) and in the buffers.
+// the field, A dx = r on it for the field's derivative along a direction of D, and A dlambda = q for lambda's (the passes that
+// read and feed them: api_facepass.hip).  The plane form of deff_solve_cg with two pointers changed: the solution is the side
+// vector's x (SideVec, ctx.hpp) instead of the field, the right-hand side its rhs -- w (r, q), zeroed where the FORWARD
+// system's row is decoupled: cg_inv == 0 -- instead of the b plane.  cg_inv and the admissibility verdict are k_cgp_prepare's
+// on the forward planes, b included.  Nothing the forward solve or the Jacobi path reads is written.  The entry points differ
+// in the vector and in where the right-hand side comes from (the host; the last map of a pass, on the device).
 
 // the arguments and the context's form: before any device work
 static int side_solve_args(deff_ctx *c, const char *who, double rtol, int64_t max_iter, int64_t check_every)
@@ -418,7 +418,7 @@ static int side_solve_args(deff_ctx *c, const char *who, double rtol, int64_t ma
     if (!(rtol >= 0.0) || !std::isfinite(rtol)) return fail(DEFF_EINVAL, "%s: rtol must be finite and >= 0", who);
     if (max_iter < 0) return fail(DEFF_EINVAL, "%s: negative max_iter", who);
     if (check_every < 1) return fail(DEFF_EINVAL, "check_every must be >= 1");
-    if (c->slab) return fail(DEFF_EINVAL, "%s: not for row-slab contexts (the rows of the image live on several devices)", who);
+    TRY(slab_refused(c, who));
     if (c->wrap_links)
         return fail(DEFF_EINVAL, "%s: the system links a wall column to the neighbouring row (explicit-only system)", who);
     if (!c->have_explicit && !c->have_matfree) return fail(DEFF_ESTATE, "no system assembled");
@@ -484,66 +484,54 @@ static int side_solve_run(deff_ctx *c, double *x, double *rhs, const CgGeom &g, 
     return DEFF_OK;
 }
 
+// One side solve into `v`: the right-hand side is the caller's plane `host_rhs` (true width), or -- host_rhs NULL -- the last map
+// of pass `rhs_map`, copied on the device (the map itself stays as it was: the mask is applied to the copy), which has to have
+// been computed for what `v` depends on (`no_rhs` otherwise).  With the same numbers in the right-hand side the three entry
+// points below run the same arithmetic, bit for bit.
+static int side_solve(deff_ctx *c, const char *who, SideVec &v, const double *host_rhs, const CellPass *rhs_map, const char *no_rhs,
+                      double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out)
+{
+    TRY(side_solve_args(c, who, rtol, max_iter, check_every));
+    if (!host_rhs && (!rhs_map->have || !v.rhs_ok)) return fail(DEFF_ESTATE, "%s: %s", who, no_rhs);
+    CgGeom g;
+    TRY(side_solve_prepare(c, who, &g));
+    TRY(dev_alloc(&v.x, c->n));
+    TRY(dev_alloc(&v.rhs, c->n));
+    v.valid = false;                                                 // from here on the solution is the new call's
+    if (&v == &c->adj) adjoint_tangent_reset(c);                     // ... and dlambda belonged to the old lambda
+    if (host_rhs)
+        TRY(plane_h2d(c, v.rhs, host_rhs));
+    else
+        HIP_TRY(hipMemcpyAsync(v.rhs, rhs_map->map, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
+    TRY(side_solve_run(c, v.x, v.rhs, g, rtol, max_iter, check_every, out));
+    v.valid = true;
+    return DEFF_OK;
+}
+
 extern "C" int deff_solve_adjoint(deff_ctx *c, const double *w, double rtol, int64_t max_iter, int64_t check_every,
                                   deff_cg_result *out)
 try {
     if (!c || !w || !out) return fail(DEFF_EINVAL, "NULL argument");
-    TRY(side_solve_args(c, "deff_solve_adjoint", rtol, max_iter, check_every));
-    CgGeom g;
-    TRY(side_solve_prepare(c, "deff_solve_adjoint", &g));
-    TRY(dev_alloc(&c->adj_lam, c->n));
-    TRY(dev_alloc(&c->adj_w, c->n));
-    // from here on lambda is the new call's, and dlambda (api_fhvp.hip) belonged to the old one
-    c->adj_valid = false;
-    adjoint_tangent_reset(c);
-    if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(c->adj_w, 0, sizeof(double) * c->n, c->stream));
-    TRY(rows_h2d(c, c->adj_w, w, (size_t)c->rows));
-    TRY(side_solve_run(c, c->adj_lam, c->adj_w, g, rtol, max_iter, check_every, out));
-    c->adj_valid = true;
-    return DEFF_OK;
+    return side_solve(c, "deff_solve_adjoint", c->adj, w, nullptr, nullptr, rtol, max_iter, check_every, out);
 }
 DEFF_API_CATCH
 
-// The right-hand side is the last deff_tangent_rhs_D's map, copied on the device into tan_w (the map itself stays as it was:
-// the mask is applied to the copy).  With the same numbers in w this is deff_solve_adjoint's arithmetic, bit for bit.
+// A dx = r', r the last deff_tangent_rhs_D's map.
 extern "C" int deff_solve_tangent(deff_ctx *c, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out)
 try {
     if (!c || !out) return fail(DEFF_EINVAL, "NULL argument");
-    TRY(side_solve_args(c, "deff_solve_tangent", rtol, max_iter, check_every));
-    if (!c->pass_tan.have || !c->tan_rhs)
-        return fail(DEFF_ESTATE, "deff_solve_tangent: no right-hand side for the current system (deff_tangent_rhs_D)");
-    CgGeom g;
-    TRY(side_solve_prepare(c, "deff_solve_tangent", &g));
-    TRY(dev_alloc(&c->tan_dx, c->n));
-    TRY(dev_alloc(&c->tan_w, c->n));
-    // from here on dx is the new call's
-    c->tan_valid = false;
-    HIP_TRY(hipMemcpyAsync(c->tan_w, c->pass_tan.map, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
-    TRY(side_solve_run(c, c->tan_dx, c->tan_w, g, rtol, max_iter, check_every, out));
-    c->tan_valid = true;
-    return DEFF_OK;
+    return side_solve(c, "deff_solve_tangent", c->tan, nullptr, &c->pass_tan,
+                      "no right-hand side for the current system (deff_tangent_rhs_D)", rtol, max_iter, check_every, out);
 }
 DEFF_API_CATCH
 
-// A dlambda = q' for the second-order field adjoint (api_fhvp.hip): deff_solve_tangent with the last
-// deff_adjoint_tangent_rhs_D's map as the right-hand side, copied into adj_dw, and adj_dl as the solution.
+// A dlambda = q' for the second-order field adjoint, q the last deff_adjoint_tangent_rhs_D's map.
 extern "C" int deff_solve_adjoint_tangent(deff_ctx *c, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out)
 try {
     if (!c || !out) return fail(DEFF_EINVAL, "NULL argument");
-    TRY(side_solve_args(c, "deff_solve_adjoint_tangent", rtol, max_iter, check_every));
-    if (!c->pass_atan.have || !c->atan_rhs)
-        return fail(DEFF_ESTATE, "deff_solve_adjoint_tangent: no right-hand side for the current system and adjoint field "
-                                 "(deff_adjoint_tangent_rhs_D)");
-    CgGeom g;
-    TRY(side_solve_prepare(c, "deff_solve_adjoint_tangent", &g));
-    TRY(dev_alloc(&c->adj_dl, c->n));
-    TRY(dev_alloc(&c->adj_dw, c->n));
-    // from here on dlambda is the new call's
-    c->atan_valid = false;
-    HIP_TRY(hipMemcpyAsync(c->adj_dw, c->pass_atan.map, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
-    TRY(side_solve_run(c, c->adj_dl, c->adj_dw, g, rtol, max_iter, check_every, out));
-    c->atan_valid = true;
-    return DEFF_OK;
+    return side_solve(c, "deff_solve_adjoint_tangent", c->atan, nullptr, &c->pass_atan,
+                      "no right-hand side for the current system and adjoint field (deff_adjoint_tangent_rhs_D)", rtol, max_iter,
+                      check_every, out);
 }
 DEFF_API_CATCH
 

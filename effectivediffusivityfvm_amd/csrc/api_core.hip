@@ -142,12 +142,9 @@ try {
     for (hipEvent_t e : c->cgs_ev) if (e) (void)hipEventDestroy(e);
     for (CellPass *p : {&c->pass_res, &c->pass_sens, &c->pass_vjp, &c->pass_tan, &c->pass_hvp, &c->pass_atan, &c->pass_fhvp}) cell_pass_free(*p);
     flux_pass_free(c->pass_flux);
-    if (c->adj_lam) (void)hipFree(c->adj_lam);
-    if (c->adj_w) (void)hipFree(c->adj_w);
-    if (c->tan_dx) (void)hipFree(c->tan_dx);
-    if (c->tan_w) (void)hipFree(c->tan_w);
-    if (c->adj_dl) (void)hipFree(c->adj_dl);
-    if (c->adj_dw) (void)hipFree(c->adj_dw);
+    for (SideVec *v : {&c->adj, &c->tan, &c->atan})
+        for (double *d : {v->x, v->rhs})
+            if (d) (void)hipFree(d);
     if (c->q_host) (void)hipHostFree(c->q_host);
     if (c->chain_counted) resident_chain_ctx_destroyed(c->device);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

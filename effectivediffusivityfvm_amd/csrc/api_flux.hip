@@ -26,7 +26,7 @@ __global__ __launch_bounds__(256) void k_flux_sections(const double *__restrict_
 // Everything that can refuse the call, before anything is touched.
 static int flux_common(deff_ctx *c, const char *who)
 {
-    if (c->slab) return fail(DEFF_EINVAL, "%s: not for row-slab contexts (the rows of the image live on several devices)", who);
+    TRY(slab_refused(c, who));
     if (!c->have_field) return fail(DEFF_ESTATE, "no field");
     TRY(use_device(c));
     return DEFF_OK;
@@ -41,11 +41,7 @@ static int flux_launch(deff_ctx *c, const double *dD, double CL, double CR, doub
     if ((it.items + 3) / 4 > 0x7fffffffu) return fail(DEFF_EINVAL, "deff_flux_field: too many work items");
     const size_t nq = (size_t)c->nimg * ((size_t)c->nxt + 1), chunks = (size_t)c->nimg * it.cpi;
     TRY(flux_pass_room(c, p, chunks));
-    if (ms) {
-        if (!p.ev0) HIP_TRY(hipEventCreate(&p.ev0));
-        if (!p.ev1) HIP_TRY(hipEventCreate(&p.ev1));
-        HIP_TRY(hipEventRecord(p.ev0, c->stream));
-    }
+    TRY(cell_pass_start(c, p, ms));
     const FluxGeom g{c->dx, c->dy, c->dx / 2, c->dy / 2};
     hipLaunchKernelGGL(k_flux, dim3((unsigned)((it.items + 3) / 4)), dim3(256), 0, c->stream, c->x[c->cur], dD, c->nx, c->nxt,
                        c->ny, c->nimg, it.ntx, it.cpi, it.kt, g, CL, CR, p.fx, p.fy, p.left, p.colpart, p.wallpart);
@@ -53,16 +49,12 @@ static int flux_launch(deff_ctx *c, const double *dD, double CL, double CR, doub
     hipLaunchKernelGGL(k_flux_sections, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, c->stream, p.colpart, p.wallpart, c->nx,
                        c->nxt, c->nimg, it.cpi, p.Q);
     HIP_TRY(hipGetLastError());
-    if (ms) HIP_TRY(hipEventRecord(p.ev1, c->stream));
-    p.have = true;
-    p.plan_kt = it.kt; p.plan_items = (int)it.per_img;           // deff_get_plan "flux_kt" / "flux_items": what was launched
+    TRY(cell_pass_launched(c, p, it, true, ms));
     if (fx) TRY(rows_d2h(c, fx, (const double *)p.fx, (size_t)c->rows));
     if (fy) TRY(rows_d2h(c, fy, (const double *)p.fy, (size_t)c->rows));
     if (left) HIP_TRY(hipMemcpyAsync(left, p.left, sizeof(double) * c->rows, hipMemcpyDeviceToHost, c->stream));
     if (sections) HIP_TRY(hipMemcpyAsync(sections, p.Q, sizeof(double) * nq, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, p.ev0, p.ev1));
-    return DEFF_OK;
+    return cell_pass_wait(c, p, ms);
 }
 
 extern "C" int deff_flux_field_D(deff_ctx *c, const double *D, double CL, double CR, double *fx, double *fy, double *left,
@@ -81,24 +73,12 @@ DEFF_API_CATCH
 extern "C" int deff_flux_field(deff_ctx *c, double *fx, double *fy, double *left, double *sections, float *ms)
 try {
     if (!c) return fail(DEFF_EINVAL, "ctx is NULL");
-    if (c->slab) return fail(DEFF_EINVAL, "deff_flux_field: not for row-slab contexts (the rows of the image live on several devices)");
-    if (!c->phase_mode || !c->have_image)
-        return fail(DEFF_ESTATE, "deff_flux_field needs a system assembled from the image (deff_assemble_2phase / _3phase); "
-                                 "pass the diffusivities to deff_flux_field_D() otherwise");
-    if (c->native3 || (c->phase_mode == 3 && c->grid_given))
-        return fail(DEFF_EINVAL, "deff_flux_field: the system was assembled with a Grid (identity rows of the flood fill): "
-                                 "its fluxes are not a function of the phase diffusivities alone");
-    TRY(flux_common(c, "deff_flux_field"));
-    TRY(consolidate(c));
-    TRY(ensure_scratch(c, sizeof(double) * c->n));
-    double *dD = (double *)c->scratch;
-    if (c->phase_mode == 2)
-        hipLaunchKernelGGL(k_fill_D_2phase, dim3(grid_for(c->n)), dim3(256), 0, c->stream, c->pix, c->W, c->ampX, c->ampY, c->nx,
-                           c->nxt, c->ny, c->rows, c->phase_D[0], c->phase_D[1], dD);
-    else
-        hipLaunchKernelGGL(k_fill_D_3phase, dim3(grid_for(c->n)), dim3(256), 0, c->stream, c->pix, c->W, c->ampX, c->ampY, c->nx,
-                           c->nxt, c->ny, c->rows, c->phase_D[0], c->phase_D[1], c->phase_D[2], dD);
-    HIP_TRY(hipGetLastError());
+    TRY(slab_refused(c, "deff_flux_field"));
+    const double *dD;
+    TRY(image_D_plane(c, "deff_flux_field", "its fluxes are", [c] {
+        TRY(flux_common(c, "deff_flux_field"));
+        return consolidate(c);
+    }, &dD));
     return flux_launch(c, dD, c->CL, c->CR, fx, fy, left, sections, ms);
 }
 DEFF_API_CATCH

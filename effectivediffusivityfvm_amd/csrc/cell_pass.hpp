@@ -1,9 +1,8 @@
-// cell_pass.hpp -- the host path of a pass over the cells of the current field that ends in one sum per image: the residual
-// (api_residual.hip), the Deff gradient (api_sens.hip), the field adjoint's pass (api_vjp.hip), the field tangent's
-// (api_tangent.hip), the Deff Hessian-vector product's (api_hvp.hip) and the field adjoint's second-order passes
-// (api_fhvp.hip).  Each entry point keeps its
-// own refusals and its own kernel launch; what is here is what they did alike: the work-item planner, the buffers, the call's
-// own event pair, the final sum and the copies out, the upload of a caller's D plane, and the device-map getter.
+// cell_pass.hpp -- the host path of a pass over the cells of the current field: the residual (api_residual.hip), the five face
+// passes that end in one sum per image (api_facepass.hip) and the flux field (api_flux.hip).  Each entry point keeps its own
+// refusals and its own kernel launch; what is here is what they do alike: the work-item planner, the buffers, the call's own
+// event pair and plan keys, the final sum and the copies out, the D plane on the device -- a caller's, or the assembled
+// image's -- and the device-map getter.
 #pragma once
 #include "ctx.hpp"
 
@@ -47,12 +46,29 @@ static inline int cell_pass_room(deff_ctx *c, CellPass &p, bool with_map, size_t
 }
 
 // Opens the timed window of a call that asked for `ms`.
-static inline int cell_pass_start(deff_ctx *c, CellPass &p, const float *ms)
+static inline int cell_pass_start(deff_ctx *c, PassPlan &p, const float *ms)
 {
     if (!ms) return DEFF_OK;
     if (!p.ev0) HIP_TRY(hipEventCreate(&p.ev0));
     if (!p.ev1) HIP_TRY(hipEventCreate(&p.ev1));
     HIP_TRY(hipEventRecord(p.ev0, c->stream));
+    return DEFF_OK;
+}
+
+// After a pass's last kernel: the end of the timed window, and what deff_get_plan reports of the launch.
+static inline int cell_pass_launched(deff_ctx *c, PassPlan &p, const CellItems &it, bool have, const float *ms)
+{
+    if (ms) HIP_TRY(hipEventRecord(p.ev1, c->stream));
+    p.have = have;
+    p.plan_kt = it.kt; p.plan_items = (int)it.per_img;           // deff_get_plan "*_kt" / "*_items": what was launched
+    return DEFF_OK;
+}
+
+// After the copies out were enqueued: waits for them, and reads the window's time.
+static inline int cell_pass_wait(deff_ctx *c, PassPlan &p, float *ms)
+{
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, p.ev0, p.ev1));
     return DEFF_OK;
 }
 
@@ -64,14 +80,10 @@ static inline int cell_pass_finish(deff_ctx *c, CellPass &p, void (*final_kernel
     double *out = p.part + it.items;
     hipLaunchKernelGGL(final_kernel, dim3(it.nimg), dim3(1024), 0, c->stream, p.part, it.per_img, out);
     HIP_TRY(hipGetLastError());
-    if (ms) HIP_TRY(hipEventRecord(p.ev1, c->stream));
-    p.have = p.map != nullptr;
-    p.plan_kt = it.kt; p.plan_items = (int)it.per_img;           // deff_get_plan "*_kt" / "*_items": what was launched
+    TRY(cell_pass_launched(c, p, it, p.map != nullptr, ms));
     if (map) TRY(rows_d2h(c, map, (const double *)p.map, (size_t)c->rows));
     if (sums) HIP_TRY(hipMemcpyAsync(sums, out, sizeof(double) * it.nimg, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, p.ev0, p.ev1));
-    return DEFF_OK;
+    return cell_pass_wait(c, p, ms);
 }
 
 // A caller's D plane (true width) in the shared upload scratch: pitch nx, pad column 0.  A pass that uploads `slots` planes
@@ -80,13 +92,38 @@ static inline int cell_pass_upload_D(deff_ctx *c, const double *D, const double 
 {
     TRY(ensure_scratch(c, sizeof(double) * c->n * slots));
     double *d = (double *)c->scratch + (size_t)slot * c->n;
-    if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(d, 0, sizeof(double) * c->n, c->stream));
-    TRY(rows_h2d(c, d, D, (size_t)c->rows));
+    TRY(plane_h2d(c, d, D));
     *dD = d;
     return DEFF_OK;
 }
 
-// deff_device_sensitivity / deff_device_field_vjp: the last map of pass `which`, or `none` as the message of DEFF_ESTATE.
+// The D plane of the system assembled from the image, in the shared upload scratch (pitch nx, pad column 0), for `who` =
+// deff_sensitivity / deff_flux_field: is there such a plane? -- `what` completes the second refusal ("its Deff is", "its fluxes
+// are") --, then `ready()`, the entry point's own refusals and its consolidate, which come between, then the fill from the pixels.
+template <typename Ready>
+static inline int image_D_plane(deff_ctx *c, const char *who, const char *what, Ready ready, const double **dD)
+{
+    if (!c->phase_mode || !c->have_image)
+        return fail(DEFF_ESTATE, "%s needs a system assembled from the image (deff_assemble_2phase / _3phase); "
+                                 "pass the diffusivities to %s_D() otherwise", who, who);
+    if (c->native3 || (c->phase_mode == 3 && c->grid_given))
+        return fail(DEFF_EINVAL, "%s: the system was assembled with a Grid (identity rows of the flood fill): "
+                                 "%s not a function of the phase diffusivities alone", who, what);
+    TRY(ready());
+    TRY(ensure_scratch(c, sizeof(double) * c->n));
+    double *d = (double *)c->scratch;
+    if (c->phase_mode == 2)
+        hipLaunchKernelGGL(k_fill_D_2phase, dim3(grid_for(c->n)), dim3(256), 0, c->stream, c->pix, c->W, c->ampX, c->ampY, c->nx,
+                           c->nxt, c->ny, c->rows, c->phase_D[0], c->phase_D[1], d);
+    else
+        hipLaunchKernelGGL(k_fill_D_3phase, dim3(grid_for(c->n)), dim3(256), 0, c->stream, c->pix, c->W, c->ampX, c->ampY, c->nx,
+                           c->nxt, c->ny, c->rows, c->phase_D[0], c->phase_D[1], c->phase_D[2], d);
+    HIP_TRY(hipGetLastError());
+    *dD = d;
+    return DEFF_OK;
+}
+
+// deff_device_sensitivity and the four like it: the last map of pass `which`, or `none` as the message of DEFF_ESTATE.
 static inline int cell_pass_device_map(deff_ctx *c, CellPass deff_ctx::*which, void **d_g, size_t *row_pitch_bytes, const char *none)
 {
     if (!c || !d_g) return fail(DEFF_EINVAL, "NULL argument");
@@ -96,12 +133,17 @@ static inline int cell_pass_device_map(deff_ctx *c, CellPass deff_ctx::*which, v
     return DEFF_OK;
 }
 
+static inline void pass_plan_free(PassPlan &p)
+{
+    if (p.ev0) (void)hipEventDestroy(p.ev0);
+    if (p.ev1) (void)hipEventDestroy(p.ev1);
+}
+
 static inline void cell_pass_free(CellPass &p)
 {
     if (p.map) (void)hipFree(p.map);
     if (p.part) (void)hipFree(p.part);
-    if (p.ev0) (void)hipEventDestroy(p.ev0);
-    if (p.ev1) (void)hipEventDestroy(p.ev1);
+    pass_plan_free(p);
 }
 
 // The flux field's buffers (api_flux.hip): the two maps, the left wall's rows, the section sums, and room for `chunks` work
@@ -127,6 +169,5 @@ static inline void flux_pass_free(FluxPass &p)
 {
     for (double *d : {p.fx, p.fy, p.left, p.colpart, p.wallpart, p.Q})
         if (d) (void)hipFree(d);
-    if (p.ev0) (void)hipEventDestroy(p.ev0);
-    if (p.ev1) (void)hipEventDestroy(p.ev1);
+    pass_plan_free(p);
 }

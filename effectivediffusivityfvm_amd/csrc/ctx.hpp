@@ -12,21 +12,18 @@
 //   api_cg.hip     conjugate gradients to a residual tolerance (deff_solve_cg) and through refilled slots (deff_solve_cg_stream);
 //                  every CG kernel, the slab forms included: their launches for one slab (cg_slab.hpp)
 //   api_residual.hip  the reference's Residual() of the current field (deff_residual, deff_residual_slot, deff_residual_D)
-//   api_sens.hip   the Deff gradient dDeff/dD per cell and its Euler sum (deff_sensitivity, deff_sensitivity_D)
-//   api_vjp.hip    the field adjoint: lambda's buffer (deff_set_adjoint, deff_get_adjoint, deff_device_adjoint) and the pass
-//                  (x, lambda, D) -> dL/dD (deff_field_vjp_D); deff_solve_adjoint itself is in api_cg.hip, beside the loop it runs
-//   api_tangent.hip  the field tangent: the pass (x, D, dD) -> r = db - dA x (deff_tangent_rhs_D) and dx's buffer
-//                  (deff_get_tangent, deff_device_tangent); deff_solve_tangent is in api_cg.hip, beside deff_solve_adjoint
-//   api_hvp.hip    the Deff Hessian-vector product: the pass (x, dx, dD, D) -> H dD (deff_sensitivity_hvp_D) and a caller's
-//                  own tangent (deff_set_tangent)
-//   api_fhvp.hip   the field adjoint's second order: dlambda's buffer and setter (its right-hand side, deff_adjoint_tangent_rhs_D,
-//                  is k_tan on lambda, in api_tangent.hip; deff_solve_adjoint_tangent is in api_cg.hip) and the pass
-//                  (x, lambda, dx, dlambda, dD, D) -> S_w dD (deff_field_vjp_hvp_D)
+//   api_facepass.hip  the five passes that are one walk over the faces (kernels_facepass.hpp) and the three side vectors they read:
+//                  the Deff gradient (deff_sensitivity, deff_sensitivity_D), the field adjoint's (x, lambda, D) -> dL/dD
+//                  (deff_field_vjp_D), the field tangent's right-hand side (deff_tangent_rhs_D) and lambda's own
+//                  (deff_adjoint_tangent_rhs_D: k_tan on lambda), the Deff Hessian-vector product (deff_sensitivity_hvp_D), the
+//                  field adjoint's second order (deff_field_vjp_hvp_D); one host path (face_pass_run) and one final kernel for
+//                  the five; set / get / device pointer of lambda, dx and dlambda (SideVec below).  The solves that compute
+//                  the three vectors are in api_cg.hip, beside the loop they run
 //   api_flux.hip   the flux field: the pass (x, D) -> fx, fy, left and the section sums (deff_flux_field, deff_flux_field_D),
 //                  kernels_flux.hpp
-//   cell_pass.hpp  the host path those six share (CellPass below): work-item planner, partial sums, the call's own event
-//                  pair, the D upload, the device-map getter; k_sens, k_vjp, k_tan, k_hvp and k_fhvp are one walk (kernels_facepass.hpp), the
-//                  final sums one body (wave_reduce.hpp)
+//   cell_pass.hpp  the host path those passes and the residual share (CellPass below): work-item planner, partial sums, the
+//                  call's own event pair, the D plane (a caller's, or the assembled image's), the device-map getter; the final
+//                  sums are one body (wave_reduce.hpp)
 //   api_volume.hip 3-D volumes: deff_volume, a private context of nx x (ny * nz) plus the z-link planes (its kernels and its solve
 //                  are in api_cg.hip, beside the plane form they extend: kernels_cg_volume.hpp)
 //   api_slab.hip   one image over several GPUs: row slabs -- one slab type, pass loop and solve loop
@@ -78,34 +75,44 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // ------------------------------------------------------------ context -----
 
-// What one pass over the cells of the current field keeps between calls (the residual, the Deff gradient, the field adjoint's
-// pass; cell_pass.hpp has what they do with it).
-struct CellPass {
-    double *map = nullptr;          // device: the last per-cell map (pitch nx), kept until the next call; the residual has none
-    double *part = nullptr;         // device: the work items' partial sums + one sum per image, grow-only
-    size_t part_cap = 0;
-    bool have = false;              // map holds a result
+// What every pass over the cells keeps for its timed window and for deff_get_plan (cell_pass.hpp: cell_pass_start, pass_record).
+struct PassPlan {
+    bool have = false;              // the pass's maps hold a result
     // The call's own event pair, created by the first call that asks for `ms`: ev0 / ev1 of the context belong to the solve
     // loops alone, which read them at every check and may call a pass in between (a deff_set_progress or deff_image_done_fn
     // callback).
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int kt = 0;                     // tuning "res_kt" / "sens_kt" / "vjp_kt" / "tan_kt" / "hvp_kt" / "fhvp_kt": tiles of 8 rows a wave streams through (0 = planner)
+    int kt = 0;                     // tuning "res_kt" / "sens_kt" / "vjp_kt" / "tan_kt" / "hvp_kt" / "fhvp_kt" / "flux_kt": tiles of 8 rows a wave streams through (0 = planner)
     // deff_get_plan "*_kt" / "*_items" of the last call that launched: the run length used (planner, override and clip
-    // applied) and the partial sums the final kernel adds per image
+    // applied) and the work items per image (the partial sums the final kernel adds)
     int plan_kt = 0, plan_items = 0;
 };
 
+// What one pass over the cells of the current field keeps between calls (the residual, the Deff gradient, the field adjoint's
+// pass; cell_pass.hpp has what they do with it).
+struct CellPass : PassPlan {
+    double *map = nullptr;          // device: the last per-cell map (pitch nx), kept until the next call; the residual has none
+    double *part = nullptr;         // device: the work items' partial sums + one sum per image, grow-only
+    size_t part_cap = 0;
+};
+
 // What the flux-field pass keeps between calls (api_flux.hip, kernels_flux.hpp; cell_pass.hpp has its room and its release).
-struct FluxPass {
+struct FluxPass : PassPlan {
     double *fx = nullptr, *fy = nullptr;    // device: the last face-flux maps (pitch nx), kept until the next call
     double *left = nullptr;                 // device: the left wall's flux per row of the stack
     double *colpart = nullptr, *wallpart = nullptr;   // device: the work items' column sums (pitch nx) and left-wall sums, grow-only
     size_t part_cap = 0;                    // chunks (images x work items per strip and image) the two hold
     double *Q = nullptr;                    // device: nimg x (nxt + 1) section sums
-    bool have = false;                      // the maps hold a result
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;          // the call's own event pair (see CellPass)
-    int kt = 0;                             // tuning "flux_kt": tiles of 8 rows a wave streams through (0 = planner)
-    int plan_kt = 0, plan_items = 0;        // deff_get_plan "flux_kt" / "flux_items" of the last call that launched
+};
+
+// A vector a side solve computes on the current matrix (api_cg.hip: side_solve) or a caller sets (api_facepass.hip:
+// side_vec_set), both buffers allocated by the first call that needs them.  x: the solution (pitch nx, pad column 0); rhs: its
+// right-hand side with the forward system's decoupled cells zeroed; rhs_ok: the pass map that is copied into rhs was computed
+// since what the vector depends on was last replaced; valid: x belongs to it.  adjoint_reset / adjoint_tangent_reset below
+// clear the two flags.
+struct SideVec {
+    double *x = nullptr, *rhs = nullptr;
+    bool rhs_ok = false, valid = false;
 };
 
 struct deff_ctx {
@@ -324,40 +331,24 @@ struct deff_ctx {
 
     // The passes over the cells of the current field (cell_pass.hpp), everything allocated by the first call that needs it:
     //   pass_res   deff_residual / deff_residual_slot / deff_residual_D (api_residual.hip): no map; plan_kt is 0 after deff_residual_D
-    //   pass_sens  deff_sensitivity / deff_sensitivity_D (api_sens.hip): the map dDeff/dD, handed out by deff_device_sensitivity
-    //   pass_vjp   deff_field_vjp_D (api_vjp.hip): the map dL/dD, handed out by deff_device_field_vjp
-    //   pass_tan   deff_tangent_rhs_D (api_tangent.hip): the map r = db - dA x, handed out by deff_device_tangent_rhs
-    //   pass_hvp   deff_sensitivity_hvp_D (api_hvp.hip): the map H dD, handed out by deff_device_sensitivity_hvp
-    //   pass_atan  deff_adjoint_tangent_rhs_D (api_tangent.hip): the map q = -dA lambda, k_tan's on lambda; a map of its own, so
+    //   pass_sens  deff_sensitivity / deff_sensitivity_D (api_facepass.hip, like the next five): the map dDeff/dD, handed out by deff_device_sensitivity
+    //   pass_vjp   deff_field_vjp_D: the map dL/dD, handed out by deff_device_field_vjp
+    //   pass_tan   deff_tangent_rhs_D: the map r = db - dA x, handed out by deff_device_tangent_rhs
+    //   pass_hvp   deff_sensitivity_hvp_D: the map H dD, handed out by deff_device_sensitivity_hvp
+    //   pass_atan  deff_adjoint_tangent_rhs_D: the map q = -dA lambda, k_tan's on lambda; a map of its own, so
     //              that pass_tan's stays
-    //   pass_fhvp  deff_field_vjp_hvp_D (api_fhvp.hip): the map S_w dD, handed out by deff_device_field_vjp_hvp
+    //   pass_fhvp  deff_field_vjp_hvp_D: the map S_w dD, handed out by deff_device_field_vjp_hvp
     CellPass pass_res, pass_sens, pass_vjp, pass_tan, pass_hvp, pass_atan, pass_fhvp;
     //   pass_flux  deff_flux_field / deff_flux_field_D (api_flux.hip): the maps fx, fy, handed out by deff_device_flux_field
     FluxPass pass_flux;
     bool grid_given = false;        // the last deff_assemble_3phase was given a Grid (deff_sensitivity refuses such a system)
 
-    // The field adjoint (api_vjp.hip; the solve itself is api_cg.hip's loop).  adj_lam: lambda of A lambda = w (pitch nx, pad
-    // column 0), adj_w: the right-hand side w' = w with the forward system's decoupled cells zeroed; both allocated by the
-    // first deff_solve_adjoint / deff_set_adjoint.  adj_valid: lambda belongs to the current system and image (adjoint_reset
-    // below: every call that replaces either clears it).
-    double *adj_lam = nullptr, *adj_w = nullptr;
-    bool adj_valid = false;
-
-    // The field tangent (api_tangent.hip; the solve is api_cg.hip's loop).  tan_dx: dx of A dx = r' (pitch nx, pad column 0),
-    // tan_w: r' = pass_tan's map with the forward system's decoupled cells zeroed; both allocated by the first
-    // deff_solve_tangent (tan_dx by deff_set_tangent too: api_hvp.hip, whose pass reads it).  tan_rhs: pass_tan's map was
-    // computed since the current system and image were set, so it may serve as a right-hand side; tan_valid: dx belongs to
-    // them.  adjoint_reset clears both.
-    double *tan_dx = nullptr, *tan_w = nullptr;
-    bool tan_rhs = false, tan_valid = false;
-
-    // The adjoint's tangent (api_fhvp.hip; its right-hand side is api_tangent.hip's pass, the solve api_cg.hip's loop).  adj_dl: dlambda of A dlambda = q' (pitch nx, pad
-    // column 0), adj_dw: q' = pass_atan's map with the forward system's decoupled cells zeroed; both allocated by the first
-    // deff_solve_adjoint_tangent (adj_dl by deff_set_adjoint_tangent too).  atan_rhs: pass_atan's map was computed since the
-    // current system, image and lambda were set; atan_valid: dlambda belongs to them.  adjoint_reset clears both, and so does
-    // every call that replaces lambda (deff_solve_adjoint, deff_set_adjoint).
-    double *adj_dl = nullptr, *adj_dw = nullptr;
-    bool atan_rhs = false, atan_valid = false;
+    // The side vectors (api_facepass.hip; their solves are api_cg.hip's loop), each for the current system and image:
+    //   adj   lambda of A lambda = w, w the caller's dL/dx (deff_solve_adjoint / deff_set_adjoint); rhs_ok is not used
+    //   tan   dx of A dx = r, r pass_tan's map (deff_solve_tangent / deff_set_tangent); deff_sensitivity_hvp_D reads it
+    //   atan  dlambda of A dlambda = q, q pass_atan's map (deff_solve_adjoint_tangent / deff_set_adjoint_tangent); for the
+    //         current lambda too: every call that replaces lambda resets it
+    SideVec adj, tan, atan;
 
     // Native 3-phase system (kernels_fill.hpp, api_fill.hip): the flood fill of the pore space as bitmaps -- one `open` and
     // one `reach` word per 64 columns of a row, fill_nw words per row --, its status words and the tiled form's `changed` words.
@@ -446,16 +437,31 @@ static inline int rows_d2h(deff_ctx *c, T *dst, const T *src, size_t rows)
     return DEFF_OK;
 }
 
+// a plane of the stack (true width on the host) into a device plane of pitch nx, the pad column zeroed
+static inline int plane_h2d(deff_ctx *c, double *dst, const double *src)
+{
+    if (c->nx != c->nxt) HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * c->n, c->stream));
+    return rows_h2d(c, dst, src, (size_t)c->rows);
+}
+
 static inline CoefSoA soa_of(deff_ctx *c) { return CoefSoA{c->a0, c->aW, c->aE, c->aS, c->aN, c->b}; }
 
 // a new system: no dictionary was looked for in it yet
 static inline void dict_reset(deff_ctx *c) { c->dict_tried = false; c->dict_outcome = 0; c->dict_rows = 0; }
 
-// a new system or image: the adjoint field was the old one's (deff_get_adjoint, deff_device_adjoint, deff_field_vjp_D:
-// DEFF_ESTATE), and so were the tangent and the map that was its right-hand side (deff_solve_tangent, deff_get_tangent,
-// deff_device_tangent: DEFF_ESTATE)
-static inline void adjoint_tangent_reset(deff_ctx *c) { c->atan_rhs = false; c->atan_valid = false; }   // a new lambda
-static inline void adjoint_reset(deff_ctx *c) { c->adj_valid = false; c->tan_rhs = false; c->tan_valid = false; adjoint_tangent_reset(c); }
+// The only places that invalidate a side vector.  A new system or image: lambda, dx and the map that was dx's right-hand
+// side were the old one's (their getters, passes and deff_solve_tangent: DEFF_ESTATE), and so was dlambda; a new lambda:
+// dlambda and its right-hand side belonged to the old one.
+static inline void side_vec_reset(SideVec &v) { v.rhs_ok = false; v.valid = false; }
+static inline void adjoint_tangent_reset(deff_ctx *c) { side_vec_reset(c->atan); }
+static inline void adjoint_reset(deff_ctx *c) { side_vec_reset(c->adj); side_vec_reset(c->tan); adjoint_tangent_reset(c); }
+
+// The refusal of every entry point that needs all rows of the image on one device.
+static inline int slab_refused(const deff_ctx *c, const char *who)
+{
+    if (c->slab) return fail(DEFF_EINVAL, "%s: not for row-slab contexts (the rows of the image live on several devices)", who);
+    return DEFF_OK;
+}
 
 // No C++ exception may unwind through the C ABI: every `extern "C" int` entry point is a
 // function-try-block ending in DEFF_API_CATCH, which turns std::bad_alloc (host vectors sized by the

@@ -1,11 +1,11 @@
 // kernels_facepass.hpp -- the face walk of the gradient passes: g[p] = a sum of one term per face of cell p, from D and one or
 // two more planes, in one streaming pass (gfx950, wave64, FP64; nothing like it in the reference).  face_pass<P> is the walk,
 // written once; a policy P says what a face and a wall contribute and what is done with the cell's sum:
-//   SensPass   the Deff gradient dDeff_raw / dD from (x, D)              k_sens, api_sens.hip
-//   VjpPass    the field adjoint's dL/dD from (x, lambda, D)             k_vjp, api_vjp.hip
-//   TanPass    the field tangent's right-hand side from (x, dD, D)       k_tan, api_tangent.hip
-//   HvpPass    the Deff Hessian-vector product from (x, dx, dD, D)       k_hvp, api_hvp.hip
-//   FieldHvpPass  the field adjoint's second order from (x, lambda, dx, dlambda, dD, D)   k_fhvp, api_fhvp.hip
+//   SensPass   the Deff gradient dDeff_raw / dD from (x, D)              k_sens
+//   VjpPass    the field adjoint's dL/dD from (x, lambda, D)             k_vjp
+//   TanPass    the field tangent's right-hand side from (x, dD, D)       k_tan
+//   HvpPass    the Deff Hessian-vector product from (x, dx, dD, D)       k_hvp
+//   FieldHvpPass  the field adjoint's second order from (x, lambda, dx, dlambda, dD, D)   k_fhvp
 // All kernels are this one text, so the order of operations per cell, the launch geometry and the order of the final sum are
 // the same by construction.
 //

@@ -44,7 +44,7 @@ __device__ __forceinline__ double wave_sum_to_lane63(double v)
 
 // The body of a __global__ __launch_bounds__(1024) kernel, one workgroup of 16 waves per image: thread t adds the partial sums
 // t, t + 1024, ... of its image in that order, the wave tree combines the 64 thread sums of a wave, thread 0 adds the 16 wave
-// sums in wave order.  out[img] = sum.  (k_residual_final, k_sens_final, k_vjp_final: one order, one text.)
+// sums in wave order.  out[img] = sum.  (k_residual_final, k_pass_final: one order, one text.)
 __device__ __forceinline__ void partials_sum_body(const double *__restrict__ partial, size_t per_img, double *__restrict__ out)
 {
     __shared__ double ws[16];

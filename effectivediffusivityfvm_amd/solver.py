@@ -413,33 +413,71 @@ class Solver:
         out = r[0] if self.nimg == 1 else np.array(r[:])
         return (out, ms.value) if timing else out
 
+    # -- helpers of the passes and side solves below ------------------------
+    def _plane(self, a):
+        """A plane of the stack, (rows, nx), as contiguous float64."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        assert a.size == self.nx * self.rows
+        return a
+
+    def _cell_pass(self, fn, planes, walls, timing):
+        """One pass entry point fn(ctx, *planes, *walls, map, sums, ms) -> (map, sums[, ms]): the map as (ny, nx), or (nimg, ny,
+        nx) for a stack, the sums a float, or an array."""
+        m = np.empty((self.rows, self.nx), dtype=np.float64)
+        e = (C.c_double * self.nimg)()
+        ms = C.c_float()
+        check(fn(self._ctx, *[a.ctypes.data_as(C.c_void_p) for a in planes], *[float(w) for w in walls],
+                 m.ctypes.data_as(C.c_void_p), e, C.byref(ms) if timing else None))
+        m = m if self.nimg == 1 else m.reshape(self.nimg, self.ny, self.nx)
+        sums = e[0] if self.nimg == 1 else np.array(e[:])
+        return (m, sums, ms.value) if timing else (m, sums)
+
+    def _side_solve(self, fn, *rhs, rtol, max_iter, check_every):
+        """One side solve fn(ctx, *rhs, rtol, max_iter, check_every, results): a CGResult, or a list for a stack."""
+        res = (CGResultC * self.nimg)()
+        check(fn(self._ctx, *rhs, float(rtol), int(max_iter), int(check_every), res))
+        outs = []
+        for r in res:
+            out = CGResult()
+            out.iters, out.rel_residual, out.deff_raw = r.iters, r.rel_residual, r.deff_raw
+            out.converged, out.loop_ms = bool(r.converged), r.loop_ms
+            out.MFL = out.MFR = None
+            outs.append(out)
+        return outs[0] if self.nimg == 1 else outs
+
+    def _device_ptr(self, fn):
+        """(device pointer, row pitch in bytes) from one of the deff_device_* getters."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(fn(self._ctx, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+    @staticmethod
+    def _require_converged(who, rs, rtol, max_iter):
+        rs = rs if isinstance(rs, list) else [rs]
+        bad = [k for k, r in enumerate(rs) if not r.converged]
+        if bad:
+            raise RuntimeError(f"{who}: CG did not converge to rtol {rtol} for image(s) {bad} "
+                               f"(rel_residual {[rs[k].rel_residual for k in bad]}, max_iter {max_iter})")
+
+    def _get_plane(self, fn):
+        a = np.empty((self.rows, self.nx), dtype=np.float64)
+        check(fn(self._ctx, a.ctypes.data_as(C.c_void_p)))
+        return a
+
     def sensitivity(self, D=None, CL=None, CR=None, timing=False):
         """The Deff gradient of the current field (deff_sensitivity / deff_sensitivity_D): (g, euler) with g[p] = d deff_raw /
         d D[p] as (ny, nx), or (nimg, ny, nx) for a stack, and euler = sum of D * g per image (a float, or an array), which
         equals deff_raw for a converged field.  D = None: the diffusivities of the system assembled from the image
         (assemble_2phase, or assemble_3phase without a grid) with its CL, CR; otherwise the plane (rows, nx) with the wall
         values.  timing=True appends the device time in ms."""
-        g = np.empty((self.rows, self.nx), dtype=np.float64)
-        e = (C.c_double * self.nimg)()
-        ms = C.c_float()
-        msp = C.byref(ms) if timing else None
         if D is None:
-            check(self._L.deff_sensitivity(self._ctx, g.ctypes.data_as(C.c_void_p), e, msp))
-        else:
-            D = np.ascontiguousarray(D, dtype=np.float64)
-            assert D.size == self.nx * self.rows
-            check(self._L.deff_sensitivity_D(self._ctx, D.ctypes.data_as(C.c_void_p), float(CL), float(CR),
-                                             g.ctypes.data_as(C.c_void_p), e, msp))
-        g = g if self.nimg == 1 else g.reshape(self.nimg, self.ny, self.nx)
-        euler = e[0] if self.nimg == 1 else np.array(e[:])
-        return (g, euler, ms.value) if timing else (g, euler)
+            return self._cell_pass(self._L.deff_sensitivity, (), (), timing)
+        return self._cell_pass(self._L.deff_sensitivity_D, (self._plane(D),), (CL, CR), timing)
 
     def device_sensitivity_ptr(self):
         """(device pointer, row pitch in bytes) of the last sensitivity map; valid until the next one, an assembly or close()."""
-        p = C.c_void_p()
-        pitch = C.c_size_t()
-        check(self._L.deff_device_sensitivity(self._ctx, C.byref(p), C.byref(pitch)))
-        return p.value, pitch.value
+        return self._device_ptr(self._L.deff_device_sensitivity)
 
     # -- flux field: face fluxes and section sums ---------------------------
     def flux_field(self, D=None, CL=None, CR=None, timing=False):
@@ -460,9 +498,7 @@ class Solver:
         if D is None:
             check(self._L.deff_flux_field(self._ctx, *out))
         else:
-            D = np.ascontiguousarray(D, dtype=np.float64)
-            assert D.size == self.nx * self.rows
-            check(self._L.deff_flux_field_D(self._ctx, D.ctypes.data_as(C.c_void_p), float(CL), float(CR), *out))
+            check(self._L.deff_flux_field_D(self._ctx, self._plane(D).ctypes.data_as(C.c_void_p), float(CL), float(CR), *out))
         if self.nimg > 1:
             fx, fy = fx.reshape(self.nimg, self.ny, self.nx), fy.reshape(self.nimg, self.ny, self.nx)
         ff = FluxField(fx, fy, left, sec)
@@ -484,120 +520,60 @@ class Solver:
         With set_tuning("cg_onchip_planes", 1) images of at most 16 384 cells iterate on one compute unit each
         (plan_value("cg_impl") 4), here and in solve_tangent and solve_adjoint_tangent.
         One image: a CGResult (deff_raw 0.0, MFL / MFR None); a stack: a list, one per image."""
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        assert w.size == self.nx * self.rows
-        res = (CGResultC * self.nimg)()
-        check(self._L.deff_solve_adjoint(self._ctx, w.ctypes.data_as(C.c_void_p), float(rtol), int(max_iter),
-                                         int(check_every), res))
-        outs = []
-        for k in range(self.nimg):
-            out = CGResult()
-            out.iters, out.rel_residual, out.deff_raw = res[k].iters, res[k].rel_residual, res[k].deff_raw
-            out.converged, out.loop_ms = bool(res[k].converged), res[k].loop_ms
-            out.MFL = out.MFR = None
-            outs.append(out)
-        return outs[0] if self.nimg == 1 else outs
+        return self._side_solve(self._L.deff_solve_adjoint, self._plane(w).ctypes.data_as(C.c_void_p), rtol=rtol,
+                                max_iter=max_iter, check_every=check_every)
 
     def set_adjoint(self, lam):
         """A caller's own lambda as the adjoint field (deff_set_adjoint)."""
-        lam = np.ascontiguousarray(lam, dtype=np.float64)
-        assert lam.size == self.nx * self.rows
-        check(self._L.deff_set_adjoint(self._ctx, lam.ctypes.data_as(C.c_void_p)))
+        check(self._L.deff_set_adjoint(self._ctx, self._plane(lam).ctypes.data_as(C.c_void_p)))
 
     def get_adjoint(self):
         """The adjoint field as (rows, nx); DeffError (DEFF_ESTATE) while none is valid for the current system."""
-        lam = np.empty((self.rows, self.nx), dtype=np.float64)
-        check(self._L.deff_get_adjoint(self._ctx, lam.ctypes.data_as(C.c_void_p)))
-        return lam
+        return self._get_plane(self._L.deff_get_adjoint)
 
     def device_adjoint_ptr(self):
         """(device pointer, row pitch in bytes) of the adjoint field; the pitch is device_field_ptr's."""
-        p = C.c_void_p()
-        pitch = C.c_size_t()
-        check(self._L.deff_device_adjoint(self._ctx, C.byref(p), C.byref(pitch)))
-        return p.value, pitch.value
+        return self._device_ptr(self._L.deff_device_adjoint)
 
     def field_vjp(self, D, CL, CR, timing=False):
         """dL/dD from the current field, the current adjoint field and the diffusivity plane D (rows, nx), in one pass
         (deff_field_vjp_D): (g, euler) with g as (ny, nx), or (nimg, ny, nx) for a stack, and euler = sum of D * g per image
         (a float, or an array), which is 0 for a converged field.  timing=True appends the device time in ms."""
-        D = np.ascontiguousarray(D, dtype=np.float64)
-        assert D.size == self.nx * self.rows
-        g = np.empty((self.rows, self.nx), dtype=np.float64)
-        e = (C.c_double * self.nimg)()
-        ms = C.c_float()
-        check(self._L.deff_field_vjp_D(self._ctx, D.ctypes.data_as(C.c_void_p), float(CL), float(CR),
-                                       g.ctypes.data_as(C.c_void_p), e, C.byref(ms) if timing else None))
-        g = g if self.nimg == 1 else g.reshape(self.nimg, self.ny, self.nx)
-        euler = e[0] if self.nimg == 1 else np.array(e[:])
-        return (g, euler, ms.value) if timing else (g, euler)
+        return self._cell_pass(self._L.deff_field_vjp_D, (self._plane(D),), (CL, CR), timing)
 
     def device_field_vjp_ptr(self):
         """(device pointer, row pitch in bytes) of the last field_vjp map; valid until the next one or close()."""
-        p = C.c_void_p()
-        pitch = C.c_size_t()
-        check(self._L.deff_device_field_vjp(self._ctx, C.byref(p), C.byref(pitch)))
-        return p.value, pitch.value
+        return self._device_ptr(self._L.deff_device_field_vjp)
 
     # -- field tangent: dx along a direction dD ---------------------------
     def tangent_rhs(self, D, dD, CL, CR, timing=False):
         """r = db - dA x along the direction dD, from the current field and the diffusivity plane D, both (rows, nx), in one
         pass (deff_tangent_rhs_D): (r, norm2) with r as (ny, nx), or (nimg, ny, nx) for a stack, and norm2 = sum of r * r per
         image (a float, or an array); for dD = D it is the forward residual's.  timing=True appends the device time in ms."""
-        D = np.ascontiguousarray(D, dtype=np.float64)
-        dD = np.ascontiguousarray(dD, dtype=np.float64)
-        assert D.size == self.nx * self.rows and dD.size == D.size
-        r = np.empty((self.rows, self.nx), dtype=np.float64)
-        n2 = (C.c_double * self.nimg)()
-        ms = C.c_float()
-        check(self._L.deff_tangent_rhs_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p), float(CL),
-                                         float(CR), r.ctypes.data_as(C.c_void_p), n2, C.byref(ms) if timing else None))
-        r = r if self.nimg == 1 else r.reshape(self.nimg, self.ny, self.nx)
-        norm2 = n2[0] if self.nimg == 1 else np.array(n2[:])
-        return (r, norm2, ms.value) if timing else (r, norm2)
+        return self._cell_pass(self._L.deff_tangent_rhs_D, (self._plane(D), self._plane(dD)), (CL, CR), timing)
 
     def device_tangent_rhs_ptr(self):
         """(device pointer, row pitch in bytes) of the last tangent_rhs map; valid until the next one or close()."""
-        p = C.c_void_p()
-        pitch = C.c_size_t()
-        check(self._L.deff_device_tangent_rhs(self._ctx, C.byref(p), C.byref(pitch)))
-        return p.value, pitch.value
+        return self._device_ptr(self._L.deff_device_tangent_rhs)
 
     def solve_tangent(self, rtol=1e-10, max_iter=1_000_000, check_every=64):
         """A dx = r on the current matrix with homogeneous walls (deff_solve_tangent), r the last tangent_rhs map, read on the
         device: solve_adjoint's iteration into a buffer of its own -- the field, the system, lambda and the map stay as they
         are.  One image: a CGResult (deff_raw 0.0, MFL / MFR None); a stack: a list, one per image."""
-        res = (CGResultC * self.nimg)()
-        check(self._L.deff_solve_tangent(self._ctx, float(rtol), int(max_iter), int(check_every), res))
-        outs = []
-        for k in range(self.nimg):
-            out = CGResult()
-            out.iters, out.rel_residual, out.deff_raw = res[k].iters, res[k].rel_residual, res[k].deff_raw
-            out.converged, out.loop_ms = bool(res[k].converged), res[k].loop_ms
-            out.MFL = out.MFR = None
-            outs.append(out)
-        return outs[0] if self.nimg == 1 else outs
+        return self._side_solve(self._L.deff_solve_tangent, rtol=rtol, max_iter=max_iter, check_every=check_every)
 
     def get_tangent(self):
         """The tangent field dx as (rows, nx); DeffError (DEFF_ESTATE) while none is valid for the current system."""
-        dx = np.empty((self.rows, self.nx), dtype=np.float64)
-        check(self._L.deff_get_tangent(self._ctx, dx.ctypes.data_as(C.c_void_p)))
-        return dx
+        return self._get_plane(self._L.deff_get_tangent)
 
     def device_tangent_ptr(self):
         """(device pointer, row pitch in bytes) of the tangent field; the pitch is device_field_ptr's."""
-        p = C.c_void_p()
-        pitch = C.c_size_t()
-        check(self._L.deff_device_tangent(self._ctx, C.byref(p), C.byref(pitch)))
-        return p.value, pitch.value
+        return self._device_ptr(self._L.deff_device_tangent)
 
     def field_jvp(self, D, dD, CL, CR, rtol=1e-10, max_iter=1_000_000, check_every=64):
         """dx = (dx/dD) dD of the current field: tangent_rhs + solve_tangent + get_tangent, as (rows, nx).  RuntimeError if the
         solve does not reach rtol."""
-        D = np.ascontiguousarray(D, dtype=np.float64)
-        dD = np.ascontiguousarray(dD, dtype=np.float64)
-        assert D.size == self.nx * self.rows and dD.size == D.size
-        self._tangent_along("field_jvp", D, dD, CL, CR, rtol, max_iter, check_every)
+        self._tangent_along("field_jvp", self._plane(D), self._plane(dD), CL, CR, rtol, max_iter, check_every)
         return self.get_tangent()
 
     def _tangent_along(self, who, D, dD, CL, CR, rtol, max_iter, check_every):
@@ -605,18 +581,12 @@ class Solver:
         check(self._L.deff_tangent_rhs_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p), float(CL),
                                          float(CR), None, None, None))
         rs = self.solve_tangent(rtol=rtol, max_iter=max_iter, check_every=check_every)
-        rs = rs if isinstance(rs, list) else [rs]
-        bad = [k for k, r in enumerate(rs) if not r.converged]
-        if bad:
-            raise RuntimeError(f"{who}: CG did not converge to rtol {rtol} for image(s) {bad} "
-                               f"(rel_residual {[rs[k].rel_residual for k in bad]}, max_iter {max_iter})")
+        self._require_converged(who, rs, rtol, max_iter)
 
     # -- Deff Hessian-vector product: H dD ---------------------------------
     def set_tangent(self, dx):
         """A caller's own dx as the tangent field (deff_set_tangent); needs a system."""
-        dx = np.ascontiguousarray(dx, dtype=np.float64)
-        assert dx.size == self.nx * self.rows
-        check(self._L.deff_set_tangent(self._ctx, dx.ctypes.data_as(C.c_void_p)))
+        check(self._L.deff_set_tangent(self._ctx, self._plane(dx).ctypes.data_as(C.c_void_p)))
 
     def sens_hvp(self, D, dD, CL, CR, timing=False):
         """hv = H dD, H the Hessian of deff_raw with respect to the diffusivity map, from the current field, the current tangent
@@ -624,32 +594,17 @@ class Solver:
         (nimg, ny, nx) for a stack, and curv = dD^T H dD per image (a float, or an array).  The tangent has to be the one along
         this dD (tangent_rhs + solve_tangent, or set_tangent): deff_hvp does all three.  timing=True appends the device time in
         ms."""
-        D = np.ascontiguousarray(D, dtype=np.float64)
-        dD = np.ascontiguousarray(dD, dtype=np.float64)
-        assert D.size == self.nx * self.rows and dD.size == D.size
-        hv = np.empty((self.rows, self.nx), dtype=np.float64)
-        cv = (C.c_double * self.nimg)()
-        ms = C.c_float()
-        check(self._L.deff_sensitivity_hvp_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p), float(CL),
-                                             float(CR), hv.ctypes.data_as(C.c_void_p), cv, C.byref(ms) if timing else None))
-        hv = hv if self.nimg == 1 else hv.reshape(self.nimg, self.ny, self.nx)
-        curv = cv[0] if self.nimg == 1 else np.array(cv[:])
-        return (hv, curv, ms.value) if timing else (hv, curv)
+        return self._cell_pass(self._L.deff_sensitivity_hvp_D, (self._plane(D), self._plane(dD)), (CL, CR), timing)
 
     def device_sens_hvp_ptr(self):
         """(device pointer, row pitch in bytes) of the last sens_hvp map; valid until the next one or close()."""
-        p = C.c_void_p()
-        pitch = C.c_size_t()
-        check(self._L.deff_device_sensitivity_hvp(self._ctx, C.byref(p), C.byref(pitch)))
-        return p.value, pitch.value
+        return self._device_ptr(self._L.deff_device_sensitivity_hvp)
 
     def deff_hvp(self, D, dD, CL, CR, rtol=1e-10, max_iter=1_000_000, check_every=64):
         """(hv, curv) = sens_hvp of the current (converged) field along dD with the tangent computed here: tangent_rhs with the
         map left on the device, solve_tangent to rtol (RuntimeError if it does not get there), then sens_hvp.  Overwrites the
         tangent's right-hand side map and the tangent field."""
-        D = np.ascontiguousarray(D, dtype=np.float64)
-        dD = np.ascontiguousarray(dD, dtype=np.float64)
-        assert D.size == self.nx * self.rows and dD.size == D.size
+        D, dD = self._plane(D), self._plane(dD)
         self._tangent_along("deff_hvp", D, dD, CL, CR, rtol, max_iter, check_every)
         return self.sens_hvp(D, dD, CL, CR)
 
@@ -659,52 +614,26 @@ class Solver:
         in one pass (deff_adjoint_tangent_rhs_D: tangent_rhs's pass on lambda with both wall values 0, into a map of its own):
         (q, norm2) with q as (ny, nx), or (nimg, ny, nx) for a stack, and norm2 = sum of q * q per image.  timing=True appends
         the device time in ms."""
-        D = np.ascontiguousarray(D, dtype=np.float64)
-        dD = np.ascontiguousarray(dD, dtype=np.float64)
-        assert D.size == self.nx * self.rows and dD.size == D.size
-        q = np.empty((self.rows, self.nx), dtype=np.float64)
-        n2 = (C.c_double * self.nimg)()
-        ms = C.c_float()
-        check(self._L.deff_adjoint_tangent_rhs_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p),
-                                                 q.ctypes.data_as(C.c_void_p), n2, C.byref(ms) if timing else None))
-        q = q if self.nimg == 1 else q.reshape(self.nimg, self.ny, self.nx)
-        norm2 = n2[0] if self.nimg == 1 else np.array(n2[:])
-        return (q, norm2, ms.value) if timing else (q, norm2)
+        return self._cell_pass(self._L.deff_adjoint_tangent_rhs_D, (self._plane(D), self._plane(dD)), (), timing)
 
     def solve_adjoint_tangent(self, rtol=1e-10, max_iter=1_000_000, check_every=64):
         """A dlambda = q on the current matrix with homogeneous walls (deff_solve_adjoint_tangent), q the last
         adjoint_tangent_rhs map, read on the device: solve_tangent's iteration into a buffer of its own -- the field, the
         system, lambda, dx and the maps stay as they are.  One image: a CGResult (deff_raw 0.0, MFL / MFR None); a stack: a
         list, one per image."""
-        res = (CGResultC * self.nimg)()
-        check(self._L.deff_solve_adjoint_tangent(self._ctx, float(rtol), int(max_iter), int(check_every), res))
-        outs = []
-        for k in range(self.nimg):
-            out = CGResult()
-            out.iters, out.rel_residual, out.deff_raw = res[k].iters, res[k].rel_residual, res[k].deff_raw
-            out.converged, out.loop_ms = bool(res[k].converged), res[k].loop_ms
-            out.MFL = out.MFR = None
-            outs.append(out)
-        return outs[0] if self.nimg == 1 else outs
+        return self._side_solve(self._L.deff_solve_adjoint_tangent, rtol=rtol, max_iter=max_iter, check_every=check_every)
 
     def get_adjoint_tangent(self):
         """dlambda as (rows, nx); DeffError (DEFF_ESTATE) while none is valid for the current system and adjoint field."""
-        dl = np.empty((self.rows, self.nx), dtype=np.float64)
-        check(self._L.deff_get_adjoint_tangent(self._ctx, dl.ctypes.data_as(C.c_void_p)))
-        return dl
+        return self._get_plane(self._L.deff_get_adjoint_tangent)
 
     def set_adjoint_tangent(self, dl):
         """A caller's own dlambda (deff_set_adjoint_tangent); needs a system."""
-        dl = np.ascontiguousarray(dl, dtype=np.float64)
-        assert dl.size == self.nx * self.rows
-        check(self._L.deff_set_adjoint_tangent(self._ctx, dl.ctypes.data_as(C.c_void_p)))
+        check(self._L.deff_set_adjoint_tangent(self._ctx, self._plane(dl).ctypes.data_as(C.c_void_p)))
 
     def device_adjoint_tangent_ptr(self):
         """(device pointer, row pitch in bytes) of dlambda; the pitch is device_field_ptr's."""
-        p = C.c_void_p()
-        pitch = C.c_size_t()
-        check(self._L.deff_device_adjoint_tangent(self._ctx, C.byref(p), C.byref(pitch)))
-        return p.value, pitch.value
+        return self._device_ptr(self._L.deff_device_adjoint_tangent)
 
     def field_vjp_hvp(self, D, dD, CL, CR, timing=False):
         """hv = S_w dD, S_w the Hessian of w^T x(D) with w = A lambda held fixed, from the current field, adjoint field,
@@ -712,42 +641,23 @@ class Solver:
         hv as (ny, nx), or (nimg, ny, nx) for a stack, and curv = dD^T S_w dD per image (a float, or an array).  The tangent
         and dlambda have to be the ones along this dD: field_hvp does all five steps.  timing=True appends the device time in
         ms."""
-        D = np.ascontiguousarray(D, dtype=np.float64)
-        dD = np.ascontiguousarray(dD, dtype=np.float64)
-        assert D.size == self.nx * self.rows and dD.size == D.size
-        hv = np.empty((self.rows, self.nx), dtype=np.float64)
-        cv = (C.c_double * self.nimg)()
-        ms = C.c_float()
-        check(self._L.deff_field_vjp_hvp_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p), float(CL),
-                                           float(CR), hv.ctypes.data_as(C.c_void_p), cv, C.byref(ms) if timing else None))
-        hv = hv if self.nimg == 1 else hv.reshape(self.nimg, self.ny, self.nx)
-        curv = cv[0] if self.nimg == 1 else np.array(cv[:])
-        return (hv, curv, ms.value) if timing else (hv, curv)
+        return self._cell_pass(self._L.deff_field_vjp_hvp_D, (self._plane(D), self._plane(dD)), (CL, CR), timing)
 
     def device_field_vjp_hvp_ptr(self):
         """(device pointer, row pitch in bytes) of the last field_vjp_hvp map; valid until the next one or close()."""
-        p = C.c_void_p()
-        pitch = C.c_size_t()
-        check(self._L.deff_device_field_vjp_hvp(self._ctx, C.byref(p), C.byref(pitch)))
-        return p.value, pitch.value
+        return self._device_ptr(self._L.deff_device_field_vjp_hvp)
 
     def field_hvp(self, D, dD, CL, CR, rtol=1e-10, max_iter=1_000_000, check_every=64):
         """(hv, curv) = field_vjp_hvp of the current (converged) field and adjoint field along dD with both tangents computed
         here: tangent_rhs and adjoint_tangent_rhs with their maps left on the device, solve_tangent and solve_adjoint_tangent
         to rtol (RuntimeError if one does not get there), then field_vjp_hvp.  Overwrites both right-hand side maps, the
         tangent field and dlambda."""
-        D = np.ascontiguousarray(D, dtype=np.float64)
-        dD = np.ascontiguousarray(dD, dtype=np.float64)
-        assert D.size == self.nx * self.rows and dD.size == D.size
+        D, dD = self._plane(D), self._plane(dD)
         self._tangent_along("field_hvp", D, dD, CL, CR, rtol, max_iter, check_every)
         check(self._L.deff_adjoint_tangent_rhs_D(self._ctx, D.ctypes.data_as(C.c_void_p), dD.ctypes.data_as(C.c_void_p),
                                                  None, None, None))
         rs = self.solve_adjoint_tangent(rtol=rtol, max_iter=max_iter, check_every=check_every)
-        rs = rs if isinstance(rs, list) else [rs]
-        bad = [k for k, r in enumerate(rs) if not r.converged]
-        if bad:
-            raise RuntimeError(f"field_hvp (adjoint tangent): CG did not converge to rtol {rtol} for image(s) {bad} "
-                               f"(rel_residual {[rs[k].rel_residual for k in bad]}, max_iter {max_iter})")
+        self._require_converged("field_hvp (adjoint tangent)", rs, rtol, max_iter)
         return self.field_vjp_hvp(D, dD, CL, CR)
 
     def set_progress(self, fn):
@@ -766,10 +676,7 @@ class Solver:
         return n.value, t.value
 
     def device_field_ptr(self):
-        p = C.c_void_p()
-        pitch = C.c_size_t()
-        check(self._L.deff_device_field(self._ctx, C.byref(p), C.byref(pitch)))
-        return p.value, pitch.value
+        return self._device_ptr(self._L.deff_device_field)
 
     def synchronize(self):
         check(self._L.deff_synchronize(self._ctx))

@@ -187,20 +187,20 @@ def _usage(unit):
 
 def test_fhvp_kernels_resources():
     """k_fhvp (kernels_facepass.hpp with FieldHvpPass, five planes besides D): nothing spilled, no AGPRs, at most 168 VGPRs --
-    three waves per SIMD -- and no LDS; k_fhvp_final uses the 16 wave sums of its reduction, 128 bytes, and no scratch.  And
+    three waves per SIMD -- and no LDS; k_pass_final, the final kernel it launches, uses the 16 wave sums of its reduction, 128 bytes, and no scratch.  And
     k_hvp keeps its four waves: the walk was not changed for it."""
     seen = set()
-    for name, u in _usage("api_fhvp").items():
+    for name, u in _usage("api_facepass").items():
         if "6k_fhvpE" in name:
             seen.add("k_fhvp")
             print(f"k_fhvp: {u}")
             assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (name, u)
             assert u["VGPRs"] <= 168 and u["AGPRs"] == 0, (name, u)
             assert u["LDS Size"] == 0 and u["Occupancy"] >= 3, (name, u)
-        if "12k_fhvp_finalE" in name:
-            seen.add("k_fhvp_final")
+        if "12k_pass_finalE" in name:
+            seen.add("k_pass_final")
             assert u["ScratchSize"] == 0 and u["LDS Size"] == 128, (name, u)
-    assert seen == {"k_fhvp", "k_fhvp_final"}
-    hvp = [u for name, u in _usage("api_hvp").items() if "5k_hvpE" in name]
+    assert seen == {"k_fhvp", "k_pass_final"}
+    hvp = [u for name, u in _usage("api_facepass").items() if "5k_hvpE" in name]
     assert len(hvp) == 1
     assert hvp[0]["VGPRs"] <= 128 and hvp[0]["Occupancy"] >= 4 and hvp[0]["ScratchSize"] == 0, hvp[0]

@@ -132,9 +132,9 @@ def test_model_zero_diffusivity_cells(oracle):
 
 def test_field_vjp_kernels_resources():
     """k_vjp (kernels_vjp.hpp) under k_sens's bars: nothing spilled, at most 128 VGPRs (four waves per SIMD: a streaming kernel
-    needs its loads in flight), no LDS; k_vjp_final uses the 16 wave sums of its reduction, 128 bytes."""
-    path = os.path.join(CSRC, "build", "api_vjp.usage.txt")
-    assert os.path.exists(path), "build/api_vjp.usage.txt missing: api_vjp.hip is not part of the build"
+    needs its loads in flight), no LDS; k_pass_final, the final kernel it launches, uses the 16 wave sums of its reduction, 128 bytes."""
+    path = os.path.join(CSRC, "build", "api_facepass.usage.txt")
+    assert os.path.exists(path), "build/api_facepass.usage.txt missing: api_facepass.hip is not part of the build"
     usage, cur = {}, None
     for line in open(path, errors="replace"):
         m = re.search(r"Function Name: (\S+)", line)
@@ -151,7 +151,7 @@ def test_field_vjp_kernels_resources():
             print(f"k_vjp: {u}")
             assert u["ScratchSize"] == 0 and u["VGPRs"] <= 128 and u["AGPRs"] == 0, (name, u)
             assert u["LDS"] == 0 and u["Occupancy"] >= 4, (name, u)
-        if "11k_vjp_finalE" in name:
-            seen.add("k_vjp_final")
+        if "12k_pass_finalE" in name:
+            seen.add("k_pass_final")
             assert u["ScratchSize"] == 0 and u["LDS"] <= 128, (name, u)
-    assert seen == {"k_vjp", "k_vjp_final"}
+    assert seen == {"k_vjp", "k_pass_final"}

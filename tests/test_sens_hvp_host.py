@@ -142,9 +142,9 @@ def test_model_zero_diffusivity_cells(oracle):
 
 def test_hvp_kernels_resources():
     """k_hvp (kernels_facepass.hpp with HvpPass) under k_tan's bars: nothing spilled, at most 128 VGPRs (four waves per SIMD: a
-    streaming kernel needs its loads in flight), no LDS; k_hvp_final uses the 16 wave sums of its reduction, 128 bytes."""
-    path = os.path.join(CSRC, "build", "api_hvp.usage.txt")
-    assert os.path.exists(path), "build/api_hvp.usage.txt missing: api_hvp.hip is not part of the build"
+    streaming kernel needs its loads in flight), no LDS; k_pass_final, the final kernel it launches, uses the 16 wave sums of its reduction, 128 bytes."""
+    path = os.path.join(CSRC, "build", "api_facepass.usage.txt")
+    assert os.path.exists(path), "build/api_facepass.usage.txt missing: api_facepass.hip is not part of the build"
     usage, cur = {}, None
     for line in open(path, errors="replace"):
         m = re.search(r"Function Name: (\S+)", line)
@@ -163,7 +163,7 @@ def test_hvp_kernels_resources():
             assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (name, u)
             assert u["VGPRs"] <= 128 and u["AGPRs"] == 0, (name, u)
             assert u["LDS Size"] == 0 and u["Occupancy"] >= 4, (name, u)
-        if "11k_hvp_finalE" in name:
-            seen.add("k_hvp_final")
+        if "12k_pass_finalE" in name:
+            seen.add("k_pass_final")
             assert u["ScratchSize"] == 0 and u["LDS Size"] == 128, (name, u)
-    assert seen == {"k_hvp", "k_hvp_final"}
+    assert seen == {"k_hvp", "k_pass_final"}

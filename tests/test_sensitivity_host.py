@@ -114,9 +114,9 @@ def test_model_zero_diffusivity_cells(oracle):
 
 def test_sensitivity_kernels_resources():
     """k_sens (kernels_sens.hpp) spills nothing, keeps to 128 VGPRs (four waves per SIMD: a streaming kernel needs its loads
-    in flight) and uses no LDS; k_sens_final uses the 16 wave sums of its reduction, 128 bytes."""
-    path = os.path.join(CSRC, "build", "api_sens.usage.txt")
-    assert os.path.exists(path), "build/api_sens.usage.txt missing: api_sens.hip is not part of the build"
+    in flight) and uses no LDS; k_pass_final, the final kernel it launches, uses the 16 wave sums of its reduction, 128 bytes."""
+    path = os.path.join(CSRC, "build", "api_facepass.usage.txt")
+    assert os.path.exists(path), "build/api_facepass.usage.txt missing: api_facepass.hip is not part of the build"
     usage, cur = {}, None
     for line in open(path, errors="replace"):
         m = re.search(r"Function Name: (\S+)", line)
@@ -132,7 +132,7 @@ def test_sensitivity_kernels_resources():
             seen.add("k_sens")
             assert u["ScratchSize"] == 0 and u["VGPRs"] <= 128 and u["AGPRs"] == 0, (name, u)
             assert u["LDS"] == 0 and u["Occupancy"] >= 4, (name, u)
-        if "12k_sens_finalE" in name:
-            seen.add("k_sens_final")
+        if "12k_pass_finalE" in name:
+            seen.add("k_pass_final")
             assert u["ScratchSize"] == 0 and u["LDS"] <= 128, (name, u)
-    assert seen == {"k_sens", "k_sens_final"}
+    assert seen == {"k_sens", "k_pass_final"}

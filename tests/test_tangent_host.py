@@ -157,9 +157,9 @@ def test_model_zero_diffusivity_cells(oracle):
 
 def test_tangent_kernels_resources():
     """k_tan (kernels_facepass.hpp with TanPass) under k_vjp's bars: nothing spilled, at most 128 VGPRs (four waves per SIMD: a
-    streaming kernel needs its loads in flight), no LDS; k_tan_final uses the 16 wave sums of its reduction, 128 bytes."""
-    path = os.path.join(CSRC, "build", "api_tangent.usage.txt")
-    assert os.path.exists(path), "build/api_tangent.usage.txt missing: api_tangent.hip is not part of the build"
+    streaming kernel needs its loads in flight), no LDS; k_pass_final, the final kernel it launches, uses the 16 wave sums of its reduction, 128 bytes."""
+    path = os.path.join(CSRC, "build", "api_facepass.usage.txt")
+    assert os.path.exists(path), "build/api_facepass.usage.txt missing: api_facepass.hip is not part of the build"
     usage, cur = {}, None
     for line in open(path, errors="replace"):
         m = re.search(r"Function Name: (\S+)", line)
@@ -176,7 +176,7 @@ def test_tangent_kernels_resources():
             print(f"k_tan: {u}")
             assert u["ScratchSize"] == 0 and u["VGPRs"] <= 128 and u["AGPRs"] == 0, (name, u)
             assert u["LDS"] == 0 and u["Occupancy"] >= 4, (name, u)
-        if "11k_tan_finalE" in name:
-            seen.add("k_tan_final")
+        if "12k_pass_finalE" in name:
+            seen.add("k_pass_final")
             assert u["ScratchSize"] == 0 and u["LDS"] <= 128, (name, u)
-    assert seen == {"k_tan", "k_tan_final"}
+    assert seen == {"k_tan", "k_pass_final"}

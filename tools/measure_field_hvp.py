@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Device time of the second-order field adjoint's pass (deff_field_vjp_hvp_D: k_fhvp + k_fhvp_final, the call's own hipEvent
-pair) against the Deff Hessian-vector pass (deff_sensitivity_hvp_D: k_hvp + k_hvp_final) on the same context, shape and planes,
+"""Device time of the second-order field adjoint's pass (deff_field_vjp_hvp_D: k_fhvp + k_pass_final, the call's own hipEvent
+pair) against the Deff Hessian-vector pass (deff_sensitivity_hvp_D: k_hvp + k_pass_final) on the same context, shape and planes,
 interleaved in the same process.  The new pass moves 56 B per cell (six planes read, one map written) at three waves per SIMD,
 the Deff pass 40 B at four; both make three divisions per face: the yardstick is the Deff pass's fastest run scaled by 56 / 40.
 Reported are the SLOWEST and the FASTEST k_fhvp run against that yardstick, beside the Deff pass's own slowest / fastest spread

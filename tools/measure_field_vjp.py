@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Device time of the field adjoint's pass (deff_field_vjp_D: k_vjp + k_vjp_final, the call's own hipEvent pair) against the Deff
-gradient's pass (deff_sensitivity_D: k_sens + k_sens_final) on the same context, shape and D plane in the same run, scaled by
+"""Device time of the field adjoint's pass (deff_field_vjp_D: k_vjp + k_pass_final, the call's own hipEvent pair) against the Deff
+gradient's pass (deff_sensitivity_D: k_sens + k_pass_final) on the same context, shape and D plane in the same run, scaled by
 32 / 24 for the third stream (byte models: x, lambda, D read and g written, 32 B/cell, against 24 B/cell); and one adjoint solve
 (deff_solve_adjoint) against one forward deff_solve_cg of the same system at the same rtol: iterations and loop_ms.  Run on
 the GPU box.

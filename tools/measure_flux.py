@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Device time of the flux-field pass (deff_flux_field_D: k_flux + k_flux_sections, the call's own hipEvent pair) against the
-field adjoint's pass (deff_field_vjp_D: k_vjp + k_vjp_final) on the same context, shape and D plane, in the same process.
+field adjoint's pass (deff_field_vjp_D: k_vjp + k_pass_final) on the same context, shape and D plane, in the same process.
 Both move 32 B per cell (the flux field reads x, D and writes fx, fy; the adjoint's pass reads x, lambda, D and writes g), so
 the adjoint's pass is the yardstick: reported are the SLOWEST flux-field run against the FASTEST adjoint run.  Run on the GPU box.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Device time of the Deff Hessian-vector pass (deff_sensitivity_hvp_D: k_hvp + k_hvp_final, the call's own hipEvent pair)
-against the field adjoint's pass (deff_field_vjp_D: k_vjp + k_vjp_final) on the same context, shape and D plane, interleaved in
+"""Device time of the Deff Hessian-vector pass (deff_sensitivity_hvp_D: k_hvp + k_pass_final, the call's own hipEvent pair)
+against the field adjoint's pass (deff_field_vjp_D: k_vjp + k_pass_final) on the same context, shape and D plane, interleaved in
 the same process.  The Hessian-vector pass moves 40 B per cell (four planes read, one map written) and makes three divisions
 per face, the adjoint's 32 B and two: the yardstick is the adjoint's pass scaled by 40 / 32.  Reported are the SLOWEST
 Hessian-vector run against that yardstick's FASTEST, beside the adjoint pass's own slowest / fastest spread in the same run.

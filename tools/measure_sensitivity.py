@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device time of the Deff gradient pass (deff_sensitivity: k_sens + k_sens_final, the call's own hipEvent pair) against its
+"""Device time of the Deff gradient pass (deff_sensitivity: k_sens + k_pass_final, the call's own hipEvent pair) against its
 24 B/cell byte model (x 8, D 8, g 8) at the two rates DESIGN.md section 4 measured on this chip, and against one CG iteration
 of the same shape (profiles/cg_results.json).  Run on the GPU box.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Device time of the field tangent's pass (deff_tangent_rhs_D: k_tan + k_tan_final, the call's own hipEvent pair) against the
-field adjoint's pass (deff_field_vjp_D: k_vjp + k_vjp_final) on the same context, shape and D plane, interleaved in the same
+"""Device time of the field tangent's pass (deff_tangent_rhs_D: k_tan + k_pass_final, the call's own hipEvent pair) against the
+field adjoint's pass (deff_field_vjp_D: k_vjp + k_pass_final) on the same context, shape and D plane, interleaved in the same
 process.  Both move 32 B per cell (three planes read, one map written) and make two divisions per face, so the adjoint's pass
 is the yardstick: reported are the SLOWEST tangent run against the FASTEST adjoint run.  Run on the GPU box.
 
