@@ -40,6 +40,7 @@ SYMBOLS = [
     "deff_volume_create", "deff_volume_destroy", "deff_volume_mesh", "deff_volume_assemble_from_D", "deff_volume_get_system",
     "deff_volume_init_linear", "deff_volume_set_field", "deff_volume_get_field", "deff_volume_device_field", "deff_volume_flux",
     "deff_volume_solve_cg", "deff_volume_get_plan",
+    "deff_volume_sensitivity_D", "deff_volume_device_sensitivity", "deff_volume_set_tuning",
 ]
 
 
@@ -180,6 +181,10 @@ def load():
         L.deff_volume_flux.argtypes = [ctx, pd, C.c_void_p, C.c_void_p]
         L.deff_volume_solve_cg.argtypes = [ctx, C.c_double, C.c_int64, C.c_int64, C.POINTER(CGResultC), C.c_void_p, C.c_void_p]
         L.deff_volume_get_plan.argtypes = [ctx, C.c_char_p, C.POINTER(C.c_int)]
+    if hasattr(L, "deff_volume_sensitivity_D"):          # DEFF_AMD_LIB may name a build from before the volumes' gradient
+        L.deff_volume_sensitivity_D.argtypes = [ctx, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.deff_volume_device_sensitivity.argtypes = [ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.deff_volume_set_tuning.argtypes = [ctx, C.c_char_p, C.c_int]
     L.deff_set_progress.argtypes = [ctx, PROGRESS_FN, C.c_void_p]
     L.deff_last_launches.argtypes = [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     ip = C.POINTER(C.c_int)

@@ -10,11 +10,14 @@ setup_context).  The field is twice differentiable too: under create_graph its b
 backward gives S_w v -- the Hessian of w^T x(D) along v: the adjoint solve again, two tangent solves and one pass over
 (x, lambda, dx, dlambda, v, D) (deff_field_vjp_hvp_D) -- for D and J v for w.
 
+Volumes have the first order: effective_diffusivity_volume is Deff of a (nz, ny, nx) volume, its backward the one-pass gradient
+(deff_volume_sensitivity_D), with the same jvp; it is once differentiable.
+
 torch is imported inside the functions only: importing the package does not import it.  D makes a host round trip (plumbing;
 the solve and the gradient run in the library's HIP kernels)."""
 import numpy as np
 
-from .solver import Solver
+from .solver import Solver, Volume
 
 _FN = None
 _GRAD_FN = None
@@ -168,6 +171,69 @@ def effective_diffusivity(D, CL=0.0, CR=1.0, rtol=1e-12, max_iter=1_000_000, sol
     if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() not in (2, 3):
         raise TypeError("D must be a float64 tensor of shape (ny, nx) or (nimg, ny, nx)")
     return _function().apply(D, float(CL), float(CR), float(rtol), int(max_iter), solver, bool(onchip))
+
+
+_VOLUME_FN = None
+
+
+def _volume_function():
+    """The torch.autograd.Function of effective_diffusivity_volume, created at first use."""
+    global _VOLUME_FN
+    if _VOLUME_FN is not None:
+        return _VOLUME_FN
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _EffectiveDiffusivityVolume(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, D, CL, CR, rtol, max_iter, volume):
+            Dh = np.ascontiguousarray(D.detach().cpu().numpy(), dtype=np.float64)
+            nz, ny, nx = Dh.shape
+            v = volume if volume is not None else Volume(nx, ny, nz)
+            try:
+                if (v.nx, v.ny, v.nz) != (nx, ny, nz):
+                    raise ValueError(f"volume is ({v.nz}, {v.ny}, {v.nx}), D is {tuple(Dh.shape)}")
+                v.assemble_from_D(Dh, CL, CR)
+                v.init_linear(CL, CR)
+                r = v.solve_cg(rtol=rtol, max_iter=max_iter)
+                _converged("effective_diffusivity_volume", r, rtol, max_iter)
+                g, _ = v.sensitivity(Dh, CL, CR)
+            finally:
+                if volume is None:
+                    v.close()
+            g = torch.from_numpy(g).to(D.device)
+            ctx.save_for_backward(g)
+            ctx.save_for_forward(g)
+            return torch.tensor(r.deff_raw, dtype=torch.float64, device=D.device)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_out):
+            (g,) = ctx.saved_tensors
+            return grad_out * g, None, None, None, None, None
+
+        @staticmethod
+        def jvp(ctx, tD, *_):
+            # forward mode (torch.autograd.forward_ad): the map is the whole Jacobian
+            return (ctx.saved_tensors[0] * tD).sum()
+
+    _VOLUME_FN = _EffectiveDiffusivityVolume
+    return _VOLUME_FN
+
+
+def effective_diffusivity_volume(D, CL=0.0, CR=1.0, rtol=1e-10, max_iter=1_000_000, volume=None):
+    """deff_raw of the diffusivity volume D -- a float64 tensor (nz, ny, nx) on any device; a 3-D tensor given to
+    effective_diffusivity is a stack of images and stays one -- as a 0-d tensor on D's device, differentiable with respect to
+    D.  Forward: Volume.assemble_from_D, the linear guess, conjugate gradients to rtol (raises RuntimeError if they do not
+    converge), then the gradient map of the converged field in one pass (deff_volume_sensitivity_D); backward: grad_out * g.
+    Once differentiable: a backward pass under create_graph=True gives a gradient that cannot be differentiated again, and
+    torch says so.  Under torch.autograd.forward_ad the tangent is (g * tD).sum().  `volume`: a Volume of the same shape to
+    reuse (its system, field and gradient map are overwritten); otherwise one is created and closed.  D makes a host round
+    trip."""
+    import torch
+    if not isinstance(D, torch.Tensor) or D.dtype != torch.float64 or D.dim() != 3:
+        raise TypeError("D must be a float64 tensor of shape (nz, ny, nx)")
+    return _volume_function().apply(D, float(CL), float(CR), float(rtol), int(max_iter), volume)
 
 
 _FIELD_FN = None

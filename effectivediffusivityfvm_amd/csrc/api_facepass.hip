@@ -2,6 +2,7 @@
 // per image, and the three side vectors they read.  Each pass is one policy of the walk, one __global__ wrapper and one entry
 // point below; face_pass_run is the host path of all of them, k_pass_final their final sum.
 //   deff_sensitivity / deff_sensitivity_D   SensPass      (x, D) -> dDeff_raw / dD per cell and its Euler sum
+//   deff_volume_sensitivity_D               SensPass      on a volume (k_sens3, volume_sens_run; the entry point is in api_volume.hip)
 //   deff_field_vjp_D                        VjpPass       (x, lambda, D) -> dL/dD
 //   deff_tangent_rhs_D                      TanPass       (x, dD, D) -> r = db - dA x and its squared norm
 //   deff_adjoint_tangent_rhs_D              TanPass       on lambda with both wall values 0: q = -dA lambda
@@ -21,6 +22,15 @@ __global__ __launch_bounds__(256) void k_sens(const double *__restrict__ x, cons
                                               double CR, double den, double *__restrict__ g, double *__restrict__ partial)
 {
     face_pass(SensPass{den}, {x}, D, nx, nxt, ny, nimg, ntx, cpi, kt, wx, wy, ww, CL, CR, g, partial);
+}
+
+// SensPass on a volume: the private context's one tall image of ny rows, slices of sy rows (FpVolume)
+__global__ __launch_bounds__(256) void k_sens3(const double *__restrict__ x, const double *__restrict__ D, int nx, int nxt, int ny,
+                                               int sy, int ntx, int cpi, int kt, double wx, double wy, double wz, double ww,
+                                               double CL, double CR, double den, double *__restrict__ g,
+                                               double *__restrict__ partial)
+{
+    face_pass(SensPass{den}, {x}, D, nx, nxt, ny, 1, ntx, cpi, kt, wx, wy, ww, CL, CR, g, partial, FpVolume{sy, wz});
 }
 
 __global__ __launch_bounds__(256) void k_vjp(const double *__restrict__ x, const double *__restrict__ lam,
@@ -225,6 +235,28 @@ try {
     return sens_run(c, dD, c->CL, c->CR, g, euler, ms);
 }
 DEFF_API_CATCH
+
+// deff_volume_sensitivity_D (api_volume.hip) on the volume's private context c of nx x (ny * nz), one image: face_pass_run's
+// steps with the volume's own face weights (c->dy is not the volume's and is not read) and k_sens3.  The caller has refused
+// what can be refused.
+int volume_sens_run(deff_ctx *c, const double *D, int ny, double dy, double dz, double CL, double CR, double *g, double *euler,
+                    float *ms)
+{
+    TRY(use_device(c));
+    TRY(consolidate(c));
+    const double *dD;
+    TRY(cell_pass_upload_D(c, D, &dD));
+    CellPass &p = c->pass_sens;
+    const CellItems it = cell_pass_items(c->nxt, c->ny, 1, p.kt);
+    if ((it.items + 3) / 4 > 0x7fffffffu) return fail(DEFF_EINVAL, "deff_volume_sensitivity_D: too many work items");
+    TRY(cell_pass_room(c, p, true, it.items));
+    TRY(cell_pass_start(c, p, ms));
+    const double dx = c->dx, den = (CR - CL) * (CR - CL);
+    hipLaunchKernelGGL(k_sens3, FACE_PASS_GRID, c->x[c->cur], dD, c->nx, c->nxt, c->ny, ny, it.ntx, it.cpi, it.kt, dy * dz / dx,
+                       dx * dz / dy, dx * dy / dz, dy * dz / (dx / 2.0), CL, CR, den, p.map, p.part);
+    HIP_TRY(hipGetLastError());
+    return cell_pass_finish(c, p, k_pass_final, it, euler, g, ms);
+}
 
 extern "C" int deff_field_vjp_D(deff_ctx *c, const double *D, double CL, double CR, double *g, double *euler, float *ms)
 try {

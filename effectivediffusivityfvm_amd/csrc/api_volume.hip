@@ -159,10 +159,42 @@ try {
 }
 DEFF_API_CATCH
 
+// The Deff gradient of the volume's field.  Everything that can refuse the call comes before anything is touched; the pass
+// (volume_sens_run, api_facepass.hip) writes the private context's pass_sens and the upload scratch, nothing else.
+extern "C" int deff_volume_sensitivity_D(deff_volume *v, const double *D, double CL, double CR, double *g, double *euler, float *ms)
+try {
+    if (!v) return fail(DEFF_EINVAL, "volume is NULL");
+    if (!D) return fail(DEFF_EINVAL, "D is NULL");
+    if (!v->c->have_field) return fail(DEFF_ESTATE, "no field");
+    if (CR == CL) return fail(DEFF_EINVAL, "deff_volume_sensitivity_D: CR == CL (Deff is a flux per unit of CR - CL)");
+    return volume_sens_run(v->c, D, v->ny, v->dy, v->dz, CL, CR, g, euler, ms);
+}
+DEFF_API_CATCH
+
+extern "C" int deff_volume_device_sensitivity(deff_volume *v, void **d_map, size_t *row_pitch_bytes)
+try {
+    if (!v || !d_map) return fail(DEFF_EINVAL, "NULL argument");
+    if (!v->c->pass_sens.have) return fail(DEFF_ESTATE, "no sensitivity map yet (deff_volume_sensitivity_D)");
+    *d_map = v->c->pass_sens.map;
+    if (row_pitch_bytes) *row_pitch_bytes = sizeof(double) * v->c->nx;
+    return DEFF_OK;
+}
+DEFF_API_CATCH
+
+extern "C" int deff_volume_set_tuning(deff_volume *v, const char *key, int value)
+try {
+    if (!v || !key) return fail(DEFF_EINVAL, "NULL argument");
+    if (value < 0) return fail(DEFF_EINVAL, "tuning value must be >= 0");
+    if (strcmp(key, "sens_kt")) return fail(DEFF_EINVAL, "deff_volume_set_tuning: unknown key '%s' (volumes take \"sens_kt\")", key);
+    v->c->pass_sens.kt = value;
+    return DEFF_OK;
+}
+DEFF_API_CATCH
+
 extern "C" int deff_volume_get_plan(deff_volume *v, const char *key, int *value)
 try {
     if (!v || !key || !value) return fail(DEFF_EINVAL, "NULL argument");
-    for (const char *k : {"cg_kr", "cg_items", "cg_restarts", "cg_impl"})
+    for (const char *k : {"cg_kr", "cg_items", "cg_restarts", "cg_impl", "sens_kt", "sens_items"})
         if (!strcmp(key, k)) return deff_get_plan(v->c, key, value);
     return fail(DEFF_EINVAL, "deff_volume_get_plan: unknown key '%s'", key);
 }

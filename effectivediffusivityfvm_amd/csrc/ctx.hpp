@@ -589,3 +589,6 @@ int volume_assemble_planes(deff_ctx *c, const double *dD, int ny, int nz, double
                            double *aF);
 int volume_solve_cg(deff_ctx *c, const double *aB, const double *aF, int ny, double rtol, int64_t max_iter, int64_t check_every,
                     deff_cg_result *out, double *MFL, double *MFR);
+// api_facepass.hip: the Deff gradient of a volume's field (k_sens3) into the private context's pass_sens; ny, dy, dz are the volume's
+int volume_sens_run(deff_ctx *c, const double *D, int ny, double dy, double dz, double CL, double CR, double *g, double *euler,
+                    float *ms);

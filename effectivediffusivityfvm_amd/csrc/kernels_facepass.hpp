@@ -1,7 +1,7 @@
 // kernels_facepass.hpp -- the face walk of the gradient passes: g[p] = a sum of one term per face of cell p, from D and one or
 // two more planes, in one streaming pass (gfx950, wave64, FP64; nothing like it in the reference).  face_pass<P> is the walk,
 // written once; a policy P says what a face and a wall contribute and what is done with the cell's sum:
-//   SensPass   the Deff gradient dDeff_raw / dD from (x, D)              k_sens
+//   SensPass   the Deff gradient dDeff_raw / dD from (x, D)              k_sens, and k_sens3 on a volume (FpVolume)
 //   VjpPass    the field adjoint's dL/dD from (x, lambda, D)             k_vjp
 //   TanPass    the field tangent's right-hand side from (x, dD, D)       k_tan
 //   HvpPass    the Deff Hessian-vector product from (x, dx, dD, D)       k_hvp
@@ -36,6 +36,16 @@ namespace deff {
 constexpr int FP_ROWS = 8;                       // rows per tile
 constexpr int FP_COLS = 128;                     // columns per strip: 2 per lane
 template <bool V> struct FpTag { static constexpr bool value = V; };
+
+// The mesh the walk runs on.  FpImage: images of ny rows, four faces per cell.  FpVolume: ONE tall image of ny rows that is a
+// volume's slices of `sy` rows one after the other (nz = ny / sy), six faces per cell: rows r - sy and r + sy hold the back
+// and front neighbours (weight wz), and a slice's first and last row have no face above / below.
+struct FpImage { static constexpr bool VOLUME = false; };
+struct FpVolume {
+    static constexpr bool VOLUME = true;
+    int sy;                                      // rows per slice
+    double wz;                                   // dx * dy / dz
+};
 
 // what a lane holds of one row: two cells (.x = a, .y = b) of D and of the policy's planes; and one cell of it
 template <int NF> struct FpRow { double2 v[NF], D; };
@@ -246,12 +256,21 @@ __device__ __forceinline__ double fp_readlane(double v, int l)
 //    fourth wave per SIMD.
 //  - Only the last strip (EDGE) knows the right wall, the cells beyond it and the pad column, by per-lane selects.
 // Addresses are 64-bit (image base + row base are wave-uniform, the lane adds its column).  No LDS, no waiting.
+// On a volume (M = FpVolume; the 2-D kernels compile none of it):
+//  - slice borders inside the tall image: the N term carried down the strip is +0.0 into a slice's first row, the S term
+//    +0.0 in its last, and an item that starts on a slice's first row has nothing above it.  The row's place in its slice is
+//    a counter, wave-uniform like the row; items and tiles may straddle borders, several of them with sy < 8.
+//  - the B and F terms: each z face is evaluated from the cell's own side (P::face's term of p; the quotient and the term of q
+//    are dead code), one division per cell and face as everywhere -- a face evaluated once would have to be carried across
+//    sy rows.  Rows r - sy and r + sy are loaded like the window's own, a row ahead and clamped into the image, and a term
+//    from outside the volume (the first / last slice) is zeroed afterwards.  g[p] = P::finish(((((cW + cE) + cN) + cS) + cB) + cF).
 // partial[img * per_img + tx * cpi + chunk] = the work item's sum of P::term (cpi = work items per strip and image).
-template <class P>
+template <class P, class M = FpImage>
 __device__ __forceinline__ void face_pass(const P &pol, const double *const (&planes)[P::NF], const double *D, int nx, int nxt,
                                           int ny, int nimg, int ntx, int cpi, int kt, double wx, double wy, double ww, double CL,
-                                          double CR, double *g, double *partial)
+                                          double CR, double *g, double *partial, const M mesh = M{})
 {
+    constexpr bool VOL = M::VOLUME;
     constexpr int NF = P::NF;
     using Row = FpRow<NF>;
     using Cell = FpCell<NF>;
@@ -301,17 +320,28 @@ __device__ __forceinline__ void face_pass(const P &pol, const double *const (&pl
             o.a.D = Di[rb + col0];
         };
 
+        // a volume's rows li - sy and li + sy, back and front of row li
+        auto load_z = [&](int li, Row &b, Row &t) __attribute__((always_inline)) {
+            if constexpr (VOL) {
+                load_row(li - mesh.sy, b);
+                load_row(li + mesh.sy, t);
+            }
+        };
         Row c, n, f;                                             // the row in hand, the next, the one in flight
+        Row zb, zf, zb2, zf2;                                    // a volume: back and front of the row in hand, and of the next in flight
         Outer o, o2;
         load_row(l_begin - 1, f);
         load_row(l_begin, c);
         load_row(l_begin + 1, n);
+        load_z(l_begin, zb, zf);
         load_outer(l_begin, o);
+        int rs = 0;                                              // a volume: the row's place in its slice
+        if constexpr (VOL) rs = l_begin % mesh.sy;
         // the N terms of the item's first row: the faces above it (nothing above an image's first row)
         double nA, nB, unused;
         fp_face<P>(fp_a(f), fp_a(c), wy, unused, nA);
         fp_face<P>(fp_b(f), fp_b(c), wy, unused, nB);
-        if (l_begin == 0) { nA = 0.0; nB = 0.0; }
+        if (VOL ? rs == 0 : l_begin == 0) { nA = 0.0; nB = 0.0; }
         double acc = 0.0;
 #pragma unroll 1
         for (int l = l_begin; l < l_end; l += FP_ROWS) {
@@ -324,6 +354,7 @@ __device__ __forceinline__ void face_pass(const P &pol, const double *const (&pl
                 const int r = l + q;
                 if (r >= l_end) break;                           // wave-uniform: the item's (or the image's) last rows
                 load_row(r + 2, f);
+                load_z(r + 1, zb2, zf2);
                 const double hwq = fp_readlane(hw, q);
                 const Cell ca = fp_a(c), cb = fp_b(c);
                 Cell ce;                                         // the next lane's a; lane 63 keeps the cell east of the strip
@@ -344,9 +375,25 @@ __device__ __forceinline__ void face_pass(const P &pol, const double *const (&pl
                 const double wA = dpp_f64_keep<0x138>(eQ, hwq);      // wave_shr:1, lane 0 keeps the strip's outer W term
                 fp_face<P>(ca, fp_a(n), wy, sA, nA2);
                 fp_face<P>(cb, fp_b(n), wy, sB, nB2);
-                if (r == ny - 1) { sA = 0.0; sB = 0.0; }             // wave-uniform
-                double ga = pol.finish(((wA + mA) + nA) + sA);
-                double gb = pol.finish(((mB + eB) + nB) + sB);
+                double ga, gb;
+                if constexpr (VOL) {
+                    if (rs == mesh.sy - 1) { sA = 0.0; sB = 0.0; nA2 = 0.0; nB2 = 0.0; }   // wave-uniform: a slice's last row
+                    rs = rs == mesh.sy - 1 ? 0 : rs + 1;
+                    double bA, bB, fA, fB;
+                    fp_face<P>(ca, fp_a(zb), mesh.wz, bA, unused);
+                    fp_face<P>(cb, fp_b(zb), mesh.wz, bB, unused);
+                    fp_face<P>(ca, fp_a(zf), mesh.wz, fA, unused);
+                    fp_face<P>(cb, fp_b(zf), mesh.wz, fB, unused);
+                    if (r < mesh.sy) { bA = 0.0; bB = 0.0; }                 // wave-uniform: the first slice, the last
+                    if (r >= ny - mesh.sy) { fA = 0.0; fB = 0.0; }
+                    ga = pol.finish(((((wA + mA) + nA) + sA) + bA) + fA);
+                    gb = pol.finish(((((mB + eB) + nB) + sB) + bB) + fB);
+                    zb = zb2; zf = zf2;
+                } else {
+                    if (r == ny - 1) { sA = 0.0; sB = 0.0; }         // wave-uniform
+                    ga = pol.finish(((wA + mA) + nA) + sA);
+                    gb = pol.finish(((mB + eB) + nB) + sB);
+                }
                 if (!va || ca.D == 0) ga = 0.0;
                 if (!vb || cb.D == 0) gb = 0.0;
                 if (va) acc += P::term(ca, ga);

@@ -683,9 +683,10 @@ class Solver:
 
 
 class Volume:
-    """One nx x ny x nz volume on the unit cube (deff_volume_*): the 7-point system from a per-cell D volume, its CG solve and
-    its Deff.  Arrays are (nz, ny, nx); A is (n, 7) = P, W, E, S(row+1), N(row-1), B(slice-1), F(slice+1).  The walls in x are
-    Dirichlet (CL, CR), y and z zero-flux.  Nothing else of Solver exists for volumes yet."""
+    """One nx x ny x nz volume on the unit cube (deff_volume_*): the 7-point system from a per-cell D volume, its CG solve, its
+    Deff and the gradient dDeff/dD.  Arrays are (nz, ny, nx); A is (n, 7) = P, W, E, S(row+1), N(row-1), B(slice-1), F(slice+1).  The walls in x are
+    Dirichlet (CL, CR), y and z zero-flux.  Nothing else of Solver (the adjoint, tangent and Hessian passes, the flux field)
+    exists for volumes yet."""
 
     def __init__(self, nx, ny, nz, device=0):
         self._L = _capi.load()
@@ -757,10 +758,35 @@ class Volume:
         return _slab_solve_cg(self._L.deff_volume_solve_cg, self._vol, self.rows, rtol, max_iter, check_every, fluxes)
 
     def plan_value(self, key):
-        """"cg_kr", "cg_items", "cg_restarts" or "cg_impl" (5 = the volume form) of the last solve_cg."""
+        """"cg_kr", "cg_items", "cg_restarts" or "cg_impl" (5 = the volume form) of the last solve_cg; "sens_kt" or "sens_items"
+        of the last sensitivity: the tiles of 8 rows a wave streamed through, and the partial sums added."""
         v = C.c_int()
         check(self._L.deff_volume_get_plan(self._vol, key.encode(), C.byref(v)))
         return v.value
+
+    def set_tuning(self, key, value):
+        """"sens_kt": tiles of 8 rows one wave of sensitivity() streams through (0 = the planner's choice); no other key."""
+        check(self._L.deff_volume_set_tuning(self._vol, key.encode(), int(value)))
+
+    def sensitivity(self, D, CL, CR, timing=False):
+        """The Deff gradient of the current field (deff_volume_sensitivity_D): (g, euler) with g[p] = d deff_raw / d D[p] as
+        (nz, ny, nx) and euler = sum of D * g, which equals deff_raw for a converged field.  D: the volume (nz, ny, nx) with
+        the wall values.  timing=True appends the device time in ms."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        assert D.size == self.nx * self.rows
+        g = np.empty((self.nz, self.ny, self.nx), dtype=np.float64)
+        e = C.c_double()
+        ms = C.c_float()
+        check(self._L.deff_volume_sensitivity_D(self._vol, D.ctypes.data_as(C.c_void_p), float(CL), float(CR),
+                                                g.ctypes.data_as(C.c_void_p), C.byref(e), C.byref(ms) if timing else None))
+        return (g, e.value, ms.value) if timing else (g, e.value)
+
+    def device_sensitivity_ptr(self):
+        """(device pointer, row pitch in bytes) of the last sensitivity map; valid until the next one or close()."""
+        p = C.c_void_p()
+        pitch = C.c_size_t()
+        check(self._L.deff_volume_device_sensitivity(self._vol, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
 
     def device_field_ptr(self):
         p = C.c_void_p()

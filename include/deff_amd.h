@@ -770,8 +770,9 @@ int deff_synchronize(deff_ctx *ctx);
 
 /* ---- volumes: the 7-point system of an nx x ny x nz mesh from a D volume, its CG solve and its Deff (not in the reference,
  * whose README lists a 3-D version as upcoming).  A first milestone: a host D volume goes in, a field converged to
- * ||b - A x||_2 <= rtol ||b||_2 and its Deff come out; everything else that exists for images (Jacobi sweeps, voxel images and
- * dictionaries, stacks, the on-chip and folded forms, row slabs, the derivative passes, the flux field) does not for volumes.
+ * ||b - A x||_2 <= rtol ||b||_2, its Deff and the gradient dDeff/dD come out; everything else that exists for images (Jacobi
+ * sweeps, voxel images and dictionaries, stacks, the on-chip and folded forms, row slabs, the adjoint, tangent and Hessian
+ * passes, the flux field) does not for volumes.
  * A volume is a type of its own: no deff_ctx entry point takes it.
  *   The domain is the unit cube: dx = 1/nx, dy = 1/ny, dz = 1/nz.  The left and right walls (x) are Dirichlet at half a cell
  * (CL, CR); y and z are zero-flux.  Arrays are D[nz][ny][nx]: cell (k, i, j) at (k*ny + i)*nx + j; slice k - 1 is "back" (B),
@@ -815,8 +816,34 @@ int deff_volume_flux(deff_volume *v, double *deff_raw, double *MFL, double *MFR)
 int deff_volume_solve_cg(deff_volume *v, double rtol, int64_t max_iter, int64_t check_every, deff_cg_result *out,
                          double *MFL, double *MFR);
 /* of the last deff_volume_solve_cg: "cg_kr", "cg_items", "cg_restarts" as deff_get_plan gives them for an image of ny*nz rows,
- * and "cg_impl" (5 = the volume form; 0 before a solve); any other key: DEFF_EINVAL */
+ * and "cg_impl" (5 = the volume form; 0 before a solve); of the last deff_volume_sensitivity_D that launched: "sens_kt" and
+ * "sens_items" as deff_get_plan gives them for an image of ny*nz rows; any other key: DEFF_EINVAL */
 int deff_volume_get_plan(deff_volume *v, const char *key, int *value);
+/* The Deff gradient of the volume's current field, meaningful for a CONVERGED one (deff_volume_solve_cg): g[p] = d deff_raw /
+ * d D[p] for every cell, in one pass over the field and the diffusivities, no second solve (deff_sensitivity_D's derivation:
+ * the system is self-adjoint, and the volume's Deff is 2E / (CR - CL)^2 because wall area and length of the unit cube are 1).
+ * Face weights, each evaluated left to right: wx = dy * dz / dx for W / E faces, wy = dx * dz / dy for N / S faces,
+ * wz = dx * dy / dz for B / F faces, ww = dy * dz / (dx / 2.0) for the two walls.  Each face of cell p adds
+ *   interior, to q:  s = Dp + Dq;  t = (s == 0) ? 0 : Dq / s;  e = xp - xq;  c = (2.0 * (t * t)) * (w * (e * e))
+ *   left / right wall:  e = xp - CL (CR);  c = ww * (e * e)
+ *   no face (the first and last row of every slice, the first and last slice):  c = +0.0
+ *   g[p] = (((((cW + cE) + cN) + cS) + cB) + cF) / ((CR - CL) * (CR - CL)),  and g[p] = 0 where D[p] == 0.
+ * These doubles, in this order (tests/volume_sens_model.py states them in numpy); x * 1.0 is exact, so a volume of one slice
+ * gives the bits of deff_sensitivity_D.  euler = sum over the cells of D[p] * g[p], which equals deff_raw for the exact
+ * solution, added in deff_sensitivity_D's fixed order over the image of ny*nz rows: the same bits on every call.
+ *   D[nz*ny*nx] on the host (true width), as deff_volume_assemble_from_D takes it.  g (nz*ny*nx, true width), euler (one
+ * double) and *ms (device time of the pass, on an event pair of its own) may each be NULL.  The map is a function of any
+ * field: no system is needed.  Refused before anything is touched, in this order: a NULL volume, a NULL D (DEFF_EINVAL), no
+ * field (DEFF_ESTATE), CR == CL (DEFF_EINVAL).  Nothing changes but the map, its partial sums and the upload scratch; a refused
+ * call leaves the previous map alone.  Negative or non-finite D: unspecified values, never a fault.
+ * deff_volume_device_sensitivity: the device buffer of the last map (row pitch as deff_volume_device_field, slice after
+ * slice), valid until the next sensitivity call or deff_volume_destroy; DEFF_ESTATE before one exists.
+ * deff_volume_set_tuning: "sens_kt" -- tiles of 8 rows one wave streams through (0 = the planner's choice, clipped to the
+ * image of ny*nz rows) -- and no other key (DEFF_EINVAL, the key named). */
+int deff_volume_sensitivity_D(deff_volume *v, const double *D, double CL, double CR,
+                              double *g /* nz*ny*nx, may be NULL */, double *euler /* may be NULL */, float *ms);
+int deff_volume_device_sensitivity(deff_volume *v, void **d_g, size_t *row_pitch_bytes);
+int deff_volume_set_tuning(deff_volume *v, const char *key, int value);
 
 #ifdef __cplusplus
 }
